@@ -1,13 +1,21 @@
 """Benchmark of the Learner.fit() hot path (BASELINE.json): Learner.train1minibatch — forward + loss + backward +
 Optimizer.step + the per-step loss read-back — on synthetic device-resident batches of the five BASELINE configs.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1 without WORLD_SIZE in the environment: this process starts N worker processes itself (one rank per GPU, RCCL) BEFORE it
 touches the GPU and relays rank 0's line; under `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N` the
-launcher's environment is used instead.  Rank 0 prints ONE JSON line:
+launcher's environment is used instead.  Rank 0 prints ONE JSON line.  A plain run sets up the headline workload, runs W warm-up
+and K timed steps, writes the outputs of the last timed step (--dump-outputs) and prints:
 
   value / ms_per_step  headline, BASELINE configs[1]: ResNet-34 + default head, 224x224, 64 images PER GPU (weak scaling), fp32
+                       (also metric, unit, higher_is_better, dtype, steps, warmup, config)
+
+--dump-outputs DIR writes what the last timed step computed (dump_outputs): loss.npy, params.npy, grads.npy.
+
+--full adds everything else, measured after the headline (--configs, --no-cpu-baseline, --no-sweep and --no-counters select
+within it):
+
   roofline             dominant kernel family of the headline (fp32-MFMA implicit-GEMM conv fwd + dgrad + wgrad): algorithmic
                        FLOPs per launch / average launch duration from HIP events that libnnl_hip.so records on the launch
                        stream during extra steps of the same command, against the dense fp32 MFMA peak (157.3 TFLOP/s)
@@ -299,6 +307,27 @@ class Clock:
             self.dist.all_reduce(t, op=self.dist.ReduceOp.MAX)
             dt, med = float(t[0].item()), float(t[1].item())
         return dt, med
+
+
+DUMP_SAMPLE = 1 << 22                  # elements of the parameter / gradient sample: 2 x 16 MB
+
+
+def dump_outputs(wl, outdir):
+    """--dump-outputs DIR: what the timed path computed in its LAST timed step, for comparing two builds output for output.
+    loss.npy (float64 [1]): the loss train1minibatch returned; params.npy / grads.npy (float32): the parameters the step updated
+    and the gradients it computed, all tensors of model.parameters() flattened in order and sampled at DUMP_SAMPLE fixed indices
+    (seed 0, sorted; every element when there are fewer)."""
+    os.makedirs(outdir, exist_ok=True)
+    params = list(wl.learner.model.parameters())
+    total = sum(p.numel() for p in params)
+    idx = np.arange(total) if total <= DUMP_SAMPLE else np.sort(np.random.RandomState(0).choice(total, DUMP_SAMPLE, replace=False))
+    with torch.no_grad():
+        idx_t = torch.from_numpy(idx).to(params[0].device)
+        flat_p = torch.cat([p.detach().reshape(-1).float() for p in params])
+        flat_g = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1).float() for p in params])
+        np.save(os.path.join(outdir, 'params.npy'), flat_p[idx_t].cpu().numpy())
+        np.save(os.path.join(outdir, 'grads.npy'), flat_g[idx_t].cpu().numpy())
+    np.save(os.path.join(outdir, 'loss.npy'), np.array([float(wl.loss)], dtype=np.float64))
 
 
 def profile_kinds(wl, n):
@@ -840,6 +869,31 @@ def worker(args):
     dt = clock.timed(wl.step, args.warmup, args.steps)
     ms = dt / args.steps * 1e3
     last_loss = wl.loss
+    if args.dump_outputs and rank == 0:
+        dump_outputs(wl, args.dump_outputs)          # before any further step: the state the last timed step left
+    out = {
+        'metric': 'ResNet-34 224x224 training throughput (Learner.train1minibatch, fwd+loss+bwd+optimizer)',
+        'value': round(args.bs * world * args.steps / dt, 2), 'unit': 'images/s', 'n_gpus': world, 'ranks_seen': ranks_seen,
+        'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': round(ms, 3), 'higher_is_better': True, 'scaling': 'weak',
+        'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
+        'config': {'workload': 'DogsCats ResNet-34 classifier, 224x224, bs=%d per GPU, SGD momentum 0.9, fp32' % args.bs,
+                   'global_batch': args.bs * world, 'image_size': args.sz, 'parallelism': 'dp%d' % world, 'last_loss': last_loss},
+    }
+    if args.full:
+        headline_roofline(args, out, wl, world, clock, dist, ms)
+    del wl
+    torch.cuda.empty_cache()
+    if args.full:
+        full_measurements(args, out, device, world, rank, clock, dist, force_dist, seed, ms)
+    if rank == 0:
+        print(json.dumps(out), flush=True)
+    if dist is not None:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def headline_roofline(args, out, wl, world, clock, dist, ms):
+    "--full: the headline's roofline (extra HIP-event-profiled steps of the same workload) and (N > 1) DP diagnostics, added to `out`"
     n_prof = min(args.steps, 10)
     prof = profile_kinds(wl, n_prof)
     roofline = mfma_roofline(prof, n_prof, kernel='igemm_taps_kernel / wino_kernel / wino2_kernel / igemm_wgrad_kernel (fp32 MFMA implicit-GEMM conv2d + linear: '
@@ -852,20 +906,14 @@ def worker(args):
                          'SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE / 8 x 1024 SIMDs) over the same kernels, from the committed counter passes')
     from neuralnetworklibrary_amd import _lib as _nl
     roofline['library_source_stamp'] = _nl.source_stamp()
-    out = {
-        'metric': 'ResNet-34 224x224 training throughput (Learner.train1minibatch, fwd+loss+bwd+optimizer)',
-        'value': round(args.bs * world * args.steps / dt, 2), 'unit': 'images/s', 'n_gpus': world, 'ranks_seen': ranks_seen,
-        'steps': args.steps, 'warmup': args.warmup, 'ms_per_step': round(ms, 3), 'higher_is_better': True, 'scaling': 'weak',
-        'vs_baseline': None, 'dtype': 'f32', 'data': 'synthetic',
-        'config': {'workload': 'DogsCats ResNet-34 classifier, 224x224, bs=%d per GPU, SGD momentum 0.9, fp32' % args.bs,
-                   'global_batch': args.bs * world, 'image_size': args.sz, 'parallelism': 'dp%d' % world, 'last_loss': last_loss},
-        'roofline': roofline,
-    }
+    out['roofline'] = roofline
     if wl.learner.grad_sync is not None and dist is not None:
         out['dp'] = dp_diagnostics(wl, clock, dist, args.steps, ms)
-    del wl
-    torch.cuda.empty_cache()
 
+
+def full_measurements(args, out, device, world, rank, clock, dist, force_dist, seed, ms):
+    """--full, after the headline workload is freed: the strong-scaling legs (N > 1) or the 1-GPU proxy sweep, the other four configs,
+    the CPU baselines and the counter passes, added to `out`"""
     # ---- strong scaling: GLOBAL batch args.bs (north-star: >= 6.5x at 8 GPUs) ----
     if world > 1 or force_dist:                      # (force_dist: rehearse the N > 1 legs on a 1-GPU box, world size 1)
         per = max(args.bs // max(world, 1) // (8 if force_dist and world == 1 else 1), 1)
@@ -962,11 +1010,6 @@ def worker(args):
         if 'error' not in mc and out['roofline'].get('traffic') is None:
             out['roofline']['traffic'], out['roofline']['mfma_busy'] = mc['traffic'], mc['mfma_busy']
             out['roofline']['counters_source'] = mc['source']
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    if dist is not None:
-        dist.barrier()
-        dist.destroy_process_group()
 
 
 def main():
@@ -976,13 +1019,20 @@ def main():
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--bs', type=int, default=64, help='images per GPU of the headline (weak scaling); also the GLOBAL batch of the strong-scaling leg')
     ap.add_argument('--sz', type=int, default=224)
-    ap.add_argument('--configs', default='all', help="'all', 'none' or a comma list of collab,tabular,lm,retinanet")
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-sweep', action='store_true', help='skip the 1-GPU bs 8/16/32 strong-scaling proxy')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='write what the last timed step computed to DIR/*.npy (loss, a fixed sample of parameters and gradients)')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure everything beyond the headline: roofline, DP diagnostics, strong-scaling legs / proxy sweep, '
+                         'the other four configs, CPU baselines, counter passes (the options below select within it)')
+    ap.add_argument('--configs', default='all', help="(--full) 'all', 'none' or a comma list of collab,tabular,lm,retinanet")
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='(--full) skip the CPU baselines')
+    ap.add_argument('--no-sweep', action='store_true', help='(--full) skip the 1-GPU bs 8/16/32 strong-scaling proxy')
     ap.add_argument('--dry-run', action='store_true', help='CPU + gloo rehearsal of the launch / timing / JSON protocol (no HIP path)')
-    ap.add_argument('--no-counters', dest='counters', action='store_false', help='N = 1: skip the three rocprofv3 --pmc child passes (HBM-side bytes, MFMA busy of this build, ~40 s)')
+    ap.add_argument('--no-counters', dest='counters', action='store_false', help='(--full) N = 1: skip the three rocprofv3 --pmc child passes (HBM-side bytes, MFMA busy of this build, ~40 s)')
     ap.add_argument('--cpu-baseline-child', default=None, help='(internal) run ONE CPU baseline in this fresh process and print its JSON')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
     if args.cpu_baseline_child:
         return cpu_baseline_child_main(args.cpu_baseline_child, args.bs, args.sz)
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:

@@ -195,6 +195,8 @@ def test_g12_objectdetectionnet_hip_vs_reference():
     from oracle import reference_math as RM, reference_nets as RN
     onet = synth.fill_detection_net_(RN.ObjectDetectionNet(K))          # torch-CPU fp32 on this host: the second adjudicator
     osd = dict(onet.named_parameters())
+    slice_names = [str(s) for s in g['slice_names'] if 'eval.grad.%s.f32' % s in g]
+    host_draws = eps_perturbed_eval_slices(K, x.cpu(), B.cpu(), Cc.cpu(), slice_names)
     for mode in ['train', 'eval']:
         net.train() if mode == 'train' else net.eval()
         onet.train() if mode == 'train' else onet.eval()
@@ -216,10 +218,9 @@ def test_g12_objectdetectionnet_hip_vs_reference():
         assert_within_reference_gap(norms, g, mode + '.grad_norms', mode + ' grad norms', slack=slack)
         if mode == 'eval':
             worst = []
-            for n in [str(s) for s in g['slice_names']]:
-                if 'eval.grad.%s.f32' % n in g:
-                    worst.append((slice_gap_ratio(sd[n].grad.reshape(-1)[:1024], g, 'eval.grad.' + n, slack, GRAD_SLICE_FLOOR,
-                                                  osd[n].grad.reshape(-1)[:1024]), n))
+            for n in slice_names:
+                hosts32 = [osd[n].grad.reshape(-1)[:1024]] + [d[n] for d in host_draws]
+                worst.append((slice_gap_ratio(sd[n].grad.reshape(-1)[:1024], g, 'eval.grad.' + n, slack, GRAD_SLICE_FLOOR, hosts32), n))
             worst.sort(reverse=True)
             print('G12 eval gradient slices, err / (%g x gap + %g x norm), worst first:' % (slack, GRAD_SLICE_FLOOR),
                   ', '.join('%s %.2f' % (n, r) for r, n in worst[:5]))
@@ -237,14 +238,42 @@ FLOORED_TENSORS = ('regressor.',)          # see the end of the test below
 # these tiny maps (NNL_CONV_WINO=2) the worst slice is fpn.P5_1.weight at 1.37 (2e-3 floor) although the two kernels agree to
 # 1e-6 on every single convolution of that size (tools/wino_debug.py) — gate flips on a 2x2 map, not arithmetic error; the
 # production sizes (G13b, G15: 20- / 10-step loss curves) run the Winograd kernel and hold their 1e-3.
+# The host's torch-CPU fp32 run is ONE draw of those gate flips, and which draw it is depends on the host: on fpn.P5_1.weight the
+# unperturbed run flips the decisive gate at one OpenMP thread (5.5e-3 from fp64) and not at 2 - 16 threads (6e-7), so the check
+# passed or failed (4.1) with the thread count of the machine.  The adjudicator is therefore the envelope of that run and four
+# torch-CPU fp32 runs from weights moved by <= 1 ulp (the yardstick of the full-size test below and of G13), which draws the flip
+# at any thread count.
 GRAD_SLICE_FLOOR = 1e-3
+EPS_DRAW_SEEDS = (100, 101, 102, 103)
 
 
-def slice_gap_ratio(got, g, key, slack, floor, host32):
-    "||got - f64|| / (slack x max(||f32 - f64||, ||host32 - f64||) + floor x ||f64||) for one gradient slice"
+def eps_perturbed_eval_slices(K, x, B, Cc, names, seeds=EPS_DRAW_SEEDS):
+    """torch-CPU fp32 oracle from the G12 weights moved by <= 1 ulp (one draw per seed), run as the generator ran it (training
+    mode, then eval mode): per draw {name: the first 1024 elements of the eval-mode weight gradient}"""
+    from oracle import reference_math as RM, reference_nets as RN, synth
+    draws = []
+    for seed in seeds:
+        net = synth.fill_detection_net_(RN.ObjectDetectionNet(K))
+        gen = torch.Generator().manual_seed(seed)
+        with torch.no_grad():
+            for p in net.parameters():
+                p.mul_(1.0 + 2.0 ** -23 * (torch.randint(0, 3, p.shape, generator=gen).float() - 1.0))
+        for mode in ['train', 'eval']:
+            net.train() if mode == 'train' else net.eval()
+            for p in net.parameters():
+                p.grad = None
+            a, r, c = net(x)
+            RM.ssd_loss(a, r, c, B, Cc, 0.5, 0.25, 2.0)[0].backward()
+        sd = dict(net.named_parameters())
+        draws.append({n: sd[n].grad.reshape(-1)[:1024].detach().clone() for n in names})
+    return draws
+
+
+def slice_gap_ratio(got, g, key, slack, floor, hosts32):
+    "||got - f64|| / (slack x max(||f32 - f64||, max over hosts32 ||host32 - f64||) + floor x ||f64||) for one gradient slice"
     r32, r64 = g[key + '.f32'], g[key + '.f64']
     got = got.detach().cpu().double().numpy().reshape(r64.shape)
-    gapn = max(np.linalg.norm(r32 - r64), np.linalg.norm(host32.detach().cpu().double().numpy().reshape(r64.shape) - r64))
+    gapn = max([np.linalg.norm(r32 - r64)] + [np.linalg.norm(h.detach().cpu().double().numpy().reshape(r64.shape) - r64) for h in hosts32])
     return float(np.linalg.norm(got - r64) / (slack * gapn + floor * np.linalg.norm(r64)))
 
 
