@@ -172,10 +172,12 @@ class StructuredDataNet(nn.Module):
             combined = cont if cont_mask is None else cont * cont_mask
         return self.head(combined)
 
-    def nnl_dp_prepare(self, x_batch):
+    def nnl_dp_prepare(self, x_batch, arm=True):
         """Data-parallel replay (Learner.use_graphs under distribute()): the renorm sync's all-gather of every rank's looked-up indices
          run EAGERLY on the step's static input, into a static buffer the captured forward reads — the collective stays
-        outside the hipGraph.  Returns True when the next forward will use the buffer."""
+        outside the hipGraph.  arm=True (before the capture): the next forward, the one being captured, reads the buffer; arm=False
+        (before a replay): the buffer is refreshed for the graph only, and the next forward that runs in Python (an evaluation, a
+        ragged eager step) gathers its own batch's indices.  Returns True when the next forward will use the buffer."""
         sync = getattr(self, 'nnl_dp', None)
         if sync is None or self.n_cat == 0 or self.embeddings[0].emb.max_norm is None:
             return False
@@ -186,8 +188,8 @@ class StructuredDataNet(nn.Module):
             self._nnl_xren = xren.clone()
         else:
             buf.copy_(xren)
-        self._nnl_xren_ready = True
-        return True
+        self._nnl_xren_ready = bool(arm)
+        return self._nnl_xren_ready
 
     @classmethod
     def from_dataobj(cls, data, fc_layer_sizes, emb_sizes='default', output_range=None, dropout_levels=None):

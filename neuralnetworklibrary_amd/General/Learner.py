@@ -168,6 +168,7 @@ class _GraphedStep:
 
     def __init__(self, warmup):
         self.left, self.graph, self.x, self.y, self.loss = max(int(warmup), 1), None, None, None, None
+        self.owned = ()              # buffers outside torch's graph pool that the captured kernels read (ops.prepared_batches)
 
     def run(self, learner, x_batch, y_batch, defer=False):
         """Non-DP: the whole step (forward, loss, backward, fused optimizer) is one graph.  Data parallel: the graph holds forward,
@@ -217,6 +218,9 @@ class _GraphedStep:
                     self.signalled = gs.capture_end()    # buckets signalled inside THIS graph (None: no overlap protocol captured)
                     gs.capturing, gs._active = False, False
             self.graph = graph
+            if dev.type == 'cuda':
+                from .. import ops
+                self.owned = ops.prepared_batches(learner.model)   # the graph points into these filter buffers: they live as long as it does
             self.opt_capture = None if dp else opt.captured()
             if not dp:
                 opt.stage_captured()                     # the captured step's own lr / decay / hyper values, before its first replay
@@ -226,8 +230,8 @@ class _GraphedStep:
             if not dp:
                 opt.replay_step(self.opt_capture)
             else:
-                for m in learner._dp_prepare_mods:    # (after the new batch has reached the static inputs, before the replay)
-                    m.nnl_dp_prepare(self.x)
+                for m in learner._dp_prepare_mods:    # (after the new batch has reached the static inputs, before the replay; the replay
+                    m.nnl_dp_prepare(self.x, arm=False)   # reads the buffer, no Python forward does: the next eager forward gathers its own)
         self.graph.replay()
         if defer and not dp:
             # fit()'s pipelined loop: start the scalar's copy into one of two pinned slots and hand back a handle; the static loss

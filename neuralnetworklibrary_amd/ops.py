@@ -213,6 +213,7 @@ _WT_PADDED = {}       # (weight data_ptr, shape, pad) -> transposed, channel-pad
 # address.  The window closes in finish_backward() (Learner: in a `finally`), before the optimizer touches the weights.
 _WINO_U_FWD, _WINO_U_BWD = {}, {}     # (weight data_ptr, kernel mode) -> U [K,4|16,3|1,C] (forward) / U' [C,...,K] (dgrad) in that kernel's layout
 _WINO_GEN = [0]                       # training-step counter (prepare_forward): the recorded modes of a weight are those of its LAST step
+_WINO_IN_STEP = [False]               # True from prepare_forward to finish_backward: only the forward calls of a training step are recorded
 _WINO_PREF = {}                       # weight data_ptr -> [modes the forward calls took, modes the dgrad calls took] (sets; 1 = 1-D, 2 = 2-D kernel):
                                       # a weight shared between geometries (RetinaNet's heads: five pyramid levels) may need BOTH layouts
 
@@ -265,6 +266,13 @@ def _conv_mods(model):
     return mods
 
 
+def prepared_batches(model):
+    """the persistent filter batches (_WinoBatch / _WtBatch) the last prepare_forward / prepare_backward of `model` ran.  A captured
+    step bakes raw pointers to their buffers and descriptor tables into its graph and must keep them alive (Learner._GraphedStep):
+    the next step at another batch size may replace the model's batch when the layers' Winograd modes change."""
+    return tuple(b for b in (getattr(model, a, None) for a in ('_nnl_wino_fwd_batch', '_nnl_wino_bwd_batch', '_nnl_wt_batch')) if b is not None)
+
+
 def _run_wino_batch(model, attr, items, out):
     if not items:
         return
@@ -289,6 +297,7 @@ def prepare_forward(model):
     took the Winograd kernel, in one launch; valid until finish_backward()."""
     _WINO_U_FWD.clear()
     _WINO_GEN[0] += 1                                    # a new training step: the modes recorded from here on replace the previous step's
+    _WINO_IN_STEP[0] = True
     if os.environ.get('NNL_WINO_PREPARE', '1') == '0':
         return
     items = []
@@ -370,6 +379,7 @@ def _finish_backward_impl():
     _WT_PADDED.clear()
     _WINO_U_FWD.clear()
     _WINO_U_BWD.clear()
+    _WINO_IN_STEP[0] = False
 
 
 def _wino_pref(key_ptr, which, g):
@@ -377,7 +387,10 @@ def _wino_pref(key_ptr, which, g):
     per weight for the next step's batch (a weight shared between geometries keeps the mode of its LAST call; calls whose mode
     differs transform their own filter: the prepared buffer is only handed over when its size is that of the mode's layout)"""
     pref = int(lib.nnl_conv2d_wino_preferred(g, which)) if (g.R == 3 and g.S == 3 and g.stride == 1) else 0
-    if pref or key_ptr in _WINO_PREF:
+    # a forward is recorded only inside a training step (prepare_forward .. finish_backward): an evaluation forward at another batch size
+    # must not change the next training step's batch (a rebuild would free buffers a captured step still reads).  Grad mode cannot tell
+    # them apart here: autograd runs every Function's forward with it off.  A dgrad only runs in a backward pass: it always records.
+    if (pref or key_ptr in _WINO_PREF) and (which == 1 or _WINO_IN_STEP[0]):
         if len(_WINO_PREF) > 8192:
             _WINO_PREF.clear()
         e = _WINO_PREF.setdefault(key_ptr, [[-1, set()], [-1, set()]])[which]

@@ -80,3 +80,18 @@ def test_headline_and_small_batch_choices(lib):
     from neuralnetworklibrary_amd import ops
     g = ops._geom(64, 56, 56, 64, 128, 3, 3, 1, 1)
     assert lib.nnl_conv2d_wino_preferred(g, 1) == lib.nnl_debug_conv_plan_times(64, 56, 56, 128, 64, out)
+
+
+def test_modes_the_graph_rebuild_test_relies_on(lib):
+    """tests/test_graph_gpu.py::test_replay_across_batch_sizes_keeps_captured_filter_buffers needs a 3x3 128 -> 128 convolution at 28 x 28
+    to take a DIFFERENT kernel at each of its three batch sizes: the 2-D Winograd kernel at 32 images (the first captured graph), the
+    1-D kernel at 24 (the ragged step whose eager warm-up rebuilds the prepared-filter batch) and the direct kernel at 5 (the evaluation
+    pass) — in the forward and in the dgrad direction."""
+    from neuralnetworklibrary_amd import ops
+    os.environ.pop('NNL_CONV_WINO', None); os.environ.pop('NNL_CONV_WINO2', None); lib.nnl_reload_env()
+    for which in (0, 1):
+        got = {N: int(lib.nnl_conv2d_wino_preferred(ops._geom(N, 28, 28, 128, 128, 3, 3, 1, 1), which)) for N in (32, 24, 5)}
+        assert got == {32: 2, 24: 1, 5: 0}, (
+            'the planner changed its choice for 3x3 128 -> 128 at 28 x 28 (which=%d): %r; test_graph_gpu.py::'
+            'test_replay_across_batch_sizes_keeps_captured_filter_buffers needs new batch sizes that still reach the 2-D, 1-D and direct '
+            'kernels (or it no longer exercises the rebuild of the prepared-filter batch)' % (which, got))

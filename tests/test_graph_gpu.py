@@ -469,3 +469,161 @@ def test_fit_loop_runs_ahead_of_the_gpu_with_per_step_schedules():
     assert_close(np.array(lf), np.array(ls), 1e-6, 1e-7, 'loss schedule')
     for a, b in zip(pf, ps):
         assert_close(a, b, 1e-6, 1e-8, 'params')
+
+
+# ---- replay across batch sizes: the prepared Winograd filter batches ------------------------------------------------------------
+class _TwoConvNet(nn.Module):
+    """two 3x3 128 -> 128 HipConv2d + BatchNorm + ReLU at 28 x 28, concat pooling, a linear head.  At 28 x 28 the dispatcher takes the
+    2-D Winograd kernel at 32 images, the 1-D kernel at 24 and the direct kernel at 5 (pinned on the CPU by
+    test_conv_planner_cpu.py::test_modes_the_graph_rebuild_test_relies_on), so the prepared-filter batch (ops._WinoBatch) changes
+    with the batch size."""
+
+    def __init__(self, n_classes=10):
+        super().__init__()
+        from neuralnetworklibrary_amd.Applications.VisionModels.retinanet import HipConv2d
+        from neuralnetworklibrary_amd.General.Core import separate_bn_layers
+        self.conv1, self.bn1 = HipConv2d(128, 128, 3, padding=1, bias=False), nn.BatchNorm2d(128)
+        self.conv2, self.bn2 = HipConv2d(128, 128, 3, padding=1, bias=False), nn.BatchNorm2d(128)
+        self.fc = nn.Linear(256, n_classes)
+        self.layer_groups = [nn.ModuleList([self.conv1, self.bn1, self.conv2, self.bn2]), nn.ModuleList([self.fc])]
+        self.param_groups = separate_bn_layers(self.layer_groups)
+
+    def forward(self, x):
+        from neuralnetworklibrary_amd import ops
+        h = ops.conv_bn_act(self.conv1, self.bn1, x, relu=True)
+        h = ops.conv_bn_act(self.conv2, self.bn2, h, relu=True)
+        return ops.linear(ops.concat_pool2d(h).reshape(x.shape[0], -1), self.fc.weight, self.fc.bias)
+
+
+def _two_conv_loss_fp64(params, x, y, eps=1e-5):
+    """the loss of _TwoConvNet in training mode, restated with torch.nn.functional in fp64 on the CPU (params: name -> tensor)"""
+    import torch.nn.functional as F
+    p = {k: v.detach().cpu().double() for k, v in params.items()}
+    h = x.detach().cpu().double()
+    for i in (1, 2):
+        h = F.conv2d(h, p['conv%d.weight' % i], padding=1)
+        h = F.relu(F.batch_norm(h, None, None, p['bn%d.weight' % i], p['bn%d.bias' % i], training=True, eps=eps))
+    pooled = torch.cat([h.amax(dim=(2, 3)), h.mean(dim=(2, 3))], 1)
+    return F.cross_entropy(F.linear(pooled, p['fc.weight'], p['fc.bias']), y.detach().cpu()).item()
+
+
+def _two_conv_setup():
+    from neuralnetworklibrary_amd.General.Core import set_default_device
+    from neuralnetworklibrary_amd.General.Learner import Learner
+    set_default_device(DEV)
+    Learner.verbose = False
+    g = torch.Generator().manual_seed(8)
+
+    def batch(n):
+        return (torch.randn(n, 128, 28, 28, generator=g).to(DEV).contiguous(memory_format=torch.channels_last),
+                torch.randint(0, 10, (n,), generator=g).to(DEV))
+    batches = {32: [batch(32) for _ in range(3)], 24: [batch(24)], 5: [batch(5)]}
+
+    class D:
+        sz, categories, bs, target_type = (28, 28), {i: str(i) for i in range(10)}, 32, 'single_label'
+        train_dl, val_dl = batches[32] + batches[24], batches[5]
+
+    def make(graphs):
+        torch.manual_seed(0)
+        learner = Learner('/tmp/nnl_graph_test', D, _TwoConvNet(), optimizer='SGD_Mom')
+        learner.init_optimizer(wd=1e-4)
+        learner.use_graphs(bool(graphs), warmup=2)
+        learner.model.train()
+        return learner
+    return batches, make
+
+
+def _n_captured(learner):
+    return sum(g.graph is not None for g in learner._graphs.values())
+
+
+def test_replay_across_batch_sizes_keeps_captured_filter_buffers():
+    """a captured step bakes raw pointers to the model's prepared Winograd filter batches (buffers, descriptor tables)
+    into its filter-transform node, and its convolutions read the transformed filters there.  An eager step at another batch size whose
+    layers take another Winograd kernel replaces the model's batch; the graph of the first signature must keep the old one alive.
+    Four epochs of 32, 32, 32, 24 images (two signatures, warm-up 2) with an evaluation pass at 5 images between epochs: epoch 1 captures
+    the 32-image step, epoch 2's eager warm-up at 24 rebuilds the batches, epoch 3 replays the 32-image graph and captures the 24-image
+    one.  Before every step that replays a graph, the batches its capture ran must still be alive (checked on the host, so no graph ever
+    runs over freed memory); the run must train like the eager run, and each replay whose capture-time batch is no longer the model's
+    must give the loss of an fp64 CPU restatement of the net on the weights it started from."""
+    import weakref
+    batches, make = _two_conv_setup()
+    order = [(32, 0), (32, 1), (32, 2), (24, 0)]
+    lr = [2e-3, 4e-3]
+
+    def run(graphs):
+        learner = make(graphs)
+        model = learner.model
+        captured = {}                    # batch size -> weak references to the (forward, dgrad) batches its capture ran
+        first_fwd, rebuilt, checks, losses = None, False, [], []
+        for epoch in range(4):
+            model.train()
+            for n, i in order:
+                x, y = batches[n][i]
+                replay = n in captured
+                if replay:
+                    for r, what in zip(captured[n], ('forward', 'dgrad')):
+                        assert r() is not None, ('epoch %d, %d images: the %s Winograd filter batch captured with this signature\'s graph '
+                                                 'was freed (a rebuild at another batch size replaced it); its replay would read freed '
+                                                 'buffers' % (epoch + 1, n, what))
+                stale = replay and model._nnl_wino_fwd_batch is not captured[n][0]()
+                before = {k: v.detach().cpu().clone() for k, v in model.named_parameters()} if stale else None
+                n_before = _n_captured(learner)
+                losses.append(learner.train1minibatch(x, y, lr, mom_batch=0.9))
+                if graphs and _n_captured(learner) > n_before:
+                    fwd, bwd = getattr(model, '_nnl_wino_fwd_batch', None), getattr(model, '_nnl_wino_bwd_batch', None)
+                    assert fwd is not None and bwd is not None, 'the captured step ran no prepared Winograd filter batch'
+                    captured[n] = (weakref.ref(fwd), weakref.ref(bwd))
+                    del fwd, bwd
+                    if first_fwd is None:
+                        first_fwd = captured[n][0]
+                if first_fwd is not None and model._nnl_wino_fwd_batch is not first_fwd():
+                    rebuilt = True
+                if stale:
+                    checks.append((epoch + 1, n, losses[-1], _two_conv_loss_fp64(before, x, y)))
+            learner.evaluate('val')      # 5 images, eval mode, no_grad: the direct kernel
+        return np.array(losses), [p.detach().cpu().numpy().copy() for p in model.parameters()], _n_captured(learner), rebuilt, checks
+
+    le, pe, ne, _, _ = run(False)
+    lg, pg, ng, rebuilt, checks = run(True)
+    assert ne == 0 and ng == 2, (ne, ng)
+    assert rebuilt, 'the forward filter batch was never replaced after the first capture: the test no longer exercises the rebuild'
+    assert len(checks) >= 3, checks
+    assert_close(lg, le, 1e-5, 1e-6, 'losses: graph replay across two signatures vs eager')
+    for a, b in zip(pg, pe):
+        assert_close(a, b, 2e-5, 2e-6, 'params')
+    for epoch, n, got, want in checks:
+        assert_close(np.array(got), np.array(want), 1e-4, 0, 'epoch %d, %d images: replayed loss vs the fp64 CPU restatement' % (epoch, n))
+
+
+def test_eval_forward_does_not_rebuild_the_training_filter_batches():
+    """ADVICE r5 (low; it triggers the rebuild above): evaluation forwards must not enter the Winograd modes the next training step
+    prepares its filters for.  Eager steps at 32 images, then no_grad eval forwards at 5 images (the direct kernel) and at 24 (the
+    1-D kernel, which a recording eval forward would add to the 2-D mode of the training step), then another step at 32: the forward
+    and dgrad filter batches are the same objects as before, and the step is bitwise that of a run without the evaluation."""
+    batches, make = _two_conv_setup()
+    lr = [2e-3, 4e-3]
+
+    def run(evals):
+        learner = make(False)
+        model = learner.model
+        for i in range(3):
+            learner.train1minibatch(*batches[32][i], lr, mom_batch=0.9)
+        fwd, bwd = model._nnl_wino_fwd_batch, model._nnl_wino_bwd_batch
+        if evals:
+            model.eval()
+            with torch.no_grad():
+                for n in evals:
+                    learner.predict1minibatch(batches[n][0][0])
+            model.train()
+        loss = learner.train1minibatch(*batches[32][0], lr, mom_batch=0.9)
+        same = (model._nnl_wino_fwd_batch is fwd, model._nnl_wino_bwd_batch is bwd)
+        return loss, [p.detach().cpu().clone() for p in model.parameters()], same
+
+    l0, p0, same0 = run(())
+    l1, p1, same1 = run((5, 24))
+    assert same0 == (True, True), same0
+    assert same1 == (True, True), 'the eval forwards rebuilt the training filter batches (forward, dgrad): %r' % (same1,)
+    assert l1 == l0, (l1, l0)
+    for a, b in zip(p1, p0):
+        assert torch.equal(a, b)

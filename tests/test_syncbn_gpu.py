@@ -344,9 +344,26 @@ def _fit_tab_replay(rank, world, port, q, graphs):
     learner.grad_sync.raise_if_overlap_error()
     n_graphs = sum(g.graph is not None for g in learner._graphs.values())
     sd = {k: v.detach().cpu().numpy() for k, v in learner.model.state_dict().items()}
-    q.put((rank, losses, sd, n_graphs))
+    # then one evaluation forward on a fresh batch, the renorm sync active: it must renorm the rows ITS batch looks up (on every rank)
+    model = learner.model
+    with torch.no_grad():
+        for e in model.embeddings:
+            e.emb.weight.mul_(2.0)                          # every row above max_norm again: the renorm changes exactly the rows it hits
+    before = [e.emb.weight.detach().cpu().numpy().copy() for e in model.embeddings]
+    (ex, _), = list(nd.ShardedBatches([_tab_eval_batch()], rank, world))
+    model.eval()
+    with torch.no_grad():
+        out = learner.predict1minibatch([ex[0].to(DEV), ex[1].to(DEV)]).cpu().numpy()
+    after = [e.emb.weight.detach().cpu().numpy().copy() for e in model.embeddings]
+    q.put((rank, losses, sd, n_graphs, out, before, after, ex[0].numpy()))
     dist.barrier()
     dist.destroy_process_group()
+
+
+def _tab_eval_batch():
+    rs = np.random.RandomState(19)
+    xcat = torch.from_numpy(np.stack([rs.randint(0, c, size=8) for c in [9, 6, 4]], 1).astype(np.int64))
+    return [xcat, torch.from_numpy(rs.standard_normal((8, 2)).astype(np.float32))], torch.zeros(8)
 
 
 def _fit_tab_replay_on(rank, world, port, q):
@@ -361,7 +378,9 @@ def test_two_process_tabular_dp_replays_with_the_renorm_sync_active():
     """config 3 under distribute() used to fall back to the eager step because the forward contained the renorm sync's
     all-gather.  The gather only needs the step's INPUT indices, so it now runs before the graph into a static buffer
     (StructuredDataNet.nnl_dp_prepare) and the step is captured and replayed: same training as eager data parallelism, embedding
-    tables identical on both ranks (the renorm hit every rank's rows), ten replays."""
+    tables identical on both ranks (the renorm hit every rank's rows), ten replays.  Then one evaluation forward on a fresh batch: it
+    runs in Python after the replays and must gather its own indices — it renorms exactly the rows either rank's evaluation batch
+    looks up (nn.Embedding's max_norm rule, checked in fp64 on the host) and gives the outputs and tables of eager data parallelism."""
     eager, replay = _run(2, _fit_tab_replay_off), _run(2, _fit_tab_replay_on)
     assert eager[0][3] == 0 and replay[0][3] == 1 and replay[1][3] == 1
     for k in replay[0][2]:
@@ -371,3 +390,22 @@ def test_two_process_tabular_dp_replays_with_the_renorm_sync_active():
             assert_close(replay[r][2][k], eager[r][2][k], 2e-5, 2e-6, 'replayed vs eager data parallelism: ' + k)
     for r in range(2):
         assert_close(np.array(replay[r][1]), np.array(eager[r][1]), 1e-5, 1e-6, 'loss curve')
+    # the first forward after the replays — an evaluation on a fresh batch — must gather and renorm its OWN
+    # batch's rows, not the ones of the last replayed step
+    max_norm = 1.5
+    for r in range(2):
+        assert_close(replay[r][4], eager[r][4], 2e-5, 2e-6, 'evaluation outputs after the replayed steps vs eager data parallelism')
+    for j in range(3):
+        assert np.array_equal(replay[0][6][j], replay[1][6][j]), 'replicas agree bitwise after the evaluation: table %d' % j
+        for r in range(2):
+            assert_close(replay[r][6][j], eager[r][6][j], 2e-5, 2e-6, 'table %d after the evaluation: replayed vs eager data parallelism' % j)
+        for res, what in ((eager, 'eager'), (replay, 'replayed')):
+            before, after = res[0][5][j].astype(np.float64), res[0][6][j].astype(np.float64)
+            hit = np.union1d(res[0][7][:, j], res[1][7][:, j])                 # rows either rank's evaluation batch looks up
+            rest = np.setdiff1d(np.arange(before.shape[0]), hit)
+            assert hit.size > 0 and rest.size > 0 and (np.linalg.norm(before[hit], axis=1) > max_norm * (1 + 1e-3)).all()
+            norms = np.linalg.norm(after[hit], axis=1)
+            assert (norms <= max_norm * (1 + 1e-6)).all(), '%s: table %d, looked-up rows %r keep norms %r > max_norm' % (
+                what, j, hit[norms > max_norm * (1 + 1e-6)].tolist(), norms[norms > max_norm * (1 + 1e-6)].tolist())
+            assert np.array_equal(after[rest], before[rest]), '%s: table %d, rows %r no rank looked up were changed' % (
+                what, j, rest[(after[rest] != before[rest]).any(1)].tolist())
