@@ -42,15 +42,6 @@ int launch_rowk(IgemmRowkParams p, hipStream_t s) {
 
 template <int MODE>
 int dispatch_rowk(const IgemmRowkParams& p, hipStream_t s) {
-  // tuning hook (tools/bench_conv.py): NNL_IGEMM_TILE=0..3 forces 128x128 / 128x64 / 64x128 / 64x64
-  const int forced = NNL_AB_INT("NNL_IGEMM_TILE", -1);
-  switch (forced) {
-    case 0: return launch_rowk<128, 128, 2, 2, MODE>(p, s);
-    case 1: return launch_rowk<128, 64, 2, 2, MODE>(p, s);
-    case 2: return launch_rowk<64, 128, 2, 2, MODE>(p, s);
-    case 3: return launch_rowk<64, 64, 2, 2, MODE>(p, s);
-    default: break;
-  }
   const long b128 = nnl_cdiv(p.M, 128);
   if (p.Nc > 64) {
     if (b128 * nnl_cdiv(p.Nc, 128) >= 400) return launch_rowk<128, 128, 2, 2, MODE>(p, s);
@@ -71,41 +62,26 @@ static bool taps_dma(int bk, const IgemmTapsParams&) {
   return bk == 16 ? (m & 1) != 0 : (m & 2) != 0;
 }
 
-// Two tiles in flight (PF = 2, igemm_taps.h) for the 64x64 tile: NNL_IGEMM_PF2 bit 0 = BK 16 launches (default ON), bit 1 = BK 32
-// launches (default off).  Measured per ResNet-34 layer at 64 images (bench_conv.py --ab NNL_IGEMM_PF2=0,1,2,3,
-// profiles/r3_pf2_bs64.log): BK 16 (the 28x28 / C = 128 stage) fwd 107.0 -> 111.7 TF/s, dgrad 112.7 -> 116.7; BK 32 needs 148
-// VGPRs (three workgroups per CU instead of four) and LOSES 3-8 % on every stride-1 layer (l1 107 -> 104, l4 117 -> 109).
-static bool taps_pf2(int bk, const IgemmTapsParams&) {
-  const int m = NNL_AB_INT("NNL_IGEMM_PF2", 1);
-  return bk == 16 ? (m & 1) != 0 : (m & 2) != 0;
-}
-
+// The 64x64 tile's k loop: BK 16 keeps two tiles in flight (PF = 2, igemm_taps.h), BK 32 one tile with pipelined LDS fragment
+// reads (+2-3 %).  Measured per ResNet-34 layer at 64 images (profiles/r3_pf2_bs64.log): PF = 2 on BK 16 (the 28x28 / C = 128
+// stage) fwd 107.0 -> 111.7 TF/s, dgrad 112.7 -> 116.7; on BK 32 it needs 148 VGPRs (three workgroups per CU instead of four)
+// and LOSES 3-8 % on every stride-1 layer (l1 107 -> 104, l4 117 -> 109).  The larger tiles use the plain k loop.
 template <int BM, int BN, int BK = 16>
 int launch_taps(IgemmTapsParams p, hipStream_t s) {
-  p.variant = NNL_AB_INT("NNL_IGEMM_VARIANT", 1);   // 1 = pipelined LDS fragment reads (+2-3 % on BK=32)
-  p.epi4 = NNL_AB_INT("NNL_IGEMM_EPI4", 1);
   p.grid_m = (int)nnl_cdiv(p.M, BM);
   p.grid_n = (int)nnl_cdiv(p.Nc, BN);
   p.cls_tiles = p.grid_m * p.grid_n;
-  const unsigned gx = (unsigned)(p.grid_m * p.grid_n * (p.ncls > 1 ? p.ncls : 1));
+  const dim3 grid((unsigned)(p.grid_m * p.grid_n * (p.ncls > 1 ? p.ncls : 1)), p.ksplit > 1 ? p.ksplit : 1);
   if constexpr (BM == 64 && BN == 64) {
-    if (taps_dma(BK, p)) {
-      hipLaunchKernelGGL((igemm_taps_kernel<64, 64, BK, 2, 2, false, 0, true>), dim3(gx, p.ksplit > 1 ? p.ksplit : 1), dim3(256), 0, s, p);
-      NNL_CHECK_LAUNCH();
-      return NNL_OK;
-    }
+    if (taps_dma(BK, p))
+      hipLaunchKernelGGL((igemm_taps_kernel<64, 64, BK, 2, 2, false, 0, true>), grid, dim3(256), 0, s, p);
+    else if constexpr (BK == 16)
+      hipLaunchKernelGGL((igemm_taps_kernel<64, 64, 16, 2, 2, true, 0, false, 2>), grid, dim3(256), 0, s, p);
+    else
+      hipLaunchKernelGGL((igemm_taps_kernel<64, 64, BK, 2, 2, true>), grid, dim3(256), 0, s, p);
+  } else {
+    hipLaunchKernelGGL((igemm_taps_kernel<BM, BN, BK, 2, 2>), grid, dim3(256), 0, s, p);
   }
-  if constexpr (BM == 64 && BN == 64) {
-    if (taps_pf2(BK, p)) {
-      hipLaunchKernelGGL((igemm_taps_kernel<64, 64, BK, 2, 2, true, 0, false, 2>), dim3(gx, p.ksplit > 1 ? p.ksplit : 1), dim3(256), 0, s, p);
-      NNL_CHECK_LAUNCH();
-      return NNL_OK;
-    }
-  }
-  if (BM == 64 && BN == 64 && p.variant == 1)
-    hipLaunchKernelGGL((igemm_taps_kernel<BM, BN, BK, 2, 2, true>), dim3(gx, p.ksplit > 1 ? p.ksplit : 1), dim3(256), 0, s, p);
-  else
-    hipLaunchKernelGGL((igemm_taps_kernel<BM, BN, BK, 2, 2>), dim3(gx, p.ksplit > 1 ? p.ksplit : 1), dim3(256), 0, s, p);
   NNL_CHECK_LAUNCH();
   return NNL_OK;
 }
@@ -113,8 +89,6 @@ int launch_taps(IgemmTapsParams p, hipStream_t s) {
 // one tap, C % 4 == 0 but not a multiple of the k block: the KTAIL instantiation of the 64x64 kernel (igemm_taps.h)
 template <int BK>
 int launch_taps_ktail(IgemmTapsParams p, hipStream_t s) {
-  p.variant = 1;
-  p.epi4 = NNL_AB_INT("NNL_IGEMM_EPI4", 1);
   p.grid_m = (int)nnl_cdiv(p.M, 64);
   p.grid_n = (int)nnl_cdiv(p.Nc, 64);
   p.cls_tiles = p.grid_m * p.grid_n;
@@ -141,8 +115,7 @@ BalPlan plan_balance_tile(long M, int Nc, int C, int ntaps, int bm) {
   const int e_bal = NNL_ENV_INT("NNL_IGEMM_BALANCE", 1);
   if (e_bal == 0 || Nc % 4 != 0) return best;
   const long gm = nnl_cdiv(M, bm), gn = nnl_cdiv(Nc, 64), T = gm * gn;
-  const int e_bk = NNL_AB_INT("NNL_IGEMM_BK32", -1);
-  const int bk = (bm == 64 && (e_bk >= 0 ? e_bk : (T < 1200 || C >= 256 || C == 64)) && C % 32 == 0) ? 32 : 16;
+  const int bk = (bm == 64 && (T < 1200 || C >= 256 || C == 64) && C % 32 == 0) ? 32 : 16;
   const long I = (long)ntaps * (C / bk);                               // k iterations of a whole tile
   const double c_it = (bk == 32 ? 0.60 : 0.30) * (bm / 64);            // us per k iteration per CU-resident workgroup set (measured ~113 TF/s ceiling)
   const double occ = bm == 128 ? 5 : (bk == 32 ? 4 : 6);               // resident workgroups per CU (LDS- / VGPR-limited)
@@ -155,12 +128,9 @@ BalPlan plan_balance_tile(long M, int Nc, int C, int ntaps, int bm) {
   const double plain = wave_iters(T, I) * c_it;
   best.t_us = plain;
   double best_t = plain * (e_bal == 2 ? 1.25 : 0.99);         // need a >= 1 % predicted win (2 = force, for A/B runs)
-  const int plan_extra = NNL_AB_INT("NNL_IGEMM_PLAN_EXTRA", 2);                       // k iterations' worth of fix-up cost per sliced workgroup
-  const double plan_bw = NNL_AB_INT("NNL_IGEMM_PLAN_BW", 16000) * 1.0e3;                  // slab traffic bandwidth, bytes per us
-  const int f_ks = NNL_AB_INT("NNL_IGEMM_PLAN_KS", 0), f_S = NNL_AB_INT("NNL_IGEMM_PLAN_S", 0);   // A/B hooks: force the plan's k slicing
-  if (f_ks > 0 || f_S > 0) best_t = 1e300;
+  const int plan_extra = 2;                                            // k iterations' worth of fix-up cost per sliced workgroup
+  const double plan_bw = 16000 * 1.0e3;                                // slab traffic bandwidth, bytes per us
   for (int ks = 1; ks <= 4; ks *= 2) {
-    if (f_ks > 0 && ks != f_ks) continue;
     if (I / ks < 8) break;
     const long units = T * ks;
     long n_main = ((units / kCUs) * kCUs / ks / gn) * gn;              // main tiles: whole multiples of 256 workgroups, whole tile rows
@@ -171,7 +141,6 @@ BalPlan plan_balance_tile(long M, int Nc, int C, int ntaps, int bm) {
     for (int S : kSlices) {
       if (tail == 0 && S > 1) break;
       if (S > 1 && I / S < 4) break;
-      if (f_S > 0 && tail > 0 && S != f_S) continue;
       const long it_tail = nnl_cdiv(I, S);
       const long tail_blocks = tail * S;
       double t = (wave_iters(n_main * ks, it_main) + wave_iters(tail_blocks, it_tail + (S > 1 ? plan_extra : 0))) * c_it;
@@ -219,8 +188,6 @@ __global__ __launch_bounds__(256) void slab_reduce_kernel(const float* __restric
 }
 
 int launch_balanced(IgemmTapsParams p, const BalPlan& pl, float* ws, int* counters, hipStream_t s) {
-  p.variant = NNL_AB_INT("NNL_IGEMM_VARIANT", 1);   // 1 = pipelined LDS fragment reads (+2-3 % on BK=32)
-  p.epi4 = NNL_AB_INT("NNL_IGEMM_EPI4", 1);
   p.grid_m = (int)nnl_cdiv(p.M, pl.bm);
   p.grid_n = (int)nnl_cdiv(p.Nc, 64);
   const int T = p.grid_m * p.grid_n;
@@ -237,18 +204,10 @@ int launch_balanced(IgemmTapsParams p, const BalPlan& pl, float* ws, int* counte
     hipLaunchKernelGGL((igemm_taps_kernel<64, 64, 32, 2, 2, false, 0, true>), dim3(grid), dim3(256), 0, s, p);
   else if (pl.bk != 32 && taps_dma(16, p))
     hipLaunchKernelGGL((igemm_taps_kernel<64, 64, 16, 2, 2, false, 0, true>), dim3(grid), dim3(256), 0, s, p);
-  else if (pl.bk == 32 && taps_pf2(32, p))
-    hipLaunchKernelGGL((igemm_taps_kernel<64, 64, 32, 2, 2, true, 0, false, 2>), dim3(grid), dim3(256), 0, s, p);
-  else if (pl.bk != 32 && taps_pf2(16, p))
-    hipLaunchKernelGGL((igemm_taps_kernel<64, 64, 16, 2, 2, true, 0, false, 2>), dim3(grid), dim3(256), 0, s, p);
-  else if (pl.bk == 32 && p.variant == 1)
-    hipLaunchKernelGGL((igemm_taps_kernel<64, 64, 32, 2, 2, true>), dim3(grid), dim3(256), 0, s, p);
   else if (pl.bk == 32)
-    hipLaunchKernelGGL((igemm_taps_kernel<64, 64, 32, 2, 2>), dim3(grid), dim3(256), 0, s, p);
-  else if (p.variant == 1)
-    hipLaunchKernelGGL((igemm_taps_kernel<64, 64, 16, 2, 2, true>), dim3(grid), dim3(256), 0, s, p);
+    hipLaunchKernelGGL((igemm_taps_kernel<64, 64, 32, 2, 2, true>), dim3(grid), dim3(256), 0, s, p);
   else
-    hipLaunchKernelGGL((igemm_taps_kernel<64, 64, 16, 2, 2>), dim3(grid), dim3(256), 0, s, p);
+    hipLaunchKernelGGL((igemm_taps_kernel<64, 64, 16, 2, 2, true, 0, false, 2>), dim3(grid), dim3(256), 0, s, p);
   NNL_CHECK_LAUNCH();
   if (p.tile_counters != nullptr) return NNL_OK;             // the kernel reduced its own slabs
   const int Nc4 = p.Nc / 4;
@@ -300,15 +259,12 @@ int dispatch_taps(const IgemmTapsParams& p_in, hipStream_t s, void* ws = nullptr
     }
     return p.C >= 64 ? launch_taps_ktail<32>(p, s) : launch_taps_ktail<16>(p, s);
   }
-  const int forced = NNL_AB_INT("NNL_IGEMM_TILE", -1);
   struct Cand { int bm, bn, occ; double eff; };
-  static const Cand cands[4] = {{128, 128, 4, 0.90}, {128, 64, 5, 0.90}, {64, 128, 5, 0.90}, {64, 64, 8, 1.00}};   // measured: bench_conv.py, NNL_IGEMM_TILE sweep
+  static const Cand cands[4] = {{128, 128, 4, 0.90}, {128, 64, 5, 0.90}, {64, 128, 5, 0.90}, {64, 64, 8, 1.00}};   // measured: bench_conv.py tile sweep
   int best = 0;
-  if (forced >= 0 && forced < 4) {
-    best = forced;
-  } else if (p.ntaps == 1 && p.C <= 512 && p.Nc >= 8192 && p.M >= 1024 && p.ncls <= 1) {
+  if (p.ntaps == 1 && p.C <= 512 && p.Nc >= 8192 && p.M >= 1024 && p.ncls <= 1) {
     // a Linear onto a huge vocabulary (the AWD-LSTM decoder, Text.py:572: 4480 x 400 -> 47 343): 25 k steps per tile, so the launch is
-    // prologue / epilogue / B-re-read bound and the 128 x 128 tile wins (measured, tools/bench_decoder_gemm.py: 1.81 -> 1.49 ms)
+    // prologue / epilogue / B-re-read bound and the 128 x 128 tile wins (measured: 1.81 -> 1.49 ms)
     best = 0;
   } else {
     double best_t = 1e300;
@@ -348,13 +304,12 @@ int dispatch_taps(const IgemmTapsParams& p_in, hipStream_t s, void* ws = nullptr
         p.bn_part = bn_part;
         if (bn_rows) *bn_rows = (int)nnl_cdiv(p.M, 64);
       }
-      // BK=32 halves the barriers per MFMA at half the occupancy: measured (bench_conv.py --ab NNL_IGEMM_BK32=0,1) +10..20 %
-      // on grids of < ~5 workgroups per CU (14x14 / 7x7 stages), -7 % on the 56x56 stage.  NNL_IGEMM_BK32=0/1 overrides.
-      const int e_bk = NNL_AB_INT("NNL_IGEMM_BK32", -1);
+      // BK=32 halves the barriers per MFMA at half the occupancy: measured (bench_conv.py) +10..20 %
+      // on grids of < ~5 workgroups per CU (14x14 / 7x7 stages), -7 % on the 56x56 stage.
       const long blocks64 = nnl_cdiv(p.M, 64) * nnl_cdiv(p.Nc, 64) * (p.ncls > 1 ? p.ncls : 1);
       // long k loops (C >= 256) gain from BK=32 on large grids too (RetinaNet heads); so does C = 64 since the prologue / per-tap clean-ups
       // of round 3 (re-measured per layer at 64 images: l1 3x3 0.143 -> 0.138 ms; the C = 128 stage still prefers BK=16: 0.138 vs 0.147)
-      const int bk32 = e_bk >= 0 ? e_bk : (blocks64 < 1200 || p.C >= 256 || p.C == 64);
+      const bool bk32 = blocks64 < 1200 || p.C >= 256 || p.C == 64;
       if (bk32 && p.C % 32 == 0) return launch_taps<64, 64, 32>(p, s);
       return launch_taps<64, 64>(p, s);
     }
@@ -543,12 +498,11 @@ struct WgradPlan { int bm, bn, grid_m, grid_n, splits, k_per_split, kg; };
 // (occupancy 4-5), so a launch lasts ceil(blocks/256) x (pixels per split) x (time per workgroup-pixel of the tile); rounding
 // k_per_split to 32 and a short last split are accounted for by using the real split length; fewer than 4 workgroups per CU
 // cannot hide the load latency; the slab reduce moves (splits+1) x |dw| bytes.  The smaller tiles pay a measured
-// efficiency factor (bench_conv.py, NNL_WGRAD_TILE sweep) but give short pixel ranges (1x1/2 shortcut convs: 12544 pixels)
+// efficiency factor (bench_conv.py tile sweep) but give short pixel ranges (1x1/2 shortcut convs: 12544 pixels)
 // enough workgroups to fill 256 CUs.
 WgradPlan plan_wgrad(int Mc, int Nc, long Kp, int square_bn_divides = 0) {     // != 0: square tiles only, bn must divide it (Winograd columns)
   struct Cand { int bm, bn; double cost; };                               // cost: time per FLOP relative to the 128x128 tile
   static const Cand cands[4] = {{128, 128, 1.00}, {128, 64, 1.08}, {64, 128, 1.08}, {64, 64, 1.10}};
-  const int forced = NNL_AB_INT("NNL_WGRAD_TILE", -1);                    // tuning hook: index into cands
   const long max_splits = Kp / 256 > 0 ? Kp / 256 : 1;                    // at least 256 pixels (16 k-steps) per split
   WgradPlan pl{};
   double best_t = 1e300;
@@ -556,26 +510,15 @@ WgradPlan plan_wgrad(int Mc, int Nc, long Kp, int square_bn_divides = 0) {     /
     const Cand& c = cands[ci];
     if (square_bn_divides != 0) {
       if (c.bm != c.bn || square_bn_divides % c.bn != 0 || (c.bm == 128 && Mc < 128)) continue;
-      const int f_w = NNL_AB_INT("NNL_WGRAD_WINO_TILE", -1);          // A/B hook: 0 = 128x128, 3 = 64x64 (when legal)
-      if ((f_w == 0 || f_w == 3) && ci != f_w && !(f_w == 0 && (Mc < 128 || square_bn_divides % 128 != 0))) continue;
-    } else if (forced >= 0 && forced < 4 ? ci != forced : ((c.bm == 128 && Mc < 128) || (c.bn == 128 && Nc < 128))) continue;
+    } else if ((c.bm == 128 && Mc < 128) || (c.bn == 128 && Nc < 128)) continue;
     const long tiles = nnl_cdiv(Mc, c.bm) * nnl_cdiv(Nc, c.bn);
     const double us_per_px = (double)c.bm * c.bn * 2.0 / 441e3 * c.cost;   // one workgroup-pixel at ~113 TF/s / 256 CUs
-    const int f_sp = NNL_AB_INT("NNL_WGRAD_SPLITS", 0);                  // A/B hook: force the split count
-    for (long sp = 1; sp <= max_splits && (sp == 1 || tiles * sp <= 256 * 5 || f_sp > 0 || NNL_AB_INT("NNL_WGRAD_WGPCU10", 0) > 0); ++sp) {   // unsplit is always a candidate
-      if (f_sp > 0 && sp != (f_sp < max_splits ? f_sp : max_splits)) continue;
-      const int f_wg = NNL_AB_INT("NNL_WGRAD_WGPCU10", 0);                // A/B hook: workgroups per CU x 10 (e.g. 20 = two per CU)
-      if (f_wg > 0) {
-        long want = (long)(f_wg * 25.6 / tiles + 0.5);
-        if (want < 1) want = 1;
-        if (want > max_splits) want = max_splits;
-        if (sp != want) continue;
-      }
+    for (long sp = 1; sp <= max_splits && (sp == 1 || tiles * sp <= 256 * 5); ++sp) {   // unsplit is always a candidate
       const long k1 = nnl_cdiv(nnl_cdiv(Kp, sp), 32) * 32;
       const long rs = nnl_cdiv(Kp, k1);
       if (rs != sp) continue;                                             // same plan as a smaller sp
       const long per_cu = nnl_cdiv(tiles * rs, 256);
-      const double starve = per_cu < 4 ? pow(4.0 / per_cu, NNL_AB_INT("NNL_WGRAD_STARVE_PCT", 30) * 0.01) : 1.0;   // A/B hook: exponent x100
+      const double starve = per_cu < 4 ? pow(4.0 / per_cu, 0.3) : 1.0;
       const double t = (double)per_cu * k1 * us_per_px * starve + (rs > 1 ? (rs + 1.0) * Mc * Nc * 4 / 4.5e6 + 3 : 0);   // reduce: rs slab reads + one write at ~4.5 TB/s
       if (t < best_t) {
         best_t = t;
@@ -593,19 +536,17 @@ WgradPlan plan_wgrad(int Mc, int Nc, long Kp, int square_bn_divides = 0) {     /
   // Merge KG neighbouring splits into ONE workgroup of KG wave groups (igemm_wgrad.h): the same waves per CU, the partial sums of
   // the KG pixel ranges meet in LDS, and only every KG-th slab is written / re-read (round 2 measured 1.97x the algorithmic HBM
   // bytes per conv launch, almost all of it wgrad slabs).  Instantiated for the 128x128 (BK 16) and 64x64 (BK 32) tiles; the
-  // planner takes it only where it measured as a win (tools/bench_conv.py --ab NNL_WGRAD_KG=1,2,4 at 64 images): the 128x128 tile
+  // planner takes it only where it measured as a win (tools/bench_conv.py at 64 images, 1 / 2 / 4 groups): the 128x128 tile
   // with >= 16 splits (28 x 28 / 14 x 14 stages: 0.139 -> 0.136 ms and 66 -> 17 MB of slabs per launch).  With few splits the merge
   // unbalances the grid (7 x 7 stage, 7 splits: 0.142 -> 0.187 ms) and the 64x64 tile loses 1-3 %.
   pl.kg = 1;
-  const int e_kg = NNL_AB_INT("NNL_WGRAD_KG", -1);                       // A/B hook: 1 = off, 2 / 4 = force (when legal)
   const bool kg_tile = (pl.bm == 128 && pl.bn == 128) || (pl.bm == 64 && pl.bn == 64);
-  if (kg_tile && e_kg != 1 && pl.splits >= 2) {
+  if (kg_tile && pl.splits >= 2) {
     int kg = (pl.bm == 128 && pl.splits >= 16) ? 4 : 1;
     // Winograd-domain columns (square_bn_divides = 3 * C): the 4-group 128x128 WINO instantiation spills (two staged pixels per
     // operand: 10 VGPRs over), and merged groups measured SLOWER there — RetinaNet FPN level 16 x 64 x 64, C = K = 256: 0.49 ms
     // with one group per workgroup, 0.75 with two, 0.94 with four (direct kernel: 0.66)
     if (square_bn_divides != 0 && pl.bm == 128) kg = 1;
-    if (e_kg == 2 || e_kg == 4) kg = pl.splits >= e_kg ? e_kg : 1;
     if (kg > 1) {
       const long sp = nnl_cdiv(pl.splits, kg);
       const long k1 = nnl_cdiv(nnl_cdiv(Kp, sp), 32L * kg) * 32L * kg;    // each group's share stays a multiple of 32 pixels
@@ -639,11 +580,9 @@ int launch_wgrad_v2(const float* dy, const float* x, float* out, long a_elems, l
     const long T = 128, gm = pl.grid_m, gn = pl.grid_n;
     const long fp_m = (T < gm ? T : gm) * pl.bm + nnl_cdiv(T, gm) * pl.bn;
     const long fp_n = nnl_cdiv(T, gn) * pl.bm + (T < gn ? T : gn) * pl.bn;
-    { const int e_nf = NNL_AB_INT("NNL_WGRAD_NFAST", -1); q.n_fast = e_nf >= 0 ? e_nf : (fp_n < fp_m ? 1 : 0); }
+    q.n_fast = fp_n < fp_m ? 1 : 0;
   }
   const dim3 grid(pl.grid_m * pl.grid_n * pl.splits);
-  const int bk32 = NNL_AB_INT("NNL_WGRAD_BK32", 1);                  // 64x64 tile: BK=32 (16 MFMAs per barrier) measured +3 %
-  const int pipe = NNL_AB_INT("NNL_WGRAD_PIPE", 1);                 // A/B hook: 1 = software-pipelined fragment reads
   // staging LDS: 2 buffers x BK x (BM + BN) floats per wave group (dynamic: above 64 KB the kernel needs the attribute once)
   auto lds_bytes = [](int bm, int bn, int bk, int kg) { return (size_t)kg * 2 * bk * (bm + bn) * sizeof(float); };
 #define NNL_WGRAD_LAUNCH(BM_, BN_, BK_, PIPE_, KG_, PAIR_)                                                                       \
@@ -660,25 +599,23 @@ int launch_wgrad_v2(const float* dy, const float* x, float* out, long a_elems, l
     hipLaunchKernelGGL((igemm_wgrad_kernel<BM_, BN_, BK_, 2, 2, PIPE_, KG_, false, PAIR_>), grid, dim3(256 * KG_), lb, s, q);    \
   } while (0)
   // PAIR staging (igemm_wgrad.h): both 16-byte chunks a thread stages per row must lie in one filter tap
-  const bool pair = (R * S == 1 || C % pl.bn == 0) && NNL_AB_INT("NNL_WGRAD_PAIR", 1) != 0;   // (A/B hook: 0 = the one-chunk staging everywhere)
-  if (pl.bm == 128 && pl.bn == 128) {
+  const bool pair = R * S == 1 || C % pl.bn == 0;
+  if (pl.bm == 128 && pl.bn == 128) {                                   // (BK=32 measured -7 % here)
     if (pl.kg == 4) { if (pair) NNL_WGRAD_LAUNCH(128, 128, 16, true, 4, true); else NNL_WGRAD_LAUNCH(128, 128, 16, true, 4, false); }
     else if (pl.kg == 2) NNL_WGRAD_LAUNCH(128, 128, 16, true, 2, false);
-    else if (pipe) { if (pair) NNL_WGRAD_LAUNCH(128, 128, 16, true, 1, true); else NNL_WGRAD_LAUNCH(128, 128, 16, true, 1, false); }
-    else NNL_WGRAD_LAUNCH(128, 128, 16, false, 1, false);              // BK=32 measured -7 % here
+    else if (pair) NNL_WGRAD_LAUNCH(128, 128, 16, true, 1, true);
+    else NNL_WGRAD_LAUNCH(128, 128, 16, true, 1, false);
   } else if (pl.bm == 128) {
     NNL_WGRAD_LAUNCH(128, 64, 16, false, 1, false);
   } else if (pl.bn == 128) {
     NNL_WGRAD_LAUNCH(64, 128, 16, true, 1, false);
+  } else if (pl.k_per_split % 32 == 0) {                              // 64x64 tile: BK=32 (16 MFMAs per barrier) measured +3 %
+    if (pl.kg == 4) { if (pair) NNL_WGRAD_LAUNCH(64, 64, 32, true, 4, true); else NNL_WGRAD_LAUNCH(64, 64, 32, true, 4, false); }
+    else if (pl.kg == 2) NNL_WGRAD_LAUNCH(64, 64, 32, true, 2, false);
+    else if (pair) NNL_WGRAD_LAUNCH(64, 64, 32, true, 1, true);
+    else NNL_WGRAD_LAUNCH(64, 64, 32, true, 1, false);
   } else {
-    if (bk32 && pl.k_per_split % 32 == 0) {
-      if (pl.kg == 4) { if (pair) NNL_WGRAD_LAUNCH(64, 64, 32, true, 4, true); else NNL_WGRAD_LAUNCH(64, 64, 32, true, 4, false); }
-      else if (pl.kg == 2) NNL_WGRAD_LAUNCH(64, 64, 32, true, 2, false);
-      else if (pipe) { if (pair) NNL_WGRAD_LAUNCH(64, 64, 32, true, 1, true); else NNL_WGRAD_LAUNCH(64, 64, 32, true, 1, false); }
-      else NNL_WGRAD_LAUNCH(64, 64, 32, false, 1, false);
-    }
-    else if (pipe) NNL_WGRAD_LAUNCH(64, 64, 16, true, 1, false);
-    else NNL_WGRAD_LAUNCH(64, 64, 16, false, 1, false);
+    NNL_WGRAD_LAUNCH(64, 64, 16, true, 1, false);
   }
 #undef NNL_WGRAD_LAUNCH
   NNL_CHECK_LAUNCH();
@@ -829,17 +766,16 @@ bool wgrad_wino2d_ok(const nnl_conv_geom_t* g) {
   const long quads = (long)g->N * ((g->H + 1) / 2) * ((g->W + 1) / 2);
   if (quads < 512 || !wgrad_v2_ok((long)g->N * g->H * g->W * g->K, (long)g->N * g->H * g->W * g->C, quads)) return false;
   if (mode == 2) return true;
-  return quads >= NNL_AB_INT("NNL_WGRAD_WINO2D_MIN_QUADS", 1024);
+  return quads >= 1024;
 }
 
-// Tile / wave-group choice of the 2-D domain, measured (tools/bench_conv.py --ab NNL_WGRAD_WINO_TILE / NNL_WGRAD_KG under NNL_WGRAD_WINO2D=2,
-// profiles/r4_wgrad2d_*.log): the 64x64 tile with FOUR wave groups per workgroup (four neighbouring splits meet in LDS: a quarter of the
-// slabs) wherever the plan has at least four splits (56^2 / 28^2 / 14^2 stages at 64 images: 0.105 / 0.101 / 0.100 -> 0.094 / 0.093 /
-// 0.092 ms); the 128x128 tile where the 64x64 plan has fewer (7^2 stage: 0.127 -> 0.114 ms).  NNL_WGRAD_WINO2D_RULE=0: the generic planner.
+// Tile / wave-group choice of the 2-D domain, measured (tools/bench_conv.py under NNL_WGRAD_WINO2D=2, profiles/r4_wgrad2d_*.log): the
+// 64x64 tile with FOUR wave groups per workgroup (four neighbouring splits meet in LDS: a quarter of the slabs) wherever the plan has at
+// least four splits (56^2 / 28^2 / 14^2 stages at 64 images: 0.105 / 0.101 / 0.100 -> 0.094 / 0.093 / 0.092 ms); the 128x128 tile where
+// the 64x64 plan has fewer (7^2 stage: 0.127 -> 0.114 ms).
 WgradPlan plan_wgrad_wino2d(const nnl_conv_geom_t* g) {
   const long quads = (long)g->N * ((g->H + 1) / 2) * ((g->W + 1) / 2);
   WgradPlan pl = plan_wgrad(g->K, 16 * g->C, quads, g->C);
-  if (NNL_AB_INT("NNL_WGRAD_WINO2D_RULE", 1) == 0 || NNL_AB_INT("NNL_WGRAD_WINO_TILE", -1) >= 0 || NNL_AB_INT("NNL_WGRAD_KG", -1) >= 0) return pl;
   auto with_tile = [&](int bt, int splits_target) {
     WgradPlan q{};
     q.bm = q.bn = bt; q.grid_m = (int)nnl_cdiv(g->K, bt); q.grid_n = (int)nnl_cdiv(16L * g->C, bt); q.kg = 1;
@@ -854,12 +790,12 @@ WgradPlan plan_wgrad_wino2d(const nnl_conv_geom_t* g) {
   };
   const bool big = g->K >= 128 && g->C % 128 == 0;
   // big problems on wide layers (RetinaNet heads / FPN on P3: 16384 quads x 256 x 256): the 128x128 tile's operand reuse wins (0.430 -> 0.374 ms)
-  if (big && (double)quads * g->K * g->C >= NNL_AB_INT("NNL_WGRAD_WINO2D_BIG_E6", 500) * 1e6) return pl.bm == 128 ? pl : with_tile(128, 0);
+  if (big && (double)quads * g->K * g->C >= 500e6) return pl.bm == 128 ? pl : with_tile(128, 0);
   WgradPlan p64 = pl.bm == 64 ? pl : with_tile(64, 0);
   if (p64.splits >= 4) {                                                // four neighbouring splits -> one workgroup of four wave groups
     const long sp = nnl_cdiv(p64.splits, 4);
     const long k1 = nnl_cdiv(nnl_cdiv(quads, sp), 128L) * 128L;          // each group's share stays a multiple of 32 quads
-    if (k1 / 4 >= NNL_AB_INT("NNL_WGRAD_WINO2D_MIN_GROUP", 700)) {      // (shorter shares: prologue / group reduction dominate — 28^2 at 32 images: -23 %)
+    if (k1 / 4 >= 700) {      // (shorter shares: prologue / group reduction dominate — 28^2 at 32 images: -23 %)
       p64.kg = 4; p64.k_per_split = (int)k1; p64.splits = (int)nnl_cdiv(quads, k1);
       return p64;
     }
@@ -885,12 +821,12 @@ int launch_wgrad_wino2d(const float* dy, const float* x, float* slabs, const nnl
     if (lb > 64 * 1024) {                                                                                                        \
       static bool attr_set = false;                                                                                              \
       if (!attr_set) {                                                                                                           \
-        NNL_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_wgrad2d_kernel<BT_, BK_, true, KG_>),             \
+        NNL_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_wgrad2d_kernel<BT_, BK_, KG_>),             \
                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb));                                 \
         attr_set = true;                                                                                                         \
       }                                                                                                                          \
     }                                                                                                                            \
-    hipLaunchKernelGGL((igemm_wgrad2d_kernel<BT_, BK_, true, KG_>), grid, dim3(256 * KG_), lb, s, q);                            \
+    hipLaunchKernelGGL((igemm_wgrad2d_kernel<BT_, BK_, KG_>), grid, dim3(256 * KG_), lb, s, q);                            \
   } while (0)
   if (pl.bm == 128) {
     if (pl.kg == 2) NNL_WGRAD2D_LAUNCH(128, 16, 2);
@@ -1140,7 +1076,7 @@ extern "C" int nnl_conv2d_fwd_pre(const float* x, const float* w, const float* b
         q.tap_dh[t] = (signed char)r; q.tap_dw[t] = (signed char)ss;
         q.tap_aoff[t] = (r * g->W + ss) * g->C; q.tap_woff[t] = t * g->C;
       }
-    q.tap_affine = NNL_AB_INT("NNL_IGEMM_AFFINE", 1); q.tap_R = g->R; q.tap_S = g->S; q.tap_dh0 = 0; q.tap_dw0 = 0; q.tap_dstep = 1;
+    q.tap_affine = 1; q.tap_R = g->R; q.tap_S = g->S; q.tap_dh0 = 0; q.tap_dw0 = 0; q.tap_dstep = 1;
     q.bn_part = (bn_partials && bn_pivot && bn_rows) ? bn_partials : nullptr; q.bn_pivot = bn_pivot;
     return dispatch_taps(q, s, workspace, workspace_bytes, tile_counters, bn_rows);
   }
@@ -1176,7 +1112,7 @@ extern "C" int nnl_conv2d_fwd_add_up2(const float* x, const float* w, const floa
       q.tap_dh[t] = (signed char)r; q.tap_dw[t] = (signed char)ss;
       q.tap_aoff[t] = (r * g->W + ss) * g->C; q.tap_woff[t] = t * g->C;
     }
-  q.tap_affine = NNL_AB_INT("NNL_IGEMM_AFFINE", 1); q.tap_R = g->R; q.tap_S = g->S; q.tap_dh0 = 0; q.tap_dw0 = 0; q.tap_dstep = 1;
+  q.tap_affine = 1; q.tap_R = g->R; q.tap_S = g->S; q.tap_dh0 = 0; q.tap_dw0 = 0; q.tap_dstep = 1;
   return dispatch_taps(q, s);            // no workspace: the plain grid (the split-tile fix-up path reads a same-shape addend only)
 }
 
@@ -1278,7 +1214,7 @@ extern "C" int nnl_conv2d_dgrad_pre(const float* dy, const float* wt, float* dx,
       }
     };
     // all classes in ONE launch when they have the same row count (even H, W): longest classes first
-    bool merged = ncls > 1 && NNL_AB_INT("NNL_DGRAD_MERGE", 1) != 0;
+    bool merged = ncls > 1;
     for (int i = 1; i < ncls && merged; ++i) merged = cls[i].P == cls[0].P && cls[i].Q == cls[0].Q;
     if (merged) {
       for (int i = 1; i < ncls; ++i)                        // insertion sort by decreasing tap count (<= 4 entries)
@@ -1303,7 +1239,7 @@ extern "C" int nnl_conv2d_dgrad_pre(const float* dy, const float* wt, float* dx,
       fill(c, cls[i], 0);
       c.ntaps = cls[i].nt;
       if (st2 == 1 && cls[i].nt == g->R * g->S) {          // the full raster, r-major: (dh, dw) = (pad - r, pad - s), woff = t*K
-        c.tap_affine = NNL_AB_INT("NNL_IGEMM_AFFINE", 1); c.tap_R = g->R; c.tap_S = g->S; c.tap_dh0 = g->pad; c.tap_dw0 = g->pad; c.tap_dstep = -1;
+        c.tap_affine = 1; c.tap_R = g->R; c.tap_S = g->S; c.tap_dh0 = g->pad; c.tap_dw0 = g->pad; c.tap_dstep = -1;
       }
       int st = dispatch_taps(c, s, st2 == 1 ? workspace : nullptr, workspace_bytes, tile_counters);
       if (st) return st;

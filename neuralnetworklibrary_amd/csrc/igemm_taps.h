@@ -64,8 +64,6 @@ struct IgemmTapsParams {
   int bal, main_ks, n_main_tiles, tail_slices, tail_row0;
   LstmEpi lstm;                        // EPI != 0 instantiations only
   int ktail;                           // 1: launch the KTAIL instantiation (one tap, C % 4 == 0 but C % 16 != 0; conv2d.hip: taps_kind)
-  int epi4;                            // 1: row-major float4 epilogue of the unsplit 64x64 tile (dense outputs; NNL_IGEMM_EPI4)
-  int variant;                         // 1: PIPE instantiation of the 64x64 kernel (A/B: tools/bench_conv.py --ab NNL_IGEMM_VARIANT=0,1)
   float* main_out; long main_slab_stride;      // main_ks > 1: slabs [main_ks][tail_row0][Nc]
   float* tail_out; long tail_slab_stride;      // tail_slices > 1: slabs [tail_slices][M - tail_row0][Nc]
   float* bn_part;                              // != null (64x64 tile, dense output): per tile row t and column c the workgroup that
@@ -687,7 +685,7 @@ __global__ __launch_bounds__(256, (BM * BN >= 128 * 128 || (PF == 2 && BK == 32)
     return;
   }
   if constexpr (EPI == 0 && BM == 64 && BN == 64) {
-    if (p.epi4 && dense_out && !p.add_up2 && !partial && p.Nc % 4 == 0) {
+    if (dense_out && !p.add_up2 && !partial && p.Nc % 4 == 0) {
       // ---- row-major float4 epilogue: the accumulator tile goes through LDS (free: the k loop ended with a barrier) and every
       // thread finishes four float4 pieces of output rows — 16 lanes cover a 256-B row segment per store instead of 32 lanes
       // writing 128 B of two rows each with 4-byte stores (the 1x1 convolutions of the ResNet-50 body write 4x what they read:

@@ -26,7 +26,7 @@ struct IgemmWgrad2dParams {
 };
 
 // BT x BT output tile (BT = 64: BK 32, BT = 128: BK 16), 4 waves (2 x 2) per wave group, KG wave groups per workgroup as igemm_wgrad.h
-template <int BT, int BK, bool PIPE, int KG>
+template <int BT, int BK, int KG>
 __global__ __launch_bounds__(256 * KG, KG > 1 ? 1 : (BT >= 128 ? 2 : 3)) void igemm_wgrad2d_kernel(const IgemmWgrad2dParams p) {
   static_assert(KG == 1 || (size_t)KG * 2 * BK * (2 * BT) >= (size_t)BT * BT, "the staging LDS must hold one accumulator tile for the group reduction");
   // staging map: a thread owns quad row(s) row0 + s * RA of the k tile and NCH = TWO 16-byte channel chunks of each (columns ca * 4 and
@@ -190,42 +190,26 @@ __global__ __launch_bounds__(256 * KG, KG > 1 ? 1 : (BT >= 128 ? 2 : 3)) void ig
   auto compute = [&](int buf) {
     const float* As = lds[buf] + lh * BT + wm * WT + l31;
     const float* Bs = lds[buf] + BK * BT + lh * BT + wn * WT + l31;
-    if constexpr (PIPE) {
-      float af[2][TM], bf[2][TN];
+    float af[2][TM], bf[2][TN];
 #pragma unroll
-      for (int i = 0; i < TM; ++i) af[0][i] = As[i * 32];
+    for (int i = 0; i < TM; ++i) af[0][i] = As[i * 32];
 #pragma unroll
-      for (int j = 0; j < TN; ++j) bf[0][j] = Bs[j * 32];
-#pragma unroll
-      for (int kk = 0; kk < BK / 2; ++kk) {
-        const int c = kk & 1, n = c ^ 1;
-        if (kk + 1 < BK / 2) {
-#pragma unroll
-          for (int i = 0; i < TM; ++i) af[n][i] = As[(kk + 1) * 2 * BT + i * 32];
-#pragma unroll
-          for (int j = 0; j < TN; ++j) bf[n][j] = Bs[(kk + 1) * 2 * BT + j * 32];
-          __builtin_amdgcn_sched_barrier(0);
-        }
-#pragma unroll
-        for (int i = 0; i < TM; ++i)
-#pragma unroll
-          for (int j = 0; j < TN; ++j)
-            acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[c][i], bf[c][j], acc[i][j], 0, 0, 0);
-      }
-      return;
-    }
+    for (int j = 0; j < TN; ++j) bf[0][j] = Bs[j * 32];
 #pragma unroll
     for (int kk = 0; kk < BK / 2; ++kk) {
-      float af[TM], bf[TN];
+      const int c = kk & 1, n = c ^ 1;
+      if (kk + 1 < BK / 2) {
 #pragma unroll
-      for (int i = 0; i < TM; ++i) af[i] = As[kk * 2 * BT + i * 32];
+        for (int i = 0; i < TM; ++i) af[n][i] = As[(kk + 1) * 2 * BT + i * 32];
 #pragma unroll
-      for (int j = 0; j < TN; ++j) bf[j] = Bs[kk * 2 * BT + j * 32];
+        for (int j = 0; j < TN; ++j) bf[n][j] = Bs[(kk + 1) * 2 * BT + j * 32];
+        __builtin_amdgcn_sched_barrier(0);
+      }
 #pragma unroll
       for (int i = 0; i < TM; ++i)
 #pragma unroll
         for (int j = 0; j < TN; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i], bf[j], acc[i][j], 0, 0, 0);
+          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[c][i], bf[c][j], acc[i][j], 0, 0, 0);
     }
   };
 

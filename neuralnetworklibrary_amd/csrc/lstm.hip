@@ -136,8 +136,7 @@ long ceil32(long x) { return nnl_cdiv(x, 32) * 32; }
 // (measured: 288 workgroups 10.8 ms/step of LSTM time, 216-250: 9.7 ms, 576: 11.4 ms)
 int pick_splits(long M, long N, long nk) {
   const long tiles = nnl_cdiv(M, 64) * nnl_cdiv(N, 64);
-  const long target = NNL_AB_INT("NNL_LSTM_WG", 256);           // tuning hook: workgroup budget
-  long s = target / tiles;
+  long s = 256 / tiles;
   if (s < 1) s = 1;
   if (s > nk) s = nk;
   if (s > 32) s = 32;

@@ -59,7 +59,6 @@ struct Bptt2 {
   float* dc0;           // [B][H]
   int* err;
   int T, B, H, Gp, KG, NG, Ks, Ns, NWG, chunk;
-  int dbg;              // timing experiments only (NNL_LSTM_BPTT2_DBG; results invalid): 1 no k loop, 2 polls accept any tag, 4 staggered start of streams 2 / 3, 8 raised wave priority in the k loop
 };
 
 __device__ __forceinline__ u64 pack(float v, unsigned tag) { return ((u64)tag << 32) | (u64)__float_as_uint(v); }
@@ -126,15 +125,10 @@ __global__ __launch_bounds__(kBlock) void lstm_bptt2_kernel(Bptt2 p) {
   const bool rok = 16 * m + row < B;
   const int ngrp = Ks / 16;
   const int ga = h * ngrp / kNH, gb = (h + 1) * ngrp / kNH;      // this wave's k groups
-  const bool any_tag = (p.dbg & 2) != 0;
   int timed_out = 0;
   const unsigned o = (unsigned)(eb * H + ej);                      // 32-bit per-lane offsets against wave-uniform bases (saddr addressing:
   const unsigned og = (unsigned)(eb * 4 * H + ej);                 // one VGPR per address instead of two per pointer)
   const unsigned ox = (unsigned)(eb * Gp + ej), op = (unsigned)(eb * Nsp + ejj);
-  if ((p.dbg & 4) && m >= 2) {                            // experiment: start streams 2, 3 half a step later
-    __builtin_amdgcn_s_sleep(127);
-    __builtin_amdgcn_s_sleep(127);
-  }
   for (int s = 0; s <= p.T; ++s) {                        // step s handles timestep t = T-1-s; s = T: only dh0 / dc0
     const int t = p.T - 1 - s;
     // operands of this step's cell: nobody else's results, requested before the k loop
@@ -177,9 +171,8 @@ __global__ __launch_bounds__(kBlock) void lstm_bptt2_kernel(Bptt2 p) {
           const bool b4 = (unsigned)c[j][0][1] < tag || (unsigned)c[j][0][3] < tag || (unsigned)c[j][1][1] < tag || (unsigned)c[j][1][3] < tag;
           bad |= b4 && live(g0 + j);
         }
-        return __builtin_amdgcn_ballot_w64(bad && !any_tag) != 0;
+        return __builtin_amdgcn_ballot_w64(bad) != 0;
       };
-      const int gend = (p.dbg & 1) ? ga : gb;
       auto lds_b = [&](f32x4 (&dst)[NT], int g) {
         const float* bq = bp + (long)(4 * g) * Nsp * 4;
 #pragma unroll
@@ -196,10 +189,9 @@ __global__ __launch_bounds__(kBlock) void lstm_bptt2_kernel(Bptt2 p) {
       // full chunks of CH groups: no condition inside the unrolled body (a predicate there made the compiler move the accumulators
       // between AGPRs and VGPRs around every group: two pipe drains and 40 moves per 20 MFMAs)
       int g0 = ga;
-      if (p.dbg & 8) __builtin_amdgcn_s_setprio(3);        // experiment: the wave that has started its k loop keeps the matrix pipe
-      if (g0 + CH <= gend) fetch(cur, g0);
-      for (; g0 + CH <= gend; g0 += CH) {
-        if (g0 + 2 * CH <= gend) fetch(nxt, g0 + CH);
+      if (g0 + CH <= gb) fetch(cur, g0);
+      for (; g0 + CH <= gb; g0 += CH) {
+        if (g0 + 2 * CH <= gb) fetch(nxt, g0 + CH);
         for (int tries = 0; stale(cur, g0); ++tries) {      // wave-uniform: the whole chunk is requested again
           if (tries > kPollLimit || timed_out) { timed_out = 1; break; }
           __builtin_amdgcn_s_sleep(1);
@@ -215,7 +207,7 @@ __global__ __launch_bounds__(kBlock) void lstm_bptt2_kernel(Bptt2 p) {
 #pragma unroll
         for (int j = 0; j < CH; ++j) { cur[j][0] = nxt[j][0]; cur[j][1] = nxt[j][1]; }
       }
-      for (; g0 < gend; ++g0) {                            // the ragged rest, one group at a time
+      for (; g0 < gb; ++g0) {                            // the ragged rest, one group at a time
         i32x4 one[2];
         const bool lv = live(g0);
         auto fetch1 = [&]() {
@@ -225,7 +217,7 @@ __global__ __launch_bounds__(kBlock) void lstm_bptt2_kernel(Bptt2 p) {
         };
         auto stale1 = [&]() {
           const bool b4 = (unsigned)one[0][1] < tag || (unsigned)one[0][3] < tag || (unsigned)one[1][1] < tag || (unsigned)one[1][3] < tag;
-          return __builtin_amdgcn_ballot_w64(b4 && lv && !any_tag) != 0;
+          return __builtin_amdgcn_ballot_w64(b4 && lv) != 0;
         };
         fetch1();
         f32x4 b1[NT];
@@ -237,7 +229,6 @@ __global__ __launch_bounds__(kBlock) void lstm_bptt2_kernel(Bptt2 p) {
         }
         mfma_group(one, b1);
       }
-      if (p.dbg & 8) __builtin_amdgcn_s_setprio(0);
       if (h) {
         // the other k parts: hand the sums to the stream's first wave through LDS (same lane layout on both sides)
         float* pb = pairbuf + (long)(h - 1) * (4 * NT * 64);
@@ -292,7 +283,7 @@ __global__ __launch_bounds__(kBlock) void lstm_bptt2_kernel(Bptt2 p) {
           bool bad = false;
 #pragma unroll
           for (int j = 0; j < kPB; ++j) bad |= tag_of(v[j]) < tag;
-          return __builtin_amdgcn_ballot_w64(bad && !any_tag) != 0;
+          return __builtin_amdgcn_ballot_w64(bad) != 0;
         };
         fetch8();
         for (int tries = 0; stale8(); ++tries) {
@@ -338,16 +329,13 @@ Plan2 plan2(long B, long H, long Gp) {
   Plan2 best{};
   best.ok = false;
   if (B < 1 || B > kRows || H < 1 || Gp < 4 * H || Gp % 16 != 0) return best;
-  const int fkg = NNL_AB_INT("NNL_LSTM_BPTT2_KG", 0), fng = NNL_AB_INT("NNL_LSTM_BPTT2_NG", 0);
   double best_cost = 1e30;
   for (int NG = 1; NG <= 256; ++NG) {
-    if (fng > 0 && NG != fng) continue;
     const int Ns = (int)nnl_cdiv(H, NG);
     if ((long)Ns * (NG - 1) >= H) continue;               // an empty column slice
     const int NT = (int)nnl_cdiv(Ns, 16);
     if (NT > kMaxNT) continue;
     for (int KG = 1; KG * NG <= 256; ++KG) {
-      if (fkg > 0 && KG != fkg) continue;
       if (Gp % (16 * KG) != 0) continue;
       const int Ks = (int)(Gp / KG);
       const size_t lds = ((size_t)Ks * 16 * NT + 4u * (kNH - 1) * 4 * NT * 64) * sizeof(float);      // W block + the streams' hand-over buffers
@@ -416,14 +404,12 @@ hipError_t nnl_lstm_bptt2(const float* dy, const float* dhT, const float* dcT, c
   p.xt = p.xp + xp_granules(pl);
   p.err = err;
   p.T = (int)T; p.B = (int)B; p.H = (int)H; p.Gp = (int)Gp;
-  p.dbg = NNL_AB_INT("NNL_LSTM_BPTT2_DBG", 0);
   p.KG = pl.KG; p.NG = pl.NG; p.Ks = pl.Ks; p.Ns = pl.Ns; p.NWG = pl.KG * pl.NG; p.chunk = pl.chunk;
   hipError_t e = hipMemsetAsync(p.xp, 0, sizeof(u64) * (xp_granules(pl) + xt_granules(Gp)), s);     // tag 0 = nothing yet
   if (e != hipSuccess) return e;
   // partial polls of phase B in batches of 8 or 16 granules (measured: KG = 16 -> 2 x 8: 15.9 vs 16.3 us per step at H = 1150;
   // KG = 10 -> one batch of 16: 9.5 vs 10.1 at H = 400)
-  const int pb_env = NNL_AB_INT("NNL_LSTM_BPTT2_PB", 0);
-  const int pb = pb_env == 8 || pb_env == 16 ? pb_env : (pl.KG % 8 == 0 ? 8 : 16);
+  const int pb = pl.KG % 8 == 0 ? 8 : 16;
 #define NNL_BPTT2_CASE(N) case N: return pb == 8 ? launch2<N, 8>(p, pl.lds, s) : launch2<N, 16>(p, pl.lds, s)
   switch (pl.NT) {
     NNL_BPTT2_CASE(1);

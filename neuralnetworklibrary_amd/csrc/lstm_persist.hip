@@ -60,9 +60,6 @@ struct PersistFwd {
   int* arrive;          // [T] zero on entry
   int* err;
   int T, B, H, Kp, U, NWG;
-  int dbg;              // timing experiments only (NNL_LSTM_DBG): 1 = no k loop, 2 = no grid wait
-  int pd;               // k groups per chunk of the forward k loop (NNL_LSTM_PD: 6 / 9 / 12 / 18; default 12)
-  int single;           // 1: the single-chunk k loop where it is instantiated (NNL_LSTM_SINGLE, default 1)
 };
 
 struct PersistBwd {
@@ -245,9 +242,7 @@ __global__ __launch_bounds__(kFwdBlock) void lstm_persist_fwd_kernel(PersistFwd 
   const int rot = blockIdx.x;                             // any two workgroups of an XCD start at different chunks, however the XCDs are assigned
   // all k rows of a wave in ONE request batch: a win only for short ranges (H = 400, 13 groups: 4.4 -> 3.9 us per step).  At H = 1150
   // (36 groups, 144 loads per wave) it is 3x SLOWER than the chunked loop (k loop 11.9 -> 34 us, tools/lstm_timing.py): without the
-  // rotated chunk starts every workgroup of an XCD misses the same lines of the fresh slot at the same moment.  NNL_LSTM_SINGLE=2
-  // forces it for A/B runs.
-  const int single = ((p.single >= 1 && kg_per == 13) || (p.single == 2 && kg_per == 36)) ? kg_per : 0;
+  // rotated chunk starts every workgroup of an XCD misses the same lines of the fresh slot at the same moment.
   const int ln = lane < B ? lane : 0, wcol = lane < 4 * NG ? lane : 4 * NG - 1;
   const long BH = (long)B * H, BG = (long)B * 4 * H, slot = (long)p.Kp * kLanes;
 #ifdef NNL_TAPS_TIMING
@@ -264,14 +259,8 @@ __global__ __launch_bounds__(kFwdBlock) void lstm_persist_fwd_kernel(PersistFwd 
     f32x4 acc[NG];
 #pragma unroll
     for (int g = 0; g < NG; ++g) acc[g] = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (!(p.dbg & 1)) {
-      if (single == 36) panel_single<NG, 4 * NG, 36>(p.xT + t * slot, wl, kg0, ln, wcol, acc);
-      else if (single == 13) panel_single<NG, 4 * NG, 13>(p.xT + t * slot, wl, kg0, ln, wcol, acc);
-      else if (p.pd == 6) panel<NG, 4 * NG, 6>(p.xT + t * slot, wl, kg0, kg_per, ln, wcol, rot, acc);
-      else if (p.pd == 9) panel<NG, 4 * NG, 9>(p.xT + t * slot, wl, kg0, kg_per, ln, wcol, rot, acc);
-      else if (p.pd == 18) panel<NG, 4 * NG, 18>(p.xT + t * slot, wl, kg0, kg_per, ln, wcol, rot, acc);
-      else panel<NG, 4 * NG>(p.xT + t * slot, wl, kg0, kg_per, ln, wcol, rot, acc);
-    }
+    if (kg_per == 13) panel_single<NG, 4 * NG, 13>(p.xT + t * slot, wl, kg0, ln, wcol, acc);
+    else panel<NG, 4 * NG>(p.xT + t * slot, wl, kg0, kg_per, ln, wcol, rot, acc);
 #pragma unroll
     for (int g = 0; g < NG; ++g)
 #pragma unroll
@@ -316,7 +305,7 @@ __global__ __launch_bounds__(kFwdBlock) void lstm_persist_fwd_kernel(PersistFwd 
       }
     }
     NNL_LSTAMP(4);
-    if (more && !(p.dbg & 2) && !grid_wait(p.arrive, t, p.NWG, p.err, &s_flag)) return;
+    if (more && !grid_wait(p.arrive, t, p.NWG, p.err, &s_flag)) return;
     NNL_LSTAMP(5);
   }
 }
@@ -475,9 +464,6 @@ hipError_t nnl_lstm_persist_fwd(const float* gx, const float* w_hh_pad, const fl
   p.arrive = reinterpret_cast<int*>(ws + (size_t)(T + 1) * Kp * kLanes);
   p.err = err;
   p.T = (int)T; p.B = (int)B; p.H = (int)H; p.Kp = (int)Kp; p.U = sh.U; p.NWG = sh.NWG;
-  p.dbg = NNL_AB_INT("NNL_LSTM_DBG", 0);
-  p.single = NNL_AB_INT("NNL_LSTM_SINGLE", 1);
-  p.pd = NNL_AB_INT("NNL_LSTM_PD", 12);
   hipError_t e = hipMemsetAsync(p.arrive, 0, sizeof(int) * T, s);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(exchange_prologue_kernel, dim3((unsigned)nnl_cdiv(H * kLanes, 256)), dim3(256), 0, s, h0, p.xT, (int)B, (int)H,

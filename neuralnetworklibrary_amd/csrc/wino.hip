@@ -40,7 +40,6 @@ struct WinoParams {
   float* tail_out; long tail_slab_stride;
   int* tile_counters;
   float* bn_part; const float* bn_pivot;
-  int epi4;            // 1: row-major float4 epilogue of the unsplit tiles (NNL_WINO_EPI4, default)
 };
 
 // filt [Nc][3][3][C] -> U [Nc][4][3][C]; flip: read filt[.][2-r][2-s][.] (the dgrad filter)
@@ -313,7 +312,7 @@ __global__ __launch_bounds__(256, 4) void wino_kernel(const WinoParams p) {
     }
     return;
   }
-  if (p.epi4 && p.Nc % 4 == 0) {
+  if (p.Nc % 4 == 0) {
     // ---- row-major float4 epilogue (as igemm_taps_kernel's): the two accumulator tiles go through LDS one after the other (the k
     // loop ended with a barrier) and every thread finishes four float4 pieces of output rows per half: 16 lanes write a 256-B row
     // segment per store; addend / bias / BatchNorm pivot come in as float4 ----
@@ -412,10 +411,9 @@ struct WPlan {
 WPlan wino_plan(long M2, int Nc, int C) {
   WPlan best{};
   const long gm = nnl_cdiv(M2, 64), gn = nnl_cdiv(Nc, 64), T = gm * gn;
-  const int e_bk = NNL_AB_INT("NNL_WINO_BK", 0);
   // BK 32 where the per-tap channel loop is short (C = 64: 134.5 -> 137.5 TF/s) or the grid small (7x7 stage: 116 -> 125); BK 16
-  // otherwise (28x28 / 14x14 stages: 144 / 151 against 141 / 147) — tools/bench_conv.py --ab NNL_WINO_BK=16,32
-  best.bk = (e_bk == 16 || e_bk == 32) ? e_bk : ((C % 32 == 0 && (C == 64 || T < 300)) ? 32 : 16);
+  // otherwise (28x28 / 14x14 stages: 144 / 151 against 141 / 147) — tools/bench_conv.py
+  best.bk = (C % 32 == 0 && (C == 64 || T < 300)) ? 32 : 16;
   if (C % best.bk != 0) best.bk = 16;
   const int bk = best.bk;
   const long I = 12L * (C / bk);
@@ -509,7 +507,6 @@ int nnl_wino_launch(const WinoProblem& q, void* ws, size_t ws_bytes, int* tile_c
   p.H = q.H; p.W = q.W; p.C = q.Cin; p.W2 = (q.W + 1) / 2; p.M2 = (int)M2; p.Nc = q.Nc; p.relu = q.relu;
   p.grid_m = (int)nnl_cdiv(M2, 64L); p.grid_n = (int)nnl_cdiv(q.Nc, 64);
   p.bn_part = q.bn_part; p.bn_pivot = q.bn_pivot;
-  p.epi4 = NNL_AB_INT("NNL_WINO_EPI4", 1);
   const long T = (long)p.grid_m * p.grid_n;
   WPlan pl = wino_plan(M2, q.Nc, q.Cin);
   if (pl.on && (tile_counters == nullptr || T > n_counters || ws_bytes < (u_floats + pl.main_floats + pl.tail_floats) * sizeof(float) ||

@@ -44,8 +44,8 @@ struct Wino2Params {
   unsigned a_bytes, b_bytes;
   int H, W, C, H2, W2; // H2 x W2 quads per image
   int ch;              // channel chunk of the k order (a multiple of BK dividing C)
-  int prio;            // 1: raise the wave priority around the MFMA block (NNL_WINO2_PRIO)
-  int fold_skip;       // 1 (default): a position is folded only into the output tiles it feeds (NNL_WINO2_FOLD_SKIP=0: all four, A/B)
+  int prio;            // always 0 (set by the launcher): the branch on it costs nothing at run time, and without it the compiler packs the
+                       // staging transform of the k loop into fewer v_pk_fma_f32 (123 / 103 instead of 121 / 102 VALU per iteration)
   int M4;              // N * H2 * W2 rows
   unsigned mg_W2, mg_H2;   // ceil(2^32 / d) (0: d = 1): quad row -> (n, i, j) by multiply-high instead of division (the epilogue did 32 runtime
                        // divisions per thread and tile: most of the 12 us fixed cost per workgroup generation the planner had fitted)
@@ -255,7 +255,7 @@ __global__ __launch_bounds__(256, OCC) void wino2_kernel(const Wino2Params p) {
     load_tile(c_nx);
     const float sr_n = sr, sc_n = sc;
     __builtin_amdgcn_sched_barrier(0);
-    if (p.prio) __builtin_amdgcn_s_setprio(2);         // (A/B: NNL_WINO2_PRIO — the MFMA block of this wave ahead of the other waves' staging)
+    if (p.prio) __builtin_amdgcn_s_setprio(2);
     compute(cur, tm);
     if (p.prio) __builtin_amdgcn_s_setprio(0);
     __builtin_amdgcn_sched_barrier(0);
@@ -269,19 +269,19 @@ __global__ __launch_bounds__(256, OCC) void wino2_kernel(const Wino2Params p) {
       const float cq0 = nu < 3 ? 1.f : 0.f, cq1 = nu == 0 ? 0.f : (nu == 2 ? -1.f : 1.f);
       const float k00 = cp0 * cq0, k01 = cp0 * cq1, k10 = cp1 * cq0, k11 = cp1 * cq1;
       // coefficients 0 / +-1, wave-uniform: corner positions feed one output tile, edge positions two, centre positions four
-      if (k00 != 0.f || !p.fold_skip) {
+      if (k00 != 0.f) {
 #pragma unroll
         for (int e = 0; e < 16; ++e) y00[e] = __builtin_fmaf(k00, tm[e], y00[e]);
       }
-      if (k01 != 0.f || !p.fold_skip) {
+      if (k01 != 0.f) {
 #pragma unroll
         for (int e = 0; e < 16; ++e) y01[e] = __builtin_fmaf(k01, tm[e], y01[e]);
       }
-      if (k10 != 0.f || !p.fold_skip) {
+      if (k10 != 0.f) {
 #pragma unroll
         for (int e = 0; e < 16; ++e) y10[e] = __builtin_fmaf(k10, tm[e], y10[e]);
       }
-      if (k11 != 0.f || !p.fold_skip) {
+      if (k11 != 0.f) {
 #pragma unroll
         for (int e = 0; e < 16; ++e) y11[e] = __builtin_fmaf(k11, tm[e], y11[e]);
       }
@@ -552,7 +552,7 @@ double w2_pos_cost(long T, long M4, int Nc, int C, int cs) {
   return nb * I * (b + a / c) + tfix * nb / c + slab_b / 11.7e6 + (3.0 + 1.5 * cs) + 4.0;
 }
 
-// Cost of one schedule (us), fitted to 477 forced-schedule timings of this kernel (tools/wino2_plan_sweep.py, profiles/r3_wino2d_plan_sweep.log:
+// Cost of one schedule (us), fitted to 477 forced-schedule timings of this kernel (profiles/r3_wino2d_plan_sweep.log:
 // five layer shapes x 16 / 32 / 64 images x both k blocks x 21 (main slices, tail slices) settings, rms error 9 %).  A CU's busiest set of
 // workgroups — m main + q tail blocks, up to `occ` of them resident — costs W * (b + a / c): W their k iterations, c = min(occ, m + q)
 // the co-resident count; `a` is the per-iteration latency a lone workgroup cannot hide (five loads, one barrier), `b` the MFMA / LDS
@@ -560,7 +560,7 @@ double w2_pos_cost(long T, long M4, int Nc, int C, int cs) {
 // the slab round trips at a fitted 11.7 TB/s and 10 us of launch + filter pre-pass.
 double w2_cost(long T, long gn, long M4, int Nc, long I, int bk, int ks, int S, W2Plan* out) {
   const double a = bk == 32 ? 0.363 : 0.226, b = bk == 32 ? 0.490 : 0.243, tfix = bk == 32 ? 12.3 : 15.0;
-  const long occ = (bk == 16 && NNL_AB_INT("NNL_WINO2_OCC", 4) != 3) ? 4 : 3;
+  const long occ = bk == 16 ? 4 : 3;
   long n_main = ((T * ks / kCUs) * kCUs / ks / gn) * gn;
   if (n_main > T) n_main = T;
   const long tail = T - n_main;
@@ -583,13 +583,12 @@ double w2_cost(long T, long gn, long M4, int Nc, long I, int bk, int ks, int S, 
 W2Plan wino2_plan(long M4, int Nc, int C) {
   W2Plan best{};
   const long gm = nnl_cdiv(M4, 64), gn = nnl_cdiv(Nc, 64), T = gm * gn;
-  const int e_bk = NNL_AB_INT("NNL_WINO2_BK", 0);
   const int f_ks = NNL_ENV_INT("NNL_WINO_PLAN_KS", 0), f_S = NNL_ENV_INT("NNL_WINO_PLAN_S", 0);
   const bool balance = NNL_ENV_INT("NNL_WINO_BALANCE", 1) != 0;
   double best_t = 1e300;
   static const int kSlices[] = {1, 2, 3, 4, 6, 8, 12, 16};
   for (int bk = 16; bk <= 32; bk *= 2) {
-    if (C % bk != 0 || ((e_bk == 16 || e_bk == 32) && bk != e_bk && C % e_bk == 0)) continue;
+    if (C % bk != 0) continue;
     const long I = 16L * (C / bk);
     for (int ks = 1; ks <= 4; ks *= 2) {
       if (ks > 1 && (!balance || I / ks < 8)) break;
@@ -605,13 +604,12 @@ W2Plan wino2_plan(long M4, int Nc, int C) {
     }
   }
   if (best_t == 1e300) {                                                   // (forced settings the shape does not allow)
-    const int bk = (e_bk == 32 && C % 32 == 0) ? 32 : 16;
-    best.t_us = w2_cost(T, gn, M4, Nc, 16L * (C / bk), bk, 1, 1, &best);
+    best.t_us = w2_cost(T, gn, M4, Nc, 16L * (C / 16), 16, 1, 1, &best);
     best_t = best.t_us;
   }
   // the position-split instantiation (small grids): NNL_WINO2_POS = -1 (default) by predicted time, 0 never, n > 0 forces n channel slices
   const int e_pos = NNL_ENV_INT("NNL_WINO2_POS", -1);
-  if (e_pos != 0 && (balance || e_pos > 0) && C % 32 == 0 && (e_bk == 0 || e_bk == 32)) {      // (a split schedule: off with NNL_WINO_BALANCE=0)
+  if (e_pos != 0 && (balance || e_pos > 0) && C % 32 == 0) {      // (a split schedule: off with NNL_WINO_BALANCE=0)
     const int csteps = C / 32;
     double pt = 1e300; int pcs = 0;
     for (int cs = 1; cs <= 8; cs *= 2) {
@@ -670,8 +668,7 @@ int nnl_wino2_launch(const WinoProblem& q, void* ws, size_t ws_bytes, int* tile_
   {
     const int e_ch = NNL_ENV_INT("NNL_WINO2_CHUNK", 0);                  // 0: the whole C (position-major order); else a multiple of 32 dividing C
     p.ch = (e_ch > 0 && e_ch % 32 == 0 && q.Cin % e_ch == 0) ? e_ch : q.Cin;
-    p.prio = NNL_AB_INT("NNL_WINO2_PRIO", 0);
-    p.fold_skip = NNL_AB_INT("NNL_WINO2_FOLD_SKIP", 1);
+    p.prio = 0;
   }
   p.H = q.H; p.W = q.W; p.C = q.Cin; p.H2 = (q.H + 1) / 2; p.W2 = (q.W + 1) / 2; p.M4 = (int)M4; p.Nc = q.Nc; p.relu = q.relu;
   {
@@ -708,7 +705,6 @@ int nnl_wino2_launch(const WinoProblem& q, void* ws, size_t ws_bytes, int* tile_
     grid = (unsigned)(pl.n_main_tiles * pl.main_ks + (T - pl.n_main_tiles) * pl.tail_slices);
   }
   if (pl.bk == 32) hipLaunchKernelGGL((wino2_kernel<32, 3>), dim3(grid), dim3(256), 0, s, p);
-  else if (NNL_AB_INT("NNL_WINO2_OCC", 4) == 3) hipLaunchKernelGGL((wino2_kernel<16, 3>), dim3(grid), dim3(256), 0, s, p);
   else hipLaunchKernelGGL((wino2_kernel<16, 4>), dim3(grid), dim3(256), 0, s, p);
   NNL_CHECK_LAUNCH();
   return NNL_OK;

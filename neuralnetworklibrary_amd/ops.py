@@ -17,13 +17,6 @@ __all__ = ['mse_loss', 'scaled_sigmoid', 'embdotbias', 'index_error_flag', 'rais
 _ERR_FLAGS = {}
 
 
-def _ab(name, default):
-    """A/B hook of a CLOSED experiment: the shipped package runs its default; the variable is read only in an
-    A/B session (NNL_AB=1 in the environment, with the `make AB=1` library for the C-side hooks)."""
-    return os.environ.get(name, default) if os.environ.get('NNL_AB') == '1' else default
-
-
-
 def _flags(device):
     key = (device.type, device.index)
     if key not in _ERR_FLAGS:
@@ -369,11 +362,6 @@ def prepare_backward(model):
 
 
 def finish_backward():
-    side_join()
-    _finish_backward_impl()
-
-
-def _finish_backward_impl():
     "closes the window of everything prepare_forward / prepare_backward exposed (the optimizer is about to change the weights)"
     _WT_ACTIVE.clear()
     _WT_PADDED.clear()
@@ -437,9 +425,6 @@ def _tile_counters(device):
     """persistent zero-at-rest ticket counters of the conv kernels' in-kernel split-tile fix-up (include/nnl.h), one buffer per
     device: every op of this package runs on torch's current stream, one conv at a time (a captured step replays on that same
     stream).  Created on first use outside stream capture (eager warm-up steps precede every capture)."""
-    import os
-    if _ab('NNL_IGEMM_FIXUP', '1') == '0':
-        return None
     t = _TILE_COUNTERS.get(device.index)
     if t is None:
         if torch.cuda.is_current_stream_capturing():
@@ -464,65 +449,6 @@ class GradSlot:
         self.tensor = None
         self.closed = False
 
-
-
-# ---- weight gradients on a SIDE STREAM (round 4) ---------------------------------------------------------------------------------
-# The language model's backward is a chain of latency-bound launches (210 BPTT timesteps x 2 kernels: <= 256 small workgroups and ~6 us
-# of dependent-launch gap each) with five big weight-gradient GEMMs hanging off it (decoder 170 GFLOP, dW_ih / dW_hh 47 GFLOP each)
-# that nothing downstream in backward depends on.  Call sites that opt in (`linear(..., wgrad_side=True)`, ops_text._LSTMRecurrence)
-# launch those GEMMs on a second HIP stream, where they fill the CUs the recurrence leaves idle; the main stream joins it in
-# finish_backward() / before the fused optimizer step (side_join).  Safety: only when the parameter has no gradient yet (autograd then
-# takes the produced tensor as `.grad` without touching its data — an accumulation kernel on the main stream would race), not under
-# data parallelism (the bucket hooks copy on the main stream), not while a hipGraph is being captured; every tensor the side launches
-# touch is recorded on that stream for the caching allocator; a gradient that needs un-padding is made dense ON the side stream (a strided view would be cloned by autograd
-# on the main stream: a race — found by tests/test_text.py).  Measured: the GEMMs do run beside the recurrence, but they take its CUs: kernel times
-# LSTM 7.08 -> 9.07 ms, wgrad 3.73 -> 4.39 ms, wall 17.33 -> 17.21 ms — hence opt-in (NNL_WGRAD_SIDE_STREAM=1), kept for the record.
-class _Side:
-    stream = None
-    used = False
-    enabled = _ab('NNL_WGRAD_SIDE_STREAM', '0') == '1'      # OPT-IN: measured +0.7 % on the LM step (profiles/r4_lm_side_stream_ab.log)
-    pending_param = None          # set by linear(..., wgrad_side=True) for the _Conv2d.forward that follows
-
-
-def side_ok(param):
-    return (_Side.enabled and param is not None and param.is_cuda and param.grad is None and getattr(param, '_nnl_grad_dst', None) is None
-            and not torch.cuda.is_current_stream_capturing())
-
-
-def side_run(fn, tensors):
-    "fn() launches its kernels on the current stream: run it with the side stream current, after everything queued on the main stream so far"
-    main = torch.cuda.current_stream()
-    if _Side.stream is None:
-        _Side.stream = torch.cuda.Stream()
-    s = _Side.stream
-    s.wait_stream(main)
-    with torch.cuda.stream(s):
-        fn()
-    for t in tensors:
-        if t is not None:
-            t.record_stream(s)
-    _Side.used = True
-
-
-def _side_wgrad(run_w, tensors, dwn, K, c_in):
-    "a linear layer's weight gradient on the side stream; returns a DENSE [K, c_in, 1, 1] tensor (un-padded there, not by autograd on the main stream)"
-    if K == dwn.shape[0] and c_in == dwn.shape[3]:
-        side_run(run_w, tensors)
-        return from_nhwc(dwn)
-    dense = torch.empty((K, c_in, 1, 1), dtype=torch.float32, device=dwn.device)
-
-    def run():
-        run_w()
-        dense.view(K, c_in).copy_(dwn.view(dwn.shape[0], dwn.shape[3])[:K, :c_in])
-    side_run(run, tuple(tensors) + (dense,))
-    return dense
-
-
-def side_join():
-    "the main stream waits for the side-stream weight gradients (before anything reads them: optimizer, accumulation into a tied weight)"
-    if _Side.used:
-        torch.cuda.current_stream().wait_stream(_Side.stream)
-        _Side.used = False
 
 
 # ---- parameters shared by several forward calls of one step (RetinaNet's heads on the five pyramid levels) ----------------------------
@@ -600,7 +526,6 @@ class _Conv2d(torch.autograd.Function):
         require_cuda(x, weight, bias)
         ctx.slot = slot
         ctx.give_slot = give_slot
-        ctx.side_param, _Side.pending_param = _Side.pending_param, None      # linear(..., wgrad_side=True): the parameter whose gradient may go to the side stream
         ctx.grad_dst = getattr(weight, '_nnl_grad_dst', None)     # data parallel: the flat all-reduce bucket (dist.GradSync)
         ctx.uses = getattr(weight, '_nnl_uses', None)             # forward uses of this weight in the current step
         if ctx.uses is not None:
@@ -652,9 +577,7 @@ class _Conv2d(torch.autograd.Function):
             return _Conv2d._backward_padded(ctx, dyn, wn, xn, g, K)
         dyn = to_nhwc(dy.float())
         db_gated = None
-        if ctx.relu == 1 and _ab('NNL_RELU_GATE', '1') == '0':
-            dyn = dyn * (y > 0)
-        elif ctx.relu:
+        if ctx.relu:
             # ReLU / sigmoid gate (+ the bias gradient of the gated dy) in one pass
             want_db = ctx.has_bias and ctx.needs_input_grad[2]
             rows = g.N * g.P * g.Q
@@ -673,7 +596,7 @@ class _Conv2d(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             g_w, dyn_w, wn_w = g, dyn, wn                   # (the weight gradient keeps the unpadded operands)
             ktail = g.R == 1 and g.S == 1 and g.K % 4 == 0 and os.environ.get('NNL_IGEMM_KTAIL', '1') != '0'     # the tap kernel masks the k tail itself
-            if g.K % 16 != 0 and g.K >= 32 and not ktail and _ab('NNL_DGRAD_PAD16', '1') != '0':
+            if g.K % 16 != 0 and g.K >= 32 and not ktail:
                 # dgrad reduces over K: the tap-table kernel needs K % 16 == 0 (RetinaNet's 36- / 180-channel output convs would
                 # fall back to the first-generation kernel, ~2.5x slower); zero channels cost one copy of dy
                 padk = 16 - g.K % 16
@@ -726,19 +649,15 @@ class _Conv2d(torch.autograd.Function):
                 dwn = torch.empty((g.K, g.R, g.S, g.C), dtype=torch.float32, device=dyn.device)
             ws_bytes = int(lib.nnl_conv2d_wgrad_workspace_bytes(g))
             ws = torch.empty(max(ws_bytes // 4, 1), dtype=torch.float32, device=dyn.device)
-            run_w = lambda: check(lib.nnl_conv2d_wgrad(ptr(xn), ptr(dyn), ptr(dwn), g, ptr(ws), ws_bytes, stream()))
-            if side_ok(getattr(ctx, 'side_param', None)) and dst is None and g.R == 1 and g.S == 1:
-                dw = _side_wgrad(run_w, (xn, dyn, dwn, ws), dwn, K, ctx.c_in)
-            else:
-                run_w()
-                dw = from_nhwc(dwn[:K, :, :, :ctx.c_in])
-                # a 1x1 filter's [K, C, 1, 1] gradient: give it EXACTLY the parameter's strides (the size-1 dimensions make them ambiguous);
-                # otherwise AccumulateGrad sees a layout mismatch and clones it into the parameter's layout — one device copy per 1x1
-                # convolution and step (53 of RetinaNet's 68 rocclr_copyBuffer launches, profiles/r5_retinanet_kernel_stats.csv)
-                wshape, wstride = getattr(ctx, 'w_layout', (None, None))
-                if (g.R == 1 and g.S == 1 and wshape == tuple(dw.shape) and wstride != tuple(dw.stride()) and dw.is_contiguous(memory_format=torch.channels_last)
-                        and wstride[1] == 1 and wstride[0] == dw.shape[1]):
-                    dw = dw.as_strided(wshape, wstride)
+            check(lib.nnl_conv2d_wgrad(ptr(xn), ptr(dyn), ptr(dwn), g, ptr(ws), ws_bytes, stream()))
+            dw = from_nhwc(dwn[:K, :, :, :ctx.c_in])
+            # a 1x1 filter's [K, C, 1, 1] gradient: give it EXACTLY the parameter's strides (the size-1 dimensions make them ambiguous);
+            # otherwise AccumulateGrad sees a layout mismatch and clones it into the parameter's layout — one device copy per 1x1
+            # convolution and step (53 of RetinaNet's 68 rocclr_copyBuffer launches, profiles/r5_retinanet_kernel_stats.csv)
+            wshape, wstride = getattr(ctx, 'w_layout', (None, None))
+            if (g.R == 1 and g.S == 1 and wshape == tuple(dw.shape) and wstride != tuple(dw.stride()) and dw.is_contiguous(memory_format=torch.channels_last)
+                    and wstride[1] == 1 and wstride[0] == dw.shape[1]):
+                dw = dw.as_strided(wshape, wstride)
         if db_gated is not None:
             db = db_gated
         elif ctx.has_bias and ctx.needs_input_grad[2]:
@@ -766,12 +685,8 @@ def _conv2d_backward_padded(ctx, dyn, wn, xn, g, K):
         dwn = torch.empty((g.K, g.R, g.S, g.C), dtype=torch.float32, device=dyn.device)
         ws_bytes = int(lib.nnl_conv2d_wgrad_workspace_bytes(g))
         ws = torch.empty(max(ws_bytes // 4, 1), dtype=torch.float32, device=dyn.device)
-        run_w = lambda: check(lib.nnl_conv2d_wgrad(ptr(xn), ptr(dyn), ptr(dwn), g, ptr(ws), ws_bytes, stream()))
-        if side_ok(getattr(ctx, 'side_param', None)) and g.R == 1 and g.S == 1:
-            dw = _side_wgrad(run_w, (xn, dyn, dwn, ws), dwn, K, ctx.c_in)
-        else:
-            run_w()
-            dw = from_nhwc(dwn[:K, :, :, :ctx.c_in])
+        check(lib.nnl_conv2d_wgrad(ptr(xn), ptr(dyn), ptr(dwn), g, ptr(ws), ws_bytes, stream()))
+        dw = from_nhwc(dwn[:K, :, :, :ctx.c_in])
     if ctx.has_bias and ctx.needs_input_grad[2]:
         db_full = torch.empty(g.K, dtype=torch.float32, device=dyn.device)
         cb = int(lib.nnl_colsum_workspace_bytes(g.N * g.P * g.Q, g.K))
@@ -907,16 +822,14 @@ class _LinearSmall(torch.autograd.Function):
         return dx, dw, db
 
 
-def linear(x, weight, bias=None, relu=False, wgrad_side=False):
+def linear(x, weight, bias=None, relu=False):
     """y = x @ weight.T + bias [+ ReLU] (nn.Linear; reference General/Layers.py:39,146; Text.py:572) on the same
     fp32-MFMA implicit-GEMM kernels: a Linear is the 1x1 convolution of a 1x1 'image' per sample.  Leading dims of x
-    are flattened into rows.  wgrad_side: the weight gradient may be computed on the side stream (see _Side above)."""
+    are flattened into rows."""
     lead = x.shape[:-1]
     x2 = x.reshape(-1, x.shape[-1])
-    if (not relu and weight.shape[0] <= 4 and x2.is_cuda and x2.shape[0] > 0
-            and _ab('NNL_LINEAR_SMALL', '1') != '0'):
+    if not relu and weight.shape[0] <= 4 and x2.is_cuda and x2.shape[0] > 0:
         return _LinearSmall.apply(x2, weight, bias).reshape(*lead, weight.shape[0])
-    _Side.pending_param = weight if (wgrad_side and weight.requires_grad) else None
     y = _Conv2d.apply(x2[:, :, None, None], weight[:, :, None, None], bias, 1, 0, int(relu), None, None)[0]
     return y.reshape(*lead, weight.shape[0])
 

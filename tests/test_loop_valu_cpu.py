@@ -38,8 +38,8 @@ def _loops(rows, needle):
 
 # (kernel name fragment of the mangled instantiation, MFMAs per iteration, VALU bound, bound on register moves or None)
 CASES = [
-    ('igemm_wgrad2d_kernelILi64ELi32ELb1ELi4E', 16, 90, None),           # Winograd-domain weight gradient, 64 x 64 tile, four wave groups (was 110+)
-    ('igemm_wgrad2d_kernelILi128ELi16ELb1ELi1E', 32, 106, None),         # ... 128 x 128 tile (was 125)
+    ('igemm_wgrad2d_kernelILi64ELi32ELi4E', 16, 90, None),           # Winograd-domain weight gradient, 64 x 64 tile, four wave groups (was 110+)
+    ('igemm_wgrad2d_kernelILi128ELi16ELi1E', 32, 106, None),         # ... 128 x 128 tile (was 125)
     ('igemm_wgrad_kernelILi64ELi64ELi32ELi2ELi2ELb1ELi1ELb0ELb1E', 16, 40, None),     # direct weight gradient, PAIR staging (one-chunk staging: 56)
     ('igemm_wgrad_kernelILi128ELi128ELi16ELi2ELi2ELb1ELi1ELb0ELb1E', 32, 56, None),   # (one-chunk staging: 70)
     ('igemm_taps_kernelILi64ELi64ELi32ELi2ELi2ELb1ELi0ELb0ELi1ELb0E', 16, 20, 0),     # forward / dgrad tap kernel: address state is scalar
