@@ -467,6 +467,23 @@ int nnl_seq_reg_bwd(const float* h, const float* grad_out, float* dh, int64_t T,
 int nnl_weight_drop(const float* src, int64_t ld_src, const float* mask, float* out, int64_t ld_out, int64_t rows, int64_t H,
                     uint64_t seed, float p, void* stream);
 
+/* ---- K5c: attention pooling of TextClassificationDecoder (Text.py:575-609), everything after attn1 ----------------------
+ * h = relu(attn1(enc_out)) [T,B,A], w2 [A] and b2 [1] (device: attn2's weight and bias), enc_out [T,B,E], x [B,T] int64 tokens:
+ *   s[t,b] = h[t,b,:].w2 + b2;  attn[:,b] = softmax of s[:,b] over the positions with x[b,t] != pad_token (the reference's
+ *   softmax -> mask -> renormalise, Text.py:598-601, up to rounding);  pooled[b,:] = sum_t attn[t,b] enc_out[t,b,:] (:604-605).
+ * A column with no non-pad token is NaN in attn and pooled (the reference's 0/0).  Backward, given dpooled [B,E] and dattn [T,B]
+ * (NULL = 0): g = enc_out.dpooled + dattn, c[b] = sum_t attn g, dlogit = attn (g - c); denc = attn dpooled (written, not
+ * accumulated), dh = dlogit w2, dw2 = sum dlogit h, *db2 = sum dlogit.  Every sum has a fixed order (bitwise repeatable, no float
+ * atomics); `counters`: >= B + 1 int32 that are zero at rest and are left zero (nnl_conv2d_tile_counters' buffer fits); the
+ * workspace (16-byte aligned) serves both directions. */
+size_t nnl_attn_pool_workspace_bytes(int64_t T, int64_t B, int64_t E, int64_t A);
+int nnl_attn_pool_fwd(const float* h, const float* w2, const float* b2, const float* enc_out, const int64_t* x, int64_t pad_token,
+                      float* attn, float* pooled, int64_t T, int64_t B, int64_t E, int64_t A, void* workspace, size_t workspace_bytes,
+                      int32_t* counters, int64_t n_counters, void* stream);
+int nnl_attn_pool_bwd(const float* h, const float* w2, const float* enc_out, const float* attn, const float* dpooled,
+                      const float* dattn, float* dh, float* denc, float* dw2, float* db2, int64_t T, int64_t B, int64_t E, int64_t A,
+                      void* workspace, size_t workspace_bytes, int32_t* counters, int64_t n_counters, void* stream);
+
 /* ---- K8: fused multi-tensor Optimizer.step ------------------------------------------------------------------------
  * Replaces Optimizer.step (General/Optimizer.py:58-70): decoupled weight decay X *= 1 - wd_g*lr_g (:60-67), global-norm
  * clip (:54-56, torch.nn.utils.clip_grad_norm_) and the torch.optim SGD(momentum) / Adam update (General/Learner.py:17-19)

@@ -22,10 +22,139 @@ from ..General.Layers import *        # noqa: F401,F403
 from ..General.Learner import *       # noqa: F401,F403
 from ..General.LossesMetrics import * # noqa: F401,F403
 from ..General.Optimizer import *     # noqa: F401,F403
-from ..General.Core import TEN, correct_foldername, default_device, list_mult, separate_bn_layers
+from ..General.Core import TEN, SplitTrainVal, correct_foldername, default_device, list_mult, separate_bn_layers
 from ..General.Layers import FullyConnectedNet
-from .. import ops
+from .. import ops, ops_text
 from ..dist import keyed_mask
+
+
+# ---- data: datasets (Text.py:127-229) -------------------------------------------------------------------------------
+
+_NO_TOKENIZER = ('tokenisation (spaCy) is not part of this package (SURVEY.md §2.1 row 14): pass token-id lists, e.g. what the '
+                 "reference's numericalize() returns")
+
+
+class TextDataset(object):
+    """Texts + labels for language modelling and text classification (Text.py:127-187).  `texts` are token-id lists (what the
+    reference computes from strings with tokenize_mp + numericalize); strings raise NotImplementedError.  `stoi` is kept as
+    given.  Same attributes as the reference: texts / labels as pandas Series, the sorted label_dict, num_tokens."""
+
+    def __init__(self, texts, labels, stoi=None, reverse=False):
+        import pandas as pd
+        texts = list(texts)
+        if any(isinstance(t, str) for t in texts):
+            raise NotImplementedError(_NO_TOKENIZER)
+        self.stoi, self.reverse = stoi, reverse
+        self.texts = pd.Series([[int(v) for v in t] for t in texts], dtype=object)
+        if reverse:
+            self.texts = pd.Series([list(reversed(t)) for t in self.texts], dtype=object)
+        self.num_tokens = sum(len(t) for t in self.texts)
+        unique_labels = sorted(list(set(labels)))
+        self.label_dict = {lab: i for i, lab in enumerate(unique_labels)}
+        self.labels = pd.Series([self.label_dict[lab] for lab in labels], dtype=np.int64)
+
+    def __len__(self):
+        return len(self.texts)
+
+    def __getitem__(self, idx):
+        return self.texts.iloc[idx], self.labels.iloc[idx]
+
+    def split_train_val(self):
+        "(train, val) datasets split by General.Core.SplitTrainVal (20 % validation, np.random) — Text.py:160-181"
+        import copy
+        all_texts, all_labels = copy.deepcopy(self.texts), copy.deepcopy(self.labels)
+        train_ds, val_ds = self, copy.deepcopy(self)
+        train_idxs, val_idxs = SplitTrainVal(list(range(len(self.texts))))
+        for ds, idxs in ((train_ds, train_idxs), (val_ds, val_idxs)):
+            ds.texts = all_texts[idxs]
+            ds.texts.index = range(len(ds.texts))
+            ds.labels = all_labels[idxs]
+            ds.labels.index = range(len(ds.labels))
+            ds.num_tokens = sum(len(t) for t in ds.texts)
+        return train_ds, val_ds
+
+    @classmethod
+    def from_csv(cls, csv_file, text_col, label_col=None, stoi=None, reverse=False):
+        raise NotImplementedError(_NO_TOKENIZER)
+
+    @classmethod
+    def from_text_files(cls, folder, labels, stoi=None, reverse=False):
+        raise NotImplementedError(_NO_TOKENIZER)
+
+
+# ---- data: text-classification batches (Text.py:334-440) -----------------------------------------------------------
+
+class TextLengthSampler(torch.utils.data.Sampler):
+    """Batches of similar-length texts (Text.py:334-381).  Sorts `ds` by text length, longest first, IN PLACE (ds.texts,
+    ds.labels re-ordered, ds.perm = the permutation: predictions of an unshuffled loader line up with the permuted labels),
+    then cuts groups of bs*bpg consecutive texts.  random=True: every pass shuffles the order of the groups after the first
+    (which stays first: the longest batch comes first) and the texts within each group, with np.random — including the pass
+    that counts the batches in the constructor, as in the reference."""
+
+    def __init__(self, ds, bs, bpg=10, random=False):
+        L = len(ds)
+        perm = list(range(L))
+        perm.sort(key=lambda i: len(ds.texts[i]), reverse=True)
+        ds.texts, ds.labels, ds.perm = ds.texts[perm], ds.labels[perm], perm
+        ds.texts.index, ds.labels.index = range(L), range(L)
+        group_sz = bs * bpg
+        self.groups = [list(range(i, min(i + group_sz, L))) for i in range(0, L, group_sz)]
+        self.bs, self.random = bs, random
+        self.length = len([x for x in self])
+
+    def __len__(self):
+        return self.length
+
+    def __iter__(self):
+        if self.random:
+            groups = self.groups[1:]
+            np.random.shuffle(groups)
+            self.groups = [self.groups[0]] + groups
+        for g in self.groups:
+            if self.random:
+                np.random.shuffle(g)
+            for i in range(0, len(g), self.bs):
+                yield g[i:min(i + self.bs, len(g))]
+
+
+class TextLengthCollater(object):
+    "Pads every text of a batch at the end to the batch's longest; CPU int64 tensors (x [bs, seqlen], y [bs]) — Text.py:383-395"
+
+    def __init__(self, pad_token):
+        self.pad_token = pad_token
+
+    def __call__(self, batch):
+        texts, labels = [list(b[0]) for b in batch], [b[1] for b in batch]
+        m = max(len(t) for t in texts)
+        x = np.array([t + [self.pad_token] * (m - len(t)) for t in texts], dtype=np.int64)
+        return TEN(x, GPU=False), TEN(np.array(labels, dtype=np.int64), GPU=False)
+
+
+class TextClassificationDataObj(object):
+    """train / val / (test) loaders of length-bucketed, end-padded batches, target_type 'text_classify' (Text.py:397-440).
+    The train sampler shuffles (random=True), val / test keep the longest-first order."""
+
+    def __init__(self, train_ds, val_ds, test_ds, bs, bpg=10, num_workers=6):
+        from torch.utils.data import DataLoader
+        self.bs, self.stoi, self.target_type = bs, train_ds.stoi, 'text_classify'
+        self.train_ds, self.val_ds, self.test_ds = train_ds, val_ds, test_ds
+        collater = TextLengthCollater(self.stoi['_pad_'])
+        sampler_train = TextLengthSampler(train_ds, bs, bpg, random=True)
+        sampler_val = TextLengthSampler(val_ds, bs, bpg, random=False)
+        if test_ds:
+            sampler_test = TextLengthSampler(test_ds, bs, bpg, random=False)
+        self.train_dl = DataLoader(train_ds, collate_fn=collater, batch_sampler=sampler_train, num_workers=num_workers)
+        self.val_dl = DataLoader(val_ds, collate_fn=collater, batch_sampler=sampler_val, num_workers=num_workers)
+        if test_ds:
+            self.test_dl = DataLoader(test_ds, collate_fn=collater, batch_sampler=sampler_test, num_workers=num_workers)
+
+    @classmethod
+    def from_csv(cls, bs, csv_train, csv_val=None, csv_test=None, text_col='text', label_col='label', reverse=False, stoi=None):
+        raise NotImplementedError(_NO_TOKENIZER)
+
+    @classmethod
+    def from_folders(cls, bs, labels, train, val=None, test=None, reverse=False, stoi=None):
+        raise NotImplementedError(_NO_TOKENIZER)
 
 
 # ---- data: language-model batches (Text.py:231-332) ----------------------------------------------------------------
@@ -254,6 +383,11 @@ class TextClassificationDecoder(nn.Module):
 
     def forward(self, enc_in, enc_out):
         attn = ops.linear(enc_out, self.attn1.weight, self.attn1.bias, relu=True)       # seqlen x bs x attn_size
+        if enc_out.dim() == 3 and enc_out.shape[0] > 1 and enc_out.shape[1] > 1:
+            # attn2 -> softmax -> pad mask -> renormalise -> weighted sum in one HIP kernel each way (ops_text.attention_pool)
+            attn, combined = ops_text.attention_pool(attn, self.attn2.weight, self.attn2.bias, enc_out, enc_in, 1)
+            return self.fc(combined), attn
+        # seqlen 1 or bs 1: the reference's .squeeze() drops that dimension too, and what follows broadcasts accordingly
         attn = ops.linear(attn, self.attn2.weight, self.attn2.bias).squeeze()          # seqlen x bs
         attn = F.softmax(attn, dim=0)
         attn = attn * (enc_in.transpose(1, 0) != 1).float()                            # ignore the pad token

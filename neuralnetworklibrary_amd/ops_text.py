@@ -234,3 +234,61 @@ class _SeqReg(torch.autograd.Function):
 def seq_activation_reg(enc_out, alpha, beta):
     "AR + TAR regulariser of RegSeqCrossEntropyLoss as a 0-dim tensor (see _SeqReg)"
     return _SeqReg.apply(enc_out, float(alpha), float(beta))
+
+
+class _AttentionPool(torch.autograd.Function):
+    """TextClassificationDecoder's attention pooling after attn1 (reference Text.py:598-605): scores h.w2 + b2, softmax over the
+    non-pad timesteps of each column, attention-weighted sum of enc_out — nnl_attn_pool_fwd / _bwd.  Saves h, enc_out and attn;
+    no host synchronisation either way."""
+
+    @staticmethod
+    def forward(ctx, h, w2, b2, enc_out, x, pad_token):
+        from .ops import _tile_counters
+        require_cuda(h, w2, b2, enc_out, x)
+        ctx.w2_shape, ctx.b2_shape = w2.shape, b2.shape
+        h, enc_out = _f32c(h), _f32c(enc_out)
+        w2, b2 = _f32c(w2).view(-1), _f32c(b2).view(-1)
+        T, B, E = enc_out.shape
+        A = h.shape[2]
+        if tuple(h.shape) != (T, B, A) or w2.numel() != A or b2.numel() != 1 or tuple(x.shape) != (B, T):
+            raise _lib.NnlError('attention_pool: shapes h %s, w2 %s, b2 %s, enc_out %s, x %s do not match'
+                                % (tuple(h.shape), tuple(w2.shape), tuple(b2.shape), tuple(enc_out.shape), tuple(x.shape)))
+        xi = x.contiguous().long()
+        dev = enc_out.device
+        attn = torch.empty(T, B, dtype=torch.float32, device=dev)
+        pooled = torch.empty(B, E, dtype=torch.float32, device=dev)
+        wsb = int(lib.nnl_attn_pool_workspace_bytes(T, B, E, A))
+        ws = torch.empty(wsb // 4, dtype=torch.float32, device=dev)
+        cnt = _tile_counters(dev)
+        check(lib.nnl_attn_pool_fwd(ptr(h), ptr(w2), ptr(b2), ptr(enc_out), ptr(xi), int(pad_token), ptr(attn), ptr(pooled),
+                                    T, B, E, A, ptr(ws), wsb, ptr(cnt), cnt.numel(), stream()))
+        ctx.save_for_backward(h, w2, enc_out, attn)
+        ctx.set_materialize_grads(False)                 # training never uses attn: its gradient stays None (no [T,B] zero fill)
+        return attn, pooled
+
+    @staticmethod
+    def backward(ctx, dattn, dpooled):
+        from .ops import _tile_counters
+        h, w2, enc_out, attn = ctx.saved_tensors
+        T, B, E = enc_out.shape
+        A = h.shape[2]
+        dev = enc_out.device
+        dpooled = torch.zeros(B, E, dtype=torch.float32, device=dev) if dpooled is None else _f32c(dpooled)
+        dattn = None if dattn is None else _f32c(dattn)
+        dh = torch.empty_like(h)
+        denc = torch.empty_like(enc_out)
+        dw2 = torch.empty(A, dtype=torch.float32, device=dev)
+        db2 = torch.empty(1, dtype=torch.float32, device=dev)
+        wsb = int(lib.nnl_attn_pool_workspace_bytes(T, B, E, A))
+        ws = torch.empty(wsb // 4, dtype=torch.float32, device=dev)
+        cnt = _tile_counters(dev)
+        check(lib.nnl_attn_pool_bwd(ptr(h), ptr(w2), ptr(enc_out), ptr(attn), ptr(dpooled), ptr(dattn), ptr(dh), ptr(denc),
+                                    ptr(dw2), ptr(db2), T, B, E, A, ptr(ws), wsb, ptr(cnt), cnt.numel(), stream()))
+        return dh, dw2.view(ctx.w2_shape), db2.view(ctx.b2_shape), denc, None, None
+
+
+def attention_pool(h, w2, b2, enc_out, x, pad_token=1):
+    """h = relu(attn1(enc_out)) [T,B,A], attn2's weight w2 [1,A] and bias b2 [1], enc_out [T,B,E], tokens x [B,T] ->
+    (attn [T,B], pooled [B,E]) of TextClassificationDecoder (reference Text.py:597-605; pad token 1 is hard-coded there).
+    A column without a non-pad token gives NaN, as the reference's 0/0 does."""
+    return _AttentionPool.apply(h, w2, b2, enc_out, x, pad_token)
