@@ -129,7 +129,7 @@ class GradSync:
             for pi, p in enumerate(b.params):
                 self._where[id(p)] = (bi, pi)
                 self._hooks.append(p.register_post_accumulate_grad_hook(self._on_grad))
-                # ops._Conv2d.backward writes the weight gradient straight into the bucket (no copy kernel) when it finds this
+                # ops._conv_wgrad writes the weight gradient straight into the bucket (no copy kernel) when it finds this
                 # AND the weight was used exactly once in the step's forward (`_nnl_uses[0] == 1`): a weight shared by several
                 # calls (RetinaNet's heads run on 5 pyramid levels) gets one gradient per use that autograd must SUM, so each
                 # of them needs its own buffer

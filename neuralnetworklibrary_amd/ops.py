@@ -4,9 +4,12 @@ Each Function is the device-side replacement of one group of eager torch ops in 
 cited per class).  Tensors are handed over as raw device pointers + sizes on torch's CURRENT stream; there
 is no CPU fallback — a non-CUDA tensor raises NnlError.
 """
+import collections
 import ctypes
 import os
+import weakref
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -60,6 +63,15 @@ def _f32c(t):
     return t.contiguous() if t.dtype == torch.float32 else t.float().contiguous()
 
 
+def _workspace(nbytes, device, *, floor=False):
+    """the scratch buffer a library call asked for (its *_workspace_bytes query): None — a NULL pointer — for zero bytes, unless
+    floor=True asks for a minimal buffer instead.  Which of the two a site passes is deliberate and kept per site: the conv entry
+    points consider the Winograd kernels only with a non-null workspace; the reductions always got a non-null pointer."""
+    if not nbytes and not floor:
+        return None
+    return torch.empty(max((nbytes + 3) // 4, 1), dtype=torch.float32, device=device)
+
+
 class _EmbDotBias(torch.autograd.Function):
     """CollabFilterNet.forward (reference Applications/CollabFiltering.py:196-204): four embedding gathers,
     row-wise dot, bias adds and the scaled sigmoid in ONE kernel; backward = the four dense scatter-adds."""
@@ -92,7 +104,7 @@ class _EmbDotBias(torch.autograd.Function):
         dU, dM = flat[:nu * D].view(nu, D), flat[nu * D:(nu + ni) * D].view(ni, D)
         dbu, dbi = flat[(nu + ni) * D:(nu + ni) * D + nu].view(nu, 1), flat[(nu + ni) * D + nu:].view(ni, 1)
         wsb = int(lib.nnl_embdotbias_bwd_workspace_bytes(x.shape[0]))          # sample-order (deterministic) scatter-add
-        ws = torch.empty(max(wsb, 4), dtype=torch.uint8, device=U.device)
+        ws = _workspace(wsb, U.device, floor=True)                              # never a null
         check(lib.nnl_embdotbias_bwd(ptr(x), ptr(U), ptr(M), ptr(z), ptr(dy), ptr(dU), ptr(dM), ptr(dbu), ptr(dbi),
                                      x.shape[0], U.shape[0], M.shape[0], U.shape[1], int(has_range), lo, hi,
                                      ptr(ws), wsb, stream()))
@@ -109,7 +121,7 @@ class _MSE(torch.autograd.Function):
         n = p.numel()
         loss = torch.empty((), dtype=torch.float32, device=p.device)
         wsb = int(lib.nnl_mse_workspace_bytes(n))
-        ws = torch.empty(wsb // 4, dtype=torch.float32, device=p.device) if wsb else None
+        ws = _workspace(wsb, p.device)
         check(lib.nnl_mse_fwd(ptr(p), ptr(t), ptr(loss), n, ptr(ws), wsb, stream()))
         ctx.save_for_backward(p, t)
         ctx.shape = pred.shape
@@ -216,7 +228,6 @@ class _WinoBatch:
     mode as nnl_conv2d_wino_preferred: 1 -> U [rows,12,ch] (1-D kernel), 2 -> U [rows,16,ch] (2-D kernel)"""
 
     def __init__(self, items):
-        import numpy as np
         dev = items[0][1].device
         self.key = _wino_batch_key(items)
         total = sum(_wino_u_numel(t.shape[0], t.shape[3], mode) for _, t, _, mode in items)
@@ -308,7 +319,6 @@ class _WtBatch:
     "persistent W^T buffers + device descriptor tables for the conv filters of one model (nnl_conv2d_weight_transpose_multi)"
 
     def __init__(self, weights):
-        import numpy as np
         dev = weights[0].device
         self.key = tuple((w.data_ptr(), tuple(w.shape)) for w in weights)
         total = sum(w.numel() for w in weights)
@@ -397,7 +407,6 @@ _PADDED_GRADS = {}
 
 
 def register_padded_grad(base, ld):
-    import weakref
     if len(_PADDED_GRADS) > 64:
         for k in [k for k, (r, _) in _PADDED_GRADS.items() if r() is None]:
             del _PADDED_GRADS[k]
@@ -517,6 +526,168 @@ def fan_param(p):
     return lst.pop(0) if lst else p
 
 
+# What a convolution's forward leaves for _conv_backward.  g: geometry of the saved (channel-padded) operands; relu: 0 none, 1 ReLU,
+# 2 sigmoid; c_in: input channels before padding; w_layout: (shape, strides) of the weight as autograd sees it; slot / give_slot: see
+# GradSlot; grad_dst: the weight's segment of the flat all-reduce bucket (dist.GradSync); uses: [forward uses of the weight this step]
+_ConvState = collections.namedtuple('_ConvState', 'g relu has_bias c_in w_layout slot give_slot grad_dst uses')
+
+
+def _conv_operands(x, weight, bias, stride, pad):
+    "(x NHWC and weight KRSC, channels padded to 4; fp32 bias or None; the geometry; the uninitialised NHWC output) of a forward call"
+    xn = _pad_c4(to_nhwc(_f32c(x) if x.dim() != 4 else x.float()))
+    wn = _pad_c4(to_nhwc(weight.float()))
+    N, H, W, C = xn.shape
+    K, R, S, _ = wn.shape
+    g = _geom(N, H, W, C, K, R, S, stride, pad)
+    y = torch.empty((N, g.P, g.Q, K), dtype=torch.float32, device=x.device)
+    return xn, wn, (None if bias is None else _f32c(bias)), g, y
+
+
+def _conv_state(x, weight, bias, g, relu, slot=None, give_slot=None):
+    "the _ConvState of one forward call (every conv Function builds it here); counts the call as a use of `weight`"
+    uses = getattr(weight, '_nnl_uses', None)
+    if uses is not None:
+        uses[0] += 1
+    return _ConvState(g, relu, bias is not None, x.shape[1], (tuple(weight.shape), tuple(weight.stride())), slot, give_slot,
+                      getattr(weight, '_nnl_grad_dst', None), uses)
+
+
+def _with_k(g, K):
+    "the geometry g with K output channels"
+    return _geom(g.N, g.H, g.W, g.C, K, g.R, g.S, g.stride, g.pad)
+
+
+def _conv_backward(st, xn, wn, y, dy, needs):
+    """(dx, dw, db) of a convolution from its _ConvState, the tensors its forward saved (y: the output, for the activation gate), the
+    logical [N,K,P,Q] output gradient and `needs` = which of the three are wanted.  (dy4, w4, g4): the operands with K padded to a
+    multiple of 4 — or to the width of the registered buffer dy arrived in — for wgrad and the bias sum; the dgrad derives its own."""
+    if dy is None:
+        return None, None, None
+    g, K = st.g, st.g.K
+    want_db = st.has_bias and needs[2]
+    db = None
+    pre = _padded_rows(dy, K) if (not st.relu and g.R == 1 and g.S == 1 and g.H == 1 and g.W == 1) else None
+    if pre is not None and pre.shape[-1] != K:
+        dy4 = pre     # arrived in a zero-padded buffer: every pass runs on the padded K, a multiple of 16 (the dgrad pads no further)
+    else:
+        dy4 = to_nhwc(dy.float())
+        if st.relu:
+            dy4, db = _conv_act_gate(y, dy4, g, st.relu, want_db)
+        if K % 4 != 0:                      # e.g. RetinaNet 36/180-channel output convs: pad dy's channels
+            dy4 = _pad_c4(dy4)
+    w4, g4 = wn, g
+    if dy4.shape[-1] != K:
+        w4, g4 = torch.nn.functional.pad(wn, (0, 0, 0, 0, 0, 0, 0, dy4.shape[-1] - K)), _with_k(g, dy4.shape[-1])
+    dx = dw = None
+    if needs[0]:
+        dx = _conv_dgrad(st, dy4, w4, g4, K)
+    elif st.slot is not None:               # closed even when nobody wants dx: a later producer must not park a tensor nobody consumes
+        st.slot.tensor, st.slot.closed = None, True
+    if needs[1]:
+        dw = _conv_wgrad(st, xn, dy4, g4, K)
+    if db is None and want_db:
+        db = _conv_bias_grad(dy4, g4, K)
+    return dx, dw, db
+
+
+def _conv_act_gate(y, dyn, g, relu, want_db):
+    "ReLU / sigmoid gate (+ the bias gradient of the gated dy) in one pass -> (gated dy, db or None)"
+    rows = g.N * g.P * g.Q
+    gated = torch.empty_like(dyn)
+    cb = int(lib.nnl_colsum_workspace_bytes(rows, g.K)) if want_db else 0
+    cws = _workspace(cb, dyn.device, floor=True) if want_db else None      # never a null
+    db = torch.empty(g.K, dtype=torch.float32, device=dyn.device) if want_db else None
+    check(lib.nnl_act_gate_colsum(ptr(dyn), ptr(y), ptr(gated), ptr(db), rows, g.K, int(relu), ptr(cws), cb, stream()))
+    return gated, db
+
+
+def _conv_dgrad_operands(dy4, w4, g4, K):
+    """(dy, W^T [C,R,S,K'], geometry) of the dgrad: the K-padded-to-4 set as is, or with K padded on to a multiple of 16; the filter
+    transpose comes from the caches of prepare_backward's window where it can"""
+    ktail = g4.R == 1 and g4.S == 1 and g4.K % 4 == 0 and os.environ.get('NNL_IGEMM_KTAIL', '1') != '0'     # the tap kernel masks the k tail itself
+    dyd, gd, padk, wkey = dy4, g4, 0, None
+    if g4.K % 16 != 0 and g4.K >= 32 and not ktail:
+        # dgrad reduces over K: the tap-table kernel needs K % 16 == 0 (RetinaNet's 36- / 180-channel output convs would
+        # fall back to the first-generation kernel, ~2.5x slower); zero channels cost one copy of dy
+        padk = 16 - g4.K % 16
+        dyd, gd = torch.nn.functional.pad(dy4, (0, padk)), _with_k(g4, g4.K + padk)
+        wkey = (w4.data_ptr(), tuple(w4.shape), padk)
+        wt = _WT_PADDED.get(wkey) if _WT_ACTIVE else None      # a shared filter (RetinaNet's output convs on five levels): padded + transposed ONCE per backward pass
+    else:
+        wt = _WT_ACTIVE.get(w4.data_ptr()) if g4.K == K else None
+        if wt is not None and tuple(wt.shape) != (g4.C, g4.R, g4.S, g4.K):
+            wt = None
+    if wt is None:
+        wd = torch.nn.functional.pad(w4, (0, 0, 0, 0, 0, 0, 0, padk)) if padk else w4
+        wt = torch.empty((gd.C, gd.R, gd.S, gd.K), dtype=torch.float32, device=dy4.device)
+        check(lib.nnl_conv2d_weight_transpose(ptr(wd), ptr(wt), gd.K, gd.R, gd.S, gd.C, stream()))
+        if wkey is not None and _WT_ACTIVE:                   # (only inside the prepare_backward .. finish_backward window: weights are fixed there)
+            _WT_PADDED[wkey] = wt
+    return dyd, wt, gd
+
+
+def _conv_dgrad(st, dy4, w4, g4, K):
+    "the logical input gradient (with the GradSlot shortcut added), or None when it was parked in st.give_slot"
+    dyd, wt, g = _conv_dgrad_operands(dy4, w4, g4, K)
+    dxn = torch.empty((g.N, g.H, g.W, g.C), dtype=torch.float32, device=dyd.device)
+    wsb = int(lib.nnl_conv2d_dgrad_workspace_bytes(g))
+    dws = _workspace(wsb, dyd.device)                       # None at 0 bytes: no Winograd kernel without a workspace
+    shortcut = None
+    if st.slot is not None:
+        shortcut, st.slot.tensor, st.slot.closed = st.slot.tensor, None, True
+    # stride 2: every output-parity class of a 3x3 / pad 1 filter has a tap, so every dx pixel passes through the epilogue
+    fuse = shortcut is not None and g.K % 16 == 0 and shortcut.numel() == dxn.numel() \
+        and (g.stride == 1 or (g.stride == 2 and g.R == 3 and g.S == 3 and g.pad == 1))
+    # a channel-padded dgrad transforms its own filter: not recorded under the weight (key 0; a 1x1 filter's mode 0 records nothing)
+    wmode = _wino_pref(w4.data_ptr() if g.K == K else 0, 1, g)
+    u = _WINO_U_BWD.get((w4.data_ptr(), wmode)) if (wmode and g.K == K) else None
+    if u is not None and u.numel() != _wino_u_numel(g.C, g.K, wmode):
+        u = None
+    check(lib.nnl_conv2d_dgrad_pre(ptr(dyd), ptr(wt), ptr(dxn), g, ptr(shortcut) if fuse else None, ptr(dws), wsb,
+                                   ptr(_tile_counters(dyd.device) if wsb else None), ptr(u), stream()))
+    if shortcut is not None and not fuse:
+        dxn += shortcut.view_as(dxn)
+    give = st.give_slot
+    if give is not None and not give.closed and st.c_in == g.C:
+        give.tensor = dxn                           # the block's first conv adds it inside its dgrad kernel
+        return None
+    return from_nhwc(dxn[..., :st.c_in] if st.c_in != g.C else dxn)
+
+
+def _conv_wgrad(st, xn, dy4, g4, K):
+    "the weight gradient in the weight's logical shape, written straight into the data-parallel bucket where that is safe"
+    dst = st.grad_dst
+    # in place only for a weight used ONCE this step: the gradients of a shared weight (RetinaNet heads on 5 pyramid
+    # levels) are summed by autograd and must not alias each other
+    if dst is not None and st.uses is not None and st.uses[0] == 1 and dst.dim() == 4 and g4.K == K and st.c_in == g4.C \
+            and dst.permute(0, 2, 3, 1).is_contiguous() and tuple(dst.shape) == (g4.K, g4.C, g4.R, g4.S):
+        dwn = dst.permute(0, 2, 3, 1)               # the bucket segment, viewed KRSC: the kernel writes it in place
+    else:
+        dwn = torch.empty((g4.K, g4.R, g4.S, g4.C), dtype=torch.float32, device=dy4.device)
+    wsb = int(lib.nnl_conv2d_wgrad_workspace_bytes(g4))
+    ws = _workspace(wsb, dy4.device, floor=True)            # never a null
+    check(lib.nnl_conv2d_wgrad(ptr(xn), ptr(dy4), ptr(dwn), g4, ptr(ws), wsb, stream()))
+    dw = from_nhwc(dwn[:K, :, :, :st.c_in])
+    # a 1x1 filter's [K, C, 1, 1] gradient: give it EXACTLY the parameter's strides (the size-1 dimensions make them ambiguous);
+    # otherwise AccumulateGrad sees a layout mismatch and clones it into the parameter's layout — one device copy per 1x1
+    # convolution and step (53 of RetinaNet's 68 rocclr_copyBuffer launches, profiles/r5_retinanet_kernel_stats.csv)
+    wshape, wstride = st.w_layout
+    if (g4.R == 1 and g4.S == 1 and wshape == tuple(dw.shape) and wstride != tuple(dw.stride()) and dw.is_contiguous(memory_format=torch.channels_last)
+            and wstride[1] == 1 and wstride[0] == dw.shape[1]):
+        dw = dw.as_strided(wshape, wstride)
+    return dw
+
+
+def _conv_bias_grad(dy4, g4, K):
+    "column sums of dy (the first K of them: the rest are padding)"
+    rows = g4.N * g4.P * g4.Q
+    db_full = torch.empty(g4.K, dtype=torch.float32, device=dy4.device)
+    cb = int(lib.nnl_colsum_workspace_bytes(rows, g4.K))
+    cws = _workspace(cb, dy4.device, floor=True)            # never a null
+    check(lib.nnl_colsum(ptr(dy4), ptr(db_full), rows, g4.K, ptr(cws), cb, stream()))
+    return db_full[:K]
+
+
 class _Conv2d(torch.autograd.Function):
     """nn.Conv2d forward/backward (reference Applications/VisionModels/retinanet.py:26-28,66-71,106-124,169-185,
     241-257,304,345) on the fp32-MFMA implicit-GEMM kernels; optional fused bias + ReLU epilogue."""
@@ -524,21 +695,11 @@ class _Conv2d(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, stride, pad, relu, slot=None, bn_pivot=None, give_slot=None):
         require_cuda(x, weight, bias)
-        ctx.slot = slot
-        ctx.give_slot = give_slot
-        ctx.grad_dst = getattr(weight, '_nnl_grad_dst', None)     # data parallel: the flat all-reduce bucket (dist.GradSync)
-        ctx.uses = getattr(weight, '_nnl_uses', None)             # forward uses of this weight in the current step
-        if ctx.uses is not None:
-            ctx.uses[0] += 1
-        xn = _pad_c4(to_nhwc(_f32c(x) if x.dim() != 4 else x.float()))
-        wn = _pad_c4(to_nhwc(weight.float()))
-        N, H, W, C = xn.shape
-        K, R, S, _ = wn.shape
-        g = _geom(N, H, W, C, K, R, S, stride, pad)
-        y = torch.empty((N, g.P, g.Q, K), dtype=torch.float32, device=x.device)
-        b = None if bias is None else _f32c(bias)
+        xn, wn, b, g, y = _conv_operands(x, weight, bias, stride, pad)
+        N, K, C = g.N, g.K, g.C
+        ctx.st = _conv_state(x, weight, bias, g, relu, slot, give_slot)
         wsb = int(lib.nnl_conv2d_fwd_workspace_bytes(g))         # balanced-schedule slabs (0 when the plain launch is used)
-        ws = torch.empty(wsb // 4, dtype=torch.float32, device=x.device) if wsb else None
+        ws = _workspace(wsb, x.device)                           # None at 0 bytes: no Winograd kernel without a workspace
         part, rows = None, _lib.i32(0)
         if bn_pivot is not None:                                  # BatchNorm statistics from the conv epilogue (include/nnl.h)
             part = torch.empty(((N * g.P * g.Q + 63) // 64) * K * 2, dtype=torch.float32, device=x.device)
@@ -553,177 +714,26 @@ class _Conv2d(torch.autograd.Function):
         else:
             part = part[:rows.value * K * 2]
         ctx.mark_non_differentiable(part)
-        ctx.set_materialize_grads(False)              # no zero-filled gradient tensor for `part` in backward
-        ctx.g, ctx.relu, ctx.has_bias = g, relu, bias is not None
-        ctx.c_in = x.shape[1]
-        ctx.w_layout = (tuple(weight.shape), tuple(weight.stride()))
+        ctx.set_materialize_grads(False)              # no zero-filled gradient tensor for `part` in backward: dy may be None
         ctx.save_for_backward(xn, wn, y if relu else None)        # relu: 0 none, 1 ReLU, 2 sigmoid (both gates need the OUTPUT y)
         return from_nhwc(y), part
 
     @staticmethod
     def backward(ctx, dy, _dpart=None):
-        if dy is None:
-            return (None,) * 9
         xn, wn, y = ctx.saved_tensors
-        g = ctx.g
-        pre = _padded_rows(dy, g.K) if (not ctx.relu and g.R == 1 and g.S == 1 and g.H == 1 and g.W == 1) else None
-        if pre is not None and pre.shape[-1] != g.K:
-            # the gradient arrived in a zero-padded buffer: run every pass on the padded K (zero channels contribute nothing)
-            dyn = pre
-            K = g.K
-            padk = dyn.shape[-1] - K
-            wn = torch.nn.functional.pad(wn, (0, 0, 0, 0, 0, 0, 0, padk))
-            g = _geom(g.N, g.H, g.W, g.C, K + padk, g.R, g.S, g.stride, g.pad)
-            return _Conv2d._backward_padded(ctx, dyn, wn, xn, g, K)
-        dyn = to_nhwc(dy.float())
-        db_gated = None
-        if ctx.relu:
-            # ReLU / sigmoid gate (+ the bias gradient of the gated dy) in one pass
-            want_db = ctx.has_bias and ctx.needs_input_grad[2]
-            rows = g.N * g.P * g.Q
-            gated = torch.empty_like(dyn)
-            cb = int(lib.nnl_colsum_workspace_bytes(rows, g.K)) if want_db else 0
-            cws = torch.empty(max(cb // 4, 1), dtype=torch.float32, device=dyn.device) if want_db else None
-            db_gated = torch.empty(g.K, dtype=torch.float32, device=dyn.device) if want_db else None
-            check(lib.nnl_act_gate_colsum(ptr(dyn), ptr(y), ptr(gated), ptr(db_gated), rows, g.K, int(ctx.relu), ptr(cws), cb, stream()))
-            dyn = gated
-        K = g.K
-        if K % 4 != 0:                      # e.g. RetinaNet 36/180-channel output convs: pad dy's channels
-            dyn = _pad_c4(dyn)
-            wn = torch.nn.functional.pad(wn, (0, 0, 0, 0, 0, 0, 0, dyn.shape[-1] - K))
-            g = _geom(g.N, g.H, g.W, g.C, dyn.shape[-1], g.R, g.S, g.stride, g.pad)
-        dx = dw = db = None
-        if ctx.needs_input_grad[0]:
-            g_w, dyn_w, wn_w = g, dyn, wn                   # (the weight gradient keeps the unpadded operands)
-            ktail = g.R == 1 and g.S == 1 and g.K % 4 == 0 and os.environ.get('NNL_IGEMM_KTAIL', '1') != '0'     # the tap kernel masks the k tail itself
-            if g.K % 16 != 0 and g.K >= 32 and not ktail:
-                # dgrad reduces over K: the tap-table kernel needs K % 16 == 0 (RetinaNet's 36- / 180-channel output convs would
-                # fall back to the first-generation kernel, ~2.5x slower); zero channels cost one copy of dy
-                padk = 16 - g.K % 16
-                dyn = torch.nn.functional.pad(dyn, (0, padk))
-                wkey = (wn.data_ptr(), tuple(wn.shape), padk)
-                g = _geom(g.N, g.H, g.W, g.C, g.K + padk, g.R, g.S, g.stride, g.pad)
-                wt = _WT_PADDED.get(wkey) if _WT_ACTIVE else None      # a shared filter (RetinaNet's output convs on five levels): padded + transposed ONCE per backward pass
-                if wt is None:
-                    wn = torch.nn.functional.pad(wn, (0, 0, 0, 0, 0, 0, 0, padk))
-            else:
-                wkey, wt = None, (_WT_ACTIVE.get(wn.data_ptr()) if g.K == K else None)
-            if wt is None or tuple(wt.shape) != (g.C, g.R, g.S, g.K):
-                wt = torch.empty((g.C, g.R, g.S, g.K), dtype=torch.float32, device=dyn.device)
-                check(lib.nnl_conv2d_weight_transpose(ptr(wn), ptr(wt), g.K, g.R, g.S, g.C, stream()))
-                if wkey is not None and _WT_ACTIVE:                   # (only inside the prepare_backward .. finish_backward window: weights are fixed there)
-                    _WT_PADDED[wkey] = wt
-            dxn = torch.empty((g.N, g.H, g.W, g.C), dtype=torch.float32, device=dyn.device)
-            wsb = int(lib.nnl_conv2d_dgrad_workspace_bytes(g))
-            dws = torch.empty(wsb // 4, dtype=torch.float32, device=dyn.device) if wsb else None
-            shortcut = None
-            if ctx.slot is not None:
-                shortcut, ctx.slot.tensor, ctx.slot.closed = ctx.slot.tensor, None, True
-            # stride 2: every output-parity class of a 3x3 / pad 1 filter has a tap, so every dx pixel passes through the epilogue
-            fuse = shortcut is not None and g.K % 16 == 0 and shortcut.numel() == dxn.numel() \
-                and (g.stride == 1 or (g.stride == 2 and g.R == 3 and g.S == 3 and g.pad == 1))
-            wmode = _wino_pref(wn.data_ptr() if g.K == K else 0, 1, g)      # (a channel-padded dgrad transforms its own filter: not recorded under the weight)
-            u = _WINO_U_BWD.get((wn.data_ptr(), wmode)) if (wmode and g.K == K) else None
-            if u is not None and u.numel() != _wino_u_numel(g.C, g.K, wmode):
-                u = None
-            check(lib.nnl_conv2d_dgrad_pre(ptr(dyn), ptr(wt), ptr(dxn), g, ptr(shortcut) if fuse else None, ptr(dws), wsb,
-                                           ptr(_tile_counters(dyn.device) if wsb else None), ptr(u), stream()))
-            if shortcut is not None and not fuse:
-                dxn += shortcut.view_as(dxn)
-            give = ctx.give_slot
-            if give is not None and not give.closed and ctx.c_in == g.C:
-                give.tensor = dxn                           # the block's first conv adds it inside its dgrad kernel
-            else:
-                dx = from_nhwc(dxn[..., :ctx.c_in] if ctx.c_in != g.C else dxn)
-            g, dyn, wn = g_w, dyn_w, wn_w
-        elif ctx.slot is not None:
-            ctx.slot.tensor, ctx.slot.closed = None, True
-        if ctx.needs_input_grad[1]:
-            dst = ctx.grad_dst
-            # in place only for a weight used ONCE this step: the gradients of a shared weight (RetinaNet heads on 5 pyramid
-            # levels) are summed by autograd and must not alias each other
-            if dst is not None and ctx.uses is not None and ctx.uses[0] == 1 and dst.dim() == 4 and g.K == K and ctx.c_in == g.C and dst.permute(0, 2, 3, 1).is_contiguous() \
-                    and tuple(dst.shape) == (g.K, g.C, g.R, g.S):
-                dwn = dst.permute(0, 2, 3, 1)               # the bucket segment, viewed KRSC: the kernel writes it in place
-            else:
-                dwn = torch.empty((g.K, g.R, g.S, g.C), dtype=torch.float32, device=dyn.device)
-            ws_bytes = int(lib.nnl_conv2d_wgrad_workspace_bytes(g))
-            ws = torch.empty(max(ws_bytes // 4, 1), dtype=torch.float32, device=dyn.device)
-            check(lib.nnl_conv2d_wgrad(ptr(xn), ptr(dyn), ptr(dwn), g, ptr(ws), ws_bytes, stream()))
-            dw = from_nhwc(dwn[:K, :, :, :ctx.c_in])
-            # a 1x1 filter's [K, C, 1, 1] gradient: give it EXACTLY the parameter's strides (the size-1 dimensions make them ambiguous);
-            # otherwise AccumulateGrad sees a layout mismatch and clones it into the parameter's layout — one device copy per 1x1
-            # convolution and step (53 of RetinaNet's 68 rocclr_copyBuffer launches, profiles/r5_retinanet_kernel_stats.csv)
-            wshape, wstride = getattr(ctx, 'w_layout', (None, None))
-            if (g.R == 1 and g.S == 1 and wshape == tuple(dw.shape) and wstride != tuple(dw.stride()) and dw.is_contiguous(memory_format=torch.channels_last)
-                    and wstride[1] == 1 and wstride[0] == dw.shape[1]):
-                dw = dw.as_strided(wshape, wstride)
-        if db_gated is not None:
-            db = db_gated
-        elif ctx.has_bias and ctx.needs_input_grad[2]:
-            db_full = torch.empty(g.K, dtype=torch.float32, device=dyn.device)
-            cb = int(lib.nnl_colsum_workspace_bytes(g.N * g.P * g.Q, g.K))
-            cws = torch.empty(max(cb // 4, 1), dtype=torch.float32, device=dyn.device)
-            check(lib.nnl_colsum(ptr(dyn), ptr(db_full), g.N * g.P * g.Q, g.K, ptr(cws), cb, stream()))
-            db = db_full[:K]
-        return dx, dw, db, None, None, None, None, None, None
+        return _conv_backward(ctx.st, xn, wn, y, dy, ctx.needs_input_grad[:3]) + (None,) * 6
 
 
-def _conv2d_backward_padded(ctx, dyn, wn, xn, g, K):
-    """backward of a linear layer (1x1 "image") whose output gradient dyn [N,1,1,Kp] is already zero-padded from K to Kp = g.K
-    channels: dgrad and wgrad on the padded K, bias gradient from the first K columns"""
-    dx = dw = db = None
-    if ctx.needs_input_grad[0]:
-        wt = torch.empty((g.C, g.R, g.S, g.K), dtype=torch.float32, device=dyn.device)
-        check(lib.nnl_conv2d_weight_transpose(ptr(wn), ptr(wt), g.K, g.R, g.S, g.C, stream()))
-        dxn = torch.empty((g.N, g.H, g.W, g.C), dtype=torch.float32, device=dyn.device)
-        wsb = int(lib.nnl_conv2d_dgrad_workspace_bytes(g))
-        dws = torch.empty(wsb // 4, dtype=torch.float32, device=dyn.device) if wsb else None
-        check(lib.nnl_conv2d_dgrad(ptr(dyn), ptr(wt), ptr(dxn), g, None, ptr(dws), wsb, ptr(_tile_counters(dyn.device) if wsb else None), stream()))
-        dx = from_nhwc(dxn[..., :ctx.c_in] if ctx.c_in != g.C else dxn)
-    if ctx.needs_input_grad[1]:
-        dwn = torch.empty((g.K, g.R, g.S, g.C), dtype=torch.float32, device=dyn.device)
-        ws_bytes = int(lib.nnl_conv2d_wgrad_workspace_bytes(g))
-        ws = torch.empty(max(ws_bytes // 4, 1), dtype=torch.float32, device=dyn.device)
-        check(lib.nnl_conv2d_wgrad(ptr(xn), ptr(dyn), ptr(dwn), g, ptr(ws), ws_bytes, stream()))
-        dw = from_nhwc(dwn[:K, :, :, :ctx.c_in])
-    if ctx.has_bias and ctx.needs_input_grad[2]:
-        db_full = torch.empty(g.K, dtype=torch.float32, device=dyn.device)
-        cb = int(lib.nnl_colsum_workspace_bytes(g.N * g.P * g.Q, g.K))
-        cws = torch.empty(max(cb // 4, 1), dtype=torch.float32, device=dyn.device)
-        check(lib.nnl_colsum(ptr(dyn), ptr(db_full), g.N * g.P * g.Q, g.K, ptr(cws), cb, stream()))
-        db = db_full[:K]
-    return dx, dw, db, None, None, None, None, None, None
-
-
-_Conv2d._backward_padded = staticmethod(_conv2d_backward_padded)
-
-
-class _NeedsView:
-    "a Function ctx seen through another needs_input_grad (so that _Conv2d.backward can serve Functions with other input lists)"
-
-    def __init__(self, ctx, needs):
-        object.__setattr__(self, '_ctx', ctx)
-        object.__setattr__(self, 'needs_input_grad', tuple(needs) + (False,) * 6)
-
-    def __getattr__(self, name):
-        return getattr(self._ctx, name)
-
-    def __setattr__(self, name, value):
-        setattr(self._ctx, name, value)
-
-
-def _conv_backward_core(ctx, dy, needs):
-    "(dx, dw, db) of a convolution whose ctx carries the fields _Conv2d.forward sets"
-    out = _Conv2d.backward(_NeedsView(ctx, needs), dy)
-    return out[0], out[1], out[2]
+def _conv(x, weight, bias, *, stride=1, pad=0, relu=0, slot=None, bn_pivot=None, give_slot=None):
+    "(y, BatchNorm partials) of _Conv2d: the one place that spells its argument order"
+    return _Conv2d.apply(x, weight, bias, int(stride), int(pad), int(relu), slot, bn_pivot, give_slot)
 
 
 def conv2d(x, weight, bias=None, stride=1, pad=0, relu=False, grad_slot=None, give_slot=None):
     """y = act(conv2d(x, weight, bias, stride, padding=pad)); relu: False / 0 none, True / 1 ReLU, 2 sigmoid (fused into the
     kernel epilogue; the backward gate and the bias gradient are one pass); x logical [N,C,H,W], weight [K,C,R,S].
     grad_slot: see GradSlot (the shortcut gradient of a residual block, added to dx inside the dgrad kernel)."""
-    return _Conv2d.apply(x, weight, bias, int(stride), int(pad), int(relu), grad_slot, None, give_slot)[0]
+    return _conv(x, weight, bias, stride=stride, pad=pad, relu=relu, slot=grad_slot, give_slot=give_slot)[0]
 
 
 class _ConvAddUp2(torch.autograd.Function):
@@ -734,26 +744,14 @@ class _ConvAddUp2(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, small, stride, pad):
         require_cuda(x, weight, bias, small)
-        ctx.slot = ctx.give_slot = None
-        ctx.grad_dst = getattr(weight, '_nnl_grad_dst', None)
-        ctx.uses = getattr(weight, '_nnl_uses', None)
-        if ctx.uses is not None:
-            ctx.uses[0] += 1
-        xn = _pad_c4(to_nhwc(x.float()))
-        wn = _pad_c4(to_nhwc(weight.float()))
+        xn, wn, b, g, y = _conv_operands(x, weight, bias, stride, pad)
         sn = to_nhwc(small.float())
-        N, H, W, C = xn.shape
-        K, R, S, _ = wn.shape
-        g = _geom(N, H, W, C, K, R, S, stride, pad)
-        if tuple(sn.shape) != (N, g.P // 2, g.Q // 2, K) or g.P % 2 or g.Q % 2:
+        ctx.small_shape = (g.N, g.P // 2, g.Q // 2, g.K)
+        if tuple(sn.shape) != ctx.small_shape or g.P % 2 or g.Q % 2:
             raise _lib.NnlError('conv_add_upsampled: `small` %s is not [N, K, P/2, Q/2] of the %dx%d output' % (tuple(small.shape), g.P, g.Q))
-        y = torch.empty((N, g.P, g.Q, K), dtype=torch.float32, device=x.device)
-        b = None if bias is None else _f32c(bias)
+        ctx.st = _conv_state(x, weight, bias, g, 0)
         check(lib.nnl_conv2d_fwd_add_up2(ptr(xn), ptr(wn), ptr(b), ptr(sn), ptr(y), g, stream()))
-        ctx.g, ctx.relu, ctx.has_bias = g, 0, bias is not None
-        ctx.c_in = x.shape[1]
-        ctx.small_shape = (N, g.P // 2, g.Q // 2, K)
-        ctx.save_for_backward(xn, wn, None)
+        ctx.save_for_backward(xn, wn)
         return from_nhwc(y)
 
     @staticmethod
@@ -765,10 +763,8 @@ class _ConvAddUp2(torch.autograd.Function):
             ds = torch.empty(ctx.small_shape, dtype=torch.float32, device=dy.device)
             check(lib.nnl_upsample2_bwd(ptr(dyn), ptr(ds), N, h, w, K, stream()))
             dsmall = from_nhwc(ds)
-        need = ctx.needs_input_grad
-        ctx_needs = (need[0], need[1], need[2])
-        dx, dw, db = _conv_backward_core(ctx, dy, ctx_needs)
-        return dx, dw, db, dsmall, None, None
+        xn, wn = ctx.saved_tensors
+        return _conv_backward(ctx.st, xn, wn, None, dy, ctx.needs_input_grad[:3]) + (dsmall, None, None)
 
 
 def conv_add_upsampled(x, weight, bias, small, stride=1, pad=0):
@@ -779,7 +775,7 @@ def conv_add_upsampled(x, weight, bias, small, stride=1, pad=0):
 def conv2d_with_bn_stats(x, weight, bias, stride, pad, bn_pivot, grad_slot=None, give_slot=None):
     """conv2d whose epilogue also reduces the BatchNorm batch statistics of its output against `bn_pivot` [K].  Returns (y, partials);
     partials is empty when this launch could not produce them (the BatchNorm then runs its own statistics pass)."""
-    return _Conv2d.apply(x, weight, bias, int(stride), int(pad), False, grad_slot, bn_pivot, give_slot)
+    return _conv(x, weight, bias, stride=stride, pad=pad, slot=grad_slot, bn_pivot=bn_pivot, give_slot=give_slot)
 
 
 def _rows_in_place(x):
@@ -816,7 +812,7 @@ class _LinearSmall(torch.autograd.Function):
         dw = torch.empty(N, K, dtype=torch.float32, device=dev) if ctx.needs_input_grad[1] else None
         db = torch.empty(N, dtype=torch.float32, device=dev) if (ctx.has_bias and ctx.needs_input_grad[2]) else None
         wsb = int(lib.nnl_linear_small_bwd_workspace_bytes(M, K, N)) if (dw is not None or db is not None) else 0
-        ws = torch.empty(max(wsb // 4, 1), dtype=torch.float32, device=dev) if wsb else None
+        ws = _workspace(wsb, dev)
         check(lib.nnl_linear_small_bwd(ptr(dy), ptr(x), ptr(w), ptr(dx), ptr(dw), ptr(db), M, K, x.stride(0) if M > 1 else K, N, ptr(ws), wsb,
                                        stream()))
         return dx, dw, db
@@ -830,7 +826,7 @@ def linear(x, weight, bias=None, relu=False):
     x2 = x.reshape(-1, x.shape[-1])
     if not relu and weight.shape[0] <= 4 and x2.is_cuda and x2.shape[0] > 0:
         return _LinearSmall.apply(x2, weight, bias).reshape(*lead, weight.shape[0])
-    y = _Conv2d.apply(x2[:, :, None, None], weight[:, :, None, None], bias, 1, 0, int(relu), None, None)[0]
+    y = _conv(x2[:, :, None, None], weight[:, :, None, None], bias, relu=relu)[0]
     return y.reshape(*lead, weight.shape[0])
 
 
@@ -867,7 +863,7 @@ class _BNAct(torch.autograd.Function):
         mean = torch.empty(C, dtype=torch.float32, device=xm.device)
         invstd = torch.empty(C, dtype=torch.float32, device=xm.device)
         wsb = int(lib.nnl_bn_workspace_bytes(rows, C))
-        ws = torch.empty(wsb // 4, dtype=torch.float32, device=xm.device)
+        ws = _workspace(wsb, xm.device)
         mask = _relu_mask(rows, C, xm.device) if relu else None      # 1 bit / element for the backward's ReLU gate
         check(lib.nnl_bn_fwd(ptr(xm), ptr(gamma), ptr(beta), ptr(rm), ptr(y), ptr(mean), ptr(invstd), ptr(running_mean),
                              ptr(running_var), rows, C, float(eps), float(momentum), int(training), int(relu), ptr(nbt),
@@ -888,7 +884,7 @@ class _BNAct(torch.autograd.Function):
         dgamma = torch.empty(C, dtype=torch.float32, device=xm.device) if gamma is not None else None
         dbeta = torch.empty(C, dtype=torch.float32, device=xm.device) if gamma is not None else None
         wsb = int(lib.nnl_bn_workspace_bytes(rows, C))
-        ws = torch.empty(wsb // 4, dtype=torch.float32, device=xm.device)
+        ws = _workspace(wsb, xm.device)
         check(lib.nnl_bn_bwd(ptr(dym), None, ptr(mask), ptr(xm), ptr(gamma), ptr(mean), ptr(invstd), ptr(dx), ptr(dres),
                              ptr(dgamma), ptr(dbeta), rows, C, int(training), int(relu), ptr(ws), wsb, stream()))
         if ctx.slot is not None and dres is not None:
@@ -915,7 +911,7 @@ class _SyncBNAct(torch.autograd.Function):
         rm = None if residual is None else _rows_view(residual)[0]
         dev = xm.device
         wsb = int(lib.nnl_bn_workspace_bytes(rows, C))
-        ws = torch.empty(wsb // 4, dtype=torch.float32, device=dev)
+        ws = _workspace(wsb, dev)
         stats = torch.empty(2 * C + 2, dtype=torch.float32, device=dev)
         check(lib.nnl_bn_sync_stats(ptr(xm), ptr(stats), rows, C, ptr(ws), wsb, stream()))
         all_stats = comm.all_gather(stats, group)                  # [world, 2C+2], rank order
@@ -939,7 +935,7 @@ class _SyncBNAct(torch.autograd.Function):
         rows, C = xm.shape
         dev = xm.device
         wsb = int(lib.nnl_bn_workspace_bytes(rows, C))
-        ws = torch.empty(wsb // 4, dtype=torch.float32, device=dev)
+        ws = _workspace(wsb, dev)
         sums = torch.empty(2 * C, dtype=torch.float32, device=dev)
         check(lib.nnl_bn_sync_bwd_reduce(ptr(dym), None, ptr(mask), ptr(xm), ptr(mean), ptr(invstd), ptr(sums), rows, C, int(relu),
                                          ptr(ws), wsb, stream()))
@@ -975,23 +971,26 @@ class DistComm:
         return out
 
 
+def _bn_mode(bn):
+    "(training, momentum, nbt incremented inside the finalize kernel, rmean, rvar); momentum None = cumulative average (bn_act only)"
+    training = bn.training or (bn.running_mean is None)
+    momentum, nbt = 0.0, None
+    if bn.training and bn.track_running_stats:
+        nbt, momentum = bn.num_batches_tracked, bn.momentum
+    stats = not training or bn.track_running_stats
+    return training, momentum, nbt, (bn.running_mean if stats else None), (bn.running_var if stats else None)
+
+
 def bn_act(bn, x, residual=None, relu=True, grad_slot=None, ext_stats=None, pivot_out=None):
     """BatchNorm (train: batch statistics + running-stat update; eval: running stats) -> (+ residual) -> ReLU in the HIP
     kernels of batchnorm.hip: the bn -> `out += residual` -> relu tail of BasicBlock / Bottleneck (reference
     retinanet.py:47-48,53-57,81-95), the stem (:372-373) and the BatchNorm1d layers (General/Layers.py:40).
     `bn` is the nn.BatchNorm{1,2}d module holding weight / bias / running stats (state_dict unchanged).  A module marked by
     dist.enable_sync_bn (`bn.nnl_sync = (group, comm)`) uses global-batch statistics in training mode."""
-    training = bn.training or (bn.running_mean is None)
-    momentum, nbt = 0.0, None
-    if bn.training and bn.track_running_stats:
-        nbt = bn.num_batches_tracked                       # incremented inside the finalize kernel
-        if bn.momentum is not None:
-            momentum = bn.momentum
-        else:                                              # cumulative moving average: the factor needs the count on the host
-            nbt.add_(1)
-            momentum, nbt = 1.0 / float(nbt.item()), None
-    rmean = bn.running_mean if (not training or bn.track_running_stats) else None
-    rvar = bn.running_var if (not training or bn.track_running_stats) else None
+    training, momentum, nbt, rmean, rvar = _bn_mode(bn)
+    if momentum is None:                                   # cumulative moving average: the factor needs the count on the host
+        nbt.add_(1)
+        momentum, nbt = 1.0 / float(nbt.item()), None
     sync = getattr(bn, 'nnl_sync', None)
     if sync is not None and training:
         return _SyncBNAct.apply(x, residual, bn.weight, bn.bias, rmean, rvar, momentum, bn.eps, relu, nbt, sync[0], sync[1],
@@ -1033,15 +1032,18 @@ def conv_bn_act(conv, bn, x, residual=None, relu=True, conv_slot=None, bn_slot=N
     fuse = (bn.training and bn.track_running_stats and bn.running_mean is not None and bn.momentum is not None
             and getattr(bn, 'nnl_sync', None) is None and x.is_cuda and conv.bias is None and not conv.fuse_relu
             and torch.is_grad_enabled() and os.environ.get('NNL_BN_EPI_STATS', '1') != '0')
+
+    def unfused(**kw):
+        return bn_act(bn, conv(x, grad_slot=conv_slot, give_slot=conv_give), residual=residual, relu=relu, grad_slot=bn_slot, **kw)
     if not fuse:
-        return bn_act(bn, conv(x, grad_slot=conv_slot, give_slot=conv_give), residual=residual, relu=relu, grad_slot=bn_slot)
+        return unfused()
     pivot = getattr(bn, '_nnl_pivot', None)
     if pivot is None or pivot.device != x.device or pivot.numel() != bn.num_features:
         if torch.cuda.is_current_stream_capturing():
-            return bn_act(bn, conv(x, grad_slot=conv_slot, give_slot=conv_give), residual=residual, relu=relu, grad_slot=bn_slot)
+            return unfused()
         pivot = torch.empty(bn.num_features, dtype=torch.float32, device=x.device)
         object.__setattr__(bn, '_nnl_pivot', pivot)                  # plain attribute: not a buffer, not in the state_dict
-        return bn_act(bn, conv(x, grad_slot=conv_slot, give_slot=conv_give), residual=residual, relu=relu, grad_slot=bn_slot, pivot_out=pivot)
+        return unfused(pivot_out=pivot)
     y, part = conv2d_with_bn_stats(x, conv.weight, None, conv.stride[0], conv.padding[0], pivot, conv_slot, conv_give)
     return bn_act(bn, y, residual=residual, relu=relu, grad_slot=bn_slot, ext_stats=(part, pivot), pivot_out=pivot)
 
@@ -1061,7 +1063,7 @@ def linear_relu_bn(lin, bn, x):
         pivot = torch.empty(bn.num_features, dtype=torch.float32, device=x.device)
         object.__setattr__(bn, '_nnl_pivot', pivot)                  # plain attribute: not a buffer, not in the state_dict
         return bn_act(bn, y, relu=False, pivot_out=pivot)
-    y, part = _Conv2d.apply(x[:, :, None, None], lin.weight[:, :, None, None], lin.bias, 1, 0, 1, None, pivot, None)
+    y, part = _conv(x[:, :, None, None], lin.weight[:, :, None, None], lin.bias, relu=1, bn_pivot=pivot)
     return bn_act(bn, y.reshape(x.shape[0], lin.weight.shape[0]), relu=False, ext_stats=(part, pivot), pivot_out=pivot)
 
 
@@ -1111,7 +1113,7 @@ class _BNReLUMaxPool(torch.autograd.Function):
         idx = torch.empty(N, P, Q, C, dtype=torch.uint8, device=dev)
         stats = torch.empty(4, C, dtype=torch.float32, device=dev)               # mean, invstd, scale, shift
         wsb = int(lib.nnl_bn_workspace_bytes(N * H * W, C))
-        ws = torch.empty(wsb // 4, dtype=torch.float32, device=dev)
+        ws = _workspace(wsb, dev)
         check(lib.nnl_bn_relu_maxpool_fwd(ptr(xn), ptr(gamma), ptr(beta), ptr(y), ptr(idx), ptr(stats[0]), ptr(stats[1]),
                                           ptr(stats[2]), ptr(stats[3]), ptr(running_mean), ptr(running_var), N, H, W, C, P, Q,
                                           ksize, stride, pad, float(eps), float(momentum), int(training), ptr(nbt), ptr(ws), wsb,
@@ -1129,7 +1131,7 @@ class _BNReLUMaxPool(torch.autograd.Function):
         dgamma = torch.empty(C, dtype=torch.float32, device=xn.device) if gamma is not None else None
         dbeta = torch.empty(C, dtype=torch.float32, device=xn.device) if gamma is not None else None
         wsb = int(lib.nnl_bn_workspace_bytes(N * H * W, C))
-        ws = torch.empty(wsb // 4, dtype=torch.float32, device=xn.device)
+        ws = _workspace(wsb, xn.device)
         check(lib.nnl_bn_relu_maxpool_bwd(ptr(dyn), ptr(y), ptr(idx), ptr(xn), ptr(gamma), ptr(beta), ptr(stats[0]), ptr(stats[1]),
                                           ptr(stats[2]), ptr(stats[3]), ptr(dx), ptr(dgamma), ptr(dbeta), N, H, W, C, P, Q, ksize, stride, pad,
                                           int(training), ptr(ws), wsb, stream()))
@@ -1151,12 +1153,7 @@ def conv_bn_relu_maxpool(conv, bn, pool, x):
     if not fuse:
         return pool(conv_bn_act(conv, bn, x, relu=True))
     y = conv(x)
-    training = bn.training or (bn.running_mean is None)
-    momentum, nbt = 0.0, None
-    if bn.training and bn.track_running_stats:
-        nbt, momentum = bn.num_batches_tracked, bn.momentum
-    rmean = bn.running_mean if (not training or bn.track_running_stats) else None
-    rvar = bn.running_var if (not training or bn.track_running_stats) else None
+    training, momentum, nbt, rmean, rvar = _bn_mode(bn)    # (momentum is not None: the cumulative average was refused above)
     return _BNReLUMaxPool.apply(y, bn.weight, bn.bias, rmean, rvar, training, momentum, bn.eps, nbt, k, s, p)
 
 
@@ -1174,7 +1171,6 @@ class TabularPlan:
     moves (data_ptr / device change)."""
 
     def __init__(self, weights):
-        import numpy as np
         dev = weights[0].device
         self.key = tuple((w.data_ptr(), tuple(w.shape)) for w in weights) + (str(dev),)
         self.sync = None
@@ -1265,7 +1261,7 @@ class _TabEmbedConcat(torch.autograd.Function):
         else:
             dout = _f32c(dout)
             wsb = int(lib.nnl_tab_scatter_bwd_workspace_bytes(bs, plan.ncat))            # sample-order (deterministic) scatter-add
-            ws = torch.empty(max(wsb, 4), dtype=torch.uint8, device=dout.device)
+            ws = _workspace(wsb, dout.device, floor=True)                                # never a null
             check(lib.nnl_tab_scatter_bwd(ptr(xcat), ptr(plan.card), ptr(plan.dim), ptr(plan.col_off), ptr(plan.col_table),
                                           ptr(plan.grad_off), ptr(row_mask), ptr(cont_mask), ptr(dout), ptr(flat), plan.grad_elems,
                                           ptr(dcont), bs, plan.ncat, plan.cat_width, n_cont, dout.shape[1], ptr(ws), wsb, stream()))
@@ -1341,7 +1337,7 @@ class _RetinaLoss(torch.autograd.Function):
         npos = torch.empty(bs, dtype=torch.float32, device=dev)
         out = torch.empty(3, dtype=torch.float32, device=dev)
         wsb = int(lib.nnl_retina_loss_workspace_bytes(bs, A))
-        ws = torch.empty(max(wsb // 4, 1), dtype=torch.float32, device=dev)
+        ws = _workspace(wsb, dev, floor=True)                   # never a null
         check(lib.nnl_retina_loss_fwd(ptr(anchors), ptr(reg), ptr(clas), ptr(boxes), ptr(cats), ptr(state), ptr(npos), ptr(out),
                                       bs, A, K, M, float(beta), float(alpha), float(gamma), ptr(ws), wsb, stream()))
         ctx.save_for_backward(anchors, reg, clas, boxes, cats, state, npos)

@@ -41,10 +41,10 @@ class _LSTMRecurrence(torch.autograd.Function):
         w_hh = w_pad                                        # [4H, Hp]: columns >= H are zero
         y = torch.empty(T, B, H, dtype=torch.float32, device=dev)
         cy = torch.empty(T, B, H, dtype=torch.float32, device=dev)
-        from .ops import lstm_timeout_flag
+        from .ops import _workspace, lstm_timeout_flag
         gates = torch.empty(T, B, G, dtype=torch.float32, device=dev)
         wsb = int(lib.nnl_lstm_workspace_bytes(T, B, H))
-        ws = torch.empty(wsb // 4, dtype=torch.float32, device=dev)
+        ws = _workspace(wsb, dev)
         check(lib.nnl_lstm_fwd(ptr(gx), ptr(w_pad), ptr(h0), ptr(c0), ptr(y), ptr(cy), ptr(gates), T, B, H, ptr(ws), wsb,
                                ptr(lstm_timeout_flag(dev)), stream()))
         ctx.save_for_backward(w_hh, h0, c0, y, cy, gates, wm)
@@ -70,9 +70,9 @@ class _LSTMRecurrence(torch.autograd.Function):
             dgates[:, :, G:].zero_()                         # only the pad columns must be zero (round 4 zero-filled all 82 MB per layer)
         dh0 = torch.empty(B, H, dtype=torch.float32, device=dev)
         dc0 = torch.empty(B, H, dtype=torch.float32, device=dev)
+        from .ops import _workspace, lstm_timeout_flag
         wsb = int(lib.nnl_lstm_workspace_bytes(T, B, H))
-        ws = torch.empty(wsb // 4, dtype=torch.float32, device=dev)
-        from .ops import lstm_timeout_flag
+        ws = _workspace(wsb, dev)
         check(lib.nnl_lstm_bwd(ptr(dy), ptr(dhT), ptr(dcT), ptr(gates), ptr(cy), ptr(c0), ptr(w_t), ptr(dgates), ptr(dh0),
                                ptr(dc0), T, B, H, ptr(ws), wsb, ptr(lstm_timeout_flag(dev)), stream()))
         dw = None
@@ -90,7 +90,7 @@ class _LSTMRecurrence(torch.autograd.Function):
             g = _lib.ConvGeom(T * B, 1, 1, Hp, Gp, 1, 1, 1, 0, 1, 1)
             dwp = torch.empty(Gp, Hp, dtype=torch.float32, device=dev)
             wb = int(lib.nnl_conv2d_wgrad_workspace_bytes(g))
-            wws = torch.empty(max(wb // 4, 1), dtype=torch.float32, device=dev)
+            wws = _workspace(wb, dev, floor=True)             # never a null
             use, p, seed = ctx.drop
             dw = torch.empty(G, H, dtype=torch.float32, device=dev) if use else dwp[:G, :H]
             check(lib.nnl_conv2d_wgrad(ptr(hprev), ptr(dgates.view(T * B, Gp)), ptr(dwp), g, ptr(wws), wb, stream()))
@@ -136,12 +136,13 @@ class _EmbeddingRowMask(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout):
+        from .ops import _workspace
         xi, rm = ctx.saved_tensors
         V, D, pad = ctx.meta
         dout = _f32c(dout)
         dW = torch.empty(V, D, dtype=torch.float32, device=dout.device)
         wsb = int(lib.nnl_embedding_rowmask_bwd_workspace_bytes(xi.numel()))         # sample-order (deterministic) scatter-add
-        ws = torch.empty(max(wsb, 4), dtype=torch.uint8, device=dout.device)
+        ws = _workspace(wsb, dout.device, floor=True)                                 # never a null
         check(lib.nnl_embedding_rowmask_bwd(ptr(xi), ptr(rm), ptr(dout), ptr(dW), xi.numel(), V, D, pad, ptr(ws), wsb, stream()))
         return None, dW, None, None
 
@@ -208,13 +209,14 @@ class _SeqReg(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, h, alpha, beta):
+        from .ops import _workspace
         require_cuda(h)
         h = _f32c(h)
         T = h.shape[0]
         R = h.numel() // max(T, 1)
         out = torch.empty(3, dtype=torch.float32, device=h.device)
         wsb = int(lib.nnl_seq_reg_workspace_bytes(T, R))
-        ws = torch.empty(max(wsb // 4, 1), dtype=torch.float32, device=h.device)
+        ws = _workspace(wsb, h.device, floor=True)          # never a null
         check(lib.nnl_seq_reg_fwd(ptr(h), ptr(out), T, R, float(alpha), float(beta), ptr(ws), wsb, stream()))
         ctx.save_for_backward(h)
         ctx.ab = (float(alpha), float(beta))
@@ -243,7 +245,7 @@ class _AttentionPool(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, h, w2, b2, enc_out, x, pad_token):
-        from .ops import _tile_counters
+        from .ops import _tile_counters, _workspace
         require_cuda(h, w2, b2, enc_out, x)
         ctx.w2_shape, ctx.b2_shape = w2.shape, b2.shape
         h, enc_out = _f32c(h), _f32c(enc_out)
@@ -258,7 +260,7 @@ class _AttentionPool(torch.autograd.Function):
         attn = torch.empty(T, B, dtype=torch.float32, device=dev)
         pooled = torch.empty(B, E, dtype=torch.float32, device=dev)
         wsb = int(lib.nnl_attn_pool_workspace_bytes(T, B, E, A))
-        ws = torch.empty(wsb // 4, dtype=torch.float32, device=dev)
+        ws = _workspace(wsb, dev)
         cnt = _tile_counters(dev)
         check(lib.nnl_attn_pool_fwd(ptr(h), ptr(w2), ptr(b2), ptr(enc_out), ptr(xi), int(pad_token), ptr(attn), ptr(pooled),
                                     T, B, E, A, ptr(ws), wsb, ptr(cnt), cnt.numel(), stream()))
@@ -268,7 +270,7 @@ class _AttentionPool(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dattn, dpooled):
-        from .ops import _tile_counters
+        from .ops import _tile_counters, _workspace
         h, w2, enc_out, attn = ctx.saved_tensors
         T, B, E = enc_out.shape
         A = h.shape[2]
@@ -280,7 +282,7 @@ class _AttentionPool(torch.autograd.Function):
         dw2 = torch.empty(A, dtype=torch.float32, device=dev)
         db2 = torch.empty(1, dtype=torch.float32, device=dev)
         wsb = int(lib.nnl_attn_pool_workspace_bytes(T, B, E, A))
-        ws = torch.empty(wsb // 4, dtype=torch.float32, device=dev)
+        ws = _workspace(wsb, dev)
         cnt = _tile_counters(dev)
         check(lib.nnl_attn_pool_bwd(ptr(h), ptr(w2), ptr(enc_out), ptr(attn), ptr(dpooled), ptr(dattn), ptr(dh), ptr(denc),
                                     ptr(dw2), ptr(db2), T, B, E, A, ptr(ws), wsb, ptr(cnt), cnt.numel(), stream()))

@@ -467,3 +467,67 @@ def test_shared_parameters_fan_out_sums_the_per_call_gradients_in_one_launch():
     with torch.no_grad(), ops.shared_params([conv], 5):
         assert not ops._FAN                                          # no autograd: nothing to fan out
         assert_close(conv(xs[1]), conv(xs[1]), rtol=0, atol=0, msg='eval')
+
+
+class _HandsOverPaddedGrad(torch.autograd.Function):
+    """identity whose backward returns its gradient the way the softmax-CE backward and the LSTM's dgates do (ops_text.py): as the
+    [:, :K] view of a zero-padded [M, ld] buffer registered with ops.register_padded_grad"""
+
+    @staticmethod
+    def forward(ctx, y):
+        return y.clone()
+
+    @staticmethod
+    def backward(ctx, dy):
+        from neuralnetworklibrary_amd import ops
+        M, K = dy.shape
+        ld = (K + 15) // 16 * 16
+        buf = torch.zeros(M, ld, dtype=torch.float32, device=dy.device)
+        buf[:, :K] = dy
+        ops.register_padded_grad(buf, ld)
+        return buf[:, :K]
+
+
+@pytest.mark.parametrize('x_grad', [True, False], ids=['dx', 'no_dx'])
+@pytest.mark.parametrize('bias', [True, False], ids=['bias', 'no_bias'])
+@pytest.mark.parametrize('K', [47, 36, 175], ids=['K47', 'K36', 'K175'])
+def test_linear_backward_of_a_registered_padded_gradient(K, bias, x_grad, monkeypatch):
+    """ops.linear whose output gradient arrives through register_padded_grad (the language model's decoder at V = 47 343 and the
+    LSTM input projections reach this path; nothing tested it on its own): K % 16 = 15 with K % 4 = 3 (47, 175) and K % 16 = 4 with
+    K % 4 = 0 (36).  The layer must recognise the padded base (checked: _padded_rows returns the [M,1,1,ld] rows) and give the dx,
+    dw, db of torch.nn.functional.linear (fp64 on the CPU), with or without bias and with the input gradient switched off."""
+    from neuralnetworklibrary_amd import ops
+    M, C = 70, 44
+    g = torch.Generator().manual_seed(K * 4 + 2 * bias + x_grad)
+    x = torch.randn(M, C, generator=g)
+    w = torch.randn(K, C, generator=g) / C ** 0.5
+    b = torch.randn(K, generator=g) if bias else None
+    dy = torch.randn(M, K, generator=g)
+    xc, wc = x.double().requires_grad_(x_grad), w.double().requires_grad_(True)
+    bc = b.double().requires_grad_(True) if bias else None
+    ref = F.linear(xc, wc, bc)
+    ref.backward(dy.double())
+
+    seen = []
+    padded_rows = ops._padded_rows
+
+    def spy(dy_, K_):
+        seen.append(padded_rows(dy_, K_))
+        return seen[-1]
+    monkeypatch.setattr(ops, '_padded_rows', spy)
+    xg, wg = x.to(DEV).requires_grad_(x_grad), w.to(DEV).requires_grad_(True)
+    bg = b.to(DEV).requires_grad_(True) if bias else None
+    out = _HandsOverPaddedGrad.apply(ops.linear(xg, wg, bg))
+    out.backward(dy.to(DEV))
+    ld = (K + 15) // 16 * 16
+    assert len(seen) == 1 and seen[0] is not None and tuple(seen[0].shape) == (M, 1, 1, ld), 'the padded buffer was not recognised'
+    assert_close(out, ref, rtol=1e-4, atol=1e-5 * ref.abs().max().item(), msg='y')
+    if x_grad:
+        assert_close(xg.grad, xc.grad, rtol=1e-4, atol=1e-5 * xc.grad.abs().max().item(), msg='dx')
+    else:
+        assert xg.grad is None
+    assert wg.grad.shape == wg.shape
+    assert_close(wg.grad, wc.grad, rtol=1e-4, atol=1e-5 * wc.grad.abs().max().item(), msg='dw')
+    if bias:
+        assert bg.grad.shape == bg.shape
+        assert_close(bg.grad, bc.grad, rtol=1e-4, atol=1e-5 * bc.grad.abs().max().item(), msg='db')

@@ -3,10 +3,13 @@
   3 tabular  Rossmann-shape StructuredDataNet bs=1024, fc [1000,500,1], Adam                      samples/s
   4 lm       AWD-LSTM LanguageModelNet 400/1150/3, V=47343, bs=64 bptt=70, Adam, RegSeqCE(2,1)    tokens/s
   5 retina   ObjectDetectionNet(20) R50-FPN 512x512 bs=16, SSD_loss, SGD momentum                 images/s
-Usage: python tools/bench_heads.py [collab tabular lm retina] [--steps 10] [--graphs]"""
+Usage: python tools/bench_heads.py [collab tabular lm retina] [--steps 10] [--graphs] [--dump-outputs DIR]
+--dump-outputs DIR writes, per configuration, DIR/<config>/{loss,params,grads}.npy of the LAST step in the format of bench.py's
+--dump-outputs.  Every configuration seeds torch's global generators first, so two processes compute the same steps."""
 import argparse
 import json
 import os
+import re
 import sys
 import time
 
@@ -28,6 +31,30 @@ class Data:
 
 
 GRAPHS = False
+DUMP = None                            # --dump-outputs DIR
+DUMP_SAMPLE = 1 << 22                  # elements of the parameter / gradient sample (bench.py's rule)
+
+
+def seed_all(seed):
+    "model initialisation, dropout and every unseeded draw of a configuration: the same in every process"
+    torch.manual_seed(seed)
+    torch.cuda.manual_seed(seed)
+
+
+def dump_outputs(learner, loss, outdir):
+    """loss.npy (float64 [1]), params.npy / grads.npy (float32): all tensors of model.parameters() flattened in order and sampled at
+    DUMP_SAMPLE fixed indices (seed 0, sorted; every element when there are fewer) — as bench.py's dump_outputs"""
+    os.makedirs(outdir, exist_ok=True)
+    params = list(learner.model.parameters())
+    total = sum(p.numel() for p in params)
+    idx = np.arange(total) if total <= DUMP_SAMPLE else np.sort(np.random.RandomState(0).choice(total, DUMP_SAMPLE, replace=False))
+    with torch.no_grad():
+        idx_t = torch.from_numpy(idx).to(params[0].device)
+        flat_p = torch.cat([p.detach().reshape(-1).float() for p in params])
+        flat_g = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1).float() for p in params])
+        np.save(os.path.join(outdir, 'params.npy'), flat_p[idx_t].cpu().numpy())
+        np.save(os.path.join(outdir, 'grads.npy'), flat_g[idx_t].cpu().numpy())
+    np.save(os.path.join(outdir, 'loss.npy'), np.array([float(loss)], dtype=np.float64))
 
 
 def run(name, learner, batches, lr, unit, units_per_step, steps, warmup=3, **kw):
@@ -46,9 +73,11 @@ def run(name, learner, batches, lr, unit, units_per_step, steps, warmup=3, **kw)
     dt = (time.perf_counter() - t0) / steps
     _lib.prof_enable(True)
     for i in range(3):
-        learner.train1minibatch(*batches[i % len(batches)], lr, **kw)
+        loss = learner.train1minibatch(*batches[i % len(batches)], lr, **kw)
     torch.cuda.synchronize()
     _lib.prof_enable(False)
+    if DUMP:
+        dump_outputs(learner, loss, os.path.join(DUMP, re.sub(r'[^A-Za-z0-9]+', '_', name).strip('_')))
     prof = {k: round(v['ms'] / 3, 3) for k, v in _lib.prof_collect().items() if v['launches']}
     print(json.dumps({'config': name, 'ms_per_step': round(dt * 1e3, 3), 'value': round(units_per_step / dt, 1), 'unit': unit,
                       'last_loss': loss, 'hip_ms_per_step_by_kind': prof}))
@@ -56,6 +85,7 @@ def run(name, learner, batches, lr, unit, units_per_step, steps, warmup=3, **kw)
 
 def collab(steps, bs):
     from neuralnetworklibrary_amd.Applications.CollabFiltering import CollabFilterNet
+    seed_all(1234)
     g = torch.Generator(device=DEV).manual_seed(1234)
     batches = [(torch.stack([torch.randint(0, 943, (bs,), device=DEV, generator=g), torch.randint(0, 1682, (bs,), device=DEV, generator=g)], 1),
                 torch.randint(1, 6, (bs,), device=DEV, generator=g).float()) for _ in range(4)]
@@ -67,6 +97,7 @@ def collab(steps, bs):
 
 def tabular(steps):
     from neuralnetworklibrary_amd.Applications.StructuredData import StructuredDataNet
+    seed_all(1236)
     cards = [1116, 5, 4, 13, 53, 13, 4, 8, 32, 23, 27, 24, 28, 9, 5, 5] + [10] * 16
     bs, n_cont = 1024, 14
     rs = np.random.RandomState(1236)
@@ -85,6 +116,7 @@ def tabular(steps):
 
 def lm(steps):
     from neuralnetworklibrary_amd.Applications.Text import LanguageModelNet, RegSeqCrossEntropyLoss, _Vocab
+    seed_all(1237)
     V, bs, bptt = 47343, 64, 70
     stoi = {i: i for i in range(V)}
     stoi['_pad_'] = 1
@@ -101,6 +133,7 @@ def lm(steps):
 
 def retina(steps):
     from neuralnetworklibrary_amd.Applications.Vision import ObjectDetectionNet, SSD_loss
+    seed_all(1238)
     bs, M = 16, 8
     rs = np.random.RandomState(1238)
     batches = []
@@ -147,8 +180,10 @@ if __name__ == '__main__':
     ap.add_argument('which', nargs='*', default=['collab', 'tabular', 'lm', 'retina'])
     ap.add_argument('--steps', type=int, default=10)
     ap.add_argument('--graphs', action='store_true', help='Learner.use_graphs(): replay the captured step (collab / tabular)')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='write what the last step of each configuration computed to DIR/<config>/*.npy (loss, a fixed sample of parameters and gradients)')
     a = ap.parse_args()
-    GRAPHS = a.graphs
+    GRAPHS, DUMP = a.graphs, a.dump_outputs
     from neuralnetworklibrary_amd.General.Core import set_default_device
     set_default_device(DEV)
     for w in a.which:
