@@ -91,7 +91,7 @@ int nnl_embdotbias_bwd(const int64_t* x, const float* U, const float* M, const f
  * Replaces the cuDNN convolutions called by nn.Conv2d inside BasicBlock.forward / Bottleneck.forward
  * (Applications/VisionModels/retinanet.py:43-59, 77-97), the stem (:304), the 1x1 downsample (:344-348),
  * PyramidFeatures (:126-148) and the RetinaNet heads (:187-217, :260-295), and their autograd backward.
- * x [N,H,W,C] NHWC, w [K,R,S,C] KRSC, y [N,P,Q,K] NHWC; P = (H+2*pad-R)/stride+1 (validated). C%4==0
+ * x [N,H,W,C] NHWC, w [K,R,S,C] KRSC, y [N,P,Q,K] NHWC; P = floor((H+2*pad-R)/stride)+1 with H+2*pad >= R (validated). C%4==0
  * (the host pads the 3-channel stem input to 4), K%4==0 for dgrad/wgrad.  fp32 in, fp32 accumulate:
  * results equal a k-ordered fmaf chain (MI355X_MICROARCH.md, Matrix cores). */
 typedef struct {
@@ -142,7 +142,8 @@ int nnl_conv2d_weight_transpose_multi(const nnl_wt_desc_t* desc, const int32_t* 
                                       double total_elems, void* stream);
 /* dx[N,H,W,C] = sum_{r,s,k} dy[n,(h+pad-r)/stride,(w+pad-s)/stride,k] * wt[c,r,s,k] (integral taps only). */
 size_t nnl_conv2d_dgrad_workspace_bytes(const nnl_conv_geom_t* g);   /* optional workspace, as for the forward */
-/* addend (optional, [N,H,W,C]; K % 16 == 0 and stride 1, or a 3x3 / pad 1 filter at stride 2): dx = dgrad + addend — the
+/* addend (optional, [N,H,W,C]; K % 16 == 0 and at most 49 filter taps, at stride 1 or with a 3x3 / pad 1 filter at stride 2 — anything
+ * else is refused with NNL_ERR_UNSUPPORTED): dx = dgrad + addend — the
  * gradient that reaches the block input through the shortcut of BasicBlock / Bottleneck (identity, or the input gradient
  * of the downsample convolution; retinanet.py:43-59,344-348) is added in the epilogue instead of by a separate autograd
  * accumulation kernel.  A stride-2 dgrad with even H and W runs its four output-parity classes in one launch. */
@@ -193,6 +194,15 @@ int nnl_debug_conv_wino2_fwd(const float* x, const float* filt, const float* bia
                             size_t ws_bytes, int32_t* counters, long n_counters, float* bn_part, const float* bn_pivot, int N,
                             int H, int W, int C, int K, int relu, int flip, void* stream);
 int nnl_debug_conv_plan_times(int N, int H, int W, int C, int K, double* out);
+
+/* Route notes (debug, host side only): which kernels a call launched, and under which plan.
+ *   nnl_debug_route_record(enable): start (1) or stop (0) recording on the CALLING THREAD; either way the buffer is cleared.
+ *   nnl_debug_route_collect(out, n): copies the notes recorded since ("name;name;...", NUL-terminated) into out[n] and clears the buffer;
+ *     returns the number of notes, or NNL_ERR_INVALID_ARG when out is NULL or too small (the buffer is kept then).
+ * A name is `kernel<template arguments>:plan flags` and maps to one launch in conv2d.hip / wino.hip / wino2.hip; text after an `@`
+ * is a numeric detail of the plan (slice counts).  Recording changes no launch; when it is off a note costs one branch. */
+int nnl_debug_route_record(int enable);
+int nnl_debug_route_collect(char* out, size_t n);
 /* dw[K,R,S,C] = sum_{n,p,q} dy[n,p,q,k] * x[n,p*stride-pad+r,q*stride-pad+s,c]; split-K partial slabs are
  * reduced in a fixed order (bitwise reproducible).  workspace: nnl_conv2d_wgrad_workspace_bytes(g). */
 size_t nnl_conv2d_wgrad_workspace_bytes(const nnl_conv_geom_t* g);

@@ -20,6 +20,10 @@ int check_geom(const nnl_conv_geom_t* g, const char* who) {
   if (g->N <= 0 || g->H <= 0 || g->W <= 0 || g->C <= 0 || g->K <= 0 || g->R <= 0 || g->S <= 0 || g->stride <= 0 ||
       g->pad < 0)
     return nnl_set_error(NNL_ERR_INVALID_ARG, "%s: non-positive dimension", who);
+  // (C division truncates towards zero: a filter larger than the padded input would still get P = 1 at stride >= 2)
+  if (g->H + 2L * g->pad < g->R || g->W + 2L * g->pad < g->S)
+    return nnl_set_error(NNL_ERR_INVALID_ARG, "%s: the %d x %d filter is larger than the padded input (%d x %d, pad %d)", who, g->R, g->S,
+                         g->H, g->W, g->pad);
   const int P = (g->H + 2 * g->pad - g->R) / g->stride + 1, Q = (g->W + 2 * g->pad - g->S) / g->stride + 1;
   if (P != g->P || Q != g->Q || P <= 0 || Q <= 0)
     return nnl_set_error(NNL_ERR_INVALID_ARG, "%s: P,Q=(%d,%d) do not match the geometry (%d,%d)", who, g->P, g->Q, P, Q);
@@ -35,6 +39,7 @@ template <int BM, int BN, int WGM, int WGN, int MODE>
 int launch_rowk(IgemmRowkParams p, hipStream_t s) {
   p.grid_m = (int)nnl_cdiv(p.M, BM);
   p.grid_n = (int)nnl_cdiv(p.Nc, BN);
+  NNL_ROUTE("rowk<%d,%d>:%s", BM, BN, MODE == IGEMM_MODE_FWD ? "fwd" : "dgrad");
   hipLaunchKernelGGL((igemm_rowk_kernel<BM, BN, 16, WGM, WGN, MODE>), dim3(p.grid_m * p.grid_n), dim3(256), 0, s, p);
   NNL_CHECK_LAUNCH();
   return NNL_OK;
@@ -72,6 +77,8 @@ int launch_taps(IgemmTapsParams p, hipStream_t s) {
   p.grid_n = (int)nnl_cdiv(p.Nc, BN);
   p.cls_tiles = p.grid_m * p.grid_n;
   const dim3 grid((unsigned)(p.grid_m * p.grid_n * (p.ncls > 1 ? p.ncls : 1)), p.ksplit > 1 ? p.ksplit : 1);
+  NNL_ROUTE("taps<%d,%d,%d>%s%s%s", BM, BN, BK, (BM == 64 && BN == 64 && taps_dma(BK, p)) ? ":dma" : "", p.ncls > 1 ? ":ncls" : "",
+            p.ksplit > 1 ? ":ksplit" : "");
   if constexpr (BM == 64 && BN == 64) {
     if (taps_dma(BK, p))
       hipLaunchKernelGGL((igemm_taps_kernel<64, 64, BK, 2, 2, false, 0, true>), grid, dim3(256), 0, s, p);
@@ -92,6 +99,7 @@ int launch_taps_ktail(IgemmTapsParams p, hipStream_t s) {
   p.grid_m = (int)nnl_cdiv(p.M, 64);
   p.grid_n = (int)nnl_cdiv(p.Nc, 64);
   p.cls_tiles = p.grid_m * p.grid_n;
+  NNL_ROUTE("taps_ktail<%d>", BK);
   hipLaunchKernelGGL((igemm_taps_kernel<64, 64, BK, 2, 2, true, 0, false, 1, true>), dim3((unsigned)(p.grid_m * p.grid_n), 1), dim3(256), 0, s, p);
   NNL_CHECK_LAUNCH();
   return NNL_OK;
@@ -196,6 +204,9 @@ int launch_balanced(IgemmTapsParams p, const BalPlan& pl, float* ws, int* counte
   p.tail_out = ws + pl.main_floats; p.tail_slab_stride = (long)(p.M - pl.tail_row0) * p.Nc;
   p.tile_counters = (pl.bm == 64) ? counters : nullptr;      // in-kernel fix-up of the split tiles (64x64 tile only)
   const unsigned grid = (unsigned)(pl.n_main_tiles * pl.main_ks + (T - pl.n_main_tiles) * pl.tail_slices);
+  NNL_ROUTE("balanced<%d>%s%s%s%s:%s@main_ks=%d,tail_slices=%d", pl.bk == 32 ? 32 : 16, p.ktail ? ":ktail" : "",
+            (!p.ktail && taps_dma(pl.bk == 32 ? 32 : 16, p)) ? ":dma" : "", pl.main_ks > 1 ? ":main_ks" : "", pl.tail_slices > 1 ? ":tail_slices" : "",
+            p.tile_counters != nullptr ? "counters" : "reduce", pl.main_ks, pl.tail_slices);
   if (p.ktail && pl.bk == 32)
     hipLaunchKernelGGL((igemm_taps_kernel<64, 64, 32, 2, 2, true, 0, false, 1, true>), dim3(grid), dim3(256), 0, s, p);
   else if (p.ktail)
@@ -213,6 +224,7 @@ int launch_balanced(IgemmTapsParams p, const BalPlan& pl, float* ws, int* counte
   const int Nc4 = p.Nc / 4;
   if (pl.main_ks > 1 && pl.tail_row0 > 0) {
     const long n4 = (long)pl.tail_row0 * Nc4;
+    NNL_ROUTE("slab_reduce:main");
     hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)nnl_cdiv(n4, 256)), dim3(256), 0, s, (const float*)p.main_out, n4, pl.main_ks,
                        p.y, n4, p.bias, p.add, Nc4, p.relu);
     NNL_CHECK_LAUNCH();
@@ -220,6 +232,7 @@ int launch_balanced(IgemmTapsParams p, const BalPlan& pl, float* ws, int* counte
   if (pl.tail_slices > 1 && p.M > pl.tail_row0) {
     const long n4 = (long)(p.M - pl.tail_row0) * Nc4;
     const long off = (long)pl.tail_row0 * p.Nc;
+    NNL_ROUTE("slab_reduce:tail");
     hipLaunchKernelGGL(slab_reduce_kernel, dim3((unsigned)nnl_cdiv(n4, 256)), dim3(256), 0, s, (const float*)p.tail_out, n4,
                        pl.tail_slices, p.y + off, n4, p.bias, p.add ? p.add + off : nullptr, Nc4, p.relu);
     NNL_CHECK_LAUNCH();
@@ -314,6 +327,17 @@ int dispatch_taps(const IgemmTapsParams& p_in, hipStream_t s, void* ws = nullptr
       return launch_taps<64, 64>(p, s);
     }
   }
+}
+
+// The affine tap mask (igemm_taps.h) builds one filter row's column bits in a 32-bit word: a 1 x S raster with S > 32 takes the tap
+// table instead (same kernel, same taps; the table's masks are 64-bit).
+bool affine_taps_ok(int S) { return S <= 32; }
+
+// The dgrad's tap table holds (dh, dw) = ((parity + pad - r) / stride, ...) as signed char: every launch that reads the table (stride 2, or a
+// stride-1 raster too wide for the affine mask) needs them within 127; beyond that the row-k kernel (integer arithmetic) serves the shape.
+bool dgrad_tap_table_ok(const nnl_conv_geom_t* g) {
+  if (g->stride == 1 && affine_taps_ok(g->S)) return true;
+  return (g->pad + g->stride - 1) / g->stride <= 127;
 }
 
 bool taps_ok(long a_elems, long b_elems, int C, int ntaps) {
@@ -596,6 +620,7 @@ int launch_wgrad_v2(const float* dy, const float* x, float* out, long a_elems, l
         attr_set = true;                                                                                                         \
       }                                                                                                                          \
     }                                                                                                                            \
+    NNL_ROUTE("wgrad<%d,%d,%d,kg%d>%s%s@splits=%d", BM_, BN_, BK_, KG_, PAIR_ ? ":pair" : "", pl.splits > 1 ? ":splitk" : "", pl.splits); \
     hipLaunchKernelGGL((igemm_wgrad_kernel<BM_, BN_, BK_, 2, 2, PIPE_, KG_, false, PAIR_>), grid, dim3(256 * KG_), lb, s, q);    \
   } while (0)
   // PAIR staging (igemm_wgrad.h): both 16-byte chunks a thread stages per row must lie in one filter tap
@@ -699,6 +724,7 @@ int launch_wgrad_wino(const float* dy, const float* x, float* slabs, const nnl_c
         attr_set = true;                                                                                                         \
       }                                                                                                                          \
     }                                                                                                                            \
+    NNL_ROUTE("wgrad_wino1d<%d,%d,kg%d>@splits=%d", BM_, BK_, KG_, pl.splits);                                                   \
     hipLaunchKernelGGL((igemm_wgrad_kernel<BM_, BN_, BK_, 2, 2, true, KG_, true>), grid, dim3(256 * KG_), lb, s, q);             \
   } while (0)
   if (pl.bm == 128) {
@@ -826,6 +852,7 @@ int launch_wgrad_wino2d(const float* dy, const float* x, float* slabs, const nnl
         attr_set = true;                                                                                                         \
       }                                                                                                                          \
     }                                                                                                                            \
+    NNL_ROUTE("wgrad_wino2d<%d,%d,kg%d>@splits=%d", BT_, BK_, KG_, pl.splits);                                                   \
     hipLaunchKernelGGL((igemm_wgrad2d_kernel<BT_, BK_, KG_>), grid, dim3(256 * KG_), lb, s, q);                            \
   } while (0)
   if (pl.bm == 128) {
@@ -920,6 +947,7 @@ int nnl_internal_gemm_tn(const float* a, const float* b, float* y, int Mc, int N
     if (st) return st;
   } else {
     const dim3 grid(pl.grid_m * pl.grid_n * pl.splits), block(256);
+    NNL_ROUTE("wgrad_kmajor<%d,%d>%s@splits=%d", pl.bm, pl.bn, pl.splits > 1 ? ":splitk" : "", pl.splits);
     if (pl.bm == 128 && pl.bn == 128)
       hipLaunchKernelGGL((igemm_kmajor_kernel<128, 128, 16, 2, 2>), grid, block, 0, s, p);
     else if (pl.bm == 128)
@@ -932,6 +960,7 @@ int nnl_internal_gemm_tn(const float* a, const float* b, float* y, int Mc, int N
   }
   if (pl.splits > 1) {
     const long n4 = (long)Mc * Nc / 4;
+    NNL_ROUTE("splitk_reduce");
     hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)nnl_cdiv(n4, 32)), dim3(256), 0, s, (const float*)ws, y, n4, pl.splits);
     NNL_CHECK_LAUNCH();
   }
@@ -1076,7 +1105,7 @@ extern "C" int nnl_conv2d_fwd_pre(const float* x, const float* w, const float* b
         q.tap_dh[t] = (signed char)r; q.tap_dw[t] = (signed char)ss;
         q.tap_aoff[t] = (r * g->W + ss) * g->C; q.tap_woff[t] = t * g->C;
       }
-    q.tap_affine = 1; q.tap_R = g->R; q.tap_S = g->S; q.tap_dh0 = 0; q.tap_dw0 = 0; q.tap_dstep = 1;
+    q.tap_affine = affine_taps_ok(g->S); q.tap_R = g->R; q.tap_S = g->S; q.tap_dh0 = 0; q.tap_dw0 = 0; q.tap_dstep = 1;
     q.bn_part = (bn_partials && bn_pivot && bn_rows) ? bn_partials : nullptr; q.bn_pivot = bn_pivot;
     return dispatch_taps(q, s, workspace, workspace_bytes, tile_counters, bn_rows);
   }
@@ -1112,7 +1141,7 @@ extern "C" int nnl_conv2d_fwd_add_up2(const float* x, const float* w, const floa
       q.tap_dh[t] = (signed char)r; q.tap_dw[t] = (signed char)ss;
       q.tap_aoff[t] = (r * g->W + ss) * g->C; q.tap_woff[t] = t * g->C;
     }
-  q.tap_affine = 1; q.tap_R = g->R; q.tap_S = g->S; q.tap_dh0 = 0; q.tap_dw0 = 0; q.tap_dstep = 1;
+  q.tap_affine = affine_taps_ok(g->S); q.tap_R = g->R; q.tap_S = g->S; q.tap_dh0 = 0; q.tap_dw0 = 0; q.tap_dstep = 1;
   return dispatch_taps(q, s);            // no workspace: the plain grid (the split-tile fix-up path reads a same-shape addend only)
 }
 
@@ -1148,7 +1177,7 @@ extern "C" int nnl_conv2d_dgrad_pre(const float* dy, const float* wt, float* dx,
   NNL_CHECK_ARG(dy && wt && dx, "conv2d_dgrad: null pointer");
   NNL_CHECK_ARG(g->K % 4 == 0, "conv2d_dgrad: K=%d must be a multiple of 4", g->K);
   {
-    const bool taps = taps_ok((long)g->N * g->P * g->Q * g->K, (long)g->C * g->R * g->S * g->K, g->K, g->R * g->S);
+    const bool taps = taps_ok((long)g->N * g->P * g->Q * g->K, (long)g->C * g->R * g->S * g->K, g->K, g->R * g->S) && dgrad_tap_table_ok(g);
     // stride 2: the addend is applied by the class that owns each dx pixel, so every output-parity class needs a tap (3x3, pad 1)
     const bool s2_full = g->stride == 2 && g->R == 3 && g->S == 3 && g->pad == 1;
     if (addend != nullptr && !(taps && (g->stride == 1 || s2_full)))
@@ -1172,7 +1201,7 @@ extern "C" int nnl_conv2d_dgrad_pre(const float* dy, const float* wt, float* dx,
     wq.u_pre = u;
     return wino_mode_launch(wmode, wq, workspace, workspace_bytes, tile_counters, kTileCounters, s);
   }
-  const int tk = taps_kind(a_elems, b_elems, g->K, g->R * g->S);
+  const int tk = dgrad_tap_table_ok(g) ? taps_kind(a_elems, b_elems, g->K, g->R * g->S) : 0;
   if (tk && (g->stride == 1 || g->stride == 2)) {
     IgemmTapsParams q{};
     q.ktail = tk == 2;
@@ -1207,6 +1236,7 @@ extern "C" int nnl_conv2d_dgrad_pre(const float* dy, const float* wt, float* dx,
         if (c.nt == 0) { need_zero = true; continue; }      // no filter tap reaches this parity class: its dx pixels are zero
         cls[ncls++] = c;
       }
+    if (need_zero) NNL_ROUTE("dgrad:need_zero");
     if (need_zero) NNL_CHECK_HIP(hipMemsetAsync(dx, 0, sizeof(float) * g->N * g->H * g->W * g->C, s));
     auto fill = [&](IgemmTapsParams& c, const Cls& k, int at) {
       for (int t = 0; t < k.nt; ++t) {
@@ -1217,6 +1247,7 @@ extern "C" int nnl_conv2d_dgrad_pre(const float* dy, const float* wt, float* dx,
     bool merged = ncls > 1;
     for (int i = 1; i < ncls && merged; ++i) merged = cls[i].P == cls[0].P && cls[i].Q == cls[0].Q;
     if (merged) {
+      NNL_ROUTE("dgrad:merged@ncls=%d", ncls);
       for (int i = 1; i < ncls; ++i)                        // insertion sort by decreasing tap count (<= 4 entries)
         for (int j = i; j > 0 && cls[j].nt > cls[j - 1].nt; --j) { const Cls t = cls[j]; cls[j] = cls[j - 1]; cls[j - 1] = t; }
       IgemmTapsParams c = q;
@@ -1232,13 +1263,14 @@ extern "C" int nnl_conv2d_dgrad_pre(const float* dy, const float* wt, float* dx,
       c.ntaps = cls[0].nt;
       return dispatch_taps(c, s, nullptr, 0, tile_counters);
     }
+    if (st2 > 1) NNL_ROUTE("dgrad:per_class@ncls=%d", ncls);
     for (int i = 0; i < ncls; ++i) {
       IgemmTapsParams c = q;
       c.P = cls[i].P; c.Q = cls[i].Q; c.M = g->N * c.P * c.Q;
       c.out_stride = st2; c.oh0 = cls[i].ph; c.ow0 = cls[i].pw;
       fill(c, cls[i], 0);
       c.ntaps = cls[i].nt;
-      if (st2 == 1 && cls[i].nt == g->R * g->S) {          // the full raster, r-major: (dh, dw) = (pad - r, pad - s), woff = t*K
+      if (st2 == 1 && cls[i].nt == g->R * g->S && affine_taps_ok(g->S)) {          // the full raster, r-major: (dh, dw) = (pad - r, pad - s), woff = t*K
         c.tap_affine = 1; c.tap_R = g->R; c.tap_S = g->S; c.tap_dh0 = g->pad; c.tap_dw0 = g->pad; c.tap_dstep = -1;
       }
       int st = dispatch_taps(c, s, st2 == 1 ? workspace : nullptr, workspace_bytes, tile_counters);
@@ -1250,7 +1282,7 @@ extern "C" int nnl_conv2d_dgrad_pre(const float* dy, const float* wt, float* dx,
 }
 
 extern "C" size_t nnl_conv2d_wgrad_workspace_bytes(const nnl_conv_geom_t* g) {
-  if (!g || g->K <= 0 || g->C <= 0) return 0;
+  if (!g || check_geom(g, "conv2d_wgrad_workspace_bytes")) return 0;
   if (wgrad_wino2d_ok(g))                                   // the 2-D Winograd-domain slabs [splits][K][16*C] (always: dU is folded to dW from them)
     return (size_t)plan_wgrad_wino2d(g).splits * g->K * 16 * g->C * sizeof(float);
   if (wgrad_wino_ok(g))                                     // the Winograd-domain slabs [splits][K][12*C] (always: dU is folded to dW from them)
@@ -1284,6 +1316,7 @@ extern "C" int nnl_conv2d_wgrad(const float* x, const float* dy, float* dw, cons
     int st2 = launch_wgrad_wino2d(dy, x, (float*)workspace, g, wp, s);
     if (st2) return st2;
     const long n_items = (long)g->K * (g->C / 4);
+    NNL_ROUTE("wgrad_wino2d_finish");
     hipLaunchKernelGGL(wino2d_wgrad_finish_kernel, dim3((unsigned)nnl_cdiv(n_items, 16L)), dim3(256), 0, s, (const float*)workspace, dw, n_items,
                        g->C / 4, wp.splits, (long)g->K * 16 * (g->C / 4));
     NNL_CHECK_LAUNCH();
@@ -1295,6 +1328,7 @@ extern "C" int nnl_conv2d_wgrad(const float* x, const float* dy, float* dw, cons
     int st2 = launch_wgrad_wino(dy, x, (float*)workspace, g, wp, s);
     if (st2) return st2;
     const long n4 = (long)g->K * 3 * (g->C / 4);
+    NNL_ROUTE("wgrad_wino1d_finish");
     hipLaunchKernelGGL(wino_wgrad_finish_kernel, dim3((unsigned)nnl_cdiv(n4, 32L)), dim3(256), 0, s, (const float*)workspace, dw, n4,
                        g->C / 4, wp.splits, (long)g->K * 12 * (g->C / 4));
     NNL_CHECK_LAUNCH();
@@ -1307,6 +1341,7 @@ extern "C" int nnl_conv2d_wgrad(const float* x, const float* dy, float* dw, cons
     if (st2) return st2;
   } else {
     const dim3 grid(pl.grid_m * pl.grid_n * pl.splits), block(256);
+    NNL_ROUTE("wgrad_kmajor<%d,%d>%s@splits=%d", pl.bm, pl.bn, pl.splits > 1 ? ":splitk" : "", pl.splits);
     if (pl.bm == 128 && pl.bn == 128)
       hipLaunchKernelGGL((igemm_kmajor_kernel<128, 128, 16, 2, 2>), grid, block, 0, s, p);
     else if (pl.bm == 128)
@@ -1319,6 +1354,7 @@ extern "C" int nnl_conv2d_wgrad(const float* x, const float* dy, float* dw, cons
   }
   if (pl.splits > 1) {
     const long n4 = (long)p.Mc * p.Nc / 4;                 // Nc = R*S*C with C % 4 == 0
+    NNL_ROUTE("splitk_reduce");
     hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)nnl_cdiv(n4, 32)), dim3(256), 0, s, (const float*)workspace, dw, n4, pl.splits);
     NNL_CHECK_LAUNCH();
   }

@@ -45,6 +45,21 @@ void nnl_prof_begin(int kind, hipStream_t s);
 void nnl_prof_end(int kind, hipStream_t s, double work);
 void nnl_prof_exec_frac(double f);   // the launch in flight executes f x its algorithmic multiplies (Winograd kernels: 1 / 1.5, 1 / 2.25)
 
+// Route notes (debug): while nnl_debug_route_record(1) is in force on the calling thread, every launch site appends the name of what it
+// launches (and the plan it picked) to a bounded thread-local buffer that nnl_debug_route_collect() hands out; off (the default) a note is
+// one predictable branch.  Host code only: nothing is read from the environment, nothing allocated, no launch depends on it.
+// A name is `kernel<template arguments>:plan flags`; whatever follows an `@` is a numeric detail (slice counts) that varies with the shape.
+bool nnl_route_on();
+void nnl_route_note(const char* name);
+#define NNL_ROUTE(...)                                \
+  do {                                                \
+    if (nnl_route_on()) {                             \
+      char route_[160];                               \
+      snprintf(route_, sizeof(route_), __VA_ARGS__);  \
+      nnl_route_note(route_);                         \
+    }                                                 \
+  } while (0)
+
 struct NnlProfScope {
   int kind; hipStream_t s; double work;
   NnlProfScope(int k, hipStream_t st, double w) : kind(k), s(st), work(w) { nnl_prof_begin(kind, s); }

@@ -73,6 +73,43 @@ void nnl_prof_end(int kind, hipStream_t s, double work) {
 
 void nnl_prof_exec_frac(double f) { g_exec_frac = f; }
 
+// ---- route notes (nnl_common.h): which kernels, under which plan, the calls of this thread launched ----
+namespace {
+thread_local bool g_route_on = false;
+thread_local char g_route[8192];
+thread_local size_t g_route_len = 0;
+thread_local int g_route_n = 0;
+}  // namespace
+
+bool nnl_route_on() { return g_route_on; }
+
+void nnl_route_note(const char* name) {
+  if (!g_route_on) return;
+  const size_t n = strlen(name);
+  ++g_route_n;                                                  // counted even when the text no longer fits (collect reports the count)
+  if (g_route_len + n + 2 > sizeof(g_route)) return;
+  memcpy(g_route + g_route_len, name, n);
+  g_route_len += n;
+  g_route[g_route_len++] = ';';
+  g_route[g_route_len] = 0;
+}
+
+extern "C" int nnl_debug_route_record(int enable) {
+  g_route_on = enable != 0;
+  g_route_len = 0; g_route_n = 0; g_route[0] = 0;
+  return NNL_OK;
+}
+
+extern "C" int nnl_debug_route_collect(char* out, size_t n) {
+  NNL_CHECK_ARG(out != nullptr, "debug_route_collect: null buffer");
+  NNL_CHECK_ARG(n > g_route_len, "debug_route_collect: buffer of %zu bytes, %zu needed", n, g_route_len + 1);
+  memcpy(out, g_route, g_route_len);
+  out[g_route_len] = 0;
+  const int notes = g_route_n;
+  g_route_len = 0; g_route_n = 0; g_route[0] = 0;
+  return notes;
+}
+
 extern "C" int nnl_prof_enable(int enable) {
   std::lock_guard<std::mutex> lk(g_mu);
   g_enabled = enable != 0;

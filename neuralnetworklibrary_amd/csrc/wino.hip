@@ -498,6 +498,7 @@ int nnl_wino_launch(const WinoProblem& q, void* ws, size_t ws_bytes, int* tile_c
   float* u = (float*)ws;
   if (q.u_pre == nullptr) {
     const long KC3 = (long)q.Nc * 3 * q.Cin;
+    NNL_ROUTE("wino1d_filter%s", q.flip ? ":flip" : "");
     hipLaunchKernelGGL(wino_filter_kernel, dim3((unsigned)nnl_cdiv(KC3, 256L)), dim3(256), 0, s, q.filt, u, KC3, q.Cin, q.flip);
     NNL_CHECK_LAUNCH();
   }
@@ -520,6 +521,8 @@ int nnl_wino_launch(const WinoProblem& q, void* ws, size_t ws_bytes, int* tile_c
     p.tile_counters = tile_counters;
     grid = (unsigned)(pl.n_main_tiles * pl.main_ks + (T - pl.n_main_tiles) * pl.tail_slices);
   }
+  NNL_ROUTE("wino1d<%d>:%s:%s@main_ks=%d,tail_slices=%d", pl.bk == 32 ? 32 : 16, pl.on ? "ksliced" : "plain", q.u_pre ? "u_pre" : "own_u",
+            pl.on ? pl.main_ks : 1, pl.on ? pl.tail_slices : 1);
   if (pl.bk == 32) hipLaunchKernelGGL(wino_kernel<32>, dim3(grid), dim3(256), 0, s, p);
   else hipLaunchKernelGGL(wino_kernel<16>, dim3(grid), dim3(256), 0, s, p);
   NNL_CHECK_LAUNCH();

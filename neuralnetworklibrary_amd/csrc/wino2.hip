@@ -659,6 +659,7 @@ int nnl_wino2_launch(const WinoProblem& q, void* ws, size_t ws_bytes, int* tile_
   float* u = (float*)ws;
   if (q.u_pre == nullptr) {
     const long KC = (long)q.Nc * q.Cin;
+    NNL_ROUTE("wino2d_filter%s", q.flip ? ":flip" : "");
     hipLaunchKernelGGL(wino2_filter_kernel, dim3((unsigned)nnl_cdiv(KC, 256L)), dim3(256), 0, s, q.filt, u, KC, q.Cin, q.flip);
     NNL_CHECK_LAUNCH();
   }
@@ -693,6 +694,7 @@ int nnl_wino2_launch(const WinoProblem& q, void* ws, size_t ws_bytes, int* tile_
     p.bal = 1; p.main_ks = pl.main_ks; p.n_main_tiles = pl.n_main_tiles; p.tail_slices = 1; p.tail_row0 = (int)M4;
     p.main_out = u + u_floats; p.main_slab_stride = M4 * q.Nc; p.tile_counters = tile_counters; p.pos_cs = pl.pos_cs;
     grid = (unsigned)(T * pl.main_ks);
+    NNL_ROUTE("wino2d<32,4,pos>:%s@slices=%d,pos_cs=%d", q.u_pre ? "u_pre" : "own_u", pl.main_ks, pl.pos_cs);
     hipLaunchKernelGGL((wino2_kernel<32, 4, true>), dim3(grid), dim3(256), 0, s, p);
     NNL_CHECK_LAUNCH();
     return NNL_OK;
@@ -704,6 +706,8 @@ int nnl_wino2_launch(const WinoProblem& q, void* ws, size_t ws_bytes, int* tile_
     p.tile_counters = tile_counters;
     grid = (unsigned)(pl.n_main_tiles * pl.main_ks + (T - pl.n_main_tiles) * pl.tail_slices);
   }
+  NNL_ROUTE("wino2d<%s>:%s:%s@main_ks=%d,tail_slices=%d", pl.bk == 32 ? "32,3" : "16,4", pl.on ? "ksliced" : "plain", q.u_pre ? "u_pre" : "own_u",
+            pl.on ? pl.main_ks : 1, pl.on ? pl.tail_slices : 1);
   if (pl.bk == 32) hipLaunchKernelGGL((wino2_kernel<32, 3>), dim3(grid), dim3(256), 0, s, p);
   else hipLaunchKernelGGL((wino2_kernel<16, 4>), dim3(grid), dim3(256), 0, s, p);
   NNL_CHECK_LAUNCH();

@@ -636,8 +636,9 @@ def _conv_dgrad(st, dy4, w4, g4, K):
     if st.slot is not None:
         shortcut, st.slot.tensor, st.slot.closed = st.slot.tensor, None, True
     # stride 2: every output-parity class of a 3x3 / pad 1 filter has a tap, so every dx pixel passes through the epilogue
-    fuse = shortcut is not None and g.K % 16 == 0 and shortcut.numel() == dxn.numel() \
-        and (g.stride == 1 or (g.stride == 2 and g.R == 3 and g.S == 3 and g.pad == 1))
+    # (more than 49 taps, or a raster wider than 32 with pad > 127: the first-generation kernel, which has no addend — the library refuses it)
+    fuse = shortcut is not None and g.K % 16 == 0 and g.R * g.S <= 49 and shortcut.numel() == dxn.numel() \
+        and ((g.stride == 1 and (g.S <= 32 or g.pad <= 127)) or (g.stride == 2 and g.R == 3 and g.S == 3 and g.pad == 1))
     # a channel-padded dgrad transforms its own filter: not recorded under the weight (key 0; a 1x1 filter's mode 0 records nothing)
     wmode = _wino_pref(w4.data_ptr() if g.K == K else 0, 1, g)
     u = _WINO_U_BWD.get((w4.data_ptr(), wmode)) if (wmode and g.K == K) else None

@@ -88,6 +88,61 @@ def test_conv2d_fwd_bwd(case):
         assert_close(bg.grad, bc.grad, rtol=1e-4, atol=1e-5 * bc.grad.abs().max().item(), msg='db')
 
 
+# (N, C, H, W, K, (R, S), stride, pad, bias, relu): the geometry classes nn.Conv2d allows and the model shapes above never use — through
+# HipConv2d (ops.py pads channels, transposes the filter and decides what to fuse on its own) against nn.Conv2d in fp64
+RECT_CASES = [
+    (2, 16, 9, 20, 32, (1, 7), 1, 3, True, False),      # rectangular filters, one symmetric padding
+    (2, 16, 20, 9, 32, (7, 1), 1, 0, False, False),
+    (3, 32, 8, 11, 16, (1, 3), 2, 1, True, True),
+    (2, 8, 11, 8, 12, (3, 1), 1, 2, True, False),
+    (2, 32, 9, 7, 48, (3, 3), 1, 0, True, False),       # pad 0
+    (2, 32, 9, 7, 48, (3, 3), 1, 2, False, True),       # pad R - 1
+    (2, 16, 8, 8, 16, (5, 5), 2, 4, True, False),       # pad R - 1 at stride 2
+    (2, 16, 17, 13, 32, (3, 3), 3, 1, True, False),     # stride 3
+    (2, 64, 16, 13, 64, (1, 1), 3, 0, False, False),
+    (2, 32, 7, 7, 32, (1, 1), 1, 1, True, False),       # a 1x1 with pad 1
+    (2, 64, 9, 12, 36, (1, 5), 1, 0, True, False),      # K = 36 / 180 with a non-"same" pad and R != S: the K-padding path of _conv_dgrad_operands
+    (1, 64, 10, 8, 180, (5, 1), 1, 4, True, False),
+    (2, 64, 8, 8, 180, (3, 3), 2, 0, True, True),
+    (1, 16, 3, 40, 16, (1, 33), 1, 16, True, False),    # a raster wider than 32 taps
+    (1, 16, 13, 13, 16, (9, 9), 1, 4, False, False),    # 81 taps
+    (2, 3, 12, 9, 8, (2, 2), 2, 0, True, False),        # even filter, 3 input channels
+    (2, 16, 10, 10, 16, (4, 4), 2, 1, False, True),
+]
+
+
+@pytest.mark.parametrize('case', RECT_CASES, ids=[str(c) for c in RECT_CASES])
+def test_conv2d_fwd_bwd_any_geometry(case):
+    from neuralnetworklibrary_amd.Applications.VisionModels.retinanet import HipConv2d
+    N, C, H, W, K, (R, S), stride, pad, has_bias, relu = case
+    torch.manual_seed(len(str(case)))
+    ref_conv = torch.nn.Conv2d(C, K, (R, S), stride=stride, padding=pad, bias=has_bias).double()
+    conv = HipConv2d(C, K, (R, S), stride=stride, padding=pad, bias=has_bias)
+    conv.load_state_dict({k: v.float() for k, v in ref_conv.state_dict().items()})
+    conv = conv.to(DEV)
+    conv.fuse_relu = bool(relu)
+    g = torch.Generator().manual_seed(7)
+    x = torch.randn(N, C, H, W, generator=g)
+    xr = x.double().requires_grad_(True)
+    pre = ref_conv(xr)
+    ref = F.relu(pre) if relu else pre
+    dy = torch.randn(ref.shape, generator=g)
+    if relu:
+        keep = pre.detach().abs() > 1e-4                  # as test_conv2d_fwd_bwd: no gradient through outputs within rounding of the ReLU step
+        assert (~keep).double().mean().item() < 0.01
+        dy = dy * keep
+    ref.backward(dy.double())
+    xg = x.to(DEV).requires_grad_(True)
+    out = conv(xg)
+    assert out.shape == ref.shape
+    out.backward(dy.to(DEV))
+    assert_close(out, ref, rtol=1e-4, atol=1e-5 * ref.abs().max().item(), msg='y')
+    assert_close(xg.grad, xr.grad, rtol=1e-4, atol=1e-5 * xr.grad.abs().max().item(), msg='dx')
+    assert_close(conv.weight.grad, ref_conv.weight.grad, rtol=1e-4, atol=1e-5 * ref_conv.weight.grad.abs().max().item(), msg='dw')
+    if has_bias:
+        assert_close(conv.bias.grad, ref_conv.bias.grad, rtol=1e-4, atol=1e-5 * ref_conv.bias.grad.abs().max().item(), msg='db')
+
+
 @pytest.mark.parametrize('N,C,h,w,K,bias', [(2, 1024, 16, 16, 256, True), (16, 512, 32, 32, 256, True), (1, 64, 3, 5, 32, False)])
 def test_conv_add_upsampled_is_the_fpn_merge(N, C, h, w, K, bias):
     """`P5_upsampled + P4_1(C4)` (reference PyramidFeatures.forward, retinanet.py:131-141) in the lateral 1x1 convolution's
@@ -197,14 +252,28 @@ def test_grad_slot_projection_shortcut_hand_over(stride, give_first):
     """A block input feeds conv1 (3x3, the GradSlot consumer) and the projection shortcut (1x1, the producer that parks its input
     gradient in the slot).  Whatever order autograd runs the two backward nodes in — there is no dependency between them — the
     gradient of the input must be the sum of both (the consumer closes the slot; a late producer returns its gradient normally)."""
+    _grad_slot_hand_over(stride, give_first, K=48, R=3, pad=1)
+
+
+@pytest.mark.parametrize('give_first', [False, True], ids=['producer_runs_first', 'consumer_runs_first'])
+@pytest.mark.parametrize('K,R,stride,pad', [(20, 3, 1, 1), (20, 3, 2, 1), (48, 5, 2, 2), (48, 5, 1, 2), (48, 9, 1, 4)], ids=str)
+def test_grad_slot_hand_over_the_kernel_cannot_fuse(K, R, stride, pad, give_first):
+    """The same hand-over where ops._conv_dgrad may NOT fuse the shortcut into the dgrad kernel and adds it afterwards (`dxn += shortcut`):
+    K = 20 stays below the 16-padding threshold (the row-k kernel has no addend), and a 5x5 / stride 2 / pad 2 consumer has output-parity
+    classes the fused addend is not defined for; a 9x9 consumer (81 taps) runs on the row-k kernel, which has no addend (the library refuses
+    one, so ops must not pass it).  (48, 5, 1, 2) is the control: stride 1 fuses up to 49 taps."""
+    _grad_slot_hand_over(stride, give_first, K=K, R=R, pad=pad)
+
+
+def _grad_slot_hand_over(stride, give_first, K, R, pad):
     from neuralnetworklibrary_amd import ops
     g = torch.Generator().manual_seed(21 + stride)
-    N, C, K, H = 2, 32, 48, 12
+    N, C, H = 2, 32, 12
     x = torch.randn(N, C, H, H, generator=g)
-    w1 = torch.randn(K, C, 3, 3, generator=g) * 0.1
+    w1 = torch.randn(K, C, R, R, generator=g) * 0.1
     wd = torch.randn(K, C, 1, 1, generator=g) * 0.1
     xr = x.double().requires_grad_(True)
-    yr = F.conv2d(xr, w1.double(), None, stride, 1) + F.conv2d(xr, wd.double(), None, stride, 0)
+    yr = F.conv2d(xr, w1.double(), None, stride, pad) + F.conv2d(xr, wd.double(), None, stride, 0)
     dy = torch.randn(yr.shape, generator=g)
     yr.backward(dy.double())
 
@@ -214,9 +283,9 @@ def test_grad_slot_projection_shortcut_hand_over(stride, give_first):
     slot = ops.GradSlot()
     if give_first:          # created first => its backward node runs LAST: the consumer has closed the slot by then
         yd = ops.conv2d(xg, wdg, None, stride, 0, give_slot=slot)
-        y1 = ops.conv2d(xg, w1g, None, stride, 1, grad_slot=slot)
+        y1 = ops.conv2d(xg, w1g, None, stride, pad, grad_slot=slot)
     else:
-        y1 = ops.conv2d(xg, w1g, None, stride, 1, grad_slot=slot)
+        y1 = ops.conv2d(xg, w1g, None, stride, pad, grad_slot=slot)
         yd = ops.conv2d(xg, wdg, None, stride, 0, give_slot=slot)
     (y1 + yd).backward(dy.to(DEV))
     assert slot.tensor is None and slot.closed
@@ -376,43 +445,75 @@ def test_winograd_2d_position_split(case, pos, monkeypatch):
     _winograd_2d_debug_entry(case, '0', pos, monkeypatch)
 
 
+@pytest.mark.parametrize('mode', ['int', 'randn'])
+@pytest.mark.parametrize('case', [(2, 64, 12, 10, 64, None), (3, 32, 9, 7, 36, None), (2, 64, 17, 33, 96, None), (1, 16, 2, 2, 8, None),
+                                  (1, 16, 5, 3, 8, None), (4, 128, 14, 14, 128, None), (4, 128, 14, 14, 128, (2, 4)), (2, 64, 17, 33, 96, (1, 3))], ids=str)
+def test_winograd_1d_debug_entry(case, mode, monkeypatch):
+    """The 1-D F(2, 3) kernel (csrc/wino.hip) through its debug entry nnl_debug_conv_wino_fwd, the twin of the 2-D test: forward with bias /
+    ReLU, addend + BatchNorm partials, the flipped dgrad filter, plain grid and forced k-slicing (NNL_WINO_PLAN_KS / _S), counters back
+    to zero, bitwise repeatability — on even AND odd widths (nnl_wino_ok admits W >= 2), on randn data at the project's tolerance and on
+    small integers bit for bit (every Winograd intermediate is a multiple of 1/4 there)."""
+    _winograd_debug_entry('1d', case, None, None, monkeypatch, mode)
+
+
 def _winograd_2d_debug_entry(case, chunk, pos, monkeypatch):
+    _winograd_debug_entry('2d', case, chunk, pos, monkeypatch, 'randn')
+
+
+def _winograd_debug_entry(kind, case, chunk, pos, monkeypatch, mode):
     from neuralnetworklibrary_amd._lib import lib, ptr, stream, check
     N, C, H, W, K, forced = case
-    monkeypatch.setenv('NNL_WINO2_CHUNK', chunk)              # k order: whole C per position (default) / 32-channel chunks outermost
-    monkeypatch.setenv('NNL_WINO2_POS', pos)                  # 0: never the position-split instantiation; n: n channel slices per position
+    entry, ws_bytes = ((lib.nnl_debug_conv_wino2_fwd, lib.nnl_debug_conv_wino2_workspace_bytes) if kind == '2d' else
+                       (lib.nnl_debug_conv_wino_fwd, lib.nnl_debug_conv_wino_workspace_bytes))
+    if kind == '2d':
+        monkeypatch.setenv('NNL_WINO2_CHUNK', chunk)          # k order: whole C per position (default) / 32-channel chunks outermost
+        monkeypatch.setenv('NNL_WINO2_POS', pos)              # 0: never the position-split instantiation; n: n channel slices per position
     if forced:
         monkeypatch.setenv('NNL_WINO_PLAN_KS', str(forced[0])); monkeypatch.setenv('NNL_WINO_PLAN_S', str(forced[1]))
     lib.nnl_reload_env()
     g = torch.Generator().manual_seed(5)
-    x = torch.randn(N, H, W, C, generator=g)
-    w = torch.randn(K, 3, 3, C, generator=g) / (C * 9) ** 0.5
-    b = torch.randn(K, generator=g)
-    add = torch.randn(N, H, W, K, generator=g)
-    piv = torch.randn(K, generator=g) * 0.1
-    dy = torch.randn(N, H, W, K, generator=g)
+    if mode == 'int':                                         # every product, partial sum and transform is exact in fp32: 81 * 2 * 2 * C quarter-units < 2^24
+        assert 81 * 4 * max(C, K) < 1 << 24
+        ri = lambda *s: torch.randint(-2, 3, s, generator=g).float()     # noqa: E731
+        x, b, add, piv, dy = ri(N, H, W, C), ri(K), ri(N, H, W, K), ri(K), ri(N, H, W, K)
+        w = torch.randint(1, 3, (K, 3, 3, C), generator=g).float() * (torch.randint(0, 2, (K, 3, 3, C), generator=g).float() * 2 - 1)
+    else:
+        x = torch.randn(N, H, W, C, generator=g)
+        w = torch.randn(K, 3, 3, C, generator=g) / (C * 9) ** 0.5
+        b = torch.randn(K, generator=g)
+        add = torch.randn(N, H, W, K, generator=g)
+        piv = torch.randn(K, generator=g) * 0.1
+        dy = torch.randn(N, H, W, K, generator=g)
     counters = torch.zeros(4096, dtype=torch.int32, device=DEV)
-    wsb = max(lib.nnl_debug_conv_wino2_workspace_bytes(N, H, W, C, K), lib.nnl_debug_conv_wino2_workspace_bytes(N, H, W, K, C))
+    wsb = max(ws_bytes(N, H, W, C, K), ws_bytes(N, H, W, K, C))
     ws = torch.empty(wsb // 4 + 4, device=DEV)
-    rows = (N * ((H + 1) // 2) * ((W + 1) // 2) + 63) // 64
+    rows = ((N * ((H + 1) // 2) * ((W + 1) // 2) if kind == '2d' else N * H * ((W + 1) // 2)) + 63) // 64
+    name = '2-D Winograd' if kind == '2d' else '1-D Winograd'
+
+    def close(got, want, what):
+        if mode == 'int':                                     # want: fp64 arithmetic on integers, exact
+            assert torch.equal(got.cpu().double(), want.double()), '%s: %s is not bit for bit the exact result' % (name, what)
+        else:
+            assert_close(got, want, rtol=1e-4, atol=1e-5 * sc, msg=name + ' ' + what)
     part = torch.zeros(rows, K, 2, device=DEV)
     xd, wd, bd, addd, pivd = x.to(DEV), w.to(DEV), b.to(DEV), add.to(DEV), piv.to(DEV)
     y = torch.empty(N, H, W, K, device=DEV)
 
     def run(xin, filt, bias, addt, out, cc, kk, relu, flip, bn):
-        check(lib.nnl_debug_conv_wino2_fwd(ptr(xin), ptr(filt), ptr(bias), ptr(addt), ptr(out), ptr(ws), wsb, ptr(counters), counters.numel(),
-                                           ptr(part) if bn else None, ptr(pivd) if bn else None, N, H, W, cc, kk, relu, flip, stream()))
+        check(entry(ptr(xin), ptr(filt), ptr(bias), ptr(addt), ptr(out), ptr(ws), wsb, ptr(counters), counters.numel(),
+                    ptr(part) if bn else None, ptr(pivd) if bn else None, N, H, W, cc, kk, relu, flip, stream()))
 
-    ref_lin = torch.nn.functional.conv2d(x.permute(0, 3, 1, 2), w.permute(0, 3, 1, 2), b, padding=1).permute(0, 2, 3, 1)
+    rt = torch.float64 if mode == 'int' else torch.float32   # (randn mode keeps the fp32 CPU reference the 2-D tests have always used)
+    ref_lin = torch.nn.functional.conv2d(x.to(rt).permute(0, 3, 1, 2), w.to(rt).permute(0, 3, 1, 2), b.to(rt), padding=1).permute(0, 2, 3, 1)
     sc = ref_lin.abs().max().item()
     run(xd, wd, bd, None, y, C, K, 1, 0, False)
-    assert_close(y, torch.relu(ref_lin), rtol=1e-4, atol=1e-5 * sc, msg='2-D Winograd forward + bias + ReLU')
+    close(y, torch.relu(ref_lin), 'forward + bias + ReLU')
     y1 = y.clone()
     run(xd, wd, bd, None, y, C, K, 1, 0, False)
     assert torch.equal(y, y1), 'bitwise reproducible'
     run(xd, wd, bd, addd, y, C, K, 0, 0, True)
     ref2 = ref_lin + add
-    assert_close(y, ref2, rtol=1e-4, atol=1e-5 * sc, msg='2-D Winograd forward + addend')
+    close(y, ref2, 'forward + addend')
     d = (ref2 - piv).reshape(-1, K).double()
     s1, s2 = part[:, :, 0].double().sum(0).cpu(), part[:, :, 1].double().sum(0).cpu()
     assert ((s1 - d.sum(0)).abs().max() / d.abs().sum(0).max()).item() < 1e-5
@@ -422,12 +523,18 @@ def _winograd_2d_debug_entry(case, chunk, pos, monkeypatch):
         wt = w.permute(3, 1, 2, 0).contiguous()               # [C][R][S][K]
         dx = torch.empty(N, H, W, C, device=DEV)
         run(dy.to(DEV), wt.to(DEV), None, None, dx, K, C, 0, 1, False)
-        refdx = torch.nn.grad.conv2d_input((N, C, H, W), w.permute(0, 3, 1, 2).contiguous(), dy.permute(0, 3, 1, 2).contiguous(),
+        refdx = torch.nn.grad.conv2d_input((N, C, H, W), w.to(rt).permute(0, 3, 1, 2).contiguous(), dy.to(rt).permute(0, 3, 1, 2).contiguous(),
                                            padding=1).permute(0, 2, 3, 1)
-        assert_close(dx, refdx, rtol=1e-4, atol=1e-5 * refdx.abs().max().item(), msg='2-D Winograd dgrad filter')
+        sc = refdx.abs().max().item()
+        close(dx, refdx, 'dgrad filter')
+        dx1 = dx.clone()
+        run(dy.to(DEV), wt.to(DEV), None, None, dx, K, C, 0, 1, False)
+        assert torch.equal(dx, dx1), 'bitwise reproducible (dgrad filter)'
+        assert int(counters.abs().sum()) == 0, 'tile counters back to zero'
     if forced:
         monkeypatch.delenv('NNL_WINO_PLAN_KS'); monkeypatch.delenv('NNL_WINO_PLAN_S')
-    monkeypatch.delenv('NNL_WINO2_CHUNK'); monkeypatch.delenv('NNL_WINO2_POS')
+    if kind == '2d':
+        monkeypatch.delenv('NNL_WINO2_CHUNK'); monkeypatch.delenv('NNL_WINO2_POS')
     lib.nnl_reload_env()
 
 
