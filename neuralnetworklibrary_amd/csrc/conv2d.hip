@@ -62,7 +62,7 @@ int dispatch_rowk(const IgemmRowkParams& p, hipStream_t s) {
 // 2 BK=32 launches, 3 both).  Measured per ResNet-34 layer (bench_conv.py --ab NNL_IGEMM_DMA=0,3): +3.5 % on the 56x56 / C=64
 // stage, -1 % on 28x28 / C=128, -7 % with BK=32 (two buffers); inside the full training step the gain on the C=64 stage
 // does not show (15.44 ms/step either way), so register staging stays the shipped path.
-static bool taps_dma(int bk, const IgemmTapsParams&) {
+static bool taps_dma(int bk) {
   const int m = NNL_ENV_INT("NNL_IGEMM_DMA", 0);
   return bk == 16 ? (m & 1) != 0 : (m & 2) != 0;
 }
@@ -77,10 +77,10 @@ int launch_taps(IgemmTapsParams p, hipStream_t s) {
   p.grid_n = (int)nnl_cdiv(p.Nc, BN);
   p.cls_tiles = p.grid_m * p.grid_n;
   const dim3 grid((unsigned)(p.grid_m * p.grid_n * (p.ncls > 1 ? p.ncls : 1)), p.ksplit > 1 ? p.ksplit : 1);
-  NNL_ROUTE("taps<%d,%d,%d>%s%s%s", BM, BN, BK, (BM == 64 && BN == 64 && taps_dma(BK, p)) ? ":dma" : "", p.ncls > 1 ? ":ncls" : "",
+  NNL_ROUTE("taps<%d,%d,%d>%s%s%s", BM, BN, BK, (BM == 64 && BN == 64 && taps_dma(BK)) ? ":dma" : "", p.ncls > 1 ? ":ncls" : "",
             p.ksplit > 1 ? ":ksplit" : "");
   if constexpr (BM == 64 && BN == 64) {
-    if (taps_dma(BK, p))
+    if (taps_dma(BK))
       hipLaunchKernelGGL((igemm_taps_kernel<64, 64, BK, 2, 2, false, 0, true>), grid, dim3(256), 0, s, p);
     else if constexpr (BK == 16)
       hipLaunchKernelGGL((igemm_taps_kernel<64, 64, 16, 2, 2, true, 0, false, 2>), grid, dim3(256), 0, s, p);
@@ -110,23 +110,22 @@ int launch_taps_ktail(IgemmTapsParams p, hipStream_t s) {
 struct BalPlan {
   int on, bk, main_ks, n_main_tiles, tail_slices, tail_row0;
   size_t main_floats, tail_floats;        // workspace: [main slabs][tail slabs]
-  int bm;                                 // tile rows: 64 (64x64 tile) or 128 (128x64 tile, BK 16)
   double t_us;                            // predicted time of the chosen plan
 };
 
 constexpr int kCUs = 256;
 constexpr long kTileCounters = 65536;   // ints in the caller's persistent tile-counter buffer (nnl_conv2d_tile_counters())
 
-BalPlan plan_balance_tile(long M, int Nc, int C, int ntaps, int bm) {
+// (a 128x64 tile under this schedule was measured 10-12 % slower on the 56x56 and 14x14 stages and removed: profiles/README.md)
+BalPlan plan_balance(long M, int Nc, int C, int ntaps) {
   BalPlan best{};
-  best.bm = bm;
   const int e_bal = NNL_ENV_INT("NNL_IGEMM_BALANCE", 1);
   if (e_bal == 0 || Nc % 4 != 0) return best;
-  const long gm = nnl_cdiv(M, bm), gn = nnl_cdiv(Nc, 64), T = gm * gn;
-  const int bk = (bm == 64 && (T < 1200 || C >= 256 || C == 64) && C % 32 == 0) ? 32 : 16;
+  const long gm = nnl_cdiv(M, 64), gn = nnl_cdiv(Nc, 64), T = gm * gn;
+  const int bk = ((T < 1200 || C >= 256 || C == 64) && C % 32 == 0) ? 32 : 16;
   const long I = (long)ntaps * (C / bk);                               // k iterations of a whole tile
-  const double c_it = (bk == 32 ? 0.60 : 0.30) * (bm / 64);            // us per k iteration per CU-resident workgroup set (measured ~113 TF/s ceiling)
-  const double occ = bm == 128 ? 5 : (bk == 32 ? 4 : 6);               // resident workgroups per CU (LDS- / VGPR-limited)
+  const double c_it = bk == 32 ? 0.60 : 0.30;                          // us per k iteration per CU-resident workgroup set (measured ~113 TF/s ceiling)
+  const double occ = bk == 32 ? 4 : 6;                                 // resident workgroups per CU (LDS- / VGPR-limited)
   auto wave_iters = [&](long blocks, long iters) {                     // busiest CU's iterations for `blocks` equal workgroups
     if (blocks <= 0) return 0.0;
     const long cap = (long)occ * kCUs;                                 // full residency waves, then the remainder on top
@@ -152,7 +151,7 @@ BalPlan plan_balance_tile(long M, int Nc, int C, int ntaps, int bm) {
       const long it_tail = nnl_cdiv(I, S);
       const long tail_blocks = tail * S;
       double t = (wave_iters(n_main * ks, it_main) + wave_iters(tail_blocks, it_tail + (S > 1 ? plan_extra : 0))) * c_it;
-      const long row0 = (n_main / gn) * bm < M ? (n_main / gn) * bm : M;
+      const long row0 = (n_main / gn) * 64 < M ? (n_main / gn) * 64 : M;
       const double main_b = ks > 1 ? (2.0 * ks + 1) * row0 * Nc * 4 : 0;
       const double tail_b = S > 1 ? (2.0 * S + 1) * (M - row0) * Nc * 4 : 0;
       t += (main_b + tail_b) / plan_bw + (ks > 1 ? 1 : 0) + (S > 1 && tail ? 1 : 0);      // slab traffic (write + re-read) + fix-up latency
@@ -168,11 +167,6 @@ BalPlan plan_balance_tile(long M, int Nc, int C, int ntaps, int bm) {
   }
   if (best.on && best.main_ks == 1 && best.tail_slices == 1) best.on = 0;
   return best;
-}
-
-BalPlan plan_balance(long M, int Nc, int C, int ntaps) {
-  // (a 128x64 tile under this schedule was measured 10-12 % slower on the 56x56 and 14x14 stages and removed: profiles/README.md)
-  return plan_balance_tile(M, Nc, C, ntaps, 64);
 }
 
 size_t balance_workspace_bytes(long M, int Nc, int C, int ntaps) {
@@ -196,24 +190,24 @@ __global__ __launch_bounds__(256) void slab_reduce_kernel(const float* __restric
 }
 
 int launch_balanced(IgemmTapsParams p, const BalPlan& pl, float* ws, int* counters, hipStream_t s) {
-  p.grid_m = (int)nnl_cdiv(p.M, pl.bm);
+  p.grid_m = (int)nnl_cdiv(p.M, 64);
   p.grid_n = (int)nnl_cdiv(p.Nc, 64);
   const int T = p.grid_m * p.grid_n;
   p.bal = 1; p.main_ks = pl.main_ks; p.n_main_tiles = pl.n_main_tiles; p.tail_slices = pl.tail_slices; p.tail_row0 = pl.tail_row0;
   p.main_out = ws; p.main_slab_stride = (long)pl.tail_row0 * p.Nc;
   p.tail_out = ws + pl.main_floats; p.tail_slab_stride = (long)(p.M - pl.tail_row0) * p.Nc;
-  p.tile_counters = (pl.bm == 64) ? counters : nullptr;      // in-kernel fix-up of the split tiles (64x64 tile only)
+  p.tile_counters = counters;                                // in-kernel fix-up of the split tiles
   const unsigned grid = (unsigned)(pl.n_main_tiles * pl.main_ks + (T - pl.n_main_tiles) * pl.tail_slices);
   NNL_ROUTE("balanced<%d>%s%s%s%s:%s@main_ks=%d,tail_slices=%d", pl.bk == 32 ? 32 : 16, p.ktail ? ":ktail" : "",
-            (!p.ktail && taps_dma(pl.bk == 32 ? 32 : 16, p)) ? ":dma" : "", pl.main_ks > 1 ? ":main_ks" : "", pl.tail_slices > 1 ? ":tail_slices" : "",
+            (!p.ktail && taps_dma(pl.bk == 32 ? 32 : 16)) ? ":dma" : "", pl.main_ks > 1 ? ":main_ks" : "", pl.tail_slices > 1 ? ":tail_slices" : "",
             p.tile_counters != nullptr ? "counters" : "reduce", pl.main_ks, pl.tail_slices);
   if (p.ktail && pl.bk == 32)
     hipLaunchKernelGGL((igemm_taps_kernel<64, 64, 32, 2, 2, true, 0, false, 1, true>), dim3(grid), dim3(256), 0, s, p);
   else if (p.ktail)
     hipLaunchKernelGGL((igemm_taps_kernel<64, 64, 16, 2, 2, true, 0, false, 1, true>), dim3(grid), dim3(256), 0, s, p);
-  else if (pl.bk == 32 && taps_dma(32, p))
+  else if (pl.bk == 32 && taps_dma(32))
     hipLaunchKernelGGL((igemm_taps_kernel<64, 64, 32, 2, 2, false, 0, true>), dim3(grid), dim3(256), 0, s, p);
-  else if (pl.bk != 32 && taps_dma(16, p))
+  else if (pl.bk != 32 && taps_dma(16))
     hipLaunchKernelGGL((igemm_taps_kernel<64, 64, 16, 2, 2, false, 0, true>), dim3(grid), dim3(256), 0, s, p);
   else if (pl.bk == 32)
     hipLaunchKernelGGL((igemm_taps_kernel<64, 64, 32, 2, 2, true>), dim3(grid), dim3(256), 0, s, p);
@@ -240,8 +234,9 @@ int launch_balanced(IgemmTapsParams p, const BalPlan& pl, float* ws, int* counte
   return NNL_OK;
 }
 
-// Tile choice: estimated time = rounds of resident workgroups x per-workgroup work / per-tile MFMA efficiency.
-// Resident workgroups per CU (VGPR/LDS limited) and efficiencies are measured values (tools/bench_conv.py).
+// Tile choice: the 64x64 family (balanced schedule, KTAIL, BK 16 / 32) for everything but a Linear onto a huge vocabulary.
+// (The 128x128, 128x64 and 64x128 tiles measured 0.90 of the 64x64 tile's MFMA efficiency at the same workgroups per CU — tools/bench_conv.py
+// tile sweep, profiles/README.md — so no grid prefers them.)
 int dispatch_taps(const IgemmTapsParams& p_in, hipStream_t s, void* ws = nullptr, size_t ws_bytes = 0, int* counters = nullptr,
                   int* bn_rows = nullptr) {
   IgemmTapsParams p = p_in;
@@ -249,84 +244,41 @@ int dispatch_taps(const IgemmTapsParams& p_in, hipStream_t s, void* ws = nullptr
   p.tile_counters = counters;                       // debug builds: the timestamp area lives behind the counters (igemm_taps.h)
 #endif
   if (bn_rows) *bn_rows = 0;
-  if (p.ktail) {
-    const bool dense = p.out_stride == 1 && p.OH == p.P && p.OW == p.Q && p.oh0 == 0 && p.ow0 == 0 && p.ksplit <= 1;
-    float* const bn_part_k = p.bn_part;
-    p.bn_part = nullptr;
-    if (ws != nullptr && dense) {
-      // few, long tiles (1024 x 500 x 1000: 128 workgroups of 32 k steps): the balanced schedule's k slices fill the chip
-      const BalPlan pl = plan_balance(p.M, p.Nc, (int)nnl_cdiv(p.C, 32) * 32, 1);
-      if (pl.on && ws_bytes >= (pl.main_floats + pl.tail_floats) * sizeof(float)) {
-        const long tiles = nnl_cdiv(p.M, pl.bm) * nnl_cdiv(p.Nc, 64);
-        int* const cnt = tiles <= kTileCounters ? counters : nullptr;
-        if (bn_part_k && cnt != nullptr) {
-          p.bn_part = bn_part_k;
-          if (bn_rows) *bn_rows = (int)nnl_cdiv(p.M, 64);
-        }
-        return launch_balanced(p, pl, (float*)ws, cnt, s);
-      }
-    }
-    if (bn_part_k && dense) {
-      p.bn_part = bn_part_k;
-      if (bn_rows) *bn_rows = (int)nnl_cdiv(p.M, 64);
-    }
-    return p.C >= 64 ? launch_taps_ktail<32>(p, s) : launch_taps_ktail<16>(p, s);
-  }
-  struct Cand { int bm, bn, occ; double eff; };
-  static const Cand cands[4] = {{128, 128, 4, 0.90}, {128, 64, 5, 0.90}, {64, 128, 5, 0.90}, {64, 64, 8, 1.00}};   // measured: bench_conv.py tile sweep
-  int best = 0;
-  if (p.ntaps == 1 && p.C <= 512 && p.Nc >= 8192 && p.M >= 1024 && p.ncls <= 1) {
+  float* const bn_part = p.bn_part;                 // statistics are produced by the 64x64 kernels only, and only into a dense output
+  p.bn_part = nullptr;
+  if (!p.ktail && p.ntaps == 1 && p.C <= 512 && p.Nc >= 8192 && p.M >= 1024 && p.ncls <= 1) {
     // a Linear onto a huge vocabulary (the AWD-LSTM decoder, Text.py:572: 4480 x 400 -> 47 343): 25 k steps per tile, so the launch is
     // prologue / epilogue / B-re-read bound and the 128 x 128 tile wins (measured: 1.81 -> 1.49 ms)
-    best = 0;
-  } else {
-    double best_t = 1e300;
-    for (int i = 0; i < 4; ++i) {
-      const Cand& c = cands[i];
-      const long blocks = nnl_cdiv(p.M, c.bm) * nnl_cdiv(p.Nc, c.bn) * (p.ncls > 1 ? p.ncls : 1);
-      const long slots = 256L * c.occ;
-      const long rounds = nnl_cdiv(blocks, slots);
-      // inside one round the CU is shared by min(occ, blocks/256) workgroups: time ~ (workgroups on the busiest CU) x tile work
-      const long last = blocks - (rounds - 1) * slots;
-      const double per_cu = (double)(rounds - 1) * c.occ + (double)nnl_cdiv(last, 256);
-      const double t = per_cu * c.bm * c.bn / c.eff;
-      if (t < best_t) { best_t = t; best = i; }
-    }
+    return launch_taps<128, 128>(p, s);
   }
-  float* const bn_part = p.bn_part;                 // statistics are produced by the 64x64 kernels only
-  p.bn_part = nullptr;
-  switch (best) {
-    case 0: return launch_taps<128, 128>(p, s);
-    case 1: return launch_taps<128, 64>(p, s);
-    case 2: return launch_taps<64, 128>(p, s);
-    default: {
-      const bool dense_out = p.out_stride == 1 && p.OH == p.P && p.OW == p.Q && p.oh0 == 0 && p.ow0 == 0 && p.ksplit <= 1;
-      if (ws != nullptr && dense_out) {
-        const BalPlan pl = plan_balance(p.M, p.Nc, p.C, p.ntaps);
-        if (pl.on && ws_bytes >= (pl.main_floats + pl.tail_floats) * sizeof(float)) {
-          const long tiles = nnl_cdiv(p.M, pl.bm) * nnl_cdiv(p.Nc, 64);
-          int* const cnt = tiles <= kTileCounters ? counters : nullptr;
-          if (bn_part && dense_out && pl.bm == 64 && cnt != nullptr) {      // split tiles are finished in-kernel: stats too
-            p.bn_part = bn_part;
-            if (bn_rows) *bn_rows = (int)nnl_cdiv(p.M, 64);
-          }
-          return launch_balanced(p, pl, (float*)ws, cnt, s);
-        }
-      }
-      if (bn_part && dense_out) {
+  const bool dense = p.out_stride == 1 && p.OH == p.P && p.OW == p.Q && p.oh0 == 0 && p.ow0 == 0 && p.ksplit <= 1;
+  const int rows64 = (int)nnl_cdiv(p.M, 64);
+  if (ws != nullptr && dense) {
+    // KTAIL: the planner sees C rounded up to the 32-wide k block (few, long tiles — 1024 x 500 x 1000: 128 workgroups of 32 k steps —
+    // are what the balanced schedule's k slices fill the chip with)
+    const BalPlan pl = plan_balance(p.M, p.Nc, p.ktail ? (int)nnl_cdiv(p.C, 32) * 32 : p.C, p.ntaps);
+    if (pl.on && ws_bytes >= (pl.main_floats + pl.tail_floats) * sizeof(float)) {
+      int* const cnt = rows64 * nnl_cdiv(p.Nc, 64) <= kTileCounters ? counters : nullptr;
+      if (bn_part && cnt != nullptr) {              // split tiles are finished in-kernel: stats too
         p.bn_part = bn_part;
-        if (bn_rows) *bn_rows = (int)nnl_cdiv(p.M, 64);
+        if (bn_rows) *bn_rows = rows64;
       }
-      // BK=32 halves the barriers per MFMA at half the occupancy: measured (bench_conv.py) +10..20 %
-      // on grids of < ~5 workgroups per CU (14x14 / 7x7 stages), -7 % on the 56x56 stage.
-      const long blocks64 = nnl_cdiv(p.M, 64) * nnl_cdiv(p.Nc, 64) * (p.ncls > 1 ? p.ncls : 1);
-      // long k loops (C >= 256) gain from BK=32 on large grids too (RetinaNet heads); so does C = 64 since the prologue / per-tap clean-ups
-      // of round 3 (re-measured per layer at 64 images: l1 3x3 0.143 -> 0.138 ms; the C = 128 stage still prefers BK=16: 0.138 vs 0.147)
-      const bool bk32 = blocks64 < 1200 || p.C >= 256 || p.C == 64;
-      if (bk32 && p.C % 32 == 0) return launch_taps<64, 64, 32>(p, s);
-      return launch_taps<64, 64>(p, s);
+      return launch_balanced(p, pl, (float*)ws, cnt, s);
     }
   }
+  if (bn_part && dense) {
+    p.bn_part = bn_part;
+    if (bn_rows) *bn_rows = rows64;
+  }
+  if (p.ktail) return p.C >= 64 ? launch_taps_ktail<32>(p, s) : launch_taps_ktail<16>(p, s);
+  // BK=32 halves the barriers per MFMA at half the occupancy: measured (bench_conv.py) +10..20 %
+  // on grids of < ~5 workgroups per CU (14x14 / 7x7 stages), -7 % on the 56x56 stage.
+  const long blocks64 = rows64 * nnl_cdiv(p.Nc, 64) * (p.ncls > 1 ? p.ncls : 1);
+  // long k loops (C >= 256) gain from BK=32 on large grids too (RetinaNet heads); so does C = 64 since the prologue / per-tap clean-ups
+  // of round 3 (re-measured per layer at 64 images: l1 3x3 0.143 -> 0.138 ms; the C = 128 stage still prefers BK=16: 0.138 vs 0.147)
+  const bool bk32 = blocks64 < 1200 || p.C >= 256 || p.C == 64;
+  if (bk32 && p.C % 32 == 0) return launch_taps<64, 64, 32>(p, s);
+  return launch_taps<64, 64>(p, s);
 }
 
 // The affine tap mask (igemm_taps.h) builds one filter row's column bits in a 32-bit word: a 1 x S raster with S > 32 takes the tap
@@ -559,15 +511,15 @@ WgradPlan plan_wgrad(int Mc, int Nc, long Kp, int square_bn_divides = 0) {     /
   }
   // Merge KG neighbouring splits into ONE workgroup of KG wave groups (igemm_wgrad.h): the same waves per CU, the partial sums of
   // the KG pixel ranges meet in LDS, and only every KG-th slab is written / re-read (round 2 measured 1.97x the algorithmic HBM
-  // bytes per conv launch, almost all of it wgrad slabs).  Instantiated for the 128x128 (BK 16) and 64x64 (BK 32) tiles; the
-  // planner takes it only where it measured as a win (tools/bench_conv.py at 64 images, 1 / 2 / 4 groups): the 128x128 tile
+  // bytes per conv launch, almost all of it wgrad slabs).  The planner takes it, and launch_wgrad_v2 instantiates it, only
+  // where it measured as a win (tools/bench_conv.py at 64 images, 1 / 2 / 4 groups): the 128x128 tile
   // with >= 16 splits (28 x 28 / 14 x 14 stages: 0.139 -> 0.136 ms and 66 -> 17 MB of slabs per launch).  With few splits the merge
   // unbalances the grid (7 x 7 stage, 7 splits: 0.142 -> 0.187 ms) and the 64x64 tile loses 1-3 %.
   pl.kg = 1;
   const bool kg_tile = (pl.bm == 128 && pl.bn == 128) || (pl.bm == 64 && pl.bn == 64);
   if (kg_tile && pl.splits >= 2) {
     int kg = (pl.bm == 128 && pl.splits >= 16) ? 4 : 1;
-    // Winograd-domain columns (square_bn_divides = 3 * C): the 4-group 128x128 WINO instantiation spills (two staged pixels per
+    // Winograd-domain columns (square_bn_divides = 3 * C): a 4-group 128x128 WINO instantiation spills (two staged pixels per
     // operand: 10 VGPRs over), and merged groups measured SLOWER there — RetinaNet FPN level 16 x 64 x 64, C = K = 256: 0.49 ms
     // with one group per workgroup, 0.75 with two, 0.94 with four (direct kernel: 0.66)
     if (square_bn_divides != 0 && pl.bm == 128) kg = 1;
@@ -584,14 +536,40 @@ bool wgrad_v2_ok(long a_elems, long b_elems, long Kp) {
   return a_elems * 4 < (1L << 32) - 64 && b_elems * 4 < (1L << 32) - 64 && Kp < (1L << 23);
 }
 
-// launches igemm_wgrad_kernel for plan pl; out = dw or the split-K slab workspace
-int launch_wgrad_v2(const float* dy, const float* x, float* out, long a_elems, long b_elems, int H, int W, int C, int P, int Q,
-                    int R, int S, int stride, int pad, int Mc, int Nc, long Kp, const WgradPlan& pl, hipStream_t s) {
+// Staging LDS of the weight-gradient kernels: 2 buffers x BK x (BM + BN) floats per wave group.
+constexpr size_t wgrad_lds_bytes(int bm_plus_bn, int bk, int kg) { return (size_t)kg * 2 * bk * bm_plus_bn * sizeof(float); }
+
+// One weight-gradient launch (igemm_wgrad_kernel / igemm_wgrad2d_kernel): `kg` wave groups of 256 threads per workgroup, the staging
+// LDS dynamic.  Above 64 KB the kernel needs the attribute, set once per instantiation; `note` records the route between the two.
+template <auto Kernel, class Params, class Note>
+int launch_wave_groups(const Params& q, int kg, size_t lds, hipStream_t s, Note note) {
+  if (lds > 64 * 1024) {
+    static bool attr_set = false;
+    if (!attr_set) {
+      NNL_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      attr_set = true;
+    }
+  }
+  note();
+  hipLaunchKernelGGL(Kernel, dim3(q.grid_m * q.grid_n * q.splits), dim3(256 * kg), lds, s, q);
+  NNL_CHECK_LAUNCH();
+  return NNL_OK;
+}
+
+template <int BM, int BN, int BK, bool PIPE, int KG, bool PAIR>
+int launch_wgrad_tile(const IgemmWgradParams& q, hipStream_t s) {
+  return launch_wave_groups<igemm_wgrad_kernel<BM, BN, BK, 2, 2, PIPE, KG, false, PAIR>>(q, KG, wgrad_lds_bytes(BM + BN, BK, KG), s, [&] {
+    NNL_ROUTE("wgrad<%d,%d,%d,kg%d>%s%s@splits=%d", BM, BN, BK, KG, PAIR ? ":pair" : "", q.splits > 1 ? ":splitk" : "", q.splits);
+  });
+}
+
+// launches igemm_wgrad_kernel for plan pl on the problem of p (p.y = dw or the split-K slab workspace)
+int launch_wgrad_v2(const IgemmKmajorParams& p, long a_elems, long b_elems, const WgradPlan& pl, hipStream_t s) {
   IgemmWgradParams q{};
-  q.a = dy; q.b = x; q.y = out;
+  q.a = p.a; q.b = p.b; q.y = p.y;
   q.a_bytes = (unsigned)(a_elems * 4); q.b_bytes = (unsigned)(b_elems * 4);
-  q.H = H; q.W = W; q.C = C; q.P = P; q.Q = Q; q.R = R; q.S = S; q.stride = stride; q.pad = pad;
-  q.Mc = Mc; q.Nc = Nc; q.Kp = (int)Kp;
+  q.H = p.H; q.W = p.W; q.C = p.C; q.P = p.P; q.Q = p.Q; q.R = p.R; q.S = p.S; q.stride = p.stride; q.pad = p.pad;
+  q.Mc = p.Mc; q.Nc = p.Nc; q.Kp = (int)p.Kp;
   q.splits = pl.splits; q.k_per_split = pl.k_per_split; q.grid_m = pl.grid_m; q.grid_n = pl.grid_n;
 #ifdef NNL_TAPS_TIMING
   { static void* dbg = nullptr; if (!dbg) (void)hipMalloc(&dbg, 3276 * 5 * 8); q.dbg_t = (unsigned long long*)dbg; g_wgrad_dbg = dbg; }
@@ -606,45 +584,20 @@ int launch_wgrad_v2(const float* dy, const float* x, float* out, long a_elems, l
     const long fp_n = nnl_cdiv(T, gn) * pl.bm + (T < gn ? T : gn) * pl.bn;
     q.n_fast = fp_n < fp_m ? 1 : 0;
   }
-  const dim3 grid(pl.grid_m * pl.grid_n * pl.splits);
-  // staging LDS: 2 buffers x BK x (BM + BN) floats per wave group (dynamic: above 64 KB the kernel needs the attribute once)
-  auto lds_bytes = [](int bm, int bn, int bk, int kg) { return (size_t)kg * 2 * bk * (bm + bn) * sizeof(float); };
-#define NNL_WGRAD_LAUNCH(BM_, BN_, BK_, PIPE_, KG_, PAIR_)                                                                       \
-  do {                                                                                                                           \
-    const size_t lb = lds_bytes(BM_, BN_, BK_, KG_);                                                                             \
-    if (lb > 64 * 1024) {                                                                                                        \
-      static bool attr_set = false;                                                                                              \
-      if (!attr_set) {                                                                                                           \
-        NNL_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_wgrad_kernel<BM_, BN_, BK_, 2, 2, PIPE_, KG_, false, PAIR_>),  \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb));                                 \
-        attr_set = true;                                                                                                         \
-      }                                                                                                                          \
-    }                                                                                                                            \
-    NNL_ROUTE("wgrad<%d,%d,%d,kg%d>%s%s@splits=%d", BM_, BN_, BK_, KG_, PAIR_ ? ":pair" : "", pl.splits > 1 ? ":splitk" : "", pl.splits); \
-    hipLaunchKernelGGL((igemm_wgrad_kernel<BM_, BN_, BK_, 2, 2, PIPE_, KG_, false, PAIR_>), grid, dim3(256 * KG_), lb, s, q);    \
-  } while (0)
+  // the instantiations plan_wgrad asks for: four wave groups on the 128x128 tile only, the 64x64 tile with BK 32 only
+  const bool t128 = pl.bm == 128 && pl.bn == 128, t64 = pl.bm == 64 && pl.bn == 64;
+  if (!(pl.kg == 1 || (pl.kg == 4 && t128)) || (t64 && pl.k_per_split % 32 != 0))
+    return nnl_set_error(NNL_ERR_UNSUPPORTED, "wgrad: no kernel for the plan <%d,%d> kg=%d k_per_split=%d", pl.bm, pl.bn, pl.kg, pl.k_per_split);
   // PAIR staging (igemm_wgrad.h): both 16-byte chunks a thread stages per row must lie in one filter tap
-  const bool pair = R * S == 1 || C % pl.bn == 0;
-  if (pl.bm == 128 && pl.bn == 128) {                                   // (BK=32 measured -7 % here)
-    if (pl.kg == 4) { if (pair) NNL_WGRAD_LAUNCH(128, 128, 16, true, 4, true); else NNL_WGRAD_LAUNCH(128, 128, 16, true, 4, false); }
-    else if (pl.kg == 2) NNL_WGRAD_LAUNCH(128, 128, 16, true, 2, false);
-    else if (pair) NNL_WGRAD_LAUNCH(128, 128, 16, true, 1, true);
-    else NNL_WGRAD_LAUNCH(128, 128, 16, true, 1, false);
-  } else if (pl.bm == 128) {
-    NNL_WGRAD_LAUNCH(128, 64, 16, false, 1, false);
-  } else if (pl.bn == 128) {
-    NNL_WGRAD_LAUNCH(64, 128, 16, true, 1, false);
-  } else if (pl.k_per_split % 32 == 0) {                              // 64x64 tile: BK=32 (16 MFMAs per barrier) measured +3 %
-    if (pl.kg == 4) { if (pair) NNL_WGRAD_LAUNCH(64, 64, 32, true, 4, true); else NNL_WGRAD_LAUNCH(64, 64, 32, true, 4, false); }
-    else if (pl.kg == 2) NNL_WGRAD_LAUNCH(64, 64, 32, true, 2, false);
-    else if (pair) NNL_WGRAD_LAUNCH(64, 64, 32, true, 1, true);
-    else NNL_WGRAD_LAUNCH(64, 64, 32, true, 1, false);
-  } else {
-    NNL_WGRAD_LAUNCH(64, 64, 16, true, 1, false);
+  const bool pair = p.R * p.S == 1 || p.C % pl.bn == 0;
+  if (t128) {                                                           // (BK=32 measured -7 % here)
+    if (pl.kg == 4) return pair ? launch_wgrad_tile<128, 128, 16, true, 4, true>(q, s) : launch_wgrad_tile<128, 128, 16, true, 4, false>(q, s);
+    return pair ? launch_wgrad_tile<128, 128, 16, true, 1, true>(q, s) : launch_wgrad_tile<128, 128, 16, true, 1, false>(q, s);
   }
-#undef NNL_WGRAD_LAUNCH
-  NNL_CHECK_LAUNCH();
-  return NNL_OK;
+  if (pl.bm == 128) return launch_wgrad_tile<128, 64, 16, false, 1, false>(q, s);
+  if (pl.bn == 128) return launch_wgrad_tile<64, 128, 16, true, 1, false>(q, s);
+  // 64x64 tile: BK=32 (16 MFMAs per barrier) measured +3 %
+  return pair ? launch_wgrad_tile<64, 64, 32, true, 1, true>(q, s) : launch_wgrad_tile<64, 64, 32, true, 1, false>(q, s);
 }
 
 // dW [K][3][3][C] from the Winograd-domain slabs dU [splits][K][4][3][C] (igemm_wgrad_kernel<..., WINO>): the slabs are summed in
@@ -711,36 +664,12 @@ int launch_wgrad_wino(const float* dy, const float* x, float* slabs, const nnl_c
   q.Mc = g->K; q.Nc = 12 * g->C; q.Kp = (int)pairs;
   q.splits = pl.splits; q.k_per_split = pl.k_per_split; q.grid_m = pl.grid_m; q.grid_n = pl.grid_n;
   q.n_fast = 1;
-  const dim3 grid(pl.grid_m * pl.grid_n * pl.splits);
-  auto lds_bytes = [](int bm, int bn, int bk, int kg) { return (size_t)kg * 2 * bk * (bm + bn) * sizeof(float); };
-#define NNL_WGRAD_WINO_LAUNCH(BM_, BN_, BK_, KG_)                                                                                \
-  do {                                                                                                                           \
-    const size_t lb = lds_bytes(BM_, BN_, BK_, KG_);                                                                             \
-    if (lb > 64 * 1024) {                                                                                                        \
-      static bool attr_set = false;                                                                                              \
-      if (!attr_set) {                                                                                                           \
-        NNL_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_wgrad_kernel<BM_, BN_, BK_, 2, 2, true, KG_, true>), \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb));                                 \
-        attr_set = true;                                                                                                         \
-      }                                                                                                                          \
-    }                                                                                                                            \
-    NNL_ROUTE("wgrad_wino1d<%d,%d,kg%d>@splits=%d", BM_, BK_, KG_, pl.splits);                                                   \
-    hipLaunchKernelGGL((igemm_wgrad_kernel<BM_, BN_, BK_, 2, 2, true, KG_, true>), grid, dim3(256 * KG_), lb, s, q);             \
-  } while (0)
-  if (pl.bm == 128) {
-    if (pl.kg == 4) NNL_WGRAD_WINO_LAUNCH(128, 128, 16, 4);
-    else if (pl.kg == 2) NNL_WGRAD_WINO_LAUNCH(128, 128, 16, 2);
-    else NNL_WGRAD_WINO_LAUNCH(128, 128, 16, 1);
-  } else if (pl.k_per_split % 32 == 0) {
-    if (pl.kg == 4) NNL_WGRAD_WINO_LAUNCH(64, 64, 32, 4);
-    else if (pl.kg == 2) NNL_WGRAD_WINO_LAUNCH(64, 64, 32, 2);
-    else NNL_WGRAD_WINO_LAUNCH(64, 64, 32, 1);
-  } else {
-    NNL_WGRAD_WINO_LAUNCH(64, 64, 16, 1);
-  }
-#undef NNL_WGRAD_WINO_LAUNCH
-  NNL_CHECK_LAUNCH();
-  return NNL_OK;
+  // the instantiations plan_wgrad asks for on Winograd-domain columns: one wave group, the 64x64 tile with BK 32 only
+  if (pl.kg != 1 || (pl.bm == 64 && pl.k_per_split % 32 != 0))
+    return nnl_set_error(NNL_ERR_UNSUPPORTED, "wgrad_wino1d: no kernel for the plan <%d> kg=%d k_per_split=%d", pl.bm, pl.kg, pl.k_per_split);
+  const auto note = [&] { NNL_ROUTE("wgrad_wino1d<%d,%d,kg1>@splits=%d", pl.bm, pl.bm == 128 ? 16 : 32, pl.splits); };
+  if (pl.bm == 128) return launch_wave_groups<igemm_wgrad_kernel<128, 128, 16, 2, 2, true, 1, true>>(q, 1, wgrad_lds_bytes(256, 16, 1), s, note);
+  return launch_wave_groups<igemm_wgrad_kernel<64, 64, 32, 2, 2, true, 1, true>>(q, 1, wgrad_lds_bytes(128, 32, 1), s, note);
 }
 
 // ---- the weight gradient in the 2-D Winograd F(2x2, 3x3) domain (igemm_wgrad2d.h, round 4) ----
@@ -839,35 +768,77 @@ int launch_wgrad_wino2d(const float* dy, const float* x, float* slabs, const nnl
   q.Mc = g->K; q.Nc = 16 * g->C; q.Kp = (int)((long)g->N * q.H2 * q.W2);
   q.splits = pl.splits; q.k_per_split = pl.k_per_split; q.grid_m = pl.grid_m; q.grid_n = pl.grid_n;
   q.n_fast = 1;
-  const dim3 grid(pl.grid_m * pl.grid_n * pl.splits);
-  auto lds_bytes = [](int bt, int bk, int kg) { return (size_t)kg * 2 * bk * 2 * bt * sizeof(float); };
-#define NNL_WGRAD2D_LAUNCH(BT_, BK_, KG_)                                                                                        \
-  do {                                                                                                                           \
-    const size_t lb = lds_bytes(BT_, BK_, KG_);                                                                                  \
-    if (lb > 64 * 1024) {                                                                                                        \
-      static bool attr_set = false;                                                                                              \
-      if (!attr_set) {                                                                                                           \
-        NNL_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&igemm_wgrad2d_kernel<BT_, BK_, KG_>),             \
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb));                                 \
-        attr_set = true;                                                                                                         \
-      }                                                                                                                          \
-    }                                                                                                                            \
-    NNL_ROUTE("wgrad_wino2d<%d,%d,kg%d>@splits=%d", BT_, BK_, KG_, pl.splits);                                                   \
-    hipLaunchKernelGGL((igemm_wgrad2d_kernel<BT_, BK_, KG_>), grid, dim3(256 * KG_), lb, s, q);                            \
-  } while (0)
-  if (pl.bm == 128) {
-    if (pl.kg == 2) NNL_WGRAD2D_LAUNCH(128, 16, 2);
-    else NNL_WGRAD2D_LAUNCH(128, 16, 1);
-  } else if (pl.k_per_split % 32 == 0) {
-    if (pl.kg == 4) NNL_WGRAD2D_LAUNCH(64, 32, 4);
-    else if (pl.kg == 2) NNL_WGRAD2D_LAUNCH(64, 32, 2);
-    else NNL_WGRAD2D_LAUNCH(64, 32, 1);
+  // the instantiations plan_wgrad_wino2d asks for: four wave groups on the 64x64 tile only, that tile with BK 32 only
+  if (!(pl.kg == 1 || (pl.kg == 4 && pl.bm == 64)) || (pl.bm == 64 && pl.k_per_split % 32 != 0))
+    return nnl_set_error(NNL_ERR_UNSUPPORTED, "wgrad_wino2d: no kernel for the plan <%d> kg=%d k_per_split=%d", pl.bm, pl.kg, pl.k_per_split);
+  const auto note = [&] { NNL_ROUTE("wgrad_wino2d<%d,%d,kg%d>@splits=%d", pl.bm, pl.bm == 128 ? 16 : 32, pl.kg, pl.splits); };
+  if (pl.bm == 128) return launch_wave_groups<igemm_wgrad2d_kernel<128, 16, 1>>(q, 1, wgrad_lds_bytes(256, 16, 1), s, note);
+  if (pl.kg == 4) return launch_wave_groups<igemm_wgrad2d_kernel<64, 32, 4>>(q, 4, wgrad_lds_bytes(128, 32, 4), s, note);
+  return launch_wave_groups<igemm_wgrad2d_kernel<64, 32, 1>>(q, 1, wgrad_lds_bytes(128, 32, 1), s, note);
+}
+
+// The direct weight gradient of problem p under plan pl: igemm_wgrad_kernel (beyond its 32-bit ranges the first-generation k-major
+// kernel) into dw, or split into the slabs of ws, which splitk_reduce_kernel then adds in index order.
+int launch_wgrad_direct(IgemmKmajorParams p, const WgradPlan& pl, float* ws, float* dw, hipStream_t s) {
+  p.grid_m = pl.grid_m; p.grid_n = pl.grid_n; p.splits = pl.splits; p.k_per_split = pl.k_per_split;
+  p.y = pl.splits > 1 ? ws : dw;
+  const long a_elems = p.Kp * p.Mc, b_elems = (long)p.N * p.H * p.W * p.C;
+  if (wgrad_v2_ok(a_elems, b_elems, p.Kp)) {
+    const int st = launch_wgrad_v2(p, a_elems, b_elems, pl, s);
+    if (st) return st;
   } else {
-    NNL_WGRAD2D_LAUNCH(64, 16, 1);
+    const dim3 grid(pl.grid_m * pl.grid_n * pl.splits), block(256);
+    NNL_ROUTE("wgrad_kmajor<%d,%d>%s@splits=%d", pl.bm, pl.bn, pl.splits > 1 ? ":splitk" : "", pl.splits);
+    if (pl.bm == 128 && pl.bn == 128)
+      hipLaunchKernelGGL((igemm_kmajor_kernel<128, 128, 16, 2, 2>), grid, block, 0, s, p);
+    else if (pl.bm == 128)
+      hipLaunchKernelGGL((igemm_kmajor_kernel<128, 64, 16, 2, 2>), grid, block, 0, s, p);
+    else if (pl.bn == 128)
+      hipLaunchKernelGGL((igemm_kmajor_kernel<64, 128, 16, 2, 2>), grid, block, 0, s, p);
+    else
+      hipLaunchKernelGGL((igemm_kmajor_kernel<64, 64, 16, 2, 2>), grid, block, 0, s, p);
+    NNL_CHECK_LAUNCH();
   }
-#undef NNL_WGRAD2D_LAUNCH
-  NNL_CHECK_LAUNCH();
+  if (pl.splits > 1) {
+    const long n4 = (long)p.Mc * p.Nc / 4;                   // Nc % 4 == 0: R*S*C with C % 4 == 0, or checked by gemm_tn
+    NNL_ROUTE("splitk_reduce");
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)nnl_cdiv(n4, 32)), dim3(256), 0, s, (const float*)ws, dw, n4, pl.splits);
+    NNL_CHECK_LAUNCH();
+  }
   return NNL_OK;
+}
+
+// The forward convolution as a tap-table GEMM: rows = output pixels, dense output, the R x S raster r-major (affine where S allows).
+IgemmTapsParams fwd_taps_params(const nnl_conv_geom_t* g, const float* x, const float* w, float* y, const float* bias, int relu) {
+  IgemmTapsParams q{};
+  q.a = x; q.b = w; q.y = y; q.bias = bias; q.add = nullptr;
+  q.a_bytes = (unsigned)((long)g->N * g->H * g->W * g->C * 4); q.b_bytes = (unsigned)((long)g->K * g->R * g->S * g->C * 4);
+  q.H = g->H; q.W = g->W; q.C = g->C; q.P = g->P; q.Q = g->Q;
+  q.in_stride = g->stride; q.ih0 = -g->pad; q.iw0 = -g->pad;
+  q.OH = g->P; q.OW = g->Q; q.out_stride = 1; q.oh0 = 0; q.ow0 = 0;
+  q.M = g->N * g->P * g->Q; q.Nc = g->K; q.b_row_stride = g->R * g->S * g->C; q.relu = relu;
+  q.ntaps = g->R * g->S;
+  for (int r = 0; r < g->R; ++r)
+    for (int ss = 0; ss < g->S; ++ss) {
+      const int t = r * g->S + ss;
+      q.tap_dh[t] = (signed char)r; q.tap_dw[t] = (signed char)ss;
+      q.tap_aoff[t] = (r * g->W + ss) * g->C; q.tap_woff[t] = t * g->C;
+    }
+  q.tap_affine = affine_taps_ok(g->S); q.tap_R = g->R; q.tap_S = g->S; q.tap_dh0 = 0; q.tap_dw0 = 0; q.tap_dstep = 1;
+  return q;
+}
+
+// y[M][N] = a[M][K] * b[N][K]^T as a one-tap GEMM
+IgemmTapsParams gemm_taps_params(const float* a, const float* b, float* y, int M, int N, int K) {
+  IgemmTapsParams q{};
+  q.a = a; q.b = b; q.y = y;
+  q.a_bytes = (unsigned)((long)M * K * 4); q.b_bytes = (unsigned)((long)N * K * 4);
+  q.H = 1; q.W = 1; q.C = K; q.P = 1; q.Q = 1; q.in_stride = 1; q.ih0 = 0; q.iw0 = 0;
+  q.OH = 1; q.OW = 1; q.out_stride = 1; q.oh0 = 0; q.ow0 = 0;
+  q.M = M; q.Nc = N; q.b_row_stride = K; q.ntaps = 1;
+  q.tap_dh[0] = 0; q.tap_dw[0] = 0; q.tap_aoff[0] = 0; q.tap_woff[0] = 0;
+  q.tap_affine = 1; q.tap_R = 1; q.tap_S = 1; q.tap_dstep = 1;
+  return q;
 }
 
 }  // namespace
@@ -880,14 +851,8 @@ int nnl_internal_gemm_nt(const float* a, const float* b, float* y, const float* 
   p.N = M; p.H = 1; p.W = 1; p.C = K; p.P = 1; p.Q = 1; p.R = 1; p.S = 1; p.stride = 1; p.pad = 0;
   p.M = M; p.Nc = N; p.Kg = K; p.relu = relu;
   if (taps_ok((long)M * K, (long)N * K, K, 1)) {
-    IgemmTapsParams q{};
-    q.a = a; q.b = b; q.y = y; q.bias = bias; q.add = add;
-    q.a_bytes = (unsigned)((long)M * K * 4); q.b_bytes = (unsigned)((long)N * K * 4);
-    q.H = 1; q.W = 1; q.C = K; q.P = 1; q.Q = 1; q.in_stride = 1; q.ih0 = 0; q.iw0 = 0;
-    q.OH = 1; q.OW = 1; q.out_stride = 1; q.oh0 = 0; q.ow0 = 0;
-    q.M = M; q.Nc = N; q.b_row_stride = K; q.relu = relu; q.ntaps = 1;
-    q.tap_dh[0] = 0; q.tap_dw[0] = 0; q.tap_aoff[0] = 0; q.tap_woff[0] = 0;
-    q.tap_affine = 1; q.tap_R = 1; q.tap_S = 1; q.tap_dstep = 1;
+    IgemmTapsParams q = gemm_taps_params(a, b, y, M, N, K);
+    q.bias = bias; q.add = add; q.relu = relu;
     return dispatch_taps(q, s);
   }
   return dispatch_rowk<IGEMM_MODE_FWD>(p, s);
@@ -898,14 +863,7 @@ int nnl_internal_gemm_nt(const float* a, const float* b, float* y, const float* 
 int nnl_internal_gemm_nt_splitk(const float* a, const float* b, float* y_slabs, int M, int N, int K, int splits, hipStream_t s) {
   if (M <= 0 || N <= 0 || K <= 0 || K % 32 != 0 || splits < 1 || !taps_ok((long)M * K, (long)N * K, K, 1))
     return nnl_set_error(NNL_ERR_INVALID_ARG, "gemm_nt_splitk: bad sizes M=%d N=%d K=%d", M, N, K);
-  IgemmTapsParams q{};
-  q.a = a; q.b = b; q.y = y_slabs; q.bias = nullptr; q.add = nullptr;
-  q.a_bytes = (unsigned)((long)M * K * 4); q.b_bytes = (unsigned)((long)N * K * 4);
-  q.H = 1; q.W = 1; q.C = K; q.P = 1; q.Q = 1; q.in_stride = 1; q.ih0 = 0; q.iw0 = 0;
-  q.OH = 1; q.OW = 1; q.out_stride = 1; q.oh0 = 0; q.ow0 = 0;
-  q.M = M; q.Nc = N; q.b_row_stride = K; q.relu = 0; q.ntaps = 1;
-  q.tap_dh[0] = 0; q.tap_dw[0] = 0; q.tap_aoff[0] = 0; q.tap_woff[0] = 0;
-  q.tap_affine = 1; q.tap_R = 1; q.tap_S = 1; q.tap_dstep = 1;
+  IgemmTapsParams q = gemm_taps_params(a, b, y_slabs, M, N, K);
   q.ksplit = splits; q.slab_stride = (long)M * N;
   return launch_taps<64, 64, 32>(q, s);
 }
@@ -937,34 +895,9 @@ int nnl_internal_gemm_tn(const float* a, const float* b, float* y, int Mc, int N
   p.a = a; p.b = b;
   p.N = (int)Kp; p.H = 1; p.W = 1; p.C = Nc; p.P = 1; p.Q = 1; p.R = 1; p.S = 1; p.stride = 1; p.pad = 0;
   p.Mc = Mc; p.Nc = Nc; p.Kp = Kp;
-  const WgradPlan pl = plan_wgrad(Mc, Nc, Kp);
-  p.grid_m = pl.grid_m; p.grid_n = pl.grid_n; p.splits = pl.splits; p.k_per_split = pl.k_per_split;
   const size_t need = nnl_internal_gemm_tn_workspace_bytes(Mc, Nc, Kp);
   if (need > 0 && (ws == nullptr || ws_bytes < need)) return nnl_set_error(NNL_ERR_WORKSPACE, "gemm_tn: workspace too small");
-  p.y = pl.splits > 1 ? (float*)ws : y;
-  if (wgrad_v2_ok(Kp * Mc, Kp * Nc, Kp)) {
-    int st = launch_wgrad_v2(a, b, p.y, Kp * Mc, Kp * Nc, 1, 1, Nc, 1, 1, 1, 1, 1, 0, Mc, Nc, Kp, pl, s);
-    if (st) return st;
-  } else {
-    const dim3 grid(pl.grid_m * pl.grid_n * pl.splits), block(256);
-    NNL_ROUTE("wgrad_kmajor<%d,%d>%s@splits=%d", pl.bm, pl.bn, pl.splits > 1 ? ":splitk" : "", pl.splits);
-    if (pl.bm == 128 && pl.bn == 128)
-      hipLaunchKernelGGL((igemm_kmajor_kernel<128, 128, 16, 2, 2>), grid, block, 0, s, p);
-    else if (pl.bm == 128)
-      hipLaunchKernelGGL((igemm_kmajor_kernel<128, 64, 16, 2, 2>), grid, block, 0, s, p);
-    else if (pl.bn == 128)
-      hipLaunchKernelGGL((igemm_kmajor_kernel<64, 128, 16, 2, 2>), grid, block, 0, s, p);
-    else
-      hipLaunchKernelGGL((igemm_kmajor_kernel<64, 64, 16, 2, 2>), grid, block, 0, s, p);
-    NNL_CHECK_LAUNCH();
-  }
-  if (pl.splits > 1) {
-    const long n4 = (long)Mc * Nc / 4;
-    NNL_ROUTE("splitk_reduce");
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)nnl_cdiv(n4, 32)), dim3(256), 0, s, (const float*)ws, y, n4, pl.splits);
-    NNL_CHECK_LAUNCH();
-  }
-  return NNL_OK;
+  return launch_wgrad_direct(p, plan_wgrad(Mc, Nc, Kp), (float*)ws, y, s);
 }
 
 // Which kernel serves a 3x3 / stride 1 / pad 1 problem (in = [N][H][W][Cin], Nc output channels)?  NNL_CONV_WINO: 0 never the
@@ -1090,22 +1023,8 @@ extern "C" int nnl_conv2d_fwd_pre(const float* x, const float* w, const float* b
     return st;
   }
   if (const int tk = taps_kind(a_elems, b_elems, g->C, g->R * g->S)) {
-    IgemmTapsParams q{};
+    IgemmTapsParams q = fwd_taps_params(g, x, w, y, bias, relu);
     q.ktail = tk == 2;
-    q.a = x; q.b = w; q.y = y; q.bias = bias; q.add = nullptr;
-    q.a_bytes = (unsigned)(a_elems * 4); q.b_bytes = (unsigned)(b_elems * 4);
-    q.H = g->H; q.W = g->W; q.C = g->C; q.P = g->P; q.Q = g->Q;
-    q.in_stride = g->stride; q.ih0 = -g->pad; q.iw0 = -g->pad;
-    q.OH = g->P; q.OW = g->Q; q.out_stride = 1; q.oh0 = 0; q.ow0 = 0;
-    q.M = p.M; q.Nc = g->K; q.b_row_stride = g->R * g->S * g->C; q.relu = relu;
-    q.ntaps = g->R * g->S;
-    for (int r = 0; r < g->R; ++r)
-      for (int ss = 0; ss < g->S; ++ss) {
-        const int t = r * g->S + ss;
-        q.tap_dh[t] = (signed char)r; q.tap_dw[t] = (signed char)ss;
-        q.tap_aoff[t] = (r * g->W + ss) * g->C; q.tap_woff[t] = t * g->C;
-      }
-    q.tap_affine = affine_taps_ok(g->S); q.tap_R = g->R; q.tap_S = g->S; q.tap_dh0 = 0; q.tap_dw0 = 0; q.tap_dstep = 1;
     q.bn_part = (bn_partials && bn_pivot && bn_rows) ? bn_partials : nullptr; q.bn_pivot = bn_pivot;
     return dispatch_taps(q, s, workspace, workspace_bytes, tile_counters, bn_rows);
   }
@@ -1127,21 +1046,8 @@ extern "C" int nnl_conv2d_fwd_add_up2(const float* x, const float* w, const floa
   hipStream_t s = (hipStream_t)stream;
   const long M = (long)g->N * g->P * g->Q;
   NnlProfScope prof(NNL_PROF_CONV_FWD, s, 2.0 * M * (double)g->K * g->R * g->S * g->C);
-  IgemmTapsParams q{};
-  q.a = x; q.b = w; q.y = y; q.bias = bias; q.add = small; q.add_up2 = 1;
-  q.a_bytes = (unsigned)(a_elems * 4); q.b_bytes = (unsigned)(b_elems * 4);
-  q.H = g->H; q.W = g->W; q.C = g->C; q.P = g->P; q.Q = g->Q;
-  q.in_stride = g->stride; q.ih0 = -g->pad; q.iw0 = -g->pad;
-  q.OH = g->P; q.OW = g->Q; q.out_stride = 1; q.oh0 = 0; q.ow0 = 0;
-  q.M = (int)M; q.Nc = g->K; q.b_row_stride = g->R * g->S * g->C; q.relu = 0;
-  q.ntaps = g->R * g->S;
-  for (int r = 0; r < g->R; ++r)
-    for (int ss = 0; ss < g->S; ++ss) {
-      const int t = r * g->S + ss;
-      q.tap_dh[t] = (signed char)r; q.tap_dw[t] = (signed char)ss;
-      q.tap_aoff[t] = (r * g->W + ss) * g->C; q.tap_woff[t] = t * g->C;
-    }
-  q.tap_affine = affine_taps_ok(g->S); q.tap_R = g->R; q.tap_S = g->S; q.tap_dh0 = 0; q.tap_dw0 = 0; q.tap_dstep = 1;
+  IgemmTapsParams q = fwd_taps_params(g, x, w, y, bias, 0);
+  q.add = small; q.add_up2 = 1;
   return dispatch_taps(q, s);            // no workspace: the plain grid (the split-tile fix-up path reads a same-shape addend only)
 }
 
@@ -1303,12 +1209,9 @@ extern "C" int nnl_conv2d_wgrad(const float* x, const float* dy, float* dw, cons
   p.N = g->N; p.H = g->H; p.W = g->W; p.C = g->C; p.P = g->P; p.Q = g->Q;
   p.R = g->R; p.S = g->S; p.stride = g->stride; p.pad = g->pad;
   p.Mc = g->K; p.Nc = g->R * g->S * g->C; p.Kp = (long)g->N * g->P * g->Q;
-  const WgradPlan pl = plan_wgrad(p.Mc, p.Nc, p.Kp);
-  p.grid_m = pl.grid_m; p.grid_n = pl.grid_n; p.splits = pl.splits; p.k_per_split = pl.k_per_split;
   const size_t need = nnl_conv2d_wgrad_workspace_bytes(g);
   if (need > 0 && (workspace == nullptr || workspace_bytes < need))
     return nnl_set_error(NNL_ERR_WORKSPACE, "conv2d_wgrad: workspace %zu B < required %zu B", workspace_bytes, need);
-  p.y = pl.splits > 1 ? (float*)workspace : dw;
   NnlProfScope prof(NNL_PROF_CONV_WGRAD, s, 2.0 * p.Kp * (double)p.Mc * p.Nc);
   if (wgrad_wino2d_ok(g)) {                                 // 2-D Winograd-domain weight gradient (igemm_wgrad2d.h) + the fold-back reduce
     const WgradPlan wp = plan_wgrad_wino2d(g);
@@ -1334,31 +1237,7 @@ extern "C" int nnl_conv2d_wgrad(const float* x, const float* dy, float* dw, cons
     NNL_CHECK_LAUNCH();
     return NNL_OK;
   }
-  const long a_elems = p.Kp * g->K, b_elems = (long)g->N * g->H * g->W * g->C;
-  if (wgrad_v2_ok(a_elems, b_elems, p.Kp)) {
-    int st2 = launch_wgrad_v2(dy, x, p.y, a_elems, b_elems, g->H, g->W, g->C, g->P, g->Q, g->R, g->S, g->stride, g->pad, p.Mc,
-                              p.Nc, p.Kp, pl, s);
-    if (st2) return st2;
-  } else {
-    const dim3 grid(pl.grid_m * pl.grid_n * pl.splits), block(256);
-    NNL_ROUTE("wgrad_kmajor<%d,%d>%s@splits=%d", pl.bm, pl.bn, pl.splits > 1 ? ":splitk" : "", pl.splits);
-    if (pl.bm == 128 && pl.bn == 128)
-      hipLaunchKernelGGL((igemm_kmajor_kernel<128, 128, 16, 2, 2>), grid, block, 0, s, p);
-    else if (pl.bm == 128)
-      hipLaunchKernelGGL((igemm_kmajor_kernel<128, 64, 16, 2, 2>), grid, block, 0, s, p);
-    else if (pl.bn == 128)
-      hipLaunchKernelGGL((igemm_kmajor_kernel<64, 128, 16, 2, 2>), grid, block, 0, s, p);
-    else
-      hipLaunchKernelGGL((igemm_kmajor_kernel<64, 64, 16, 2, 2>), grid, block, 0, s, p);
-    NNL_CHECK_LAUNCH();
-  }
-  if (pl.splits > 1) {
-    const long n4 = (long)p.Mc * p.Nc / 4;                 // Nc = R*S*C with C % 4 == 0
-    NNL_ROUTE("splitk_reduce");
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)nnl_cdiv(n4, 32)), dim3(256), 0, s, (const float*)workspace, dw, n4, pl.splits);
-    NNL_CHECK_LAUNCH();
-  }
-  return NNL_OK;
+  return launch_wgrad_direct(p, plan_wgrad(p.Mc, p.Nc, p.Kp), (float*)workspace, dw, s);
 }
 
 extern "C" size_t nnl_colsum_workspace_bytes(int64_t rows, int64_t cols) {

@@ -401,11 +401,11 @@ __global__ __launch_bounds__(256, 4) void wino_kernel(const WinoParams p) {
   }
 }
 
-// ---- schedule: the balanced plan of conv2d.hip (plan_balance_tile) for I = 12 * C / BK iterations per tile ----
+// ---- schedule: the balanced plan of conv2d.hip (plan_balance) for I = 12 * C / BK iterations per tile ----
 struct WPlan {
   int bk, on, main_ks, n_main_tiles, tail_slices, tail_row0;
   size_t main_floats, tail_floats;
-  double t_us;                           // predicted launch time (same cost model as conv2d.hip's plan_balance_tile)
+  double t_us;                           // predicted launch time (same cost model as conv2d.hip's plan_balance)
 };
 
 WPlan wino_plan(long M2, int Nc, int C) {

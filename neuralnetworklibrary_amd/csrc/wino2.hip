@@ -528,7 +528,7 @@ __global__ __launch_bounds__(256, OCC) void wino2_kernel(const Wino2Params p) {
   }
 }
 
-// ---- schedule: the balanced plan of conv2d.hip (plan_balance_tile) for I = 16 * C / BK iterations per tile ----
+// ---- schedule: the balanced plan of conv2d.hip (plan_balance) for I = 16 * C / BK iterations per tile ----
 struct W2Plan {
   int bk, on, main_ks, n_main_tiles, tail_slices, tail_row0;
   size_t main_floats, tail_floats;

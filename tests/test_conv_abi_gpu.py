@@ -252,7 +252,7 @@ def _bal(bk, extra=('',)):
 # site was added or renamed without this file being told
 KNOWN = set(
     ['rowk<%d,%d>:%s' % (bm, bn, m) for bm, bn in ((64, 64), (128, 64), (64, 128), (128, 128)) for m in ('fwd', 'dgrad')] +
-    ['taps<%d,%d,16>%s' % (bm, bn, n) for bm, bn in ((128, 128), (128, 64), (64, 128)) for n in ('', ':ncls')] +
+    ['taps<128,128,16>', 'taps<128,128,16>:ncls'] +
     ['taps<64,64,%d>%s%s%s' % (bk, d, n, k) for bk in (16, 32) for d in ('', ':dma') for n in ('', ':ncls') for k in ('', ':ksplit')] +
     ['taps_ktail<16>', 'taps_ktail<32>'] + _bal(16, ('', ':ktail', ':dma')) + _bal(32, ('', ':ktail', ':dma')) +
     ['slab_reduce:main', 'slab_reduce:tail', 'dgrad:merged', 'dgrad:per_class', 'dgrad:need_zero'] +
@@ -260,11 +260,10 @@ KNOWN = set(
     ['wino1d<%d>:%s:%s' % (bk, pl, u) for bk in (16, 32) for pl in ('plain', 'ksliced') for u in ('own_u', 'u_pre')] +
     ['wino2d<%s>:%s:%s' % (t, pl, u) for t in ('32,3', '16,4') for pl in ('plain', 'ksliced') for u in ('own_u', 'u_pre')] +
     ['wino2d<32,4,pos>:own_u', 'wino2d<32,4,pos>:u_pre'] +
-    ['wgrad<%s,kg%d>%s%s' % (t, kg, pr, sp) for t in ('128,128,16', '128,64,16', '64,128,16', '64,64,32', '64,64,16') for kg in (1, 2, 4)
-     for pr in ('', ':pair') for sp in ('', ':splitk')] +
+    ['wgrad<%s>%s%s' % (t, pr, sp) for t in ('128,128,16,kg1', '128,128,16,kg4', '64,64,32,kg1') for pr in ('', ':pair') for sp in ('', ':splitk')] +
+    ['wgrad<%s,kg1>%s' % (t, sp) for t in ('128,64,16', '64,128,16') for sp in ('', ':splitk')] +
     ['wgrad_kmajor<%d,%d>%s' % (bm, bn, sp) for bm, bn in ((64, 64), (128, 64), (64, 128), (128, 128)) for sp in ('', ':splitk')] +
-    ['wgrad_wino1d<%s,kg%d>' % (t, kg) for t in ('128,16', '64,32', '64,16') for kg in (1, 2, 4)] +
-    ['wgrad_wino2d<%s,kg%d>' % (t, kg) for t in ('128,16', '64,32', '64,16') for kg in (1, 2, 4)] +
+    ['wgrad_wino1d<128,16,kg1>', 'wgrad_wino1d<64,32,kg1>', 'wgrad_wino2d<128,16,kg1>', 'wgrad_wino2d<64,32,kg1>', 'wgrad_wino2d<64,32,kg4>'] +
     ['splitk_reduce', 'wgrad_wino1d_finish', 'wgrad_wino2d_finish'])
 
 # the routes the sweep must reach, per entry point; what KNOWN holds beyond these is accounted for in NOT_REACHED below
@@ -326,22 +325,15 @@ ROUTES = {
 }
 assert all(r in KNOWN for rs in ROUTES.values() for r in rs)
 
-# Launch sites the sweep does not reach, and why.  Dead instantiations are reported, not removed.
+# Launch sites the sweep does not reach, and why.  An instantiation that no input can select does not belong here: it is removed from the
+# dispatcher, and from KNOWN.
 NOT_REACHED = {
-    'taps<128,64,16>, taps<64,128,16>, taps<128,128,16> by cost':
-        'dispatch_taps: every 128-row / 128-column candidate carries eff 0.90 on the same per-CU workgroup count as the 64 x 64 tile of a '
-        'quarter / half its area, so the 64 x 64 tile wins the cost formula for every (M, Nc, ncls) — checked exhaustively over 1 .. 4000 tile '
-        'rows; only the one-tap Nc >= 8192 rule launches a 128 x 128 tile.  Dead code in the default dispatcher.',
-    'wgrad<*,kg2>, wgrad<64,64,32,kg4>, wgrad<64,64,16,kg1>, wgrad_wino1d<*,kg2|kg4>, wgrad_wino1d<64,16>, wgrad_wino2d<128,16,kg2>, '
-    'wgrad_wino2d<64,32,kg2>, wgrad_wino2d<64,16>':
-        'plan_wgrad only ever sets kg to 1 or (128 x 128 tile, >= 16 splits) 4, plan_wgrad_wino2d to 1 or (64 x 64) 4, and k_per_split is '
-        'always a multiple of 32: no input selects these instantiations.',
     'wgrad<128,128,16,kg1>, wgrad_wino1d<128,16,kg1>':
         'reached only from 1.5e10 flop per pass upwards (64 x 512 x 14 x 14 -> 512 at stride 2; 17 x 128 x 28 x 28 -> 512 under NNL_WGRAD_WINO=2): each '
         'would take the fifth named slot AND 1.5e10 of the 0.3e10 flop the list has left under its 1e11 cap.  The four slots in use go to the 2-D '
         'Winograd-domain kg4 plan (what ResNet-34 takes at 64 images) and the three other direct tile shapes.',
     'balanced<16>:ktail:main_ks*':
-        'KTAIL under the 16-wide k block means a (rounded) C below 256, at most 14 k steps per tile; plan_balance_tile needs 8 per slice for '
+        'KTAIL under the 16-wide k block means a (rounded) C below 256, at most 14 k steps per tile; plan_balance needs 8 per slice for '
         'main_ks = 2.  No input selects it.',
     'balanced<*>:dma:* beyond the three dma cases, balanced<32>:ktail:main_ks:tail_slices in the forward':
         'the LDS-DMA experiment (NNL_IGEMM_DMA) is run on three shapes, not on every plan; the KTAIL plan with both slicings runs in the dgrad.',
