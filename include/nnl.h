@@ -494,6 +494,40 @@ int nnl_attn_pool_bwd(const float* h, const float* w2, const float* enc_out, con
                       const float* dattn, float* dh, float* denc, float* dw2, float* db2, int64_t T, int64_t B, int64_t E, int64_t A,
                       void* workspace, size_t workspace_bytes, int32_t* counters, int64_t n_counters, void* stream);
 
+/* ---- K9: image augmentation of the classification Transform (Applications/Vision.py:449-507), everything after decode ------
+ * One fp32 NHWC minibatch out [bs, sz_h, sz_w, 3] from a uint8 arena that holds every image of a dataset back to back (HWC, RGB);
+ * desc[i] = {byte offset, H, W} of image i (int64: the arena may exceed 2 GB), params[b] = what Transform.__call__ drew for sample
+ * b.  Per output pixel, the reference's chain run backwards (Vision.py:449-507): undo np.rot90(img, rot) (:493) and np.fliplr
+ * (:492); apply the inverse map m of cv2.warpAffine(getRotationMatrix2D(...), borderMode=BORDER_REFLECT) (:488-489): source
+ * (m[0] x + m[1] y + m[2], m[3] x + m[4] y + m[5]), bilinear over its four integer taps, each tap index reflected on its own
+ * (fedcba|abcdefgh|hgfedcb, any distance); each tap is a pixel of cv2.resize(crop, (sz_w, sz_h), INTER_LINEAR) (:484): source
+ * coordinate (o + 0.5) (L_src / sz) - 0.5, two taps per axis clamped to the crop; the crop window (:469-481) is read from the
+ * arena as float(v) / 255.0f (open_image, :54-61).  Neither the resized nor the warped image is ever written.  Unlike cv2.warpAffine
+ * the source coordinates are NOT rounded to 1/32 pixel.  Every source index is finally clamped into its image and into the arena:
+ * no table can make the kernel read outside [arena, arena + arena_bytes).
+ * lighting != 0 (the training transform): the geometric pass also writes per-workgroup channel sums to the workspace and a second
+ * launch adds them in a fixed order (no float atomics: bitwise repeatable), applies clip((x - mu) cont + bal + mu, 0, 1) with mu
+ * the per-channel mean of the sample's transformed image (:496-498) to every sample without NNL_IMAGE_AUG_NO_LIGHTING, then
+ * (x - mean) / std (:504), in place.  lighting == 0 (the eval transform): one launch, normalised in the geometric pass.
+ * mean_std: HOST pointer to {mean[3], std[3]}, NULL = no normalisation (stats=None). */
+typedef struct {
+  int64_t offset;        /* byte offset of pixel (0, 0), channel 0 in the arena */
+  int64_t H, W;
+} nnl_image_desc_t;
+enum { NNL_IMAGE_AUG_NO_WARP = 1, NNL_IMAGE_AUG_FLIP = 2, NNL_IMAGE_AUG_NO_LIGHTING = 4 };
+typedef struct {
+  int64_t image;                              /* row of desc */
+  int32_t crop_y, crop_x, crop_h, crop_w;     /* crop window in the image (the whole image for crop_type None) */
+  float m[6];                                 /* inverse rotate-zoom map (ignored with NNL_IMAGE_AUG_NO_WARP) */
+  int32_t flags;                              /* NNL_IMAGE_AUG_* */
+  int32_t rot;                                /* k of np.rot90, 0..3 (1 and 3 need sz_h == sz_w) */
+  float bal, cont;
+} nnl_image_aug_param_t;                      /* 64 bytes */
+size_t nnl_image_aug_workspace_bytes(int64_t bs, int64_t sz_h, int64_t sz_w);
+int nnl_image_aug(const uint8_t* arena, int64_t arena_bytes, const nnl_image_desc_t* desc, int64_t n_images,
+                  const nnl_image_aug_param_t* params, int64_t bs, int64_t sz_h, int64_t sz_w, const float* mean_std, int lighting,
+                  float* out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- K8: fused multi-tensor Optimizer.step ------------------------------------------------------------------------
  * Replaces Optimizer.step (General/Optimizer.py:58-70): decoupled weight decay X *= 1 - wd_g*lr_g (:60-67), global-norm
  * clip (:54-56, torch.nn.utils.clip_grad_norm_) and the torch.optim SGD(momentum) / Adam update (General/Learner.py:17-19)

@@ -1,12 +1,16 @@
-"""Vision application of the drop-in API: model + loss side of the reference's Applications/Vision.py
-(§5 ImageClassificationNet :1203-1373, §6 ObjectDetectionNet and the SSD loss :1376-1663).
+"""Vision application of the drop-in API: the reference's Applications/Vision.py — data side (§3 Transform / get_transforms
+:399-517, §4 ImageDataset / ImageDataObj :642-875 for classification), models and losses (§5 ImageClassificationNet :1203-1373,
+§6 ObjectDetectionNet and the SSD loss :1376-1663) and ImageLearner.
 
-On the hot path and HIP-backed: every convolution (ops.conv2d, K1), the classifier head linears, and the
-detection loss — `SSD_loss.__call__` is ONE fused anchor-match + focal + smooth-L1 kernel per batch
-(ops.retina_loss, K6) with no host synchronisation, replacing the reference's per-image Python loop
-(Vision.py:1636), per-positive-anchor scalar indexing loop (:1593) and `.nonzero()` syncs (:1506-1507).
-Out of scope here (CPU image decode / augmentation / display / mAP evaluation): the
-cv2/skimage-based Transform / ImageDataset / ImageDataObj classes and ImageLearner's visualisation helpers.
+On the hot path and HIP-backed: every convolution (ops.conv2d, K1), the classifier head linears, the detection loss —
+`SSD_loss.__call__` is ONE fused anchor-match + focal + smooth-L1 kernel per batch (ops.retina_loss, K6) with no host
+synchronisation, replacing the reference's per-image Python loop (Vision.py:1636), per-positive-anchor scalar indexing loop (:1593)
+and `.nonzero()` syncs (:1506-1507) — and the classification transform chain: the dataset's decoded uint8 images live in HBM and
+`device_data.ImageBatches` cuts, crops, resizes, rotate-zooms, flips, lights and normalises each minibatch there (ops.image_aug,
+K9), replacing the per-image cv2 / numpy `Transform.__call__` (:449-507) in DataLoader workers.
+Out of scope here: file decode and the csv / folder / json constructors (the data classes take decoded H x W x 3 uint8 arrays),
+`pad` and `max_noise` (cv2.GaussianBlur), the detection data side (TransformBBox, AspectRatioSampler / AspectRatioCollater,
+'bbox' targets) and ImageLearner's display / TTA helpers.
 """
 import numpy as np
 import torch
@@ -50,6 +54,182 @@ def jaccard(Boxes1, Boxes2):
     ih = (torch.min(b1[:, :, 3], b2[:, :, 3]) - torch.max(b1[:, :, 1], b2[:, :, 1])).clamp(min=0)
     inter = iw * ih
     return inter / (a1.unsqueeze(1) + a2.unsqueeze(0) - inter)
+
+
+# ---- §3 image transforms, §4 datasets (classification) -----------------------------------------------------------
+
+_DEVICE_PATH = ('the transform chain runs on the GPU per minibatch: iterate device_data.ImageBatches (ImageDataObj.train_dl / '
+                'val_dl / test_dl), which feeds Transform.sample() draws to ops.image_aug')
+
+
+class Transform(object):
+    """Parameters of the classification transform chain (Vision.py:399-507): crop -> resize -> random rotate-zoom -> random
+    LR-flip ('SideOn') or dihedral ('TopDown') -> random lighting (balance + contrast) -> normalisation.  Same arguments and
+    attributes as the reference.  This class HOLDS the parameters and DRAWS them (`sample`, the reference's draw order); the
+    arithmetic is the HIP kernel behind ops.image_aug, run per minibatch by device_data.ImageBatches.
+    crop_type: 'center', 'random', a float crop point in [0, 1], or None (the whole image, resized without keeping aspect)."""
+
+    def __init__(self, tfm_type, crop_type, pad=None, sz=224, max_deg=10, max_zoom=1.05,
+                 bal_range=[-0.05, 0.05], cont_range=[0.95, 1.05], max_noise=None, stats=imagenet_stats):
+        if pad:
+            raise NotImplementedError('Transform(pad=...): border padding (cv2.copyMakeBorder) is not part of the device transform chain')
+        if max_noise:
+            raise NotImplementedError('Transform(max_noise=...): blurred noise (cv2.GaussianBlur) is not part of the device transform chain')
+        if sz is None:
+            raise NotImplementedError('Transform(sz=None): a minibatch tensor needs one output size; pass sz')
+        if tfm_type not in ('Basic', 'SideOn', 'TopDown'):
+            raise ValueError("tfm_type must be 'Basic', 'SideOn' or 'TopDown' (got %r)" % (tfm_type,))
+        if not (crop_type is None or crop_type in ('center', 'random') or type(crop_type) == float):
+            raise ValueError("crop_type must be 'center', 'random', a float or None (got %r)" % (crop_type,))
+        if max_deg and not max_zoom:
+            raise ValueError('max_deg needs max_zoom: the rotate-zoom step uses both (the reference hits a NameError here)')
+        if bal_range and not cont_range:
+            raise ValueError('bal_range needs cont_range: the lighting step uses both (the reference hits a NameError here)')
+        if type(sz) == int:
+            sz = (sz, sz)
+        sz = (int(sz[0]), int(sz[1]))
+        if tfm_type == 'TopDown' and sz[0] != sz[1]:
+            raise ValueError("tfm_type='TopDown' rotates by multiples of 90 degrees and needs a square sz (got %r)" % (sz,))
+        self.tfm_type, self.crop_type = tfm_type, crop_type
+        self.pad, self.sz, self.max_deg, self.max_zoom = pad, sz, max_deg, max_zoom
+        self.bal_range, self.cont_range = bal_range, cont_range
+        self.max_noise, self.stats = max_noise, stats
+
+    def __call__(self, img):
+        raise NotImplementedError('Transform.__call__ on a host array: ' + _DEVICE_PATH)
+
+    def sample(self, rng, H, W):
+        """One image's random parameters from `rng` (np.random.RandomState), drawn in exactly the order of Vision.py:452-481:
+        flip, rot, then deg, zoom, bal, cont (each only if its range is set), then the random-crop origin (only for
+        crop_type 'random' on a non-square image).  Returns a dict; what was not drawn is None.
+        (lo + (hi - lo) * random_sample() IS RandomState.uniform(lo, hi), same stream and same bits, at a sixth of the call cost.)"""
+        u = rng.random_sample
+        s = dict(flip=int(rng.randint(0, 2)), rot=int(rng.randint(0, 4)), deg=None, zoom=None, bal=None, cont=None, origin=None)
+        if self.max_deg: s['deg'] = -self.max_deg + (self.max_deg - -self.max_deg) * u()
+        if self.max_zoom: s['zoom'] = 1 + (self.max_zoom - 1) * u()
+        if self.bal_range: s['bal'] = self.bal_range[0] + (self.bal_range[1] - self.bal_range[0]) * u()
+        if self.cont_range: s['cont'] = self.cont_range[0] + (self.cont_range[1] - self.cont_range[0]) * u()
+        if self.crop_type == 'random' and H != W:
+            s['origin'] = int(rng.randint(0, abs(H - W) + 1))
+        return s
+
+    def crop_windows(self, H, W, origin=None):
+        """(y, x, h, w) arrays of the crops of images H x W (int arrays) (Vision.py:469-481); origin: the drawn offsets along the
+        longer side for crop_type 'random'"""
+        H, W = np.asarray(H, dtype=np.int64), np.asarray(W, dtype=np.int64)
+        zero = np.zeros_like(H)
+        if self.crop_type is None:
+            return zero, zero, H, W
+        L = np.minimum(H, W)
+        slack = np.maximum(H, W) - L
+        if self.crop_type == 'center': o = slack // 2
+        elif self.crop_type == 'random': o = np.where(slack > 0, np.asarray(origin, dtype=np.int64), 0)
+        else: o = (slack * self.crop_type).astype(np.int64)                      # int((rows - L) * crop_point)
+        return np.where(H > L, o, 0), np.where(H > L, 0, o), L, L
+
+    def inverse_maps(self, deg, zoom):
+        """[n, 6] coefficients that take a pixel of cv2.warpAffine's output back to its source coordinate: the inverses of
+        cv2.getRotationMatrix2D((sz_w // 2, sz_h // 2), deg, zoom) (Vision.py:488), computed in float64 and rounded to fp32."""
+        deg, zoom = np.asarray(deg, dtype=np.float64), np.asarray(zoom, dtype=np.float64)
+        a, b = zoom * np.cos(np.radians(deg)), zoom * np.sin(np.radians(deg))
+        cx, cy = self.sz[1] // 2, self.sz[0] // 2
+        M = np.zeros((len(deg), 3, 3), dtype=np.float64)
+        M[:, 0, 0], M[:, 0, 1], M[:, 0, 2] = a, b, (1 - a) * cx - b * cy
+        M[:, 1, 0], M[:, 1, 1], M[:, 1, 2] = -b, a, b * cx + (1 - a) * cy
+        M[:, 2, 2] = 1
+        return np.linalg.inv(M)[:, :2].reshape(-1, 6).astype(np.float32)
+
+    def param_table(self, images, shapes, draws):
+        """ops.IMAGE_AUG_PARAM rows for image numbers `images` of sizes `shapes` [(H, W)] from `draws` [sample() dicts, or chosen
+        values].  As in the reference, flip counts for 'SideOn' / 'TopDown' only and rot for 'TopDown' only (:492-493); the
+        rotate-zoom runs iff max_deg is set (:487) and the lighting iff bal_range is (:496)."""
+        n = len(images)
+        t = np.zeros(n, dtype=ops.IMAGE_AUG_PARAM)
+        col = lambda k, dtype: np.array([d[k] for d in draws], dtype=dtype)
+        hw = np.asarray(shapes, dtype=np.int64).reshape(n, 2)
+        t['image'] = images
+        t['crop_y'], t['crop_x'], t['crop_h'], t['crop_w'] = self.crop_windows(
+            hw[:, 0], hw[:, 1], [d.get('origin') or 0 for d in draws] if self.crop_type == 'random' else None)
+        flags = np.zeros(n, dtype=np.int32)
+        if self.max_deg: t['m'] = self.inverse_maps(col('deg', np.float64), col('zoom', np.float64))
+        else: flags |= ops.IMAGE_AUG_NO_WARP
+        if self.tfm_type in ('SideOn', 'TopDown'): flags |= np.where(col('flip', np.int32) == 1, ops.IMAGE_AUG_FLIP, 0).astype(np.int32)
+        if self.tfm_type == 'TopDown': t['rot'] = col('rot', np.int32)
+        if self.bal_range: t['bal'], t['cont'] = col('bal', np.float64), col('cont', np.float64)
+        else: flags |= ops.IMAGE_AUG_NO_LIGHTING
+        t['flags'] = flags
+        return t
+
+    def param_row(self, image, H, W, flip=0, rot=0, deg=None, zoom=None, bal=None, cont=None, origin=None):
+        "param_table for one image: a 0-d ops.IMAGE_AUG_PARAM record"
+        return self.param_table([image], [(H, W)], [dict(flip=flip, rot=rot, deg=deg, zoom=zoom, bal=bal, cont=cont, origin=origin)])[0]
+
+
+def get_transforms(tfm_type, sz=224, stats=imagenet_stats):
+    """[tfm_eval, tfm_aug] for single_label / multi_label classification (Vision.py:509-517): tfm_aug trains, tfm_eval serves
+    val and test."""
+    tfm_eval = Transform('Basic', 'center', None, sz, None, None, None, None, stats=stats)
+    tfm_aug = Transform(tfm_type, 'random', None, sz, stats=stats)
+    return [tfm_eval, tfm_aug]
+
+
+class ImageDataset(object):
+    """Image dataset for single_label or multi_label classification (Vision.py:642-698), 'train', 'val' or 'test'.
+    images: list of {'img': H x W x 3 uint8 array (decoded RGB), 'target': int label | 0-1 array | 0 for test}.  The reference
+    keeps file names under 'img' and decodes per item; decoding is left to the caller here, and a file name raises.
+    Attributes as the reference: IMG_PATH, images, transform, target_type, ds_type, y."""
+
+    def __init__(self, IMG_PATH, images, transform, target_type, ds_type):
+        if target_type == 'bbox':
+            raise NotImplementedError("target_type 'bbox': the detection data side (TransformBBox, AspectRatioSampler / AspectRatioCollater) is not built")
+        if target_type not in ('single_label', 'multi_label'):
+            raise ValueError("target_type must be 'single_label' or 'multi_label' (got %r)" % (target_type,))
+        for im in images:
+            a = im['img']
+            if isinstance(a, str):
+                raise NotImplementedError("images[i]['img'] is a file name: image decode is not built; pass the decoded H x W x 3 uint8 array")
+            if not (isinstance(a, np.ndarray) and a.dtype == np.uint8 and a.ndim == 3 and a.shape[2] == 3 and a.size > 0):
+                raise ValueError("images[i]['img'] must be a non-empty H x W x 3 uint8 array")
+        self.IMG_PATH = IMG_PATH
+        self.images = images
+        self.transform = transform
+        self.target_type = target_type
+        self.ds_type = ds_type
+        self.y = [images[i]['target'] for i in range(len(images))]
+
+    def __len__(self):
+        return len(self.images)
+
+    def __getitem__(self, idx):
+        raise NotImplementedError('ImageDataset[i] would transform one image on the host: ' + _DEVICE_PATH)
+
+
+class ImageDataObj(object):
+    """Datasets and loaders for train, validation and (optionally) test data (Vision.py:814-875), classification targets.
+    transforms = [tfm_eval, tfm_aug]: tfm_aug trains, tfm_eval serves val and test.  Attributes as the reference: categories,
+    target_type, bs, sz, train_ds / val_ds / test_ds, train_dl / val_dl / test_dl (test_* are None unless test_name is given).
+    The loaders are device_data.ImageBatches: the images are uploaded once and every minibatch is cut and transformed on the
+    GPU, so `num_workers` is accepted and ignored; `seed` seeds the epoch permutations and the transform draws.
+    The file-based constructors (from_csv, from_folders, from_json_bbox) need image decode and are not built."""
+
+    def __init__(self, PATH, target_type, categories, bs, transforms, train_images, val_images,
+                 test_images=None, train_name='train', val_name='val', test_name=None, num_workers=8, seed=0):
+        from ..device_data import ImageBatches
+        tfm_eval, tfm_aug = transforms[0], transforms[1]
+        self.target_type, self.categories, self.bs = target_type, categories, bs
+        self.sz = tfm_eval.sz
+
+        PATH = correct_foldername(PATH)
+        self.train_ds = ImageDataset(PATH + train_name + '/', train_images, tfm_aug, target_type, 'train')
+        self.val_ds = ImageDataset(PATH + val_name + '/', val_images, tfm_eval, target_type, 'val')
+        if test_name: self.test_ds = ImageDataset(PATH + test_name + '/', test_images, tfm_eval, target_type, 'test')
+        else: self.test_ds = None
+
+        from .. import dist as nnl_dist                    # under torch.distributed every rank takes its slice of each global minibatch
+        self.train_dl = ImageBatches(self.train_ds, bs, shuffle=True, seed=seed, rank=nnl_dist.rank(), world=nnl_dist.world_size())
+        self.val_dl = ImageBatches(self.val_ds, bs, shuffle=False, seed=seed)
+        if test_name: self.test_dl = ImageBatches(self.test_ds, bs, shuffle=False, seed=seed)
+        else: self.test_dl = None
 
 
 # ---- §5 image classification ---------------------------------------------------------------------------------

@@ -15,7 +15,7 @@ import torch
 from . import _lib
 from ._lib import check, lib, ptr, require_cuda, stream
 
-__all__ = ['mse_loss', 'scaled_sigmoid', 'embdotbias', 'index_error_flag', 'raise_if_index_error', 'conv2d', 'to_nhwc', 'from_nhwc', 'linear', 'bn_act', 'concat_pool2d', 'TabularPlan', 'tab_embed_concat', 'embedding_renorm_drop', 'retina_loss']
+__all__ = ['mse_loss', 'scaled_sigmoid', 'embdotbias', 'index_error_flag', 'raise_if_index_error', 'conv2d', 'to_nhwc', 'from_nhwc', 'linear', 'bn_act', 'concat_pool2d', 'TabularPlan', 'tab_embed_concat', 'embedding_renorm_drop', 'retina_loss', 'image_aug']
 
 _ERR_FLAGS = {}
 
@@ -1360,6 +1360,39 @@ class _RetinaLoss(torch.autograd.Function):
 def retina_loss(anchors, reg, clas, boxes, cats, beta=0.5, alpha=0.25, gamma=2.0):
     """[ (1-beta)*reg_loss + beta*clas_loss, reg_loss, clas_loss ] for a batch (see include/nnl.h, K6)."""
     return _RetinaLoss.apply(anchors, reg, clas, boxes, cats, beta, alpha, gamma)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# K9 image augmentation: the classification Transform on a device-resident uint8 dataset (include/nnl.h).
+# ---------------------------------------------------------------------------------------------------------
+# nnl_image_aug_param_t: one 64-byte row per sample of the minibatch
+IMAGE_AUG_PARAM = np.dtype([('image', '<i8'), ('crop_y', '<i4'), ('crop_x', '<i4'), ('crop_h', '<i4'), ('crop_w', '<i4'),
+                            ('m', '<f4', (6,)), ('flags', '<i4'), ('rot', '<i4'), ('bal', '<f4'), ('cont', '<f4')])
+IMAGE_AUG_NO_WARP, IMAGE_AUG_FLIP, IMAGE_AUG_NO_LIGHTING = 1, 2, 4
+
+
+def image_aug(arena, desc, params, sz, stats=None, lighting=False):
+    """Transform.__call__ (reference Applications/Vision.py:449-507) for one minibatch, everything after decode, in one launch
+    (eval) or two (lighting): arena uint8 [bytes] = every image of the dataset back to back (HWC, RGB); desc int64 [n_images, 3] =
+    (byte offset, H, W) per image; params uint8 [bs, 64] = IMAGE_AUG_PARAM rows; sz = (sz_h, sz_w); stats = [mean[3], std[3]] or
+    None.  Returns fp32 [bs, sz_h, sz_w, 3] (NHWC: `from_nhwc` gives the logical NCHW view).  Not differentiable: images are data."""
+    require_cuda(arena, desc, params)
+    if arena.dtype != torch.uint8 or desc.dtype != torch.int64 or params.dtype != torch.uint8:
+        raise TypeError('image_aug: arena and params must be uint8 and desc int64')
+    if not (arena.is_contiguous() and desc.is_contiguous() and params.is_contiguous()):
+        raise ValueError('image_aug: arena, desc and params must be contiguous')
+    if desc.dim() != 2 or desc.shape[1] != 3 or params.dim() != 2 or params.shape[1] != IMAGE_AUG_PARAM.itemsize:
+        raise ValueError('image_aug: desc must be [n_images, 3] and params [bs, %d]' % IMAGE_AUG_PARAM.itemsize)
+    bs, (sz_h, sz_w) = params.shape[0], sz
+    out = torch.empty(bs, sz_h, sz_w, 3, dtype=torch.float32, device=arena.device)
+    ms = None
+    if stats is not None:
+        ms = (ctypes.c_float * 6)(*[float(np.float32(v)) for v in list(stats[0]) + list(stats[1])])
+    wsb = int(lib.nnl_image_aug_workspace_bytes(bs, sz_h, sz_w)) if lighting else 0
+    ws = _workspace(wsb, arena.device)
+    check(lib.nnl_image_aug(ptr(arena), arena.numel(), ptr(desc), desc.shape[0], ptr(params), bs, sz_h, sz_w, ms, int(bool(lighting)),
+                            ptr(out), ptr(ws), wsb, stream()))
+    return out
 
 
 from .ops_text import (lstm_layer, embedding_rowmask, softmax_cross_entropy, cross_entropy_nd, seq_activation_reg)  # noqa: E402,F401
