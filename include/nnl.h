@@ -528,6 +528,39 @@ int nnl_image_aug(const uint8_t* arena, int64_t arena_bytes, const nnl_image_des
                   const nnl_image_aug_param_t* params, int64_t bs, int64_t sz_h, int64_t sz_w, const float* mean_std, int lighting,
                   float* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- K10: detection minibatch — TransformBBox.__call__ (Applications/Vision.py:559-603) and AspectRatioCollater (:758-812) -------
+ * One padded minibatch from the arena / descriptor table of K9, in ONE launch: out fp32 NHWC [bs, Hp, Wp, 3], boxes fp32 [bs, N, 4],
+ * cats int64 [bs, N].  image_mean[i] = the three channel means of image i as float(v) / 255 (np.mean(img, axis=(0, 1)), :576): they
+ * depend on the image alone, so the caller computes them once from exact integer sums and lighting needs no workspace and no second
+ * launch.  params[k] = what TransformBBox drew for sample k and what the collater derived from it; row_jit, col_jit and rand_scale are
+ * those of the first sample of the minibatch (:764-766).
+ * Image, per output pixel (oy, ox) of sample k, the chain run backwards: y = oy - row_jit, x = ox - col_jit; outside [0, rh) x [0, rw)
+ * the value is 0.0f, the zeros of the collater written after normalisation (:780-781, :793-796).  Inside: the taps of
+ * cv2.resize(img, (rw, rh), INTER_LINEAR) (:774) from the H x W source — source coordinate (o + 0.5) (L_src / r) - 0.5, two taps per axis
+ * clamped, no antialiasing; with NNL_IMAGE_AUG_FLIP source column c is W - 1 - c (np.fliplr before the resize, :583-584); each tap
+ * is u = float(v) / 255.0f (open_image, :54-61), lit unless NNL_IMAGE_AUG_NO_LIGHTING as clip((u - mu_c) cont + bal + mu_c, 0, 1)
+ * (:576-577), then (. - mean_c) / std_c (:580); the four taps are interpolated last.  Every source index is clamped into its image
+ * and into the arena: no table can make the kernel read outside [arena, arena + arena_bytes).
+ * Boxes, slot j of sample k: j < box_count: box box_first + j of the float64 arena [n_boxes, 4] (xmin, ymin, xmax, ymax), in FLOAT64
+ * and without fused multiply-adds, as numpy does it: flipped x (W - xmax, W - xmin) (:598-600), (b scale) rand_scale (:776), + col_jit
+ * on x and + row_jit on y (:782-784), then ONE rounding to fp32 (:805); its category from cat_arena.  Otherwise box and category are -1
+ * (:801-802, :808-809).  The box range is clamped into the arenas.  The box work rides in extra workgroups of the image launch.
+ * mean_std: HOST pointer to {mean[3], std[3]}, NULL = no normalisation.  bs in [1, 65535], Hp and Wp in [1, 16384], N in [1, 2^20],
+ * row_jit and col_jit >= 0. */
+typedef struct {
+  int64_t image;                 /* row of desc and of image_mean */
+  int64_t box_first;             /* first box of the image in box_arena / cat_arena */
+  int32_t box_count;
+  int32_t rh, rw;                /* resized size: int(H scale rand_scale), int(W scale rand_scale) */
+  int32_t flags;                 /* NNL_IMAGE_AUG_FLIP, NNL_IMAGE_AUG_NO_LIGHTING */
+  float bal, cont;
+  double scale;                  /* the image's own scale (get_AspectRatioScale) */
+} nnl_detect_aug_param_t;        /* 48 bytes */
+int nnl_detect_aug(const uint8_t* arena, int64_t arena_bytes, const nnl_image_desc_t* desc, int64_t n_images, const float* image_mean,
+                   const double* box_arena, const int64_t* cat_arena, int64_t n_boxes, const nnl_detect_aug_param_t* params,
+                   int64_t bs, int64_t Hp, int64_t Wp, int64_t N, int64_t row_jit, int64_t col_jit, double rand_scale,
+                   const float* mean_std, float* out, float* boxes, int64_t* cats, void* stream);
+
 /* ---- K8: fused multi-tensor Optimizer.step ------------------------------------------------------------------------
  * Replaces Optimizer.step (General/Optimizer.py:58-70): decoupled weight decay X *= 1 - wd_g*lr_g (:60-67), global-norm
  * clip (:54-56, torch.nn.utils.clip_grad_norm_) and the torch.optim SGD(momentum) / Adam update (General/Learner.py:17-19)

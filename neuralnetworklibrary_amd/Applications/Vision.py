@@ -7,10 +7,13 @@ On the hot path and HIP-backed: every convolution (ops.conv2d, K1), the classifi
 synchronisation, replacing the reference's per-image Python loop (Vision.py:1636), per-positive-anchor scalar indexing loop (:1593)
 and `.nonzero()` syncs (:1506-1507) — and the classification transform chain: the dataset's decoded uint8 images live in HBM and
 `device_data.ImageBatches` cuts, crops, resizes, rotate-zooms, flips, lights and normalises each minibatch there (ops.image_aug,
-K9), replacing the per-image cv2 / numpy `Transform.__call__` (:449-507) in DataLoader workers.
+K9), replacing the per-image cv2 / numpy `Transform.__call__` (:449-507) in DataLoader workers.  The detection data side
+(TransformBBox :519-612, AspectRatioSampler / AspectRatioCollater :700-812, 'bbox' datasets) works the same way:
+`device_data.DetectionBatches` groups the images by aspect ratio and one kernel per minibatch (ops.detect_aug, K10) lights,
+normalises, flips, resizes, jitters and pads the images and flips, scales and shifts their boxes in float64.
 Out of scope here: file decode and the csv / folder / json constructors (the data classes take decoded H x W x 3 uint8 arrays),
-`pad` and `max_noise` (cv2.GaussianBlur), the detection data side (TransformBBox, AspectRatioSampler / AspectRatioCollater,
-'bbox' targets) and ImageLearner's display / TTA helpers.
+`pad` and `max_noise` (cv2.GaussianBlur), TransformBBoxShowPreds, TTA_bbox and TransformBBox.get_values, and ImageLearner's
+display / TTA helpers.
 """
 import numpy as np
 import torch
@@ -54,6 +57,47 @@ def jaccard(Boxes1, Boxes2):
     ih = (torch.min(b1[:, :, 3], b2[:, :, 3]) - torch.max(b1[:, :, 1], b2[:, :, 1])).clamp(min=0)
     inter = iw * ih
     return inter / (a1.unsqueeze(1) + a2.unsqueeze(0) - inter)
+
+
+# ---- §1.2 bounding-box utilities (Vision.py:191-269) -------------------------------------------------------------
+
+def hw_to_mm(box):
+    "height-width box [xmin, ymin, width, height] -> min-max box [xmin, ymin, xmax, ymax], inclusive pixel ends (Vision.py:191-193)"
+    x, y, w, h = box[0], box[1], box[2], box[3]
+    return np.array([x, y, x + w - 1, y + h - 1])
+
+
+def mm_to_hw(box):
+    "min-max box [xmin, ymin, xmax, ymax] -> height-width box [xmin, ymin, width, height] (Vision.py:195-197)"
+    x0, y0, x1, y1 = box[0], box[1], box[2], box[3]
+    return np.array([x0, y0, x1 - x0 + 1, y1 - y0 + 1])
+
+
+def convert_bbox_list(bbox_list):
+    "standard bbox list [(b_1, c_1), ..., (b_n, c_n)] -> (boxes [n, 4], cats [n]) arrays (Vision.py:199-210)"
+    return np.array([b for b, _ in bbox_list]), np.array([c for _, c in bbox_list])
+
+
+def rev_bbox_list(bbox_list):
+    """loader form [boxes [N, 4], cats [N]] (tensors or arrays, padded with -1) -> standard bbox list [(b_1, c_1), ..., (b_n, c_n)]:
+    everything from the first category -1 on is padding (Vision.py:212-232)"""
+    boxes, cats = [ARR(t) if torch.is_tensor(t) else np.asarray(t) for t in bbox_list[:2]]
+    out = []
+    for b, c in zip(boxes, cats):
+        if c == -1:
+            break
+        out.append((b, c))
+    return out
+
+
+def get_AspectRatioScale(img, min_side, max_side):
+    """(aspect_ratio, scale) of an H x W x C image for a 'bbox' dataset (Vision.py:258-269): aspect_ratio = W / H; scale takes the
+    shorter side to min_side unless that takes the longer side beyond max_side, then it takes the longer side to max_side."""
+    rows, cols = img.shape[0], img.shape[1]
+    scale = min_side / min(rows, cols)
+    if max(rows, cols) * scale > max_side:
+        scale = max_side / max(rows, cols)
+    return cols / rows, scale
 
 
 # ---- §3 image transforms, §4 datasets (classification) -----------------------------------------------------------
@@ -173,17 +217,101 @@ def get_transforms(tfm_type, sz=224, stats=imagenet_stats):
     return [tfm_eval, tfm_aug]
 
 
+_DEVICE_PATH_BBOX = ('the detection transform and collater run on the GPU per minibatch: iterate device_data.DetectionBatches '
+                     "(ImageDataObj(..., 'bbox', ...).train_dl / val_dl / test_dl), which feeds TransformBBox.sample() draws to ops.detect_aug")
+
+
+class TransformBBox(object):
+    """Parameters of the detection transform (Vision.py:519-603): random lighting (balance + contrast about the image's channel
+    means) -> normalisation -> random LR-flip ('SideOn') of image and boxes; rand_scale and the jitter are drawn per image and
+    applied per minibatch by the collater (:758-812), which resizes every image by scale * rand_scale, pads it on the top and left
+    by the jitter and pads the minibatch to a multiple of 32.  Same arguments and attributes as the reference.  This class HOLDS
+    the parameters and DRAWS them (`sample`, the reference's draw order); the arithmetic is the HIP kernel behind ops.detect_aug,
+    run per minibatch by device_data.DetectionBatches.  L (the length of the reference's pre-drawn value lists) is kept and unused."""
+
+    def __init__(self, tfm_type, bal_range=[-0.05, 0.05], cont_range=[0.95, 1.05], stats=imagenet_stats, scale_range=[0.8, 1.2],
+                 jitter=20, L=100000):
+        if tfm_type not in ('Basic', 'SideOn'):
+            raise ValueError("tfm_type must be 'Basic' or 'SideOn' (got %r)" % (tfm_type,))
+        if bal_range and not cont_range:
+            raise ValueError('bal_range needs cont_range: the lighting step uses both (the reference hits a TypeError here)')
+        if int(jitter) < 0:
+            raise ValueError('jitter must be >= 0 (got %r)' % (jitter,))
+        self.tfm_type, self.stats, self.jitter, self.L = tfm_type, stats, jitter, L
+        self.scale_range, self.bal_range, self.cont_range = scale_range, bal_range, cont_range
+        self.iter = None
+
+    def get_values(self):
+        raise NotImplementedError('TransformBBox.get_values (pre-drawn values for TTA_bbox) is not built: ' + _DEVICE_PATH_BBOX)
+
+    def __call__(self, img, target):
+        raise NotImplementedError('TransformBBox.__call__ on a host array: ' + _DEVICE_PATH_BBOX)
+
+    def sample(self, rng):
+        """One image's random parameters from `rng` (np.random.RandomState), drawn in exactly the order of Vision.py:565-575:
+        row_jit, col_jit, flip (drawn for 'Basic' too), rand_scale, then bal and cont (only if bal_range is set; else None)."""
+        s = dict(row_jit=int(rng.randint(0, self.jitter + 1)), col_jit=int(rng.randint(0, self.jitter + 1)),
+                 flip=int(rng.randint(0, 2)), rand_scale=float(rng.uniform(self.scale_range[0], self.scale_range[1])),
+                 bal=None, cont=None)
+        if self.bal_range:
+            s['bal'] = float(rng.uniform(self.bal_range[0], self.bal_range[1]))
+            s['cont'] = float(rng.uniform(self.cont_range[0], self.cont_range[1]))
+        return s
+
+    def batch_table(self, images, shapes, scales, box_ranges, draws):
+        """What the collater makes of one minibatch (Vision.py:764-766, 774, 790-792, 799): image numbers `images` of sizes `shapes`
+        [(H, W)], intrinsic `scales`, `box_ranges` [(first, count)] in the box arena and `draws` [sample() dicts, or chosen values]
+        -> (ops.DETECT_AUG_PARAM rows, dict(rand_scale, row_jit, col_jit, Hp, Wp, N)).  rand_scale and the jitter are those of the
+        FIRST sample; flip counts for 'SideOn' only (:583, :598) and the lighting runs iff bal_range is set (:573)."""
+        n = len(images)
+        rand_scale, row_jit, col_jit = float(draws[0]['rand_scale']), int(draws[0]['row_jit']), int(draws[0]['col_jit'])
+        t = np.zeros(n, dtype=ops.DETECT_AUG_PARAM)
+        for k in range(n):
+            (H, W), scale = shapes[k], float(scales[k])
+            rw, rh = int(W * scale * rand_scale), int(H * scale * rand_scale)                   # cv2.resize(img, (rw, rh)), :774
+            if rw < 1 or rh < 1:
+                raise ValueError('image %d (%d x %d) resized by scale %r * rand_scale %r has an empty side (%d x %d)'
+                                 % (images[k], H, W, scale, rand_scale, rh, rw))
+            flags = 0
+            if self.tfm_type == 'SideOn' and draws[k]['flip'] == 1: flags |= ops.IMAGE_AUG_FLIP
+            if self.bal_range: t[k]['bal'], t[k]['cont'] = draws[k]['bal'], draws[k]['cont']
+            else: flags |= ops.IMAGE_AUG_NO_LIGHTING
+            t[k]['image'], t[k]['rh'], t[k]['rw'], t[k]['flags'], t[k]['scale'] = images[k], rh, rw, flags, scale
+            t[k]['box_first'], t[k]['box_count'] = box_ranges[k]
+        Hp = 32 * -(-int(t['rh'].max() + row_jit) // 32)
+        Wp = 32 * -(-int(t['rw'].max() + col_jit) // 32)
+        return t, dict(rand_scale=rand_scale, row_jit=row_jit, col_jit=col_jit, Hp=Hp, Wp=Wp, N=max(1, int(t['box_count'].max())))
+
+
+def get_transforms_bbox(tfm_type, jitter=20, scale_range=[0.8, 1.2]):
+    """[tfm_eval, tfm_aug] for bounding-box object detection (Vision.py:605-612): tfm_aug trains, tfm_eval (no lighting, no flip, no
+    jitter, rand_scale 1) serves val and test."""
+    tfm_eval = TransformBBox('Basic', None, None, jitter=0, scale_range=[1, 1])
+    tfm_aug = TransformBBox(tfm_type, jitter=jitter, scale_range=scale_range)
+    return [tfm_eval, tfm_aug]
+
+
 class ImageDataset(object):
-    """Image dataset for single_label or multi_label classification (Vision.py:642-698), 'train', 'val' or 'test'.
-    images: list of {'img': H x W x 3 uint8 array (decoded RGB), 'target': int label | 0-1 array | 0 for test}.  The reference
-    keeps file names under 'img' and decodes per item; decoding is left to the caller here, and a file name raises.
+    """Image dataset for single_label / multi_label classification or bbox object detection (Vision.py:642-698), 'train', 'val' or
+    'test'.  images: list of {'img': H x W x 3 uint8 array (decoded RGB), 'target': int label | 0-1 array | 0 for test}; for 'bbox'
+    'target' is a standard bbox list [(box [xmin, ymin, xmax, ymax], category), ...] (or [] or 0) and every image also carries
+    'scale' and 'aspect_ratio' (get_AspectRatioScale), as the reference's from_json_bbox stores them.  The reference keeps file
+    names under 'img' and decodes per item; decoding is left to the caller here, and a file name raises.
     Attributes as the reference: IMG_PATH, images, transform, target_type, ds_type, y."""
 
     def __init__(self, IMG_PATH, images, transform, target_type, ds_type):
+        if target_type == 'bbox' and not isinstance(transform, TransformBBox):
+            raise NotImplementedError("target_type 'bbox' needs a TransformBBox (get_transforms_bbox): the classification Transform crops "
+                                      "and resizes to one size and does not move bbox targets")
+        if target_type != 'bbox' and isinstance(transform, TransformBBox):
+            raise ValueError("a TransformBBox goes with target_type 'bbox' (got %r): classification datasets take a Transform (get_transforms)" % (target_type,))
+        if target_type not in ('single_label', 'multi_label', 'bbox'):
+            raise ValueError("target_type must be 'single_label', 'multi_label' or 'bbox' (got %r)" % (target_type,))
         if target_type == 'bbox':
-            raise NotImplementedError("target_type 'bbox': the detection data side (TransformBBox, AspectRatioSampler / AspectRatioCollater) is not built")
-        if target_type not in ('single_label', 'multi_label'):
-            raise ValueError("target_type must be 'single_label' or 'multi_label' (got %r)" % (target_type,))
+            for im in images:
+                if 'scale' not in im or 'aspect_ratio' not in im:
+                    raise ValueError("a 'bbox' dataset needs images[i]['scale'] and images[i]['aspect_ratio']: "
+                                     "aspect_ratio, scale = get_AspectRatioScale(img, min_side, max_side)")
         for im in images:
             a = im['img']
             if isinstance(a, str):
@@ -210,14 +338,17 @@ class ImageDataObj(object):
     target_type, bs, sz, train_ds / val_ds / test_ds, train_dl / val_dl / test_dl (test_* are None unless test_name is given).
     The loaders are device_data.ImageBatches: the images are uploaded once and every minibatch is cut and transformed on the
     GPU, so `num_workers` is accepted and ignored; `seed` seeds the epoch permutations and the transform draws.
+    target_type 'bbox' (transforms = get_transforms_bbox(...)): the loaders are device_data.DetectionBatches; train_dl groups the
+    images by aspect ratio into minibatches of bs (AspectRatioSampler, :700-728), val_dl and test_dl have batch size 1 in dataset
+    order (:865-870; Learner.predict relies on it), and sz is None: every minibatch has its own padded size.
     The file-based constructors (from_csv, from_folders, from_json_bbox) need image decode and are not built."""
 
     def __init__(self, PATH, target_type, categories, bs, transforms, train_images, val_images,
                  test_images=None, train_name='train', val_name='val', test_name=None, num_workers=8, seed=0):
-        from ..device_data import ImageBatches
+        from ..device_data import DetectionBatches, ImageBatches
         tfm_eval, tfm_aug = transforms[0], transforms[1]
         self.target_type, self.categories, self.bs = target_type, categories, bs
-        self.sz = tfm_eval.sz
+        self.sz = tfm_eval.sz if target_type != 'bbox' else None
 
         PATH = correct_foldername(PATH)
         self.train_ds = ImageDataset(PATH + train_name + '/', train_images, tfm_aug, target_type, 'train')
@@ -226,6 +357,11 @@ class ImageDataObj(object):
         else: self.test_ds = None
 
         from .. import dist as nnl_dist                    # under torch.distributed every rank takes its slice of each global minibatch
+        if target_type == 'bbox':
+            self.train_dl = DetectionBatches(self.train_ds, bs, grouped=True, seed=seed, rank=nnl_dist.rank(), world=nnl_dist.world_size())
+            self.val_dl = DetectionBatches(self.val_ds, 1, grouped=False, seed=seed)
+            self.test_dl = DetectionBatches(self.test_ds, 1, grouped=False, seed=seed) if test_name else None
+            return
         self.train_dl = ImageBatches(self.train_ds, bs, shuffle=True, seed=seed, rank=nnl_dist.rank(), world=nnl_dist.world_size())
         self.val_dl = ImageBatches(self.val_ds, bs, shuffle=False, seed=seed)
         if test_name: self.test_dl = ImageBatches(self.test_ds, bs, shuffle=False, seed=seed)
@@ -545,7 +681,9 @@ def mAP(predictions, targets, categories, thresholds=COCO_thresholds, verbose=Tr
 
 class ImageLearner(Learner):
     """Learner for image data (Vision.py:1803-1812): inherits fit / evaluate / predict unchanged, plus compute_mAP for
-    object detection.  The visualisation, TTA and pycocotools conveniences of the reference's ImageLearner are UI / external
+    object detection.  With data = ImageDataObj(..., 'bbox', ..., get_transforms_bbox(...), ...) the whole detection workflow runs
+    from the public API: fit trains from device_data.DetectionBatches minibatches (a new padded size runs the step eagerly),
+    predict('val') divides each image's boxes by its 'scale', compute_mAP scores them.  The visualisation, TTA and pycocotools conveniences of the reference's ImageLearner are UI / external
     tooling (out of scope)."""
 
     def compute_mAP(self, predictions=None, thresh=0.05, max_overlap=0.5, rel_thresh=None, top_k=1000, max_boxes=20,

@@ -15,6 +15,11 @@ schedules agree on every rank and the union of the ranks' minibatches is exactly
 uint8 images live in HBM back to back and each minibatch is cropped, resized, rotate-zoomed, flipped, lit and normalised there
 by the HIP augmenter (ops.image_aug) — at 5 520 img/s per GPU the reference's per-image cv2 / numpy Transform.__call__
 (Vision.py:449-507) in DataLoader workers, not the training step, would set the epoch time.
+
+`DetectionBatches` is the detection loader (ImageDataset with 'bbox' targets): the same arena, plus every image's boxes and
+categories, in HBM; minibatches grouped by aspect ratio (AspectRatioSampler, Vision.py:700-728); one kernel per minibatch
+(ops.detect_aug) does TransformBBox.__call__ (:559-603) and AspectRatioCollater (:758-812), whose cv2.resize per image in ONE
+DataLoader worker would otherwise set the epoch time of the RetinaNet step.
 """
 import numpy as np
 import torch
@@ -23,7 +28,7 @@ from . import ops
 
 from .dist import shard_bounds
 
-__all__ = ['DeviceBatches', 'ImageBatches']
+__all__ = ['DeviceBatches', 'ImageBatches', 'DetectionBatches']
 
 
 def _map(f, x):
@@ -79,6 +84,18 @@ class DeviceBatches:
             yield _map(take, self.x), take(self.y)
 
 
+def _upload_images(images, device):
+    """The decoded uint8 H x W x 3 arrays of a dataset back to back in one device arena: (host arrays, [(H, W)], arena uint8 [bytes],
+    desc int64 [n, 3] = byte offset, H, W per image)"""
+    imgs = [np.ascontiguousarray(im['img']) for im in images]
+    shapes = [(a.shape[0], a.shape[1]) for a in imgs]
+    desc = np.zeros((len(imgs), 3), dtype=np.int64)
+    desc[:, 1:] = shapes
+    desc[1:, 0] = np.cumsum([a.size for a in imgs], dtype=np.int64)[:-1]
+    arena = torch.from_numpy(np.concatenate([a.reshape(-1) for a in imgs])).to(device)
+    return imgs, shapes, arena, torch.from_numpy(desc).to(device)
+
+
 class ImageBatches:
     """Iterable of (x, y) minibatches of an Applications.Vision.ImageDataset, transformed on `device` by ops.image_aug.
 
@@ -100,13 +117,7 @@ class ImageBatches:
         self.explicit_params = explicit_params
         self.epoch = 0
         self.dp_info = None          # (rows of the last yielded shard that count, rows of its GLOBAL minibatch): Learner reads it
-        imgs = [np.ascontiguousarray(im['img']) for im in ds.images]
-        self.shapes = [(a.shape[0], a.shape[1]) for a in imgs]
-        desc = np.zeros((self.n, 3), dtype=np.int64)
-        desc[:, 1:] = self.shapes
-        desc[1:, 0] = np.cumsum([a.size for a in imgs], dtype=np.int64)[:-1]
-        self.arena = torch.from_numpy(np.concatenate([a.reshape(-1) for a in imgs])).to(self.device)
-        self.desc = torch.from_numpy(desc).to(self.device)
+        _, self.shapes, self.arena, self.desc = _upload_images(ds.images, self.device)
         if ds.ds_type == 'test':
             y = torch.zeros(self.n, dtype=torch.int64)
         elif ds.target_type == 'single_label':
@@ -144,3 +155,84 @@ class ImageBatches:
             out = ops.image_aug(self.arena, self.desc, params, tfm.sz, tfm.stats, lighting=bool(tfm.bal_range))
             idx = params.view(torch.int64)[:, 0]                          # the table's image numbers, already on the device
             yield ops.from_nhwc(out), self.y.index_select(0, idx)
+
+
+class DetectionBatches:
+    """Iterable of (x, [boxes, cats]) minibatches of an Applications.Vision.ImageDataset with 'bbox' targets, built on `device` by
+    ops.detect_aug.
+
+    Uploaded once: the image arena and descriptor table (as ImageBatches), every image's channel means of float(v) / 255 (exact
+    int64 channel sums taken on the host, divided by 255 H W in float64, rounded to fp32: the mu of the lighting step, Vision.py:576),
+    the float64 box arena [total, 4] and the int64 category arena [total]; `box_range` [n, 2] = (first, count) per image.
+    grouped=True (train; AspectRatioSampler, :711-728): the image numbers are stably sorted by 'aspect_ratio' and cut into
+    consecutive groups of bs * world; every epoch takes the groups in a new order from np.random.RandomState(seed + epoch).
+    grouped=False (val, test): groups of bs * world in dataset order.  From the same per-epoch stream, after the group permutation,
+    per GLOBAL minibatch and in batch order, one `TransformBBox.sample` per sample — identical on every rank.  rand_scale and the
+    jitter of the minibatch are its FIRST sample's (:764-766); resized sizes, Hp, Wp (multiples of 32) and N = max(1, most boxes
+    of one image) are those of the global minibatch (TransformBBox.batch_table), so a rank's `shard_bounds` slice of the rows gives
+    exactly its rows of the single-process minibatch.  One small H2D per minibatch (the parameter rows), one launch.
+    Yields x: the logical [n, 3, Hp, Wp] view of the kernel's NHWC output (ops.to_nhwc is free), [boxes fp32 [n, N, 4], cats int64
+    [n, N]] padded with -1 — what SSD_loss and ComputeMaxOverlaps take.  The last group may be ragged.
+    explicit_params(b, image_indices) -> [TransformBBox.sample()-style dicts], one per sample: replaces the draws for global
+    minibatch b (tests inject draws through it)."""
+
+    def __init__(self, ds, bs, grouped, seed=0, rank=0, world=1, device=None, explicit_params=None):
+        from .General.Core import default_device
+        self.device = torch.device(device if device is not None else default_device())
+        self.ds, self.transform, self.n = ds, ds.transform, len(ds)
+        self.bs, self.grouped, self.seed, self.rank, self.world = int(bs), grouped, int(seed), int(rank), int(world)
+        self.explicit_params = explicit_params
+        self.epoch = 0
+        self.dp_info = None          # (rows of the last yielded shard that count, rows of its GLOBAL minibatch): Learner reads it
+        imgs, self.shapes, self.arena, self.desc = _upload_images(ds.images, self.device)
+        sums = np.stack([a.reshape(-1, 3).sum(axis=0, dtype=np.int64) for a in imgs])
+        pixels = np.array([255.0 * H * W for H, W in self.shapes], dtype=np.float64)
+        self.image_mean = torch.from_numpy((sums.astype(np.float64) / pixels[:, None]).astype(np.float32)).to(self.device)
+        self.scales = [float(im['scale']) for im in ds.images]
+        boxes, cats, self.box_range = [], [], np.zeros((self.n, 2), dtype=np.int64)
+        for i, im in enumerate(ds.images):
+            target = 0 if ds.ds_type == 'test' else im['target']                       # ImageDataset.__getitem__, Vision.py:683-686
+            if isinstance(target, (int, np.integer)) or len(target) == 0:             # TransformBBox.__call__, :594
+                target = []
+            self.box_range[i] = (len(boxes), len(target))
+            boxes += [np.asarray(b, dtype=np.float64).reshape(4) for b, _ in target]
+            cats += [int(c) for _, c in target]
+        if not boxes:                                                                  # the arenas are never empty: one unused row
+            boxes, cats = [np.zeros(4)], [-1]
+        self.box_arena = torch.from_numpy(np.stack(boxes).astype(np.float64)).to(self.device)
+        self.cat_arena = torch.from_numpy(np.asarray(cats, dtype=np.int64)).to(self.device)
+        g = self.bs * self.world
+        if grouped:
+            ratios = [im['aspect_ratio'] for im in ds.images]
+            order = sorted(range(self.n), key=lambda i: ratios[i])                      # stable, as list.sort (:716)
+        else:
+            order = list(range(self.n))
+        self.groups = [np.array(order[i:i + g], dtype=np.int64) for i in range(0, self.n, g)]
+
+    def __len__(self):
+        return len(self.groups)
+
+    def _table(self, rng, b, idx):
+        "the parameter rows and the batch values of GLOBAL minibatch b (image numbers idx): the same on every rank"
+        if self.explicit_params is not None:
+            draws = list(self.explicit_params(b, idx))
+            assert len(draws) == len(idx), 'explicit_params must return one draw per sample'
+        else:
+            draws = [self.transform.sample(rng) for _ in idx]
+        return self.transform.batch_table([int(i) for i in idx], [self.shapes[i] for i in idx], [self.scales[i] for i in idx],
+                                          [tuple(self.box_range[i]) for i in idx], draws)
+
+    def __iter__(self):
+        rng = np.random.RandomState(self.seed + self.epoch)       # identical on every rank
+        order = rng.permutation(len(self.groups)) if self.grouped else np.arange(len(self.groups))
+        self.epoch += 1
+        tfm = self.transform
+        for b, gi in enumerate(order):
+            idx = self.groups[gi]
+            table, v = self._table(rng, b, idx)
+            a, z, ghost = shard_bounds(len(idx), self.rank, self.world)   # balanced contiguous cut, as dist.ShardedBatches
+            self.dp_info = (0 if ghost else z - a, len(idx))
+            params = torch.from_numpy(table[a:z].view(np.uint8).reshape(z - a, ops.DETECT_AUG_PARAM.itemsize)).to(self.device)
+            out, boxes, cats = ops.detect_aug(self.arena, self.desc, self.image_mean, self.box_arena, self.cat_arena, params, v['Hp'],
+                                              v['Wp'], v['N'], v['row_jit'], v['col_jit'], v['rand_scale'], tfm.stats)
+            yield ops.from_nhwc(out), [boxes, cats]

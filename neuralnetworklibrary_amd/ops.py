@@ -1395,5 +1395,48 @@ def image_aug(arena, desc, params, sz, stats=None, lighting=False):
     return out
 
 
+# ---------------------------------------------------------------------------------------------------------
+# K10 detection minibatch: TransformBBox + AspectRatioCollater on the device-resident dataset (include/nnl.h).
+# ---------------------------------------------------------------------------------------------------------
+# nnl_detect_aug_param_t: one 48-byte row per sample of the minibatch
+DETECT_AUG_PARAM = np.dtype([('image', '<i8'), ('box_first', '<i8'), ('box_count', '<i4'), ('rh', '<i4'), ('rw', '<i4'),
+                             ('flags', '<i4'), ('bal', '<f4'), ('cont', '<f4'), ('scale', '<f8')])
+
+
+def detect_aug(arena, desc, image_mean, box_arena, cat_arena, params, Hp, Wp, N, row_jit, col_jit, rand_scale, stats=None):
+    """TransformBBox.__call__ and AspectRatioCollater (reference Applications/Vision.py:559-603, 758-812) for one minibatch, everything
+    after decode, in one launch: arena uint8 [bytes] and desc int64 [n_images, 3] as for `image_aug`; image_mean fp32 [n_images, 3] =
+    channel means of float(v) / 255 per image; box_arena float64 [n_boxes, 4] (xmin, ymin, xmax, ymax) and cat_arena int64 [n_boxes] =
+    every image's boxes back to back (n_boxes >= 1); params uint8 [bs, 48] = DETECT_AUG_PARAM rows; row_jit, col_jit, rand_scale: the
+    minibatch's values; stats = [mean[3], std[3]] or None.  Returns (fp32 [bs, Hp, Wp, 3] NHWC, fp32 [bs, N, 4], int64 [bs, N]).
+    Not differentiable: images and boxes are data."""
+    require_cuda(arena, desc, image_mean, box_arena, cat_arena, params)
+    if arena.dtype != torch.uint8 or desc.dtype != torch.int64 or params.dtype != torch.uint8:
+        raise TypeError('detect_aug: arena and params must be uint8 and desc int64')
+    if image_mean.dtype != torch.float32 or box_arena.dtype != torch.float64 or cat_arena.dtype != torch.int64:
+        raise TypeError('detect_aug: image_mean must be float32, box_arena float64 and cat_arena int64')
+    if not all(t.is_contiguous() for t in (arena, desc, image_mean, box_arena, cat_arena, params)):
+        raise ValueError('detect_aug: every input must be contiguous')
+    if desc.dim() != 2 or desc.shape[1] != 3 or tuple(image_mean.shape) != (desc.shape[0], 3):
+        raise ValueError('detect_aug: desc must be [n_images, 3] and image_mean [n_images, 3]')
+    if box_arena.dim() != 2 or box_arena.shape[1] != 4 or box_arena.shape[0] < 1 or tuple(cat_arena.shape) != (box_arena.shape[0],):
+        raise ValueError('detect_aug: box_arena must be [n_boxes, 4] with n_boxes >= 1 and cat_arena [n_boxes]')
+    if params.dim() != 2 or params.shape[1] != DETECT_AUG_PARAM.itemsize:
+        raise ValueError('detect_aug: params must be [bs, %d]' % DETECT_AUG_PARAM.itemsize)
+    bs, Hp, Wp, N = params.shape[0], int(Hp), int(Wp), int(N)
+    out = torch.empty(bs, Hp, Wp, 3, dtype=torch.float32, device=arena.device)
+    boxes = torch.empty(bs, N, 4, dtype=torch.float32, device=arena.device)
+    cats = torch.empty(bs, N, dtype=torch.int64, device=arena.device)
+    ms = None
+    if stats is not None:
+        ms = (ctypes.c_float * 6)(*[float(np.float32(v)) for v in list(stats[0]) + list(stats[1])])
+    check(lib.nnl_detect_aug(ptr(arena), arena.numel(), ptr(desc), desc.shape[0], ptr(image_mean), ptr(box_arena), ptr(cat_arena),
+                             box_arena.shape[0], ptr(params), bs, Hp, Wp, N, int(row_jit), int(col_jit), float(rand_scale), ms,
+                             ptr(out), ptr(boxes), ptr(cats), stream()))
+    return out, boxes, cats
+
+
+__all__ += ['detect_aug']
+
 from .ops_text import (lstm_layer, embedding_rowmask, softmax_cross_entropy, cross_entropy_nd, seq_activation_reg)  # noqa: E402,F401
 __all__ += ['lstm_layer', 'embedding_rowmask', 'softmax_cross_entropy', 'cross_entropy_nd', 'seq_activation_reg', 'conv_add_upsampled']
