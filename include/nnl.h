@@ -439,6 +439,20 @@ int nnl_debug_lstm_bptt2_plan(int64_t B, int64_t H, int32_t* out5);
 size_t nnl_mse_workspace_bytes(int64_t n);
 int nnl_mse_fwd(const float* pred, const float* target, float* loss, int64_t n, void* workspace, size_t workspace_bytes, void* stream);
 int nnl_mse_bwd(const float* pred, const float* target, const float* grad_out, float* dpred, int64_t n, void* stream);
+/* nn.BCEWithLogitsLoss() — `loss_func_dict['multi_label']` (General/Learner.py:20), the loss of the multi-label image classifier
+ * (Planet notebook): *loss = mean(max(x, 0) - x t + log1p(exp(-|x|))) over n fp32 elements, targets anywhere in [0, 1] (one launch up
+ * to 65 536 elements, fixed-order sum: bitwise reproducible); backward: dlogits = *grad_out (device scalar, NULL = 1) *
+ * (sigmoid(x) - t) / n, 16-byte accesses when the three pointers are 16-byte aligned.  Workspace only above 65 536 elements. */
+size_t nnl_bce_logits_workspace_bytes(int64_t n);
+int nnl_bce_logits_fwd(const float* logits, const float* target, float* loss, int64_t n, void* workspace, size_t workspace_bytes, void* stream);
+int nnl_bce_logits_bwd(const float* logits, const float* target, const float* grad_out, float* dlogits, int64_t n, void* stream);
+/* fbeta_loss.__call__ (General/LossesMetrics.py:70-78), the multi-label F-beta metric, on pred / target fp32 [N, C]: per row
+ * p_c = use_thresh ? (sigmoid(pred_c) >= threshold) : pred_c, tp = sum p t, prec = tp / (sum p + eps), rec = tp / (sum t + eps),
+ * f = (1 + beta2) prec rec / (beta2 prec + rec + eps), all in fp32 in that order; *out = mean over the rows, summed in a fixed
+ * order.  One launch up to 4 096 rows, two (and a workspace) above. */
+size_t nnl_fbeta_workspace_bytes(int64_t N, int64_t C);
+int nnl_fbeta(const float* pred, const float* target, float* out, int64_t N, int64_t C, float beta2, float threshold, int use_thresh, float eps,
+              void* workspace, size_t workspace_bytes, void* stream);
 /* FullyConnectedNet's 'sigmoidal' output activation (General/Layers.py:150-152): y = lo + (hi - lo) * sig, sig = sigmoid(x) (both
  * written); backward: dx = dy * (hi - lo) * sig * (1 - sig). */
 int nnl_scaled_sigmoid_fwd(const float* x, float* y, float* sig, int64_t n, float lo, float hi, void* stream);

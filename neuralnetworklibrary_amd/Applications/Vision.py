@@ -13,7 +13,7 @@ K9), replacing the per-image cv2 / numpy `Transform.__call__` (:449-507) in Data
 normalises, flips, resizes, jitters and pads the images and flips, scales and shifts their boxes in float64.
 Out of scope here: file decode and the csv / folder / json constructors (the data classes take decoded H x W x 3 uint8 arrays),
 `pad` and `max_noise` (cv2.GaussianBlur), TransformBBoxShowPreds, TTA_bbox and TransformBBox.get_values, and ImageLearner's
-display / TTA helpers.
+display helpers (show_images, show_bbox_preds) and coco_pascal_eval.
 """
 import numpy as np
 import torch
@@ -680,11 +680,90 @@ def mAP(predictions, targets, categories, thresholds=COCO_thresholds, verbose=Tr
 
 
 class ImageLearner(Learner):
-    """Learner for image data (Vision.py:1803-1812): inherits fit / evaluate / predict unchanged, plus compute_mAP for
-    object detection.  With data = ImageDataObj(..., 'bbox', ..., get_transforms_bbox(...), ...) the whole detection workflow runs
+    """Learner for image data (Vision.py:1803-1812): inherits fit / evaluate / predict unchanged, plus data_resize,
+    switch_transform_stats, confusion_matrix and TTA for classification and compute_mAP for object detection.
+    Classification (data = ImageDataObj(..., 'single_label' | 'multi_label', ..., get_transforms(...), ...)): the progressive-resizing
+    workflow of the Planet notebook — fit at one size, data_resize(sz, bs), fit again, TTA('val') — runs on the device-resident
+    images; a resize changes the Transform objects the loaders share with the datasets and uploads nothing.
+    With data = ImageDataObj(..., 'bbox', ..., get_transforms_bbox(...), ...) the whole detection workflow runs
     from the public API: fit trains from device_data.DetectionBatches minibatches (a new padded size runs the step eagerly),
-    predict('val') divides each image's boxes by its 'scale', compute_mAP scores them.  The visualisation, TTA and pycocotools conveniences of the reference's ImageLearner are UI / external
-    tooling (out of scope)."""
+    predict('val') divides each image's boxes by its 'scale', compute_mAP scores them.  The visualisation helpers (show_images,
+    show_bbox_preds), TTA_bbox and the pycocotools convenience of the reference's ImageLearner are UI / external tooling (out of
+    scope)."""
+
+    def _transforms(self):
+        "the Transform objects of the train, val and (if any) test datasets: the ones their loaders read at every minibatch"
+        tfms = [self.data.train_ds.transform, self.data.val_ds.transform]
+        if self.data.test_ds:
+            tfms += [self.data.test_ds.transform]
+        return tfms
+
+    def data_resize(self, sz, bs=None):
+        """Transform the images to size `sz` from now on, and with `bs` also change the batch size of the loaders (Vision.py:1814-1833),
+        'single_label' / 'multi_label' data.  The loaders become views of the resident images (ImageBatches.with_transform: nothing is
+        uploaded again; training stays shuffled and sharded by rank); captured steps of the old shape are dropped."""
+        if self.data.target_type == 'bbox':
+            raise ValueError("data_resize is for 'single_label' / 'multi_label' data: a 'bbox' minibatch has its own padded size")
+        if type(sz) == int:
+            sz = (sz, sz)
+        sz = (int(sz[0]), int(sz[1]))
+        tfms = self._transforms()
+        if sz[0] != sz[1] and any(t.tfm_type == 'TopDown' for t in tfms):
+            raise ValueError("tfm_type='TopDown' rotates by multiples of 90 degrees and needs a square sz (got %r)" % (sz,))
+        self.data.sz = sz
+        for tfm in tfms:
+            tfm.sz = sz
+        if bs:
+            d = self.data
+            d.bs = bs
+            tr = d.train_dl
+            view = tr._view(tr.transform, bs, True, tr.seed, tr.rank, tr.world)
+            view.epoch = tr.epoch                       # the epoch permutations go on, they do not start over
+            d.train_dl = view
+            d.val_dl = d.val_dl.with_transform(d.val_dl.transform, bs)
+            if d.test_dl:
+                d.test_dl = d.test_dl.with_transform(d.test_dl.transform, bs)
+        self._graphs = {}
+
+    def switch_transform_stats(self, new_stats):
+        "Normalise with `new_stats` = [mean, std] from now on, in the train, val and test transforms (Vision.py:1835-1844)."
+        for tfm in self._transforms():
+            tfm.stats = new_stats
+
+    def confusion_matrix(self, pred_labels=None):
+        "Plot the confusion matrix of the validation set, 'single_label' only; predict('val') if no labels are given (Vision.py:1846-1857)."
+        if self.target_type != 'single_label':
+            raise ValueError("confusion_matrix works only with target_type 'single_label' (got %r)" % (self.target_type,))
+        from sklearn.metrics import confusion_matrix
+        true_labels = self.data.val_ds.y
+        if pred_labels is None:
+            pred_probs, pred_labels = self.predict('val')
+        cm = confusion_matrix(true_labels, pred_labels)
+        classes = {self.data.categories[x]: x for x in self.data.categories}
+        plot_confusion_matrix(cm, classes)
+
+    def tta_transforms(self, beta=0.4):
+        """([tfm0 .. tfm4], weights) of TTA (Vision.py:2014-2023, 2033): the evaluation transform and four light augmentations (rotation
+        up to 5 degrees, no zoom) cropped at 0, 1/3, 2/3 and the end of the longer side; type, stats and size of the TRAIN transform."""
+        tfm = self.data.train_ds.transform
+        tfm_type, stats, sz = tfm.tfm_type, tfm.stats, tfm.sz
+        tfms = [Transform('Basic', 'center', None, sz, None, None, None, None, stats=stats)]
+        tfms += [Transform(tfm_type, c, None, sz, 5, 1.0, stats=stats) for c in (0.0, 0.33, 0.67, 1.0)]
+        return tfms, [beta] + [(1 - beta) / 4] * 4
+
+    def TTA(self, ds_type, beta=0.4):
+        """Test-time augmentation of the 'val' or 'test' set, 'single_label' / 'multi_label' (Vision.py:1983-2034): predictions under
+        the five transforms of `tta_transforms`, combined with weights beta, (1 - beta) / 4 x 4; returns what combine_preds returns
+        (probabilities [n, ncat], labels).  The five loaders are views of the one resident copy of the set; view k draws its
+        rotations, flips and lighting from RandomState(loader seed + k) (the reference's draws are unseeded)."""
+        if self.target_type not in ('single_label', 'multi_label'):
+            raise ValueError("TTA works only with target_type 'single_label' or 'multi_label' (got %r)" % (self.target_type,))
+        if ds_type not in ('val', 'test'):
+            raise ValueError("ds_type must be 'val' or 'test' (got %r)" % (ds_type,))
+        dl = self.data.val_dl if ds_type == 'val' else self.data.test_dl
+        tfms, weights = self.tta_transforms(beta)
+        preds = [self.predict(dl.with_transform(tfm, bs=self.data.bs, seed=dl.seed + k))[0] for k, tfm in enumerate(tfms)]
+        return combine_preds(preds, self.target_type, weights)
 
     def compute_mAP(self, predictions=None, thresh=0.05, max_overlap=0.5, rel_thresh=None, top_k=1000, max_boxes=20,
                     dup=None, inc=None, mAP_thresholds=COCO_thresholds):

@@ -32,7 +32,7 @@ from .Core import (ARR, bn_types, combine_models, correct_foldername, default_de
 from .LossesMetrics import AUC
 from .Optimizer import Optimizer, get_param_dict
 
-__all__ = ['Learner', 'HipMSELoss', 'HipCrossEntropyLoss', 'end_metrics', 'SGD_Mom', 'Adam2', 'opt_dict', 'loss_func_dict', 'plot_confusion_matrix']
+__all__ = ['Learner', 'HipMSELoss', 'HipCrossEntropyLoss', 'HipBCEWithLogitsLoss', 'end_metrics', 'SGD_Mom', 'Adam2', 'opt_dict', 'loss_func_dict', 'plot_confusion_matrix']
 
 # registries (General/Learner.py:16-21)
 end_metrics = {'auc': AUC}
@@ -66,8 +66,22 @@ class HipMSELoss(nn.MSELoss):
         return super().forward(input, target)
 
 
+class HipBCEWithLogitsLoss(nn.BCEWithLogitsLoss):
+    """nn.BCEWithLogitsLoss() (the default loss of the 'multi_label' target type, reference General/Learner.py:20) on the HIP kernels of
+    csrc/loss.hip (one launch forward, one backward) when there is no `weight` / `pos_weight`, the reduction is 'mean', logits and
+    target are same-shape CUDA fp32 tensors with at least one element and the target needs no gradient; torch's otherwise."""
+
+    def forward(self, input, target):
+        if (self.weight is None and self.pos_weight is None and self.reduction == 'mean' and input.is_cuda and target.is_cuda
+                and input.dtype == torch.float32 and target.dtype == torch.float32 and input.shape == target.shape
+                and input.numel() > 0 and not target.requires_grad):
+            from ..ops import bce_with_logits
+            return bce_with_logits(input, target)
+        return super().forward(input, target)
+
+
 loss_func_dict = {'cont': HipMSELoss(), 'cat': HipCrossEntropyLoss(), 'single_label': HipCrossEntropyLoss(),
-                  'multi_label': nn.BCEWithLogitsLoss()}
+                  'multi_label': HipBCEWithLogitsLoss()}
 
 
 def _dist():

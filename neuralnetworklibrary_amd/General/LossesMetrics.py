@@ -1,8 +1,9 @@
 """Extra losses / metrics of the drop-in API (mirror of the reference's General/LossesMetrics.py).
 
 These are eval-side elementwise metrics (out of scope for kernels); they stay plain
-torch expressions, vectorised where the reference loops in Python (kPrecision).  Same names, call
-signatures and results.
+torch expressions, vectorised where the reference loops in Python (kPrecision) — except fbeta_loss, which the
+multi-label image workflow evaluates at five thresholds per validation minibatch: on CUDA fp32 [N, C] tensors
+it is one HIP launch (ops.fbeta).  Same names, call signatures and results.
 """
 import torch
 import torch.nn.functional as F
@@ -38,6 +39,10 @@ class fbeta_loss(object):
         self.threshold, self.use_thresh = threshold, use_thresh
 
     def __call__(self, y_pred, y_true):
+        if (y_pred.is_cuda and y_true.is_cuda and y_pred.dtype == torch.float32 and y_true.dtype == torch.float32
+                and y_pred.dim() == 2 and y_pred.shape == y_true.shape and y_pred.shape[0] > 0 and y_pred.shape[1] > 0):
+            from ..ops import fbeta
+            return fbeta(y_pred, y_true, self.beta, self.threshold, self.use_thresh, self.eps)
         b2 = self.beta ** 2
         y_pred = (y_pred.sigmoid() >= self.threshold).float() if self.use_thresh else y_pred.float()
         y_true = y_true.float()

@@ -114,6 +114,11 @@ SIGNATURES = {
     'nnl_mse_workspace_bytes': (sz, [i64]),
     'nnl_mse_fwd': (C.c_int, [c_p, c_p, c_p, i64, c_p, sz, c_p]),
     'nnl_mse_bwd': (C.c_int, [c_p, c_p, c_p, c_p, i64, c_p]),
+    'nnl_bce_logits_workspace_bytes': (sz, [i64]),
+    'nnl_bce_logits_fwd': (C.c_int, [c_p, c_p, c_p, i64, c_p, sz, c_p]),
+    'nnl_bce_logits_bwd': (C.c_int, [c_p, c_p, c_p, c_p, i64, c_p]),
+    'nnl_fbeta_workspace_bytes': (sz, [i64, i64]),
+    'nnl_fbeta': (C.c_int, [c_p, c_p, c_p, i64, i64, C.c_float, C.c_float, C.c_int, C.c_float, c_p, sz, c_p]),
     'nnl_scaled_sigmoid_fwd': (C.c_int, [c_p, c_p, c_p, i64, C.c_float, C.c_float, c_p]),
     'nnl_scaled_sigmoid_bwd': (C.c_int, [c_p, c_p, c_p, i64, C.c_float, C.c_float, c_p]),
     'nnl_seq_reg_workspace_bytes': (sz, [i64, i64]),

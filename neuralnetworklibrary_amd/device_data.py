@@ -126,6 +126,21 @@ class ImageBatches:
             y = torch.as_tensor(np.asarray(ds.y, dtype=np.float32))
         self.y = y.to(self.device)
 
+    def _view(self, transform, bs, shuffle, seed, rank, world):
+        "a loader over THIS loader's arena, descriptor table and labels (nothing is uploaded) with its own transform, batch size and draws"
+        v = object.__new__(ImageBatches)
+        v.__dict__.update(self.__dict__)
+        v.transform, v.bs, v.shuffle, v.seed, v.rank, v.world = transform, int(bs), shuffle, int(seed), int(rank), int(world)
+        v.explicit_params, v.epoch, v.dp_info = None, 0, None
+        return v
+
+    def with_transform(self, transform, bs=None, shuffle=False, seed=None):
+        """A second loader over the SAME device arena, descriptor table and labels — no re-upload — that applies `transform` (an
+        Applications.Vision.Transform) with its own batch size (default: this loader's) and seed (default: this loader's).  It is a
+        rank-local loader of the full set, as `val_dl` is.  ImageLearner.TTA runs its five transforms over one resident copy of the
+        images this way (the reference builds five datasets and DataLoaders, Vision.py:2025-2031)."""
+        return self._view(transform, self.bs if bs is None else bs, shuffle, self.seed if seed is None else seed, 0, 1)
+
     def __len__(self):
         g = self.bs * self.world
         return (self.n + g - 1) // g

@@ -15,7 +15,7 @@ import torch
 from . import _lib
 from ._lib import check, lib, ptr, require_cuda, stream
 
-__all__ = ['mse_loss', 'scaled_sigmoid', 'embdotbias', 'index_error_flag', 'raise_if_index_error', 'conv2d', 'to_nhwc', 'from_nhwc', 'linear', 'bn_act', 'concat_pool2d', 'TabularPlan', 'tab_embed_concat', 'embedding_renorm_drop', 'retina_loss', 'image_aug']
+__all__ = ['mse_loss', 'bce_with_logits', 'fbeta', 'scaled_sigmoid', 'embdotbias', 'index_error_flag', 'raise_if_index_error', 'conv2d', 'to_nhwc', 'from_nhwc', 'linear', 'bn_act', 'concat_pool2d', 'TabularPlan', 'tab_embed_concat', 'embedding_renorm_drop', 'retina_loss', 'image_aug']
 
 _ERR_FLAGS = {}
 
@@ -139,6 +139,51 @@ class _MSE(torch.autograd.Function):
 def mse_loss(pred, target):
     "mean((pred - target)^2) as a 0-dim tensor; gradient with respect to `pred` only (targets are data)"
     return _MSE.apply(pred, target)
+
+
+class _BCEWithLogits(torch.autograd.Function):
+    """nn.BCEWithLogitsLoss() (reference General/Learner.py:20, the 'multi_label' loss): one launch forward, one backward."""
+
+    @staticmethod
+    def forward(ctx, input, target):
+        require_cuda(input, target)
+        x, t = _f32c(input).reshape(-1), _f32c(target).reshape(-1)
+        n = x.numel()
+        loss = torch.empty((), dtype=torch.float32, device=x.device)
+        wsb = int(lib.nnl_bce_logits_workspace_bytes(n))
+        ws = _workspace(wsb, x.device)
+        check(lib.nnl_bce_logits_fwd(ptr(x), ptr(t), ptr(loss), n, ptr(ws), wsb, stream()))
+        ctx.save_for_backward(x, t)
+        ctx.shape = input.shape
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        x, t = ctx.saved_tensors
+        g = _f32c(dloss).reshape(1)
+        dx = torch.empty_like(x)
+        check(lib.nnl_bce_logits_bwd(ptr(x), ptr(t), ptr(g), ptr(dx), x.numel(), stream()))
+        return dx.view(ctx.shape), None
+
+
+def bce_with_logits(input, target):
+    "mean(max(x, 0) - x t + log1p(exp(-|x|))) as a 0-dim tensor; gradient with respect to `input` only (targets are data)"
+    return _BCEWithLogits.apply(input, target)
+
+
+def fbeta(pred, target, beta, threshold=0.5, use_thresh=True, eps=1e-9):
+    """fbeta_loss.__call__ (reference General/LossesMetrics.py:70-78) on [N, C] logits (use_thresh) or 0/1 predictions and 0/1 targets:
+    the mean over the rows of the F-beta score, a 0-dim tensor, in one launch (no gradient: a metric)."""
+    require_cuda(pred, target)
+    p, t = _f32c(pred.detach()), _f32c(target.detach())
+    if p.dim() != 2 or p.shape != t.shape or p.numel() == 0:
+        raise ValueError('fbeta: pred and target must be non-empty [N, C] tensors of one shape (got %s, %s)' % (tuple(pred.shape), tuple(target.shape)))
+    N, C = p.shape
+    out = torch.empty((), dtype=torch.float32, device=p.device)
+    wsb = int(lib.nnl_fbeta_workspace_bytes(N, C))
+    ws = _workspace(wsb, p.device)
+    check(lib.nnl_fbeta(ptr(p), ptr(t), ptr(out), N, C, float(beta) ** 2, float(threshold), int(bool(use_thresh)), float(eps), ptr(ws), wsb, stream()))
+    return out
 
 
 class _ScaledSigmoid(torch.autograd.Function):
