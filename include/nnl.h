@@ -326,11 +326,41 @@ int nnl_concat_pool_bwd(const float* dout, const int32_t* argmax, float* dx, int
 int nnl_bbox_decode(const float* anchors, const float* reg, const float* clas, int64_t bs, int64_t A, int64_t K,
                     const float* mean4, const float* std4, float thresh, float width, float height, float* cand_boxes,
                     int32_t* cand_classes, float* cand_scores, int32_t* cand_order, int32_t* cand_count, void* stream);
+/* nnl_bbox_decode with the clip window [x_min, x_max] x [y_min, y_max] (0 <= x_min < x_max, 0 <= y_min < y_max) in place of
+ * [0, width] x [0, height]: ImageLearner.TTA_bbox clips every pass's boxes to the part of the padded, jittered minibatch that IS the
+ * image, [col_jit, col_jit + rw] x [row_jit, row_jit + rh], so that the undone boxes lie inside the original image. */
+int nnl_bbox_decode_window(const float* anchors, const float* reg, const float* clas, int64_t bs, int64_t A, int64_t K,
+                           const float* mean4, const float* std4, float thresh, float x_min, float y_min, float x_max, float y_max,
+                           float* cand_boxes, int32_t* cand_classes, float* cand_scores, int32_t* cand_order, int32_t* cand_count,
+                           void* stream);
 size_t nnl_nms_workspace_bytes(int64_t bs, int64_t top_k);
 int nnl_nms(const float* cand_boxes, const int32_t* cand_classes, const float* cand_scores, const int32_t* cand_order,
             const int32_t* cand_count, int64_t bs, int64_t cap, int64_t top_k, float max_overlap, float* kept_boxes,
             int32_t* kept_classes, float* kept_scores, int32_t* kept_count, void* workspace, size_t workspace_bytes,
             void* stream);
+
+/* ---- K11: detection test-time augmentation — the undo and concatenation of ImageLearner.TTA_bbox (Applications/Vision.py:2084-2112)
+ * The reference maps every pass's surviving boxes back to the original image with four numpy expressions per (pass, image) and
+ * concatenates the passes as Python lists.  Here, for L images, P passes and M slots per pass, in ONE launch (one workgroup per image):
+ * boxes [L,P,M,4] (xmin, ymin, xmax, ymax), classes [L,P,M], scores [L,P,M]; counts [L,P] = survivors of (image, pass), in slots
+ * [0, count) in descending score order.  undo [L,P]: x -= col_jit, y -= row_jit (:2093), every coordinate times inv (:2094; inv =
+ * 1 / (rand_scale scale) taken in float64 by the caller and rounded ONCE to fp32, as numpy does with a Python float against a float32
+ * array), then with flip != 0 (xmin, xmax) = (cols - xmax, cols - xmin) (:2096).  fp32, every operation rounded on its own (no fused
+ * multiply-add): bit for bit what numpy computes.
+ * Out, in the layout nnl_nms reads with cap = P M: image l's candidates compacted in pass order, then slot order (:2105-2112);
+ * cand_order = that position, so that nnl_nms's tie rule (score descending, order ascending) sees the reference's concatenation
+ * order; cand_count [L].  The slots past cand_count are written too (box 0, class -1, score 0, order = position): the output is a
+ * function of the input alone, no atomics.  A count outside [0, M] is not followed: that pass contributes nothing and *err_flag
+ * (device int32, may be NULL) is set to 1.  L in [1, 2^31), P in [1, 64], M >= 1, P M <= 2^20. */
+typedef struct {
+  float col_jit, row_jit;        /* the pass's jitter: left and top padding of the transformed image */
+  float inv;                     /* fp32(1.0 / (rand_scale * scale)) */
+  float cols;                    /* width of the ORIGINAL image */
+  int32_t flip;                  /* != 0: the pass mirrored the image */
+} nnl_tta_undo_t;                /* 20 bytes */
+int nnl_tta_bbox_merge(const float* boxes, const int32_t* classes, const float* scores, const int32_t* counts,
+                       const nnl_tta_undo_t* undo, int64_t L, int64_t P, int64_t M, float* cand_boxes, int32_t* cand_classes,
+                       float* cand_scores, int32_t* cand_order, int32_t* cand_count, int32_t* err_flag, void* stream);
 
 /* ---- K3: categorical-embedding front end of StructuredDataNet --------------------------------------------
  * Replaces, per categorical column j, EmbeddingDrop.forward (General/Layers.py:74-76: nn.Embedding(max_norm=1.5)

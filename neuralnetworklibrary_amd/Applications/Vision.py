@@ -687,9 +687,9 @@ class ImageLearner(Learner):
     images; a resize changes the Transform objects the loaders share with the datasets and uploads nothing.
     With data = ImageDataObj(..., 'bbox', ..., get_transforms_bbox(...), ...) the whole detection workflow runs
     from the public API: fit trains from device_data.DetectionBatches minibatches (a new padded size runs the step eagerly),
-    predict('val') divides each image's boxes by its 'scale', compute_mAP scores them.  The visualisation helpers (show_images,
-    show_bbox_preds), TTA_bbox and the pycocotools convenience of the reference's ImageLearner are UI / external tooling (out of
-    scope)."""
+    predict('val') divides each image's boxes by its 'scale', TTA_bbox('val', transforms) merges five passes over the resident set,
+    compute_mAP scores either.  The visualisation helpers (show_images, show_bbox_preds) and the pycocotools convenience of the
+    reference's ImageLearner are UI / external tooling (out of scope)."""
 
     def _transforms(self):
         "the Transform objects of the train, val and (if any) test datasets: the ones their loaders read at every minibatch"
@@ -764,6 +764,100 @@ class ImageLearner(Learner):
         tfms, weights = self.tta_transforms(beta)
         preds = [self.predict(dl.with_transform(tfm, bs=self.data.bs, seed=dl.seed + k))[0] for k, tfm in enumerate(tfms)]
         return combine_preds(preds, self.target_type, weights)
+
+    TTA_BBOX_PASSES = 5
+
+    def TTA_bbox(self, ds_type, transforms, thresh=0.05, max_overlap=0.5, rel_thresh=None, top_k=1000, max_boxes=20, dup=None, inc=None):
+        """Test-time augmentation of the 'val' or 'test' set, target_type 'bbox' (Vision.py:2036-2121): five passes over the set at batch
+        size 1 in dataset order — transforms[0] (tfm_eval) once, transforms[1] (tfm_aug) four times — each through BBoxPredictor with
+        the given arguments; every pass's boxes are mapped back to the original image (minus the jitter, times 1 / (rand_scale scale),
+        un-mirrored), the five lists of an image are concatenated in pass order and nms(...) runs once more on the union.  Returns what
+        predict('val') returns: [boxes, classes, scores] per image, so compute_mAP(predictions=learner.TTA_bbox('val', transforms)).
+        The passes are views of the one resident copy of the set (DetectionBatches.with_transform); the undo and the concatenation
+        are one kernel (ops.tta_bbox_merge) and the final NMS one batched nnl_nms over all images.  With rel_thresh, dup and inc all
+        None the only list filter is the max_boxes cut, and every (pass, image) leaves its first max_boxes survivors on the device:
+        no device->host copy and no synchronisation until the one copy of the final result.  With any of the three set, each (pass,
+        image) goes through BBoxPredictor.__call__ as in predict and the pruned lists are uploaded once.
+        Three deliberate differences from the reference:
+          * every pass clips its boxes to the part of the padded, jittered minibatch that IS the image, [col_jit, col_jit + rw] x
+            [row_jit, row_jit + rh] (nnl_bbox_decode_window), so every returned box lies inside its original image (short of it by at
+            most the int() truncation of the resize); the reference, and predict, clip to the padded minibatch, whose padding of up to
+            31 pixels and whose jitter border map to places outside the image.  TTA_bbox under identity passes therefore equals
+            predict exactly when the eval minibatch needs no padding, and differs from it only in boxes that reach into the padding;
+          * a pass un-mirrors only the images it mirrored ('SideOn' and a flip draw of 1, the NNL_IMAGE_AUG_FLIP flag of batch_table);
+            the reference un-mirrors passes 1-4 on the draw alone, which mirrors the correct boxes of a 'Basic' tfm_aug;
+          * pass k draws its per-image values from RandomState(loader seed + k) through TransformBBox.sample, one draw per image in
+            dataset order (at batch size 1 every image is its minibatch's first, so its own rand_scale and jitter apply); the
+            reference pre-draws unseeded lists (get_values)."""
+        from ..General.Learner import _raise_if_index_error
+        from .VisionModels.retinanet import _device_nms_kept, _kept_to_host, _prune
+        if self.target_type != 'bbox':
+            raise ValueError("TTA_bbox works only with target_type 'bbox' (got %r)" % (self.target_type,))
+        if ds_type not in ('val', 'test'):
+            raise ValueError("ds_type must be 'val' or 'test' (got %r)" % (ds_type,))
+        dl = self.data.val_dl if ds_type == 'val' else self.data.test_dl
+        if dl is None:
+            raise ValueError("TTA_bbox('test', ...) needs a test set: the data object has none")
+        if not (isinstance(transforms, (list, tuple)) and len(transforms) == 2 and all(isinstance(t, TransformBBox) for t in transforms)):
+            raise ValueError('transforms must be [tfm_eval, tfm_aug], two TransformBBox (get_transforms_bbox)')
+        P, L = self.TTA_BBOX_PASSES, dl.n
+        views = [dl.with_transform(transforms[0] if k == 0 else transforms[1], bs=1, seed=dl.seed + k) for k in range(P)]
+        on_device = rel_thresh is None and dup is None and inc is None
+        predictor, dev = self.model.BBoxPredictor, dl.device
+        self.model.eval()
+        with torch.no_grad():
+            if on_device:
+                M = max(1, int(top_k) if max_boxes is None else min(int(max_boxes), int(top_k)))
+                limit = M if max_boxes is None else int(max_boxes)           # max_boxes 0: slots exist, counts are 0
+                boxes = torch.zeros(L, P, M, 4, dtype=torch.float32, device=dev)
+                classes = torch.zeros(L, P, M, dtype=torch.int32, device=dev)
+                scores = torch.zeros(L, P, M, dtype=torch.float32, device=dev)
+                counts = torch.zeros(L, P, dtype=torch.int32, device=dev)
+            else:
+                lists = [[None] * P for _ in range(L)]
+            for k, view in enumerate(views):
+                for j, (x_batch, _) in enumerate(view):
+                    x_batch = to_cuda(x_batch)
+                    y_pred = self.predict1minibatch(x_batch)
+                    if isinstance(y_pred, tuple):
+                        y_pred = y_pred[0]
+                    anchors, reg, clas = y_pred
+                    d = view.last_draws[j]                                      # the part of the padded minibatch that is the image
+                    window = (d['col_jit'], d['row_jit'], d['col_jit'] + d['rw'], d['row_jit'] + d['rh'])
+                    if on_device:
+                        kb, kc, ks, kn = predictor.survivors_on_device(x_batch, reg, clas, anchors, thresh, max_overlap, top_k, window)
+                        m = min(kb.shape[1], M)                                 # rows past kept_count are uninitialised memory (torch.empty in
+                        # _device_nms_kept) and are copied as they are: `counts` guards every read of the table, in the merge kernel too
+                        boxes[j, k, :m], classes[j, k, :m], scores[j, k, :m] = kb[0, :m], kc[0, :m], ks[0, :m]
+                        torch.clamp(kn, max=min(m, limit), out=counts[j, k:k + 1])
+                    else:
+                        B, Cl, Sc = predictor(x_batch, reg, clas, anchors, thresh, max_overlap, rel_thresh, top_k, max_boxes, dup, inc, window)
+                        lists[j][k] = (B[0], Cl[0], Sc[0])
+            if not on_device:                                               # the pruned lists, packed into the same table: one upload
+                M = max(1, max(len(lists[j][k][0]) for j in range(L) for k in range(P)))
+                hb, hc = np.zeros((L, P, M, 4), dtype=np.float32), np.zeros((L, P, M), dtype=np.int32)
+                hs, hn = np.zeros((L, P, M), dtype=np.float32), np.zeros((L, P), dtype=np.int32)
+                for j in range(L):
+                    for k in range(P):
+                        B, Cl, Sc = lists[j][k]
+                        n = hn[j, k] = len(B)
+                        if n:
+                            hb[j, k, :n], hc[j, k, :n], hs[j, k, :n] = np.stack(B), np.asarray(Cl), np.asarray(Sc)
+                boxes, classes, scores, counts = (torch.from_numpy(a).to(dev) for a in (hb, hc, hs, hn))
+            cols = [W for _, W in dl.shapes]
+            undo = np.stack([ops.tta_undo_rows(view.last_draws, dl.scales, cols) for view in views], axis=1)        # [L, P]
+            undo = torch.from_numpy(np.ascontiguousarray(undo).view(np.uint8).reshape(L, P, ops.TTA_UNDO.itemsize)).to(dev)
+            merged = []
+            for a in range(0, L, 32768):                                    # nnl_nms takes fewer than 65536 images per call
+                z = min(a + 32768, L)
+                cand = ops.tta_bbox_merge(boxes[a:z], classes[a:z], scores[a:z], counts[a:z], undo[a:z])
+                merged.append((_device_nms_kept(cand, z - a, P * M, top_k, max_overlap, dev), z - a))
+            out = []
+            for kept, n in merged:
+                for b, c, s in _kept_to_host(kept, n):
+                    out.append(list(_prune(list(b), list(c), list(s), rel_thresh, max_boxes, dup, inc)) if len(b) else [[], [], []])
+        _raise_if_index_error(local=True)
+        return out
 
     def compute_mAP(self, predictions=None, thresh=0.05, max_overlap=0.5, rel_thresh=None, top_k=1000, max_boxes=20,
                     dup=None, inc=None, mAP_thresholds=COCO_thresholds):

@@ -394,9 +394,9 @@ def jaccard(Boxes1, Boxes2):
     return inter / (np.expand_dims(areas1, axis=1) + np.expand_dims(areas2, axis=0) - inter)
 
 
-def _device_nms(cand, bs, cap, top_k, max_overlap, device):
-    """sorted top_k + greedy same-class NMS for a batch of candidate lists on the GPU (nnl_nms); returns per image the
-    survivors as numpy arrays (boxes [m,4] f32, classes [m] i64, scores [m] f32) — ONE device->host copy for the batch."""
+def _device_nms_kept(cand, bs, cap, top_k, max_overlap, device):
+    """sorted top_k + greedy same-class NMS for a batch of candidate lists on the GPU (nnl_nms): the survivors stay on the device —
+    (kept_boxes [bs, top_k, 4] f32, kept_classes [bs, top_k] i32, kept_scores [bs, top_k] f32, kept_count [bs] i32), top_k cut to cap"""
     from ..._lib import check, lib, ptr, stream
     cbox, ccls, cscore, corder, ccount = cand
     top_k = int(min(top_k, cap))
@@ -408,10 +408,22 @@ def _device_nms(cand, bs, cap, top_k, max_overlap, device):
     ws = torch.empty(wsb // 4 + 1, dtype=torch.float32, device=device)
     check(lib.nnl_nms(ptr(cbox), ptr(ccls), ptr(cscore), ptr(corder), ptr(ccount), bs, cap, top_k, float(max_overlap), ptr(kbox),
                       ptr(kcls), ptr(kscore), ptr(kcount), ptr(ws), wsb, stream()))
+    return kbox, kcls, kscore, kcount
+
+
+def _kept_to_host(kept, bs):
+    "the survivors of _device_nms_kept per image as numpy arrays (boxes [m,4] f32, classes [m] i64, scores [m] f32): ONE device->host copy for the batch"
+    kbox, kcls, kscore, kcount = kept
     counts = kcount.cpu().numpy()
     mx = int(counts.max()) if bs else 0
     hb, hc, hs = kbox[:, :mx].cpu().numpy(), kcls[:, :mx].cpu().numpy().astype(np.int64), kscore[:, :mx].cpu().numpy()
     return [(hb[i, :counts[i]], hc[i, :counts[i]], hs[i, :counts[i]]) for i in range(bs)]
+
+
+def _device_nms(cand, bs, cap, top_k, max_overlap, device):
+    """sorted top_k + greedy same-class NMS for a batch of candidate lists on the GPU (nnl_nms); returns per image the
+    survivors as numpy arrays (boxes [m,4] f32, classes [m] i64, scores [m] f32) — ONE device->host copy for the batch."""
+    return _kept_to_host(_device_nms_kept(cand, bs, cap, top_k, max_overlap, device), bs)
 
 
 def _drop(seq, idxs):
@@ -509,8 +521,12 @@ class BBoxPredictor(object):
     def __init__(self, mean=[0., 0., 0., 0.], std=[0.1, 0.1, 0.2, 0.2]):
         self.mean, self.std = np.asarray(mean, np.float32), np.asarray(std, np.float32)
 
-    def __call__(self, img_batch, reg, clas, anchors, thresh=0.05, max_overlap=0.5, rel_thresh=None, top_k=1000,
-                 max_boxes=20, dup=None, inc=None):
+    def survivors_on_device(self, img_batch, reg, clas, anchors, thresh=0.05, max_overlap=0.5, top_k=1000, window=None):
+        """Decode + NMS of the whole batch (nnl_bbox_decode, nnl_nms) with the result left on the device: (kept_boxes [bs, k, 4] f32,
+        kept_classes [bs, k] i32, kept_scores [bs, k] f32, kept_count [bs] i32), k = min(top_k, anchors), survivors in descending
+        score order in slots [0, kept_count).  No device->host copy, no synchronisation: ImageLearner.TTA_bbox collects every pass this
+        way.  The list filters of nms() are not applied.  window = (x_min, y_min, x_max, y_max): clip the boxes to it (nnl_bbox_decode_window)
+        in place of the whole padded batch [0, width] x [0, height]."""
         from ..._lib import check, lib, ptr, require_cuda, stream
         require_cuda(reg, clas, anchors)
         bs, _, height, width = img_batch.shape
@@ -521,11 +537,20 @@ class BBoxPredictor(object):
         cscore = torch.empty(bs, A, dtype=torch.float32, device=dev)
         corder = torch.empty(bs, A, dtype=torch.int32, device=dev)
         ccount = torch.empty(bs, dtype=torch.int32, device=dev)
-        check(lib.nnl_bbox_decode(ptr(anchors), ptr(reg), ptr(clas), bs, A, K, self.mean.ctypes.data, self.std.ctypes.data,
-                                  float(thresh), float(width), float(height), ptr(cbox), ptr(ccls), ptr(cscore), ptr(corder),
-                                  ptr(ccount), stream()))
+        head = (ptr(anchors), ptr(reg), ptr(clas), bs, A, K, self.mean.ctypes.data, self.std.ctypes.data, float(thresh))
+        tail = (ptr(cbox), ptr(ccls), ptr(cscore), ptr(corder), ptr(ccount), stream())
+        if window is None:
+            check(lib.nnl_bbox_decode(*head, float(width), float(height), *tail))
+        else:
+            check(lib.nnl_bbox_decode_window(*head, *[float(v) for v in window], *tail))
+        return _device_nms_kept((cbox, ccls, cscore, corder, ccount), bs, A, top_k, max_overlap, dev)
+
+    def __call__(self, img_batch, reg, clas, anchors, thresh=0.05, max_overlap=0.5, rel_thresh=None, top_k=1000,
+                 max_boxes=20, dup=None, inc=None, window=None):
+        bs = img_batch.shape[0]
+        kept = self.survivors_on_device(img_batch, reg, clas, anchors, thresh, max_overlap, top_k, window)
         PredBoxes, PredClasses, ConfScores = [], [], []
-        for b, c, s in _device_nms((cbox, ccls, cscore, corder, ccount), bs, A, top_k, max_overlap, dev):
+        for b, c, s in _kept_to_host(kept, bs):
             B, C, S = _prune(list(b), list(c), list(s), rel_thresh, max_boxes, dup, inc) if len(b) else ([], [], [])
             PredBoxes.append(B); PredClasses.append(C); ConfScores.append(S)
         return PredBoxes, PredClasses, ConfScores

@@ -14,6 +14,9 @@
 // contraction: the library is built with -ffp-contract=off), so keep / suppress decisions are identical; box coordinates
 // can differ from a CPU run by the ulp of expf.  The rest of nms (relative thresholds, inclusion / duplicate filters on the
 // few surviving boxes) is list logic and stays on the host (Applications/VisionModels/retinanet.py).
+//   5. tta_bbox_merge_kernel  (K11) the undo and concatenation of TTA_bbox (Applications/Vision.py:2084-2112): the survivors of
+//                           every (pass, image) mapped back to the original image and compacted per image into the candidate
+//                           layout that steps 2-4 read, so the final NMS of all images is ONE nnl_nms call.
 #include "nnl_common.h"
 
 namespace {
@@ -29,7 +32,8 @@ __device__ __forceinline__ unsigned desc_key(float s) {        // larger score -
 
 __global__ __launch_bounds__(256) void bbox_decode_kernel(const float* __restrict__ anchors, const float* __restrict__ reg,
                                                           const float* __restrict__ clas, int A, int K, f32x4 mean, f32x4 stdv,
-                                                          float thresh, float width, float height, float* __restrict__ cbox,
+                                                          float thresh, float xlo, float ylo, float width, float height,
+                                                          float* __restrict__ cbox,
                                                           int* __restrict__ ccls, float* __restrict__ cscore,
                                                           int* __restrict__ corder, int* __restrict__ ccount) {
   const int a = blockIdx.x * blockDim.x + threadIdx.x, img = blockIdx.y;
@@ -51,7 +55,7 @@ __global__ __launch_bounds__(256) void bbox_decode_kernel(const float* __restric
   const float pcx = cx + w * dx, pcy = cy + h * dy;
   const float pw = w * expf(dw), ph = h * expf(dh);
   float x0 = pcx - 0.5f * pw, y0 = pcy - 0.5f * ph, x1 = pcx + 0.5f * pw, y1 = pcy + 0.5f * ph;
-  x0 = fmaxf(x0, 0.f); y0 = fmaxf(y0, 0.f);
+  x0 = fmaxf(x0, xlo); y0 = fmaxf(y0, ylo);                         // the window: [0, width] x [0, height] for nnl_bbox_decode
   x1 = fminf(x1, width); y1 = fminf(y1, height);
   if (!((x1 - x0) > 0.f) || !((y1 - y0) > 0.f)) return;
   const int pos = atomicAdd(&ccount[img], 1);
@@ -185,12 +189,85 @@ __global__ __launch_bounds__(64) void nms_scan_kernel(const float* __restrict__ 
   if (lane == 0) kcount[img] = nkept;
 }
 
+// K11: the undo and concatenation of TTA_bbox (Applications/Vision.py:2084-2112).  One workgroup per image; the first wave takes the P
+// counts (P <= 64, one per lane), turns them into offsets with a wave-level inclusive prefix, and every thread then moves slots: slot
+// (p, r) with r < count[p] goes to position offset[p] + r.  Every output position is written by exactly one thread (the positions past
+// the total get a filler), so the output depends on the input alone.
+constexpr int kMergeBlock = 256;
+
+__device__ __forceinline__ f32x4 tta_undo_box(const f32x4 b, const nnl_tta_undo_t u) {
+  // numpy, one array operation at a time (:2093-2096): (v - jit) * inv, then the mirror about the original width.  cols - x * inv would
+  // contract into a fused multiply-add: the pragma and -ffp-contract=off on the build line keep every operation rounded on its own.
+#pragma clang fp contract(off)
+  float x0 = (b[0] - u.col_jit) * u.inv, y0 = (b[1] - u.row_jit) * u.inv;
+  float x1 = (b[2] - u.col_jit) * u.inv, y1 = (b[3] - u.row_jit) * u.inv;
+  if (u.flip) {
+    const float m0 = u.cols - x1, m1 = u.cols - x0;
+    x0 = m0; x1 = m1;
+  }
+  const f32x4 out = {x0, y0, x1, y1};
+  return out;
+}
+
+__global__ __launch_bounds__(kMergeBlock) void tta_bbox_merge_kernel(const float* __restrict__ boxes, const int* __restrict__ classes,
+                                                                     const float* __restrict__ scores, const int* __restrict__ counts,
+                                                                     const nnl_tta_undo_t* __restrict__ undo, int P, int M,
+                                                                     float* __restrict__ cbox, int* __restrict__ ccls,
+                                                                     float* __restrict__ cscore, int* __restrict__ corder,
+                                                                     int* __restrict__ ccount, int* __restrict__ err_flag) {
+  __shared__ int s_cnt[NNL_WAVE], s_off[NNL_WAVE + 1];
+  __shared__ nnl_tta_undo_t s_undo[NNL_WAVE];
+  const long img = blockIdx.x;
+  const int t = threadIdx.x;
+  if (t < NNL_WAVE) {                                             // the first wave: lane p owns pass p
+    int c = 0;
+    if (t < P) {
+      c = counts[img * P + t];
+      if (c < 0 || c > M) {                                       // not followed: the pass contributes nothing
+        c = 0;
+        if (err_flag) *err_flag = 1;
+      }
+      s_undo[t] = undo[img * P + t];
+    }
+    int incl = c;
+#pragma unroll
+    for (int o = 1; o < NNL_WAVE; o <<= 1) {
+      const int v = __shfl_up(incl, o, NNL_WAVE);
+      if (t >= o) incl += v;
+    }
+    s_cnt[t] = c;
+    s_off[t] = incl - c;
+    if (t == NNL_WAVE - 1) s_off[NNL_WAVE] = incl;
+  }
+  __syncthreads();
+  const int cap = P * M, total = s_off[NNL_WAVE];
+  const long in0 = img * cap, out0 = img * cap;
+  for (int s = t; s < cap; s += kMergeBlock) {
+    const int p = s / M, r = s - p * M;
+    if (r < s_cnt[p]) {
+      const int d = s_off[p] + r;                                 // < total <= cap
+      reinterpret_cast<f32x4*>(cbox)[out0 + d] = tta_undo_box(reinterpret_cast<const f32x4*>(boxes)[in0 + s], s_undo[p]);
+      ccls[out0 + d] = classes[in0 + s];
+      cscore[out0 + d] = scores[in0 + s];
+      corder[out0 + d] = d;
+    }
+  }
+  for (int d = total + t; d < cap; d += kMergeBlock) {            // the filler: never read by nnl_nms
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    reinterpret_cast<f32x4*>(cbox)[out0 + d] = zero;
+    ccls[out0 + d] = -1;
+    cscore[out0 + d] = 0.f;
+    corder[out0 + d] = d;
+  }
+  if (t == 0) ccount[img] = total;
+}
+
 }  // namespace
 
-extern "C" int nnl_bbox_decode(const float* anchors, const float* reg, const float* clas, int64_t bs, int64_t A, int64_t K,
-                               const float* mean4, const float* std4, float thresh, float width, float height,
-                               float* cand_boxes, int32_t* cand_classes, float* cand_scores, int32_t* cand_order,
-                               int32_t* cand_count, void* stream) {
+static int bbox_decode_launch(const float* anchors, const float* reg, const float* clas, int64_t bs, int64_t A, int64_t K,
+                              const float* mean4, const float* std4, float thresh, float x_min, float y_min, float x_max, float y_max,
+                              float* cand_boxes, int32_t* cand_classes, float* cand_scores, int32_t* cand_order, int32_t* cand_count,
+                              void* stream) {
   NNL_CHECK_ARG(anchors && reg && clas && mean4 && std4 && cand_boxes && cand_classes && cand_scores && cand_order && cand_count,
                 "bbox_decode: null pointer");
   NNL_CHECK_ARG(bs > 0 && bs < 65536 && A > 0 && A < (1L << 30) && K > 0, "bbox_decode: bad sizes");
@@ -199,9 +276,29 @@ extern "C" int nnl_bbox_decode(const float* anchors, const float* reg, const flo
   NNL_CHECK_HIP(hipMemsetAsync(cand_count, 0, sizeof(int32_t) * bs, s));
   const f32x4 mean = {mean4[0], mean4[1], mean4[2], mean4[3]}, stdv = {std4[0], std4[1], std4[2], std4[3]};
   hipLaunchKernelGGL(bbox_decode_kernel, dim3((unsigned)nnl_cdiv(A, 256), (unsigned)bs), dim3(256), 0, s, anchors, reg, clas, (int)A,
-                     (int)K, mean, stdv, thresh, width, height, cand_boxes, cand_classes, cand_scores, cand_order, cand_count);
+                     (int)K, mean, stdv, thresh, x_min, y_min, x_max, y_max, cand_boxes, cand_classes, cand_scores, cand_order,
+                     cand_count);
   NNL_CHECK_LAUNCH();
   return NNL_OK;
+}
+
+extern "C" int nnl_bbox_decode(const float* anchors, const float* reg, const float* clas, int64_t bs, int64_t A, int64_t K,
+                               const float* mean4, const float* std4, float thresh, float width, float height,
+                               float* cand_boxes, int32_t* cand_classes, float* cand_scores, int32_t* cand_order,
+                               int32_t* cand_count, void* stream) {
+  return bbox_decode_launch(anchors, reg, clas, bs, A, K, mean4, std4, thresh, 0.f, 0.f, width, height, cand_boxes, cand_classes,
+                            cand_scores, cand_order, cand_count, stream);
+}
+
+extern "C" int nnl_bbox_decode_window(const float* anchors, const float* reg, const float* clas, int64_t bs, int64_t A, int64_t K,
+                                      const float* mean4, const float* std4, float thresh, float x_min, float y_min, float x_max,
+                                      float y_max, float* cand_boxes, int32_t* cand_classes, float* cand_scores, int32_t* cand_order,
+                                      int32_t* cand_count, void* stream) {
+  NNL_CHECK_ARG(x_min >= 0.f && y_min >= 0.f && x_max > x_min && y_max > y_min,
+                "bbox_decode_window: the window must be 0 <= x_min < x_max, 0 <= y_min < y_max (got [%g, %g] x [%g, %g])", x_min, x_max,
+                y_min, y_max);
+  return bbox_decode_launch(anchors, reg, clas, bs, A, K, mean4, std4, thresh, x_min, y_min, x_max, y_max, cand_boxes, cand_classes,
+                            cand_scores, cand_order, cand_count, stream);
 }
 
 static inline int64_t nms_words(int64_t top_k) { return nnl_cdiv(top_k, 64); }
@@ -240,6 +337,24 @@ extern "C" int nnl_nms(const float* cand_boxes, const int32_t* cand_classes, con
   hipLaunchKernelGGL(nms_scan_kernel, dim3((unsigned)bs), dim3(64), words * sizeof(u64), s, (const float*)sbox, (const int*)scls,
                      (const float*)sscore, (const int*)scount, (int)top_k, words, (const u64*)mask, kept_boxes, kept_classes,
                      kept_scores, kept_count);
+  NNL_CHECK_LAUNCH();
+  return NNL_OK;
+}
+
+extern "C" int nnl_tta_bbox_merge(const float* boxes, const int32_t* classes, const float* scores, const int32_t* counts,
+                                  const nnl_tta_undo_t* undo, int64_t L, int64_t P, int64_t M, float* cand_boxes,
+                                  int32_t* cand_classes, float* cand_scores, int32_t* cand_order, int32_t* cand_count,
+                                  int32_t* err_flag, void* stream) {
+  NNL_CHECK_ARG(boxes && classes && scores && counts && undo && cand_boxes && cand_classes && cand_scores && cand_order && cand_count,
+                "tta_bbox_merge: null pointer");
+  NNL_CHECK_ARG(L > 0 && L < (1L << 31) && P > 0 && P <= NNL_WAVE && M > 0 && M <= (1L << 20) && P * M <= (1L << 20),
+                "tta_bbox_merge: bad sizes (L %lld in [1, 2^31), P %lld in [1, 64], M %lld >= 1, P M <= 2^20)", (long long)L,
+                (long long)P, (long long)M);
+  static_assert(sizeof(nnl_tta_undo_t) == 20, "nnl_tta_undo_t is five 4-byte fields");
+  hipStream_t s = (hipStream_t)stream;
+  NnlProfScope prof(NNL_PROF_ELEMENTWISE, s, (double)L * P * M * 48.0);
+  hipLaunchKernelGGL(tta_bbox_merge_kernel, dim3((unsigned)L), dim3(kMergeBlock), 0, s, boxes, classes, scores, counts, undo, (int)P,
+                     (int)M, cand_boxes, cand_classes, cand_scores, cand_order, cand_count, err_flag);
   NNL_CHECK_LAUNCH();
   return NNL_OK;
 }

@@ -199,6 +199,7 @@ class DetectionBatches:
         self.explicit_params = explicit_params
         self.epoch = 0
         self.dp_info = None          # (rows of the last yielded shard that count, rows of its GLOBAL minibatch): Learner reads it
+        self.last_draws = None       # kept by `with_transform` views only
         imgs, self.shapes, self.arena, self.desc = _upload_images(ds.images, self.device)
         sums = np.stack([a.reshape(-1, 3).sum(axis=0, dtype=np.int64) for a in imgs])
         pixels = np.array([255.0 * H * W for H, W in self.shapes], dtype=np.float64)
@@ -224,6 +225,23 @@ class DetectionBatches:
             order = list(range(self.n))
         self.groups = [np.array(order[i:i + g], dtype=np.int64) for i in range(0, self.n, g)]
 
+    def with_transform(self, transform, bs=None, seed=None):
+        """A second loader over the SAME image arena, descriptor table, channel means, box and category arenas — no re-upload — that
+        applies `transform` (an Applications.Vision.TransformBBox) with its own batch size (default: this loader's) and seed (default:
+        this loader's): not grouped, dataset order, rank-local over the full set, epoch 0, no explicit_params (as
+        ImageBatches.with_transform).  A view REMEMBERS what its last iteration applied: `last_draws[i]` = dict(row_jit, col_jit,
+        rand_scale: the values of image i's minibatch, i.e. its first sample's; flip: 1 iff image i was mirrored, the
+        NNL_IMAGE_AUG_FLIP flag of its row; rh, rw: its resized size; sample: the TransformBBox.sample() draw of image i itself), None for an image not reached
+        yet.  ImageLearner.TTA_bbox runs its five passes over one resident copy of the set this way and undoes them from last_draws
+        (the reference builds five datasets and DataLoaders and pre-draws L values per transform copy, Vision.py:2068-2073)."""
+        v = object.__new__(DetectionBatches)
+        v.__dict__.update(self.__dict__)
+        v.transform, v.bs, v.seed = transform, int(self.bs if bs is None else bs), int(self.seed if seed is None else seed)
+        v.grouped, v.rank, v.world, v.explicit_params, v.epoch, v.dp_info = False, 0, 1, None, 0, None
+        v.groups = [np.arange(i, min(i + v.bs, v.n), dtype=np.int64) for i in range(0, v.n, v.bs)]
+        v.last_draws = [None] * v.n
+        return v
+
     def __len__(self):
         return len(self.groups)
 
@@ -234,14 +252,22 @@ class DetectionBatches:
             assert len(draws) == len(idx), 'explicit_params must return one draw per sample'
         else:
             draws = [self.transform.sample(rng) for _ in idx]
-        return self.transform.batch_table([int(i) for i in idx], [self.shapes[i] for i in idx], [self.scales[i] for i in idx],
-                                          [tuple(self.box_range[i]) for i in idx], draws)
+        table, v = self.transform.batch_table([int(i) for i in idx], [self.shapes[i] for i in idx], [self.scales[i] for i in idx],
+                                              [tuple(self.box_range[i]) for i in idx], draws)
+        if self.last_draws is not None:
+            for k, i in enumerate(idx):
+                self.last_draws[int(i)] = dict(row_jit=v['row_jit'], col_jit=v['col_jit'], rand_scale=v['rand_scale'],
+                                               flip=int(bool(table[k]['flags'] & ops.IMAGE_AUG_FLIP)), rh=int(table[k]['rh']),
+                                               rw=int(table[k]['rw']), sample=draws[k])
+        return table, v
 
     def __iter__(self):
         rng = np.random.RandomState(self.seed + self.epoch)       # identical on every rank
         order = rng.permutation(len(self.groups)) if self.grouped else np.arange(len(self.groups))
         self.epoch += 1
         tfm = self.transform
+        if self.last_draws is not None:
+            self.last_draws = [None] * self.n
         for b, gi in enumerate(order):
             idx = self.groups[gi]
             table, v = self._table(rng, b, idx)

@@ -1483,5 +1483,55 @@ def detect_aug(arena, desc, image_mean, box_arena, cat_arena, params, Hp, Wp, N,
 
 __all__ += ['detect_aug']
 
+
+# ---------------------------------------------------------------------------------------------------------
+# K11 detection test-time augmentation: the undo and concatenation of TTA_bbox (include/nnl.h).
+# ---------------------------------------------------------------------------------------------------------
+# nnl_tta_undo_t: one 20-byte row per (image, pass)
+TTA_UNDO = np.dtype([('col_jit', '<f4'), ('row_jit', '<f4'), ('inv', '<f4'), ('cols', '<f4'), ('flip', '<i4')])
+
+
+def tta_undo_rows(draws, scales, cols):
+    """The TTA_UNDO rows of one pass (reference Applications/Vision.py:2086-2096): draws = the pass's per-image values in dataset order
+    (DetectionBatches.last_draws: row_jit, col_jit, rand_scale and flip AS APPLIED), scales [n] the images' own scales and cols [n]
+    their original widths.  inv = 1 / (rand_scale scale) in float64, rounded once to fp32 (numpy: a Python float against a float32
+    array)."""
+    rows = np.zeros(len(draws), dtype=TTA_UNDO)
+    for i, d in enumerate(draws):
+        rows[i] = (d['col_jit'], d['row_jit'], np.float32(1.0 / (float(d['rand_scale']) * float(scales[i]))), cols[i], int(d['flip'] != 0))
+    return rows
+
+
+def tta_bbox_merge(boxes, classes, scores, counts, undo):
+    """The per-pass survivors of TTA_bbox mapped back to the original images and concatenated per image, in one launch: boxes fp32
+    [L, P, M, 4], classes int32 [L, P, M], scores fp32 [L, P, M], counts int32 [L, P] (survivors in slots [0, count), descending
+    score), undo uint8 [L, P, 20] = TTA_UNDO rows.  Returns (cand_boxes [L, P M, 4], cand_classes, cand_scores, cand_order [L, P M],
+    cand_count [L]): what nnl_nms reads with cap = P M.  A count outside [0, M] raises the device's index-error flag
+    (`raise_if_index_error`) and that pass contributes nothing."""
+    require_cuda(boxes, classes, scores, counts, undo)
+    if boxes.dtype != torch.float32 or scores.dtype != torch.float32 or classes.dtype != torch.int32 or counts.dtype != torch.int32 \
+            or undo.dtype != torch.uint8:
+        raise TypeError('tta_bbox_merge: boxes and scores must be float32, classes and counts int32 and undo uint8')
+    if not all(t.is_contiguous() for t in (boxes, classes, scores, counts, undo)):
+        raise ValueError('tta_bbox_merge: every input must be contiguous')
+    if boxes.dim() != 4 or boxes.shape[3] != 4:
+        raise ValueError('tta_bbox_merge: boxes must be [L, P, M, 4]')
+    L, P, M = boxes.shape[:3]
+    if tuple(classes.shape) != (L, P, M) or tuple(scores.shape) != (L, P, M) or tuple(counts.shape) != (L, P) \
+            or tuple(undo.shape) != (L, P, TTA_UNDO.itemsize):
+        raise ValueError('tta_bbox_merge: classes and scores must be [L, P, M], counts [L, P] and undo [L, P, %d]' % TTA_UNDO.itemsize)
+    dev = boxes.device
+    cbox = torch.empty(L, P * M, 4, dtype=torch.float32, device=dev)
+    ccls = torch.empty(L, P * M, dtype=torch.int32, device=dev)
+    cscore = torch.empty(L, P * M, dtype=torch.float32, device=dev)
+    corder = torch.empty(L, P * M, dtype=torch.int32, device=dev)
+    ccount = torch.empty(L, dtype=torch.int32, device=dev)
+    check(lib.nnl_tta_bbox_merge(ptr(boxes), ptr(classes), ptr(scores), ptr(counts), ptr(undo), L, P, M, ptr(cbox), ptr(ccls), ptr(cscore),
+                                 ptr(corder), ptr(ccount), ptr(index_error_flag(dev)), stream()))
+    return cbox, ccls, cscore, corder, ccount
+
+
+__all__ += ['tta_bbox_merge', 'tta_undo_rows']
+
 from .ops_text import (lstm_layer, embedding_rowmask, softmax_cross_entropy, cross_entropy_nd, seq_activation_reg)  # noqa: E402,F401
 __all__ += ['lstm_layer', 'embedding_rowmask', 'softmax_cross_entropy', 'cross_entropy_nd', 'seq_activation_reg', 'conv_add_upsampled']
