@@ -235,6 +235,8 @@ int nnl_act_gate_colsum(const float* dy, const float* y, float* g, float* colsum
  *   running = (1-momentum)*running + momentum*batch   (running_* may be NULL: track_running_stats=False);
  * training==0: normalise with running_mean / running_var.
  * y = (x-mean)*invstd*gamma + beta [+ residual] [ReLU].  save_mean/save_invstd [C] are kept for backward.
+ * Evaluated per channel as x*scale + shift (scale = invstd*gamma, shift = beta - mean*scale) while |mean*scale| <= 16, and as
+ * (x - mean)*scale + beta above: the first form's rounding error grows with |mean*scale| (2^-23 * |mean*scale|), not with |y|.
  * num_batches_tracked (device int64, may be NULL): nn.BatchNorm's step counter, incremented by the training call.
  * ext_partials / ext_rows / ext_pivot (optional, training only): the (sum, sum of squares) partials written by the
  * convolution that produced x (nnl_conv2d_fwd, bn_partials) with the pivot it used — the statistics pass over x is skipped.
@@ -275,6 +277,17 @@ int nnl_bn_relu_maxpool_bwd(const float* dpool, const float* y, const uint8_t* i
                             float* dx, float* dgamma, float* dbeta,
                             int64_t N, int64_t H, int64_t W, int64_t C, int64_t P, int64_t Q, int ks, int stride, int pad,
                             int training, void* workspace, size_t workspace_bytes, void* stream);
+
+/* What the BatchNorm entry points above would launch for a [rows, C] matrix, from the planner functions they call themselves
+ * (csrc/batchnorm.hip: make_shape, ew_grid, bnpool_grid).  Host-only: no HIP call, works without a GPU.  out10 (TEN int32) =
+ *   [0] VEC   floats per access: 4 when C % 4 == 0, else 1          [1] L    lanes of a wave along the channel groups (CG = C / VEC)
+ *   [2] rpb   rows one block covers per loop iteration              [3] gx   row blocks = partials per channel of the reductions
+ *   [4] gy    channel-group tiles                                   [5] 1 when gx was clamped to the row-block cap / gy, else 0
+ *   [6] blocks of the elementwise (apply) kernels                   [7] the row-block cap itself
+ *   [8] [9] nnl_bn_relu_maxpool_bwd's reduction grid over the inputs (y == NULL) and over the pooled outputs (y given) for the stem
+ *           geometry N,H,W,P,Q; -1 when N <= 0 or C is refused by nnl_bn_relu_maxpool_supported.
+ * Returns 1, or 0 (out10 untouched) for sizes the entry points refuse. */
+int nnl_debug_bn_plan(int64_t rows, int64_t C, int64_t N, int64_t H, int64_t W, int64_t P, int64_t Q, int32_t* out10);
 
 /* Cross-replica (synchronised) training-mode BatchNorm for data parallelism (global-batch statistics equal
  * to the single-GPU reference's).  Split-phase, the host runs the collective in between (neuralnetworklibrary_amd/ops.py):

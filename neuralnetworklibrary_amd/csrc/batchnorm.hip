@@ -26,12 +26,18 @@ template <> __device__ __forceinline__ void vset<1>(float& v, int i, float x) { 
 
 constexpr int kBlock = 256;
 constexpr int kMaxRowBlocks = 1024;
+// bn_apply evaluates y = (x - pivot)*scale + offset per channel.  (pivot, offset) = (0, beta - mean*scale) is the plain scale & shift
+// form: it rounds two terms of magnitude |mean*scale|, an absolute error of up to 2^-23 * |mean*scale| in y whatever |y| is.  Above
+// this value of |mean*scale| (error 1.9e-6, a fifth of the 1e-5 the tests allow y) a channel takes (pivot, offset) = (mean, beta)
+// instead: x - mean is exact to an ulp of x and the rest scales with |y|.  x - 0 is exact, so below it nothing changes.
+constexpr float kCentreAbove = 16.f;
 constexpr int kFinLanes = 64;     // partial-sum lanes per channel in the finalize kernels (4 channels per block)
 
 struct Shape {
   int L;        // lanes per row inside a wave (power of two <= 64)
   int rpb;      // rows covered by one block iteration = 4 waves * 64 / L
   int gx, gy;   // grid: row blocks x channel-group tiles
+  bool capped;  // gx was clamped to kMaxRowBlocks / gy: a thread slot then owns more than 4 rows
 };
 
 Shape make_shape(long rows, long CG) {
@@ -43,6 +49,7 @@ Shape make_shape(long rows, long CG) {
   long gx = nnl_cdiv(rows, (long)s.rpb * 4);              // at least 4 rows per thread
   long cap = kMaxRowBlocks / (s.gy > 0 ? s.gy : 1);
   if (cap < 1) cap = 1;
+  s.capped = gx > cap;
   if (gx > cap) gx = cap;
   if (gx < 1) gx = 1;
   s.gx = (int)gx;
@@ -158,7 +165,8 @@ __device__ __forceinline__ void finish_stats(int c, int C, float m, float var, f
                                              float* __restrict__ invstd, float* __restrict__ running_mean,
                                              float* __restrict__ running_var, float* __restrict__ scale,
                                              float* __restrict__ shift, float eps, float momentum,
-                                             float* __restrict__ pivot_out = nullptr) {
+                                             float* __restrict__ pivot_out = nullptr,
+                                             float* __restrict__ apply_pivot = nullptr) {
   const float is = 1.f / sqrtf(var + eps);
   mean[c] = m;
   if (pivot_out) pivot_out[c] = m;                 // next step's pivot for the conv-epilogue statistics (read above, before this)
@@ -171,7 +179,10 @@ __device__ __forceinline__ void finish_stats(int c, int C, float m, float var, f
   const float gm = gamma ? gamma[c] : 1.f;
   const float sc = is * gm;
   scale[c] = sc;
-  shift[c] = (beta ? beta[c] : 0.f) - m * sc;
+  const float bt = beta ? beta[c] : 0.f;
+  const bool centred = apply_pivot != nullptr && fabsf(m * sc) > kCentreAbove;
+  if (apply_pivot) apply_pivot[c] = centred ? m : 0.f;
+  shift[c] = centred ? bt : bt - m * sc;
 }
 
 // ---- finalize: mean / invstd, running statistics, per-channel scale & shift ----------------------------------
@@ -182,7 +193,7 @@ __global__ void bn_finalize_kernel(const float* __restrict__ x, const float* __r
                                    float* __restrict__ running_mean, float* __restrict__ running_var,
                                    float* __restrict__ scale, float* __restrict__ shift, long rows, int C, float eps,
                                    float momentum, long long* __restrict__ num_batches_tracked,
-                                   float* __restrict__ pivot_out) {
+                                   float* __restrict__ pivot_out, float* __restrict__ apply_pivot) {
   __shared__ float red[256 / LANES][LANES][2];
   const int c = blockIdx.x * (256 / LANES) + threadIdx.x / LANES;
   float s1, s2;
@@ -193,7 +204,7 @@ __global__ void bn_finalize_kernel(const float* __restrict__ x, const float* __r
   const float m = x[c] + s1 / n;
   float var = (s2 - s1 * (s1 / n)) / n;
   var = fmaxf(var, 0.f);
-  finish_stats(c, C, m, var, n, gamma, beta, mean, invstd, running_mean, running_var, scale, shift, eps, momentum, pivot_out);
+  finish_stats(c, C, m, var, n, gamma, beta, mean, invstd, running_mean, running_var, scale, shift, eps, momentum, pivot_out, apply_pivot);
 }
 
 // ---- cross-replica BatchNorm (SyncBN) ---------------------------------------------------------------
@@ -223,7 +234,7 @@ __global__ void bn_sync_merge_kernel(const float* __restrict__ all_stats, int wo
                                      const float* __restrict__ beta, float* __restrict__ mean, float* __restrict__ invstd,
                                      float* __restrict__ running_mean, float* __restrict__ running_var,
                                      float* __restrict__ scale, float* __restrict__ shift, int C, float eps, float momentum,
-                                     long long* __restrict__ num_batches_tracked) {
+                                     long long* __restrict__ num_batches_tracked, float* __restrict__ apply_pivot) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
   if (c == 0 && num_batches_tracked) *num_batches_tracked += 1;
@@ -239,23 +250,27 @@ __global__ void bn_sync_merge_kernel(const float* __restrict__ all_stats, int wo
     M2 += st[C + c] + d * d * (n * (nr / nn));
     n = nn;
   }
-  finish_stats(c, C, m, fmaxf(M2 / n, 0.f), n, gamma, beta, mean, invstd, running_mean, running_var, scale, shift, eps, momentum);
+  finish_stats(c, C, m, fmaxf(M2 / n, 0.f), n, gamma, beta, mean, invstd, running_mean, running_var, scale, shift, eps, momentum, nullptr,
+               apply_pivot);
 }
 
 __global__ void bn_eval_scale_kernel(const float* __restrict__ gamma, const float* __restrict__ beta,
                                      const float* __restrict__ running_mean, const float* __restrict__ running_var,
                                      float* __restrict__ scale, float* __restrict__ shift, float* __restrict__ invstd,
-                                     int C, float eps) {
+                                     int C, float eps, float* __restrict__ apply_pivot) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
   const float is = 1.f / sqrtf(running_var[c] + eps);
   const float sc = is * (gamma ? gamma[c] : 1.f);
   scale[c] = sc;
-  shift[c] = (beta ? beta[c] : 0.f) - running_mean[c] * sc;
+  const float bt = beta ? beta[c] : 0.f, m = running_mean[c];
+  const bool centred = apply_pivot != nullptr && fabsf(m * sc) > kCentreAbove;
+  if (apply_pivot) apply_pivot[c] = centred ? m : 0.f;
+  shift[c] = centred ? bt : bt - m * sc;
   if (invstd) invstd[c] = is;
 }
 
-// ---- apply: y = x*scale + shift (+ residual) (ReLU) ---------------------------------------------------------------
+// ---- apply: y = (x - pivot)*scale + shift (+ residual) (ReLU); pivot = 0 except in the channels kCentreAbove names ----------
 // ReLU keep-bits: bit (i*VEC + e) of the mask says whether element e of vector i was positive after the ReLU.  The backward
 // kernels read the mask (1 bit per element) instead of re-reading y (32 bits per element).
 template <int VEC>
@@ -265,8 +280,8 @@ __device__ __forceinline__ unsigned keep_bits(const unsigned* __restrict__ mask,
 }
 
 template <int VEC>
-__global__ __launch_bounds__(kBlock) void bn_apply_kernel(const float* __restrict__ x, const float* __restrict__ scale,
-                                                           const float* __restrict__ shift,
+__global__ __launch_bounds__(kBlock) void bn_apply_kernel(const float* __restrict__ x, const float* __restrict__ pivot,
+                                                           const float* __restrict__ scale, const float* __restrict__ shift,
                                                            const float* __restrict__ residual, float* __restrict__ y,
                                                            long total_v, int CG, int relu, unsigned* __restrict__ mask) {
   typedef typename VecT<VEC>::type V;
@@ -276,6 +291,7 @@ __global__ __launch_bounds__(kBlock) void bn_apply_kernel(const float* __restric
   const int g = (int)((unsigned long)i0 % (unsigned)CG);
   const V sc = reinterpret_cast<const V*>(scale)[g];
   const V sh = reinterpret_cast<const V*>(shift)[g];
+  const V pv = reinterpret_cast<const V*>(pivot)[g];
   for (long base = i0 - lane; base < total_v; base += stride) {      // wave-uniform trip count (the mask is packed by shuffles)
     const long i = base + lane;
     const bool ok = i < total_v;
@@ -286,10 +302,10 @@ __global__ __launch_bounds__(kBlock) void bn_apply_kernel(const float* __restric
       if (residual) {
         const V rv = reinterpret_cast<const V*>(residual)[i];
 #pragma unroll
-        for (int e = 0; e < VEC; ++e) vset<VEC>(out, e, vget<VEC>(xv, e) * vget<VEC>(sc, e) + vget<VEC>(sh, e) + vget<VEC>(rv, e));
+        for (int e = 0; e < VEC; ++e) vset<VEC>(out, e, (vget<VEC>(xv, e) - vget<VEC>(pv, e)) * vget<VEC>(sc, e) + vget<VEC>(sh, e) + vget<VEC>(rv, e));
       } else {
 #pragma unroll
-        for (int e = 0; e < VEC; ++e) vset<VEC>(out, e, vget<VEC>(xv, e) * vget<VEC>(sc, e) + vget<VEC>(sh, e));
+        for (int e = 0; e < VEC; ++e) vset<VEC>(out, e, (vget<VEC>(xv, e) - vget<VEC>(pv, e)) * vget<VEC>(sc, e) + vget<VEC>(sh, e));
       }
       if (relu) {
 #pragma unroll
@@ -517,7 +533,7 @@ int ew_grid(long total_v, long CG) {
 
 }  // namespace
 
-// workspace layout (floats): [partials: kMaxRowBlocks*C*2][scale C][shift C][coef 3C]
+// workspace layout (floats): [partials: kMaxRowBlocks*C*2][scale C][shift C][coef 3C (backward); its first C: the forward's apply pivot]
 extern "C" size_t nnl_bn_workspace_bytes(int64_t rows, int64_t C) {
   if (rows <= 0 || C <= 0) return 0;
   return (size_t)((long)kMaxRowBlocks * C * 2 + 5 * C) * sizeof(float);
@@ -537,6 +553,7 @@ extern "C" int nnl_bn_fwd(const float* x, const float* gamma, const float* beta,
   float* part = (float*)workspace;
   float* scale = part + (long)kMaxRowBlocks * C * 2;
   float* shift = scale + C;
+  float* apv = shift + C;                          // bn_apply's per-channel pivot: in the backward's coefficient area, free until then
   const int VEC = (C % 4 == 0) ? 4 : 1;
   const long CG = C / VEC;
   NnlProfScope prof(NNL_PROF_ELEMENTWISE, s, (double)rows * C * (training ? 12.0 : 8.0) + (residual ? 4.0 * rows * C : 0.0));
@@ -545,11 +562,11 @@ extern "C" int nnl_bn_fwd(const float* x, const float* gamma, const float* beta,
     if (ext_rows >= 1024)      // one partial per 64-row tile of the convolution: thousands on the early stages
       hipLaunchKernelGGL(bn_finalize_kernel<256>, dim3((unsigned)C), dim3(256), 0, s, ext_pivot, ext_partials, (int)ext_rows, gamma, beta,
                          save_mean, save_invstd, running_mean, running_var, scale, shift, (long)rows, (int)C, eps, momentum,
-                         (long long*)num_batches_tracked, pivot_out);
+                         (long long*)num_batches_tracked, pivot_out, apv);
     else
       hipLaunchKernelGGL(bn_finalize_kernel<kFinLanes>, dim3((unsigned)nnl_cdiv(C, 4)), dim3(256), 0, s, ext_pivot, ext_partials,
                          (int)ext_rows, gamma, beta, save_mean, save_invstd, running_mean, running_var, scale, shift, (long)rows,
-                         (int)C, eps, momentum, (long long*)num_batches_tracked, pivot_out);
+                         (int)C, eps, momentum, (long long*)num_batches_tracked, pivot_out, apv);
     NNL_CHECK_LAUNCH();
   } else if (training) {
     const Shape sh = make_shape(rows, CG);
@@ -560,20 +577,20 @@ extern "C" int nnl_bn_fwd(const float* x, const float* gamma, const float* beta,
     NNL_CHECK_LAUNCH();
     hipLaunchKernelGGL(bn_finalize_kernel<kFinLanes>, dim3((unsigned)nnl_cdiv(C, 4)), dim3(256), 0, s, x, part, sh.gx, gamma, beta,
                        save_mean, save_invstd, running_mean, running_var, scale, shift, (long)rows, (int)C, eps, momentum,
-                       (long long*)num_batches_tracked, pivot_out);
+                       (long long*)num_batches_tracked, pivot_out, apv);
     NNL_CHECK_LAUNCH();
   } else {
     NNL_CHECK_HIP(hipMemcpyAsync(save_mean, running_mean, sizeof(float) * C, hipMemcpyDeviceToDevice, s));
     hipLaunchKernelGGL(bn_eval_scale_kernel, dim3((unsigned)nnl_cdiv(C, 256)), dim3(256), 0, s, gamma, beta, running_mean,
-                       running_var, scale, shift, save_invstd, (int)C, eps);
+                       running_var, scale, shift, save_invstd, (int)C, eps, apv);
     NNL_CHECK_LAUNCH();
   }
   const long total_v = rows * CG;
   if (VEC == 4)
-    hipLaunchKernelGGL(bn_apply_kernel<4>, dim3(ew_grid(total_v, CG)), dim3(kBlock), 0, s, x, scale, shift, residual, y, total_v,
+    hipLaunchKernelGGL(bn_apply_kernel<4>, dim3(ew_grid(total_v, CG)), dim3(kBlock), 0, s, x, apv, scale, shift, residual, y, total_v,
                        (int)CG, relu, relu ? relu_mask : nullptr);
   else
-    hipLaunchKernelGGL(bn_apply_kernel<1>, dim3(ew_grid(total_v, CG)), dim3(kBlock), 0, s, x, scale, shift, residual, y, total_v,
+    hipLaunchKernelGGL(bn_apply_kernel<1>, dim3(ew_grid(total_v, CG)), dim3(kBlock), 0, s, x, apv, scale, shift, residual, y, total_v,
                        (int)CG, relu, relu ? relu_mask : nullptr);
   NNL_CHECK_LAUNCH();
   return NNL_OK;
@@ -860,12 +877,12 @@ extern "C" int nnl_bn_relu_maxpool_fwd(const float* x, const float* gamma, const
     NNL_CHECK_LAUNCH();
     hipLaunchKernelGGL(bn_finalize_kernel<kFinLanes>, dim3((unsigned)nnl_cdiv(C, 4)), dim3(256), 0, s, x, part, sh.gx, gamma, beta,
                        save_mean, save_invstd, running_mean, running_var, scale, shift, rows, (int)C, eps, momentum,
-                       (long long*)num_batches_tracked, (float*)nullptr);
+                       (long long*)num_batches_tracked, (float*)nullptr, (float*)nullptr);
     NNL_CHECK_LAUNCH();
   } else {
     NNL_CHECK_HIP(hipMemcpyAsync(save_mean, running_mean, sizeof(float) * C, hipMemcpyDeviceToDevice, s));
     hipLaunchKernelGGL(bn_eval_scale_kernel, dim3((unsigned)nnl_cdiv(C, 256)), dim3(256), 0, s, gamma, beta, running_mean,
-                       running_var, scale, shift, save_invstd, (int)C, eps);
+                       running_var, scale, shift, save_invstd, (int)C, eps, (float*)nullptr);
     NNL_CHECK_LAUNCH();
   }
   const long total = (long)N * P * Q * CG;
@@ -956,18 +973,19 @@ extern "C" int nnl_bn_sync_fwd(const float* x, const float* all_stats, int world
   hipStream_t s = (hipStream_t)stream;
   float* scale = (float*)workspace + (long)kMaxRowBlocks * C * 2;
   float* shift = scale + C;
+  float* apv = shift + C;
   NnlProfScope prof(NNL_PROF_ELEMENTWISE, s, (double)rows * C * 8.0 + (residual ? 4.0 * rows * C : 0.0));
   hipLaunchKernelGGL(bn_sync_merge_kernel, dim3((unsigned)nnl_cdiv(C, 256)), dim3(256), 0, s, all_stats, world, gamma, beta,
                      save_mean, save_invstd, running_mean, running_var, scale, shift, (int)C, eps, momentum,
-                     (long long*)num_batches_tracked);
+                     (long long*)num_batches_tracked, apv);
   NNL_CHECK_LAUNCH();
   const int VEC = (C % 4 == 0) ? 4 : 1;
   const long CG = C / VEC, total_v = rows * CG;
   if (VEC == 4)
-    hipLaunchKernelGGL(bn_apply_kernel<4>, dim3(ew_grid(total_v, CG)), dim3(kBlock), 0, s, x, scale, shift, residual, y, total_v,
+    hipLaunchKernelGGL(bn_apply_kernel<4>, dim3(ew_grid(total_v, CG)), dim3(kBlock), 0, s, x, apv, scale, shift, residual, y, total_v,
                        (int)CG, relu, relu ? relu_mask : nullptr);
   else
-    hipLaunchKernelGGL(bn_apply_kernel<1>, dim3(ew_grid(total_v, CG)), dim3(kBlock), 0, s, x, scale, shift, residual, y, total_v,
+    hipLaunchKernelGGL(bn_apply_kernel<1>, dim3(ew_grid(total_v, CG)), dim3(kBlock), 0, s, x, apv, scale, shift, residual, y, total_v,
                        (int)CG, relu, relu ? relu_mask : nullptr);
   NNL_CHECK_LAUNCH();
   return NNL_OK;
@@ -1024,4 +1042,19 @@ extern "C" int nnl_bn_sync_bwd(const float* dy, const float* y, const uint32_t* 
                        (int)CG, (int)C, relu, relu_mask);
   NNL_CHECK_LAUNCH();
   return NNL_OK;
+}
+
+// ---- planner query (debug, host only: no HIP call) ---------------------------------------------------------------------
+extern "C" int nnl_debug_bn_plan(int64_t rows, int64_t C, int64_t N, int64_t H, int64_t W, int64_t P, int64_t Q, int32_t* out10) {
+  if (rows <= 0 || C <= 0 || C >= (1 << 24) || out10 == nullptr) return 0;
+  const int VEC = (C % 4 == 0) ? 4 : 1;
+  const long CG = C / VEC;
+  const Shape sh = make_shape(rows, CG);
+  out10[0] = VEC; out10[1] = sh.L; out10[2] = sh.rpb; out10[3] = sh.gx; out10[4] = sh.gy; out10[5] = sh.capped ? 1 : 0;
+  out10[6] = ew_grid(rows * CG, CG);
+  out10[7] = kMaxRowBlocks;
+  const bool stem = N > 0 && H > 0 && W > 0 && P > 0 && Q > 0 && bnpool_ok(C);
+  out10[8] = stem ? (int32_t)bnpool_grid((long)N * H * W * (C / 4)) : -1;
+  out10[9] = stem ? (int32_t)bnpool_grid((long)N * P * Q * (C / 4)) : -1;
+  return 1;
 }

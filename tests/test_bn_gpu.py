@@ -116,3 +116,84 @@ def test_conv_bn_act_epilogue_statistics(offset):
         for name, a, b in (('dx', xg.grad, xc.grad), ('dres', rg.grad, rc.grad), ('dw', conv.weight.grad, wc.grad),
                            ('dgamma', bn.weight.grad, ref_bn.weight.grad), ('dbeta', bn.bias.grad, ref_bn.bias.grad)):
             assert_close(a, b.float(), 2e-3, 2e-3 * b.abs().max().item(), tag + name)
+
+
+# ---- module modes that ops.bn_act accepts, against the torch module in fp64 -------------------------------------------------------------------
+def _module_pair(mk, C, g, **kw):
+    """the module under test (fp32, on the GPU) and its fp64 twin with the same parameters and buffers"""
+    ref = mk(C, **kw).double()
+    with torch.no_grad():
+        if ref.affine:
+            ref.weight.copy_(torch.randn(C, generator=g) * 0.3 + 1)
+            ref.bias.copy_(torch.randn(C, generator=g) * 0.3)
+        if ref.track_running_stats:
+            ref.running_mean.copy_(torch.randn(C, generator=g) * 0.1)
+            ref.running_var.copy_(torch.rand(C, generator=g) + 0.5)
+    bn = mk(C, **kw)
+    bn.load_state_dict(ref.state_dict())
+    return bn.to(DEV), ref
+
+
+def _module_step(bn, ref, x, dy, res, relu, tag):
+    from neuralnetworklibrary_amd import ops
+    for m in (bn, ref):
+        for p in m.parameters():
+            p.grad = None
+    xc = x.double().detach().requires_grad_(True)
+    rc = res.double().requires_grad_(True) if res is not None else None
+    yc = ref(xc)
+    yc = yc + rc if res is not None else yc
+    yc = torch.relu(yc) if relu else yc
+    yc.backward(dy.double())
+    xg = x.to(DEV).requires_grad_(True)
+    rg = res.to(DEV).requires_grad_(True) if res is not None else None
+    yg = ops.bn_act(bn, xg, residual=rg, relu=relu)
+    yg.backward(dy.to(DEV))
+    assert yg.shape == yc.shape
+    assert_close(yg, yc, 1e-4, 1e-5, tag + 'y')
+    assert_close(xg.grad, xc.grad, 1e-3, 1e-5 * xc.grad.abs().max().item() + 1e-7, tag + 'dx')
+    if res is not None:
+        assert_close(rg.grad, rc.grad, 1e-5, 1e-6, tag + 'dres')
+    if ref.affine:
+        assert_close(bn.weight.grad, ref.weight.grad, 1e-3, 1e-4 * ref.weight.grad.abs().max().item(), tag + 'dgamma')
+        assert_close(bn.bias.grad, ref.bias.grad, 1e-3, 1e-4 * ref.bias.grad.abs().max().item(), tag + 'dbeta')
+    else:
+        assert bn.weight is None and bn.bias is None
+    if ref.track_running_stats:
+        assert_close(bn.running_mean, ref.running_mean, 1e-5, 1e-5, tag + 'running_mean')
+        assert_close(bn.running_var, ref.running_var, 1e-4, 1e-6, tag + 'running_var')
+        assert int(bn.num_batches_tracked) == int(ref.num_batches_tracked), tag + 'num_batches_tracked'
+    else:
+        assert bn.running_mean is None and bn.running_var is None and bn.num_batches_tracked is None
+
+
+MODULE_MODES = [  # name, module, input shape, module arguments, training, residual, relu, steps, channels-last input
+    ('affine=False', nn.BatchNorm2d, (4, 12, 5, 7), dict(affine=False), True, True, True, 1, False),
+    ('affine=False,eval', nn.BatchNorm2d, (4, 12, 5, 7), dict(affine=False), False, False, True, 1, False),
+    ('track_running_stats=False,train', nn.BatchNorm2d, (3, 8, 6, 5), dict(track_running_stats=False), True, False, True, 1, False),
+    ('track_running_stats=False,eval', nn.BatchNorm2d, (3, 8, 6, 5), dict(track_running_stats=False), False, True, False, 1, False),
+    ('momentum=None', nn.BatchNorm2d, (4, 16, 3, 5), dict(momentum=None), True, False, True, 3, False),
+    ('momentum=None,1d', nn.BatchNorm1d, (9, 6), dict(momentum=None), True, False, False, 3, False),
+    ('[N,C,L]', nn.BatchNorm1d, (5, 12, 7), dict(), True, True, True, 1, False),
+    ('[N,C,L],odd C,eval', nn.BatchNorm1d, (5, 7, 3), dict(), False, False, True, 1, False),
+    ('C=14,relu,residual', nn.BatchNorm1d, (64, 14), dict(), True, True, True, 1, False),
+    ('C=14,relu,residual,2d', nn.BatchNorm2d, (3, 14, 5, 3), dict(), True, True, True, 1, False),
+    ('channels-last', nn.BatchNorm2d, (4, 16, 7, 5), dict(), True, True, True, 1, True),
+    ('channels-last,eval', nn.BatchNorm2d, (4, 16, 7, 5), dict(), False, False, True, 1, True),
+]
+
+
+@pytest.mark.parametrize('mode', MODULE_MODES, ids=[m[0] for m in MODULE_MODES])
+def test_bn_act_module_modes(mode):
+    name, mk, shape, kw, training, has_res, relu, steps, channels_last = mode
+    g = torch.Generator().manual_seed(sum(shape))
+    bn, ref = _module_pair(mk, shape[1], g, **kw)
+    bn.train(training); ref.train(training)
+    for step in range(steps):
+        x = torch.randn(shape, generator=g) * 1.7 + 0.5 * (step + 1)
+        res = torch.randn(shape, generator=g) if has_res else None
+        dy = torch.randn(shape, generator=g)
+        if channels_last:
+            x, dy = x.contiguous(memory_format=torch.channels_last), dy.contiguous(memory_format=torch.channels_last)
+            res = res.contiguous(memory_format=torch.channels_last) if has_res else None
+        _module_step(bn, ref, x, dy, res, relu, '%s step %d ' % (name, step))
