@@ -271,7 +271,9 @@ int nnl_bn_relu_maxpool_fwd(const float* x, const float* gamma, const float* bet
 /* dx [N,H,W,C], dgamma, dbeta from the pooled gradient dpool [N,P,Q,C]: every input pixel gathers dpool over the windows whose
  * arg-max it is (no atomics: reproducible), gated by the recomputed ReLU, then the two BatchNorm backward passes.  y (optional: the
  * forward's pooled output) lets the reduction pass run over the pooled outputs alone (xhat at an arg-max = (y - beta) / gamma):
- * it then reads neither x nor the windows. */
+ * it then reads neither x nor the windows.  The geometry is checked as in the forward: the call is refused (-1, nothing launched)
+ * unless ks*ks <= 255, 2*pad <= ks, P == (H + 2*pad - ks)/stride + 1 and Q likewise (idx and dpool are indexed by P and Q as
+ * stated), C passes nnl_bn_relu_maxpool_supported and N*H*W*C < 2^33. */
 int nnl_bn_relu_maxpool_bwd(const float* dpool, const float* y, const uint8_t* idx, const float* x, const float* gamma,
                             const float* beta, const float* mean, const float* invstd, const float* scale, const float* shift,
                             float* dx, float* dgamma, float* dbeta,

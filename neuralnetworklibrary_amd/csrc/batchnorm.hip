@@ -7,6 +7,9 @@
 // Statistics use the shifted-data form: S1 = sum(x - K), S2 = sum((x - K)^2) with the pivot K = x[0][c], so
 // var = (S2 - S1^2/n)/n has no catastrophic cancellation when |mean| >> std.  Per-block partial sums are combined
 // in a fixed order by a second tiny kernel => bitwise reproducible run to run.
+//
+// Host side: every entry point is argument checks, bind_workspace and a sequence of launch_* calls; each launch_* holds its kernel's
+// only VEC dispatch and plans its own grid.
 #include "nnl_common.h"
 
 namespace {
@@ -56,50 +59,13 @@ Shape make_shape(long rows, long CG) {
   return s;
 }
 
-// ---- pass 1 of training forward: partial (S1, S2) per block ------------------------------------------------
+// Epilogue of the two row reductions (bn_stats_kernel, bn_bwd_reduce_kernel): the block's rpb = kBlock / L thread rows meet in LDS,
+// thread row 0 adds them in row order and writes the block's pair of sums per channel to part[blockIdx.x][c][2].
 template <int VEC>
-__global__ __launch_bounds__(kBlock) void bn_stats_kernel(const float* __restrict__ x, float* __restrict__ part,
-                                                           long rows, int C, int L) {
-  typedef typename VecT<VEC>::type V;
+__device__ __forceinline__ void store_block_partials(const float (&s1)[VEC], const float (&s2)[VEC], float* __restrict__ part, int C,
+                                                     int L, int tx, int ty, int g, bool ok) {
   __shared__ float red[kBlock * 2 * VEC];
-  const int CG = C / VEC;
-  const int tx = threadIdx.x & (L - 1), ty = threadIdx.x / L;
   const int rpb = kBlock / L;
-  const int g = blockIdx.y * L + tx;
-  const bool ok = g < CG;
-  float s1[VEC], s2[VEC], piv[VEC];
-#pragma unroll
-  for (int e = 0; e < VEC; ++e) { s1[e] = 0.f; s2[e] = 0.f; piv[e] = 0.f; }
-  if (ok) {
-    const V pv = *reinterpret_cast<const V*>(x + (long)g * VEC);
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) piv[e] = vget<VEC>(pv, e);
-    const long rstep = (long)gridDim.x * rpb;
-    long r = (long)blockIdx.x * rpb + ty;
-    const float* xp = x + (long)g * VEC;
-    for (; r + 3 * rstep < rows; r += 4 * rstep) {          // 4 independent 16-B loads in flight per lane
-      V v[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const V*>(xp + (r + u * rstep) * C);
-#pragma unroll
-      for (int u = 0; u < 4; ++u)
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) {
-          const float d = vget<VEC>(v[u], e) - piv[e];
-          s1[e] += d;
-          s2[e] += d * d;
-        }
-    }
-    for (; r < rows; r += rstep) {
-      const V v = *reinterpret_cast<const V*>(xp + r * C);
-#pragma unroll
-      for (int e = 0; e < VEC; ++e) {
-        const float d = vget<VEC>(v, e) - piv[e];
-        s1[e] += d;
-        s2[e] += d * d;
-      }
-    }
-  }
 #pragma unroll
   for (int e = 0; e < VEC; ++e) {
     red[(threadIdx.x * VEC + e) * 2 + 0] = s1[e];
@@ -121,14 +87,59 @@ __global__ __launch_bounds__(kBlock) void bn_stats_kernel(const float* __restric
   }
 }
 
-// Sum the per-block partials of channel c: 64 lanes each add a strided subset (fixed order), then a fixed-order
-// tree over the lanes in LDS.  Block = 256 threads = 4 channels x 64 lanes.  Returns the sums to lane 0.
+// ---- pass 1 of training forward: partial (S1, S2) per block ------------------------------------------------
+template <int VEC>
+__device__ __forceinline__ void stats_accumulate(const typename VecT<VEC>::type& v, const float (&piv)[VEC], float (&s1)[VEC],
+                                                 float (&s2)[VEC]) {
+#pragma unroll
+  for (int e = 0; e < VEC; ++e) {
+    const float d = vget<VEC>(v, e) - piv[e];
+    s1[e] += d;
+    s2[e] += d * d;
+  }
+}
+
+template <int VEC>
+__global__ __launch_bounds__(kBlock) void bn_stats_kernel(const float* __restrict__ x, float* __restrict__ part,
+                                                           long rows, int C, int L) {
+  typedef typename VecT<VEC>::type V;
+  const int CG = C / VEC;
+  const int tx = threadIdx.x & (L - 1), ty = threadIdx.x / L;
+  const int rpb = kBlock / L;
+  const int g = blockIdx.y * L + tx;
+  const bool ok = g < CG;
+  float s1[VEC], s2[VEC], piv[VEC];
+#pragma unroll
+  for (int e = 0; e < VEC; ++e) { s1[e] = 0.f; s2[e] = 0.f; piv[e] = 0.f; }
+  if (ok) {
+    const V pv = *reinterpret_cast<const V*>(x + (long)g * VEC);
+#pragma unroll
+    for (int e = 0; e < VEC; ++e) piv[e] = vget<VEC>(pv, e);
+    const long rstep = (long)gridDim.x * rpb;
+    long r = (long)blockIdx.x * rpb + ty;
+    const float* xp = x + (long)g * VEC;
+    for (; r + 3 * rstep < rows; r += 4 * rstep) {          // 4 independent 16-B loads in flight per lane
+      V v[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) v[u] = *reinterpret_cast<const V*>(xp + (r + u * rstep) * C);
+#pragma unroll
+      for (int u = 0; u < 4; ++u) stats_accumulate<VEC>(v[u], piv, s1, s2);
+    }
+    for (; r < rows; r += rstep) stats_accumulate<VEC>(*reinterpret_cast<const V*>(xp + r * C), piv, s1, s2);
+  }
+  store_block_partials<VEC>(s1, s2, part, C, L, tx, ty, g, ok);
+}
+
+// Opening of the finalize-type kernels.  Sums the per-block partials of channel c = the block's first channel + threadIdx.x / LANES:
+// LANES lanes each add a strided subset (fixed order), then a fixed-order tree over the lanes in LDS.  Block = 256 threads =
+// 256 / LANES channels x LANES lanes.  Every thread of the channel gets the sums; true for the one that finishes it (lane 0, c < C).
 template <int LANES = kFinLanes>
-__device__ __forceinline__ void reduce_partials(const float* __restrict__ part, int nparts, int C, int c, bool cok,
-                                                float (*red)[LANES][2], float& s1, float& s2) {
+__device__ __forceinline__ bool reduce_partials(const float* __restrict__ part, int nparts, int C, int& c, float& s1, float& s2) {
+  __shared__ float red[256 / LANES][LANES][2];
   const int lane = threadIdx.x & (LANES - 1), ch = threadIdx.x / LANES;
+  c = blockIdx.x * (256 / LANES) + ch;
   float a = 0.f, b = 0.f;
-  if (cok) {
+  if (c < C) {
     typedef float f32x2 __attribute__((ext_vector_type(2)));
     const f32x2* pp = reinterpret_cast<const f32x2*>(part) + c;          // (S1, S2) pairs, stride C
     int p = lane;
@@ -157,9 +168,22 @@ __device__ __forceinline__ void reduce_partials(const float* __restrict__ part, 
   }
   s1 = red[ch][0][0];
   s2 = red[ch][0][1];
+  return c < C && lane == 0;
 }
 
-// tail shared by the finalize kernels: invstd, running statistics (unbiased variance), per-channel scale & shift
+// bn_apply's per-channel affine y = (x - pivot)*scale + shift from the statistics: the pivot is the mean in the channels kCentreAbove
+// names and 0 elsewhere; without apply_pivot (the stem's x*scale + shift) no channel is centred
+__device__ __forceinline__ void store_affine(int c, float m, float is, const float* __restrict__ gamma, const float* __restrict__ beta,
+                                             float* __restrict__ scale, float* __restrict__ shift, float* __restrict__ apply_pivot) {
+  const float sc = is * (gamma ? gamma[c] : 1.f);
+  scale[c] = sc;
+  const float bt = beta ? beta[c] : 0.f;
+  const bool centred = apply_pivot != nullptr && fabsf(m * sc) > kCentreAbove;
+  if (apply_pivot) apply_pivot[c] = centred ? m : 0.f;
+  shift[c] = centred ? bt : bt - m * sc;
+}
+
+// tail shared by the finalize kernels: invstd, running statistics (unbiased variance), per-channel affine
 __device__ __forceinline__ void finish_stats(int c, int C, float m, float var, float n, const float* __restrict__ gamma,
                                              const float* __restrict__ beta, float* __restrict__ mean,
                                              float* __restrict__ invstd, float* __restrict__ running_mean,
@@ -176,13 +200,7 @@ __device__ __forceinline__ void finish_stats(int c, int C, float m, float var, f
     const float unbiased = n > 1.f ? var * (n / (n - 1.f)) : var;
     running_var[c] = (1.f - momentum) * running_var[c] + momentum * unbiased;
   }
-  const float gm = gamma ? gamma[c] : 1.f;
-  const float sc = is * gm;
-  scale[c] = sc;
-  const float bt = beta ? beta[c] : 0.f;
-  const bool centred = apply_pivot != nullptr && fabsf(m * sc) > kCentreAbove;
-  if (apply_pivot) apply_pivot[c] = centred ? m : 0.f;
-  shift[c] = centred ? bt : bt - m * sc;
+  store_affine(c, m, is, gamma, beta, scale, shift, apply_pivot);
 }
 
 // ---- finalize: mean / invstd, running statistics, per-channel scale & shift ----------------------------------
@@ -194,11 +212,9 @@ __global__ void bn_finalize_kernel(const float* __restrict__ x, const float* __r
                                    float* __restrict__ scale, float* __restrict__ shift, long rows, int C, float eps,
                                    float momentum, long long* __restrict__ num_batches_tracked,
                                    float* __restrict__ pivot_out, float* __restrict__ apply_pivot) {
-  __shared__ float red[256 / LANES][LANES][2];
-  const int c = blockIdx.x * (256 / LANES) + threadIdx.x / LANES;
+  int c;
   float s1, s2;
-  reduce_partials<LANES>(part, nparts, C, c, c < C, red, s1, s2);
-  if (c >= C || (threadIdx.x & (LANES - 1)) != 0) return;
+  if (!reduce_partials<LANES>(part, nparts, C, c, s1, s2)) return;
   if (c == 0 && num_batches_tracked) *num_batches_tracked += 1;     // nn.BatchNorm's counter, without its own launch
   const float n = (float)rows;
   const float m = x[c] + s1 / n;
@@ -212,11 +228,9 @@ __global__ void bn_finalize_kernel(const float* __restrict__ x, const float* __r
 // count split as hi*65536 + lo (both exact in fp32).  One all_gather of 2C+2 floats per BN layer.
 __global__ void bn_sync_local_kernel(const float* __restrict__ x, const float* __restrict__ part, int nparts,
                                      float* __restrict__ stats, long rows, int C) {
-  __shared__ float red[4][kFinLanes][2];
-  const int c = blockIdx.x * 4 + threadIdx.x / kFinLanes;
+  int c;
   float s1, s2;
-  reduce_partials(part, nparts, C, c, c < C, red, s1, s2);
-  if (c >= C || (threadIdx.x & (kFinLanes - 1)) != 0) return;
+  if (!reduce_partials(part, nparts, C, c, s1, s2)) return;
   const float n = (float)rows;
   stats[c] = x[c] + s1 / n;
   stats[C + c] = fmaxf(s2 - s1 * (s1 / n), 0.f);
@@ -261,12 +275,7 @@ __global__ void bn_eval_scale_kernel(const float* __restrict__ gamma, const floa
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= C) return;
   const float is = 1.f / sqrtf(running_var[c] + eps);
-  const float sc = is * (gamma ? gamma[c] : 1.f);
-  scale[c] = sc;
-  const float bt = beta ? beta[c] : 0.f, m = running_mean[c];
-  const bool centred = apply_pivot != nullptr && fabsf(m * sc) > kCentreAbove;
-  if (apply_pivot) apply_pivot[c] = centred ? m : 0.f;
-  shift[c] = centred ? bt : bt - m * sc;
+  store_affine(c, running_mean[c], is, gamma, beta, scale, shift, apply_pivot);
   if (invstd) invstd[c] = is;
 }
 
@@ -333,6 +342,20 @@ __global__ __launch_bounds__(kBlock) void bn_apply_kernel(const float* __restric
 }
 
 // ---- backward pass 1: partial (sum g, sum g*xhat) per block, g = dy * [y > 0] ---------------------------------------
+// one row's contribution to (sum g, sum g*xhat); g = dy gated by the keep bits kb (by_mask) or by y > 0
+template <int VEC>
+__device__ __forceinline__ void bwd_accumulate(typename VecT<VEC>::type gv, const typename VecT<VEC>::type& xv, int relu, bool by_mask,
+                                               unsigned kb, const typename VecT<VEC>::type& yv, const float (&mu)[VEC],
+                                               const float (&is)[VEC], float (&s1)[VEC], float (&s2)[VEC]) {
+#pragma unroll
+  for (int e = 0; e < VEC; ++e) {
+    float gg = vget<VEC>(gv, e);
+    if (relu && (by_mask ? !((kb >> e) & 1u) : !(vget<VEC>(yv, e) > 0.f))) gg = 0.f;
+    s1[e] += gg;
+    s2[e] += gg * ((vget<VEC>(xv, e) - mu[e]) * is[e]);
+  }
+}
+
 template <int VEC>
 __global__ __launch_bounds__(kBlock) void bn_bwd_reduce_kernel(const float* __restrict__ dy, const float* __restrict__ y,
                                                                 const float* __restrict__ x, const float* __restrict__ mean,
@@ -340,7 +363,6 @@ __global__ __launch_bounds__(kBlock) void bn_bwd_reduce_kernel(const float* __re
                                                                 long rows, int C, int L, int relu,
                                                                 const unsigned* __restrict__ mask) {
   typedef typename VecT<VEC>::type V;
-  __shared__ float red[kBlock * 2 * VEC];
   const int CG = C / VEC;
   const int tx = threadIdx.x & (L - 1), ty = threadIdx.x / L;
   const int rpb = kBlock / L;
@@ -369,14 +391,7 @@ __global__ __launch_bounds__(kBlock) void bn_bwd_reduce_kernel(const float* __re
         }
       }
 #pragma unroll
-      for (int u = 0; u < 2; ++u)
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) {
-          float gg = vget<VEC>(dv[u], e);
-          if (relu && (mask ? !((kb[u] >> e) & 1u) : !(vget<VEC>(yv[u], e) > 0.f))) gg = 0.f;
-          s1[e] += gg;
-          s2[e] += gg * ((vget<VEC>(xv[u], e) - mu[e]) * is[e]);
-        }
+      for (int u = 0; u < 2; ++u) bwd_accumulate<VEC>(dv[u], xv[u], relu, mask != nullptr, kb[u], yv[u], mu, is, s1, s2);
     }
     for (; r < rows; r += rstep) {
       const long off = r * C + (long)g * VEC;
@@ -388,34 +403,19 @@ __global__ __launch_bounds__(kBlock) void bn_bwd_reduce_kernel(const float* __re
         if (mask) kb = keep_bits<VEC>(mask, off / VEC);
         else yv = *reinterpret_cast<const V*>(y + off);
       }
-#pragma unroll
-      for (int e = 0; e < VEC; ++e) {
-        float gg = vget<VEC>(dv, e);
-        if (relu && (mask ? !((kb >> e) & 1u) : !(vget<VEC>(yv, e) > 0.f))) gg = 0.f;
-        s1[e] += gg;
-        s2[e] += gg * ((vget<VEC>(xv, e) - mu[e]) * is[e]);
-      }
+      bwd_accumulate<VEC>(dv, xv, relu, mask != nullptr, kb, yv, mu, is, s1, s2);
     }
   }
-#pragma unroll
-  for (int e = 0; e < VEC; ++e) {
-    red[(threadIdx.x * VEC + e) * 2 + 0] = s1[e];
-    red[(threadIdx.x * VEC + e) * 2 + 1] = s2[e];
-  }
-  __syncthreads();
-  if (ty == 0 && ok) {
-#pragma unroll
-    for (int e = 0; e < VEC; ++e) {
-      float a = 0.f, b = 0.f;
-      for (int j = 0; j < rpb; ++j) {
-        a += red[((j * L + tx) * VEC + e) * 2 + 0];
-        b += red[((j * L + tx) * VEC + e) * 2 + 1];
-      }
-      const long c = (long)g * VEC + e;
-      part[((long)blockIdx.x * C + c) * 2 + 0] = a;
-      part[((long)blockIdx.x * C + c) * 2 + 1] = b;
-    }
-  }
+  store_block_partials<VEC>(s1, s2, part, C, L, tx, ty, g, ok);
+}
+
+// the per-channel coefficients of dx = a*g + bq*x + c0, from dx = a * (g - s1/n - xhat*s2/n) with xhat = (x - mu)*is, a = gamma*is
+__device__ __forceinline__ void store_bwd_coef(float* __restrict__ coef, int c, int C, float a, float is, float mu, float s1, float s2,
+                                               float n) {
+  const float bq = -a * is * (s2 / n);
+  coef[c] = a;
+  coef[C + c] = bq;
+  coef[2 * C + c] = -a * (s1 / n) - bq * mu;
 }
 
 // finalize backward: dbeta, dgamma and the three per-channel coefficients of dx = a*g + b*x + c0
@@ -423,23 +423,16 @@ __global__ void bn_bwd_finalize_kernel(const float* __restrict__ part, int npart
                                        const float* __restrict__ mean, const float* __restrict__ invstd,
                                        float* __restrict__ dgamma, float* __restrict__ dbeta, float* __restrict__ coef,
                                        long rows, int C, int training) {
-  __shared__ float red[4][kFinLanes][2];
-  const int c = blockIdx.x * 4 + threadIdx.x / kFinLanes;
+  int c;
   float s1, s2;
-  reduce_partials(part, nparts, C, c, c < C, red, s1, s2);
-  if (c >= C || (threadIdx.x & (kFinLanes - 1)) != 0) return;
+  if (!reduce_partials(part, nparts, C, c, s1, s2)) return;
   if (dbeta) dbeta[c] = s1;
   if (dgamma) dgamma[c] = s2;
   const float gm = gamma ? gamma[c] : 1.f;
   const float is = invstd[c], mu = mean[c];
   const float a = gm * is;
   if (training) {
-    // dx = a * (g - s1/n - xhat*s2/n),  xhat = (x - mu)*is   =>  dx = a*g + bq*x + c0
-    const float n = (float)rows;
-    const float bq = -a * is * (s2 / n);
-    coef[c] = a;
-    coef[C + c] = bq;
-    coef[2 * C + c] = -a * (s1 / n) - bq * mu;
+    store_bwd_coef(coef, c, C, a, is, mu, s1, s2, (float)rows);
   } else {
     coef[c] = a;
     coef[C + c] = 0.f;
@@ -450,11 +443,9 @@ __global__ void bn_bwd_finalize_kernel(const float* __restrict__ part, int npart
 // SyncBN backward: (a) this rank's (sum g, sum g*xhat) -> sums[2C] (all-reduced by the host), (b) coefficients from the
 // GLOBAL sums and row count; dgamma / dbeta stay LOCAL sums (the gradient all-reduce averages them like every parameter)
 __global__ void bn_sync_bwd_sums_kernel(const float* __restrict__ part, int nparts, float* __restrict__ sums, int C) {
-  __shared__ float red[4][kFinLanes][2];
-  const int c = blockIdx.x * 4 + threadIdx.x / kFinLanes;
+  int c;
   float s1, s2;
-  reduce_partials(part, nparts, C, c, c < C, red, s1, s2);
-  if (c >= C || (threadIdx.x & (kFinLanes - 1)) != 0) return;
+  if (!reduce_partials(part, nparts, C, c, s1, s2)) return;
   sums[c] = s1;
   sums[C + c] = s2;
 }
@@ -469,13 +460,8 @@ __global__ void bn_sync_bwd_coef_kernel(const float* __restrict__ local_sums, co
   for (int r = 0; r < world; ++r) n += sync_count(all_stats + r * (2L * C + 2), C);
   if (dbeta) dbeta[c] = local_sums[c];
   if (dgamma) dgamma[c] = local_sums[C + c];
-  const float s1 = global_sums[c], s2 = global_sums[C + c];
-  const float is = invstd[c], mu = mean[c];
-  const float a = (gamma ? gamma[c] : 1.f) * is;
-  const float bq = -a * is * (s2 / n);
-  coef[c] = a;
-  coef[C + c] = bq;
-  coef[2 * C + c] = -a * (s1 / n) - bq * mu;
+  const float is = invstd[c];
+  store_bwd_coef(coef, c, C, (gamma ? gamma[c] : 1.f) * is, is, mean[c], global_sums[c], global_sums[C + c], n);
 }
 
 // ---- backward pass 2: dx = a*g + b*x + c0 ; dres = g -----------------------------------------------------------------
@@ -533,11 +519,127 @@ int ew_grid(long total_v, long CG) {
 
 }  // namespace
 
-// workspace layout (floats): [partials: kMaxRowBlocks*C*2][scale C][shift C][coef 3C (backward); its first C: the forward's apply pivot]
+// ---- host side: workspace, one launcher per kernel family, entry points ---------------------------------------------------------------
 extern "C" size_t nnl_bn_workspace_bytes(int64_t rows, int64_t C) {
   if (rows <= 0 || C <= 0) return 0;
-  return (size_t)((long)kMaxRowBlocks * C * 2 + 5 * C) * sizeof(float);
+  return (size_t)((long)kMaxRowBlocks * C * 2 + 5 * C) * sizeof(float);       // 5 C = scale + shift + coef 3C: bind_workspace below
 }
+
+namespace {
+
+// The workspace, in floats: [part: kMaxRowBlocks*C*2 per-block partials][scale C][shift C][coef 3C].  coef holds the backward's
+// a / bq / c0; until the backward runs its first C floats are free, and the forward keeps bn_apply's per-channel pivot there.
+struct Workspace { float *part, *scale, *shift, *coef, *apply_pivot; };
+
+int bind_workspace(void* workspace, size_t workspace_bytes, long rows, long C, const char* who, Workspace& ws) {
+  if (workspace == nullptr || workspace_bytes < nnl_bn_workspace_bytes(rows, C))
+    return nnl_set_error(NNL_ERR_WORKSPACE, "%s: workspace too small", who);
+  ws.part = (float*)workspace;
+  ws.scale = ws.part + (long)kMaxRowBlocks * C * 2;
+  ws.shift = ws.scale + C;
+  ws.coef = ws.apply_pivot = ws.shift + C;
+  return NNL_OK;
+}
+
+// what the forward's finalize-type kernels read and write per channel, as the entry point received it
+struct ChannelStats {
+  const float *gamma, *beta;
+  float *save_mean, *save_invstd, *running_mean, *running_var;
+  float *scale, *shift, *apply_pivot;        // the affine bn_apply evaluates; apply_pivot == nullptr: x*scale + shift in every channel
+  float* pivot_out;
+  int64_t* num_batches_tracked;
+  float eps, momentum;
+};
+
+#define NNL_TRY(call)               \
+  do {                              \
+    const int rc_ = (call);         \
+    if (rc_ != NNL_OK) return rc_;  \
+  } while (0)
+
+int vec_of(long C) { return C % 4 == 0 ? 4 : 1; }          // floats per access
+
+// Each launcher holds the only VEC dispatch of its kernel and plans its own grid.  The two row reductions report their number of
+// row blocks = partials per channel, which the finalize that follows needs.
+int launch_stats(const float* x, float* part, long rows, long C, hipStream_t s, int& nparts) {
+  const int VEC = vec_of(C);
+  const Shape sh = make_shape(rows, C / VEC);
+  const auto kernel = VEC == 4 ? bn_stats_kernel<4> : bn_stats_kernel<1>;
+  hipLaunchKernelGGL(kernel, dim3(sh.gx, sh.gy), dim3(kBlock), 0, s, x, part, rows, (int)C, sh.L);
+  NNL_CHECK_LAUNCH();
+  nparts = sh.gx;
+  return NNL_OK;
+}
+
+// from_conv: the partials are the producing convolution's, one per 64-row tile, around its pivot (from 1024 of them one block of 256
+// lanes per channel); else bn_stats_kernel's <= kMaxRowBlocks around x's first row
+int launch_finalize(const float* pivot, const float* part, int nparts, bool from_conv, const ChannelStats& cs, long rows, long C,
+                    hipStream_t s) {
+  const bool wide = from_conv && nparts >= 1024;
+  const auto kernel = wide ? bn_finalize_kernel<256> : bn_finalize_kernel<kFinLanes>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)(wide ? C : nnl_cdiv(C, 4))), dim3(256), 0, s, pivot, part, nparts, cs.gamma, cs.beta,
+                     cs.save_mean, cs.save_invstd, cs.running_mean, cs.running_var, cs.scale, cs.shift, rows, (int)C, cs.eps, cs.momentum,
+                     (long long*)cs.num_batches_tracked, cs.pivot_out, cs.apply_pivot);
+  NNL_CHECK_LAUNCH();
+  return NNL_OK;
+}
+
+// the forward's statistics and per-channel affine from x alone: training = statistics pass + finalize, eval = the running statistics
+int launch_channel_affine(const float* x, float* part, const ChannelStats& cs, long rows, long C, int training, hipStream_t s) {
+  if (training) {
+    int nparts;
+    NNL_TRY(launch_stats(x, part, rows, C, s, nparts));
+    return launch_finalize(x, part, nparts, false, cs, rows, C, s);
+  }
+  NNL_CHECK_HIP(hipMemcpyAsync(cs.save_mean, cs.running_mean, sizeof(float) * C, hipMemcpyDeviceToDevice, s));
+  hipLaunchKernelGGL(bn_eval_scale_kernel, dim3((unsigned)nnl_cdiv(C, 256)), dim3(256), 0, s, cs.gamma, cs.beta, cs.running_mean,
+                     cs.running_var, cs.scale, cs.shift, cs.save_invstd, (int)C, cs.eps, cs.apply_pivot);
+  NNL_CHECK_LAUNCH();
+  return NNL_OK;
+}
+
+int launch_apply(const float* x, const Workspace& ws, const float* residual, float* y, long rows, long C, int relu, uint32_t* relu_mask,
+                 hipStream_t s) {
+  const int VEC = vec_of(C);
+  const long CG = C / VEC, total_v = rows * CG;
+  const auto kernel = VEC == 4 ? bn_apply_kernel<4> : bn_apply_kernel<1>;
+  hipLaunchKernelGGL(kernel, dim3(ew_grid(total_v, CG)), dim3(kBlock), 0, s, x, ws.apply_pivot, ws.scale, ws.shift, residual, y, total_v,
+                     (int)CG, relu, relu ? relu_mask : nullptr);
+  NNL_CHECK_LAUNCH();
+  return NNL_OK;
+}
+
+int launch_bwd_reduce(const float* dy, const float* y, const uint32_t* relu_mask, const float* x, const float* mean, const float* invstd,
+                      float* part, long rows, long C, int relu, hipStream_t s, int& nparts) {
+  const int VEC = vec_of(C);
+  const Shape sh = make_shape(rows, C / VEC);
+  const auto kernel = VEC == 4 ? bn_bwd_reduce_kernel<4> : bn_bwd_reduce_kernel<1>;
+  hipLaunchKernelGGL(kernel, dim3(sh.gx, sh.gy), dim3(kBlock), 0, s, dy, y, x, mean, invstd, part, rows, (int)C, sh.L, relu, relu_mask);
+  NNL_CHECK_LAUNCH();
+  nparts = sh.gx;
+  return NNL_OK;
+}
+
+int launch_bwd_finalize(const float* part, int nparts, const float* gamma, const float* mean, const float* invstd, float* dgamma,
+                        float* dbeta, float* coef, long rows, long C, int training, hipStream_t s) {
+  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((unsigned)nnl_cdiv(C, 4)), dim3(256), 0, s, part, nparts, gamma, mean, invstd, dgamma,
+                     dbeta, coef, rows, (int)C, training);
+  NNL_CHECK_LAUNCH();
+  return NNL_OK;
+}
+
+int launch_bwd_apply(const float* dy, const float* y, const uint32_t* relu_mask, const float* x, const float* coef, float* dx, float* dres,
+                     long rows, long C, int relu, hipStream_t s) {
+  const int VEC = vec_of(C);
+  const long CG = C / VEC, total_v = rows * CG;
+  const auto kernel = VEC == 4 ? bn_bwd_apply_kernel<4> : bn_bwd_apply_kernel<1>;
+  hipLaunchKernelGGL(kernel, dim3(ew_grid(total_v, CG)), dim3(kBlock), 0, s, dy, y, x, coef, dx, dres, total_v, (int)CG, (int)C, relu,
+                     relu_mask);
+  NNL_CHECK_LAUNCH();
+  return NNL_OK;
+}
+
+}  // namespace
 
 extern "C" int nnl_bn_fwd(const float* x, const float* gamma, const float* beta, const float* residual, float* y,
                           float* save_mean, float* save_invstd, float* running_mean, float* running_var, int64_t rows,
@@ -547,53 +649,17 @@ extern "C" int nnl_bn_fwd(const float* x, const float* gamma, const float* beta,
   NNL_CHECK_ARG(rows > 0 && C > 0 && C < (1 << 24), "bn_fwd: bad sizes rows=%ld C=%ld", (long)rows, (long)C);
   NNL_CHECK_ARG(x && y && save_mean && save_invstd, "bn_fwd: null pointer");
   NNL_CHECK_ARG(training || (running_mean && running_var), "bn_fwd: eval mode needs running statistics");
-  if (workspace == nullptr || workspace_bytes < nnl_bn_workspace_bytes(rows, C))
-    return nnl_set_error(NNL_ERR_WORKSPACE, "bn_fwd: workspace too small");
+  Workspace ws;
+  NNL_TRY(bind_workspace(workspace, workspace_bytes, rows, C, "bn_fwd", ws));
   hipStream_t s = (hipStream_t)stream;
-  float* part = (float*)workspace;
-  float* scale = part + (long)kMaxRowBlocks * C * 2;
-  float* shift = scale + C;
-  float* apv = shift + C;                          // bn_apply's per-channel pivot: in the backward's coefficient area, free until then
-  const int VEC = (C % 4 == 0) ? 4 : 1;
-  const long CG = C / VEC;
   NnlProfScope prof(NNL_PROF_ELEMENTWISE, s, (double)rows * C * (training ? 12.0 : 8.0) + (residual ? 4.0 * rows * C : 0.0));
-  if (training && ext_partials != nullptr && ext_rows > 0 && ext_pivot != nullptr) {
-    // the producing convolution already reduced every 64-row tile: only the finalize (pivot = the conv's pivot)
-    if (ext_rows >= 1024)      // one partial per 64-row tile of the convolution: thousands on the early stages
-      hipLaunchKernelGGL(bn_finalize_kernel<256>, dim3((unsigned)C), dim3(256), 0, s, ext_pivot, ext_partials, (int)ext_rows, gamma, beta,
-                         save_mean, save_invstd, running_mean, running_var, scale, shift, (long)rows, (int)C, eps, momentum,
-                         (long long*)num_batches_tracked, pivot_out, apv);
-    else
-      hipLaunchKernelGGL(bn_finalize_kernel<kFinLanes>, dim3((unsigned)nnl_cdiv(C, 4)), dim3(256), 0, s, ext_pivot, ext_partials,
-                         (int)ext_rows, gamma, beta, save_mean, save_invstd, running_mean, running_var, scale, shift, (long)rows,
-                         (int)C, eps, momentum, (long long*)num_batches_tracked, pivot_out, apv);
-    NNL_CHECK_LAUNCH();
-  } else if (training) {
-    const Shape sh = make_shape(rows, CG);
-    if (VEC == 4)
-      hipLaunchKernelGGL(bn_stats_kernel<4>, dim3(sh.gx, sh.gy), dim3(kBlock), 0, s, x, part, (long)rows, (int)C, sh.L);
-    else
-      hipLaunchKernelGGL(bn_stats_kernel<1>, dim3(sh.gx, sh.gy), dim3(kBlock), 0, s, x, part, (long)rows, (int)C, sh.L);
-    NNL_CHECK_LAUNCH();
-    hipLaunchKernelGGL(bn_finalize_kernel<kFinLanes>, dim3((unsigned)nnl_cdiv(C, 4)), dim3(256), 0, s, x, part, sh.gx, gamma, beta,
-                       save_mean, save_invstd, running_mean, running_var, scale, shift, (long)rows, (int)C, eps, momentum,
-                       (long long*)num_batches_tracked, pivot_out, apv);
-    NNL_CHECK_LAUNCH();
-  } else {
-    NNL_CHECK_HIP(hipMemcpyAsync(save_mean, running_mean, sizeof(float) * C, hipMemcpyDeviceToDevice, s));
-    hipLaunchKernelGGL(bn_eval_scale_kernel, dim3((unsigned)nnl_cdiv(C, 256)), dim3(256), 0, s, gamma, beta, running_mean,
-                       running_var, scale, shift, save_invstd, (int)C, eps, apv);
-    NNL_CHECK_LAUNCH();
-  }
-  const long total_v = rows * CG;
-  if (VEC == 4)
-    hipLaunchKernelGGL(bn_apply_kernel<4>, dim3(ew_grid(total_v, CG)), dim3(kBlock), 0, s, x, apv, scale, shift, residual, y, total_v,
-                       (int)CG, relu, relu ? relu_mask : nullptr);
+  const ChannelStats cs{gamma, beta, save_mean, save_invstd, running_mean, running_var, ws.scale, ws.shift, ws.apply_pivot, pivot_out,
+                        num_batches_tracked, eps, momentum};
+  if (training && ext_partials != nullptr && ext_rows > 0 && ext_pivot != nullptr)    // the producing convolution already reduced every
+    NNL_TRY(launch_finalize(ext_pivot, ext_partials, (int)ext_rows, true, cs, rows, C, s));   // 64-row tile around its own pivot
   else
-    hipLaunchKernelGGL(bn_apply_kernel<1>, dim3(ew_grid(total_v, CG)), dim3(kBlock), 0, s, x, apv, scale, shift, residual, y, total_v,
-                       (int)CG, relu, relu ? relu_mask : nullptr);
-  NNL_CHECK_LAUNCH();
-  return NNL_OK;
+    NNL_TRY(launch_channel_affine(x, ws.part, cs, rows, C, training, s));
+  return launch_apply(x, ws, residual, y, rows, C, relu, relu_mask, s);
 }
 
 extern "C" int nnl_bn_bwd(const float* dy, const float* y, const uint32_t* relu_mask, const float* x, const float* gamma,
@@ -602,34 +668,14 @@ extern "C" int nnl_bn_bwd(const float* dy, const float* y, const uint32_t* relu_
                           void* stream) {
   NNL_CHECK_ARG(rows > 0 && C > 0 && C < (1 << 24), "bn_bwd: bad sizes");
   NNL_CHECK_ARG(dy && x && mean && invstd && dx && (y || relu_mask || !relu), "bn_bwd: null pointer");
-  if (workspace == nullptr || workspace_bytes < nnl_bn_workspace_bytes(rows, C))
-    return nnl_set_error(NNL_ERR_WORKSPACE, "bn_bwd: workspace too small");
+  Workspace ws;
+  NNL_TRY(bind_workspace(workspace, workspace_bytes, rows, C, "bn_bwd", ws));
   hipStream_t s = (hipStream_t)stream;
-  float* part = (float*)workspace;
-  float* coef = part + (long)kMaxRowBlocks * C * 2 + 2 * C;
-  const int VEC = (C % 4 == 0) ? 4 : 1;
-  const long CG = C / VEC;
-  const Shape sh = make_shape(rows, CG);
   NnlProfScope prof(NNL_PROF_ELEMENTWISE, s, (double)rows * C * (relu ? 28.0 : 20.0) + (dres ? 4.0 * rows * C : 0.0));
-  if (VEC == 4)
-    hipLaunchKernelGGL(bn_bwd_reduce_kernel<4>, dim3(sh.gx, sh.gy), dim3(kBlock), 0, s, dy, y, x, mean, invstd, part, (long)rows,
-                       (int)C, sh.L, relu, relu_mask);
-  else
-    hipLaunchKernelGGL(bn_bwd_reduce_kernel<1>, dim3(sh.gx, sh.gy), dim3(kBlock), 0, s, dy, y, x, mean, invstd, part, (long)rows,
-                       (int)C, sh.L, relu, relu_mask);
-  NNL_CHECK_LAUNCH();
-  hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((unsigned)nnl_cdiv(C, 4)), dim3(256), 0, s, part, sh.gx, gamma, mean, invstd,
-                     dgamma, dbeta, coef, (long)rows, (int)C, training);
-  NNL_CHECK_LAUNCH();
-  const long total_v = rows * CG;
-  if (VEC == 4)
-    hipLaunchKernelGGL(bn_bwd_apply_kernel<4>, dim3(ew_grid(total_v, CG)), dim3(kBlock), 0, s, dy, y, x, coef, dx, dres, total_v,
-                       (int)CG, (int)C, relu, relu_mask);
-  else
-    hipLaunchKernelGGL(bn_bwd_apply_kernel<1>, dim3(ew_grid(total_v, CG)), dim3(kBlock), 0, s, dy, y, x, coef, dx, dres, total_v,
-                       (int)CG, (int)C, relu, relu_mask);
-  NNL_CHECK_LAUNCH();
-  return NNL_OK;
+  int nparts;
+  NNL_TRY(launch_bwd_reduce(dy, y, relu_mask, x, mean, invstd, ws.part, rows, C, relu, s, nparts));
+  NNL_TRY(launch_bwd_finalize(ws.part, nparts, gamma, mean, invstd, dgamma, dbeta, ws.coef, rows, C, training, s));
+  return launch_bwd_apply(dy, y, relu_mask, x, ws.coef, dx, dres, rows, C, relu, s);
 }
 
 // ---- BatchNorm -> ReLU -> MaxPool2d in one pass (the ResNet stem: reference retinanet.py:372-374) -----------------------------
@@ -715,12 +761,31 @@ __device__ __forceinline__ f32x4 bnpool_grad(const float* __restrict__ dpool, co
 
 constexpr int kPoolRedBlock = 1024;          // 16 waves per block: the gathers are latency-bound, so 2 blocks x 16 waves fill a CU
 
+// Epilogue of the two stem reductions: threads t, t + C4, t + 2*C4 ... of a block hold the same four channels; the first C4 threads add
+// them in thread order and write the block's pair of sums per channel to part[blockIdx.x][c][2].
+__device__ __forceinline__ void store_pool_block_partials(const float (&s1)[4], const float (&s2)[4], float* __restrict__ part, int C,
+                                                          int C4) {
+  __shared__ float red[kPoolRedBlock][8];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) { red[threadIdx.x][e * 2] = s1[e]; red[threadIdx.x][e * 2 + 1] = s2[e]; }
+  __syncthreads();
+  if ((int)threadIdx.x < C4) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      float a = 0.f, b = 0.f;
+      for (int j = threadIdx.x; j < kPoolRedBlock; j += C4) { a += red[j][e * 2]; b += red[j][e * 2 + 1]; }
+      const long c = (long)threadIdx.x * 4 + e;
+      part[((long)blockIdx.x * C + c) * 2 + 0] = a;
+      part[((long)blockIdx.x * C + c) * 2 + 1] = b;
+    }
+  }
+}
+
 __global__ __launch_bounds__(kPoolRedBlock) void bnpool_bwd_reduce_kernel(const float* __restrict__ dpool, const uint8_t* __restrict__ idx,
                                                                    const float* __restrict__ x, const float* __restrict__ scale,
                                                                    const float* __restrict__ shift, const float* __restrict__ mean,
                                                                    const float* __restrict__ invstd, float* __restrict__ part,
                                                                    int N, int C, PoolGeom g) {
-  __shared__ float red[kPoolRedBlock][8];
   const long total = (long)N * g.H * g.W * g.C4;
   const long i0 = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const int c4 = (int)(i0 % g.C4);
@@ -737,19 +802,7 @@ __global__ __launch_bounds__(kPoolRedBlock) void bnpool_bwd_reduce_kernel(const 
 #pragma unroll
     for (int e = 0; e < 4; ++e) { s1[e] += gg[e]; s2[e] += gg[e] * ((xv[e] - mu[e]) * is[e]); }
   }
-#pragma unroll
-  for (int e = 0; e < 4; ++e) { red[threadIdx.x][e * 2] = s1[e]; red[threadIdx.x][e * 2 + 1] = s2[e]; }
-  __syncthreads();
-  if ((int)threadIdx.x < g.C4) {                                   // threads t, t + C4, t + 2*C4 ... hold the same channels
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      float a = 0.f, b = 0.f;
-      for (int j = threadIdx.x; j < kPoolRedBlock; j += g.C4) { a += red[j][e * 2]; b += red[j][e * 2 + 1]; }
-      const long c = (long)threadIdx.x * 4 + e;
-      part[((long)blockIdx.x * C + c) * 2 + 0] = a;
-      part[((long)blockIdx.x * C + c) * 2 + 1] = b;
-    }
-  }
+  store_pool_block_partials(s1, s2, part, C, g.C4);
 }
 
 // The same two sums taken over the POOLED outputs instead of the inputs: sum_in g*f = sum_out dpool * [y > 0] * f(arg-max), and at
@@ -761,7 +814,6 @@ __global__ __launch_bounds__(kPoolRedBlock) void bnpool_bwd_reduce_out_kernel(co
                                                                        const float* __restrict__ gamma, const float* __restrict__ beta,
                                                                        const float* __restrict__ mean, const float* __restrict__ invstd,
                                                                        float* __restrict__ part, int N, int C, PoolGeom g) {
-  __shared__ float red[kPoolRedBlock][8];
   const long total = (long)N * g.P * g.Q * g.C4;
   const long i0 = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const int c4 = (int)(i0 % g.C4);
@@ -800,19 +852,7 @@ __global__ __launch_bounds__(kPoolRedBlock) void bnpool_bwd_reduce_out_kernel(co
       s2[e] += d[e] * xh;
     }
   }
-#pragma unroll
-  for (int e = 0; e < 4; ++e) { red[threadIdx.x][e * 2] = s1[e]; red[threadIdx.x][e * 2 + 1] = s2[e]; }
-  __syncthreads();
-  if ((int)threadIdx.x < g.C4) {
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      float a = 0.f, b = 0.f;
-      for (int j = threadIdx.x; j < kPoolRedBlock; j += g.C4) { a += red[j][e * 2]; b += red[j][e * 2 + 1]; }
-      const long c = (long)threadIdx.x * 4 + e;
-      part[((long)blockIdx.x * C + c) * 2 + 0] = a;
-      part[((long)blockIdx.x * C + c) * 2 + 1] = b;
-    }
-  }
+  store_pool_block_partials(s1, s2, part, C, g.C4);
 }
 
 __global__ __launch_bounds__(kBlock) void bnpool_bwd_apply_kernel(const float* __restrict__ dpool, const uint8_t* __restrict__ idx,
@@ -846,6 +886,17 @@ unsigned bnpool_grid(long total) {                                 // <= kMaxRow
   return (unsigned)(g < 1 ? 1 : g);
 }
 
+// What both stem entry points accept: a window position kh*ks + kw fits idx's byte, no window lies wholly in the padding, P and Q are
+// what the pooling yields (the kernels index y, idx and dpool by them as stated), and N*H*W*C/4 stays inside the kernels' index range.
+int check_stem_geometry(const char* who, long N, long H, long W, long C, long P, long Q, int ks, int stride, int pad) {
+  NNL_CHECK_ARG(N > 0 && H > 0 && W > 0 && P > 0 && Q > 0 && ks > 0 && ks * ks <= 255 && stride > 0 && pad >= 0 && 2 * pad <= ks,
+                "%s: bad geometry", who);
+  NNL_CHECK_ARG(P == (H + 2 * pad - ks) / stride + 1 && Q == (W + 2 * pad - ks) / stride + 1, "%s: P/Q do not match", who);
+  NNL_CHECK_ARG(bnpool_ok(C), "%s: C=%ld needs C %% 4 == 0 and C/4 dividing 256", who, C);
+  NNL_CHECK_ARG(N * H * W * C < (1L << 31) * 4, "%s: tensor too large", who);
+  return NNL_OK;
+}
+
 }  // namespace
 
 extern "C" int nnl_bn_relu_maxpool_supported(int64_t C) { return bnpool_ok(C) ? 1 : 0; }
@@ -855,39 +906,21 @@ extern "C" int nnl_bn_relu_maxpool_fwd(const float* x, const float* gamma, const
                                        float* running_mean, float* running_var, int64_t N, int64_t H, int64_t W, int64_t C,
                                        int64_t P, int64_t Q, int ks, int stride, int pad, float eps, float momentum, int training,
                                        int64_t* num_batches_tracked, void* workspace, size_t workspace_bytes, void* stream) {
-  const long rows = (long)N * H * W;
-  NNL_CHECK_ARG(N > 0 && H > 0 && W > 0 && P > 0 && Q > 0 && ks > 0 && ks * ks <= 255 && stride > 0 && pad >= 0 && 2 * pad <= ks,
-                "bn_relu_maxpool_fwd: bad geometry");
-  NNL_CHECK_ARG(P == (H + 2 * pad - ks) / stride + 1 && Q == (W + 2 * pad - ks) / stride + 1, "bn_relu_maxpool_fwd: P/Q do not match");
-  NNL_CHECK_ARG(bnpool_ok(C), "bn_relu_maxpool_fwd: C=%ld needs C %% 4 == 0 and C/4 dividing 256", (long)C);
+  NNL_TRY(check_stem_geometry("bn_relu_maxpool_fwd", N, H, W, C, P, Q, ks, stride, pad));
   NNL_CHECK_ARG(x && y && idx && save_mean && save_invstd && save_scale && save_shift, "bn_relu_maxpool_fwd: null pointer");
   NNL_CHECK_ARG(training || (running_mean && running_var), "bn_relu_maxpool_fwd: eval mode needs running statistics");
-  NNL_CHECK_ARG(rows * C < (1L << 31) * 4, "bn_relu_maxpool_fwd: tensor too large");
-  if (workspace == nullptr || workspace_bytes < nnl_bn_workspace_bytes(rows, C))
-    return nnl_set_error(NNL_ERR_WORKSPACE, "bn_relu_maxpool_fwd: workspace too small");
+  const long rows = (long)N * H * W, CG = C / 4;
+  Workspace ws;
+  NNL_TRY(bind_workspace(workspace, workspace_bytes, rows, C, "bn_relu_maxpool_fwd", ws));
   hipStream_t s = (hipStream_t)stream;
-  float* part = (float*)workspace;
-  float* scale = save_scale;                       // kept for the backward: its ReLU gate is recomputed from exactly these values
-  float* shift = save_shift;
-  const long CG = C / 4;
   NnlProfScope prof(NNL_PROF_ELEMENTWISE, s, (double)rows * C * (training ? 8.0 : 4.0) + (double)N * P * Q * C * 5.0);
-  if (training) {
-    const Shape sh = make_shape(rows, CG);
-    hipLaunchKernelGGL(bn_stats_kernel<4>, dim3(sh.gx, sh.gy), dim3(kBlock), 0, s, x, part, rows, (int)C, sh.L);
-    NNL_CHECK_LAUNCH();
-    hipLaunchKernelGGL(bn_finalize_kernel<kFinLanes>, dim3((unsigned)nnl_cdiv(C, 4)), dim3(256), 0, s, x, part, sh.gx, gamma, beta,
-                       save_mean, save_invstd, running_mean, running_var, scale, shift, rows, (int)C, eps, momentum,
-                       (long long*)num_batches_tracked, (float*)nullptr, (float*)nullptr);
-    NNL_CHECK_LAUNCH();
-  } else {
-    NNL_CHECK_HIP(hipMemcpyAsync(save_mean, running_mean, sizeof(float) * C, hipMemcpyDeviceToDevice, s));
-    hipLaunchKernelGGL(bn_eval_scale_kernel, dim3((unsigned)nnl_cdiv(C, 256)), dim3(256), 0, s, gamma, beta, running_mean,
-                       running_var, scale, shift, save_invstd, (int)C, eps, (float*)nullptr);
-    NNL_CHECK_LAUNCH();
-  }
+  // the affine goes to save_scale / save_shift, kept for the backward: its ReLU gate is recomputed from exactly these values
+  const ChannelStats cs{gamma, beta, save_mean, save_invstd, running_mean, running_var, save_scale, save_shift, /*apply_pivot*/ nullptr,
+                        /*pivot_out*/ nullptr, num_batches_tracked, eps, momentum};
+  NNL_TRY(launch_channel_affine(x, ws.part, cs, rows, C, training, s));
   const long total = (long)N * P * Q * CG;
-  hipLaunchKernelGGL(bnpool_fwd_kernel, dim3((unsigned)nnl_cdiv(total, kBlock)), dim3(kBlock), 0, s, x, scale, shift, y, idx, (int)N,
-                     (int)H, (int)W, (int)CG, (int)P, (int)Q, ks, stride, pad);
+  hipLaunchKernelGGL(bnpool_fwd_kernel, dim3((unsigned)nnl_cdiv(total, kBlock)), dim3(kBlock), 0, s, x, save_scale, save_shift, y, idx,
+                     (int)N, (int)H, (int)W, (int)CG, (int)P, (int)Q, ks, stride, pad);
   NNL_CHECK_LAUNCH();
   return NNL_OK;
 }
@@ -897,66 +930,45 @@ extern "C" int nnl_bn_relu_maxpool_bwd(const float* dpool, const float* y, const
                                        const float* shift, float* dx, float* dgamma, float* dbeta, int64_t N,
                                        int64_t H, int64_t W, int64_t C, int64_t P, int64_t Q, int ks, int stride, int pad,
                                        int training, void* workspace, size_t workspace_bytes, void* stream) {
-  const long rows = (long)N * H * W;
-  NNL_CHECK_ARG(N > 0 && H > 0 && W > 0 && P > 0 && Q > 0 && ks > 0 && stride > 0 && pad >= 0, "bn_relu_maxpool_bwd: bad geometry");
-  NNL_CHECK_ARG(bnpool_ok(C), "bn_relu_maxpool_bwd: C=%ld needs C %% 4 == 0 and C/4 dividing 256", (long)C);
+  NNL_TRY(check_stem_geometry("bn_relu_maxpool_bwd", N, H, W, C, P, Q, ks, stride, pad));
   NNL_CHECK_ARG(dpool && idx && x && mean && invstd && scale && shift && dx, "bn_relu_maxpool_bwd: null pointer");
-  if (workspace == nullptr || workspace_bytes < nnl_bn_workspace_bytes(rows, C))
-    return nnl_set_error(NNL_ERR_WORKSPACE, "bn_relu_maxpool_bwd: workspace too small");
+  const long rows = (long)N * H * W;
+  Workspace ws;
+  NNL_TRY(bind_workspace(workspace, workspace_bytes, rows, C, "bn_relu_maxpool_bwd", ws));
   hipStream_t s = (hipStream_t)stream;
-  float* part = (float*)workspace;
-  float* coef = part + (long)kMaxRowBlocks * C * 2 + 2 * C;
   const PoolGeom g{(int)H, (int)W, (int)(C / 4), (int)P, (int)Q, ks, stride, pad};
   const long total = rows * (C / 4);
-  const unsigned grid = bnpool_grid(total);
   NnlProfScope prof(NNL_PROF_ELEMENTWISE, s, (double)rows * C * 12.0 + (double)N * P * Q * C * 10.0);
+  unsigned grid;
   if (y != nullptr) {                      // sums over the pooled outputs (no x, no gather)
-    const unsigned go = bnpool_grid((long)N * P * Q * (C / 4));
-    hipLaunchKernelGGL(bnpool_bwd_reduce_out_kernel, dim3(go), dim3(kPoolRedBlock), 0, s, dpool, y, idx, x, gamma, beta, mean, invstd,
-                       part, (int)N, (int)C, g);
-    NNL_CHECK_LAUNCH();
-    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((unsigned)nnl_cdiv(C, 4)), dim3(256), 0, s, part, (int)go, gamma, mean, invstd,
-                       dgamma, dbeta, coef, rows, (int)C, training);
-    NNL_CHECK_LAUNCH();
+    grid = bnpool_grid((long)N * P * Q * (C / 4));
+    hipLaunchKernelGGL(bnpool_bwd_reduce_out_kernel, dim3(grid), dim3(kPoolRedBlock), 0, s, dpool, y, idx, x, gamma, beta, mean, invstd,
+                       ws.part, (int)N, (int)C, g);
   } else {
-    hipLaunchKernelGGL(bnpool_bwd_reduce_kernel, dim3(grid), dim3(kPoolRedBlock), 0, s, dpool, idx, x, scale, shift, mean, invstd, part,
+    grid = bnpool_grid(total);
+    hipLaunchKernelGGL(bnpool_bwd_reduce_kernel, dim3(grid), dim3(kPoolRedBlock), 0, s, dpool, idx, x, scale, shift, mean, invstd, ws.part,
                        (int)N, (int)C, g);
-    NNL_CHECK_LAUNCH();
-    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((unsigned)nnl_cdiv(C, 4)), dim3(256), 0, s, part, (int)grid, gamma, mean, invstd,
-                       dgamma, dbeta, coef, rows, (int)C, training);
-    NNL_CHECK_LAUNCH();
   }
-  hipLaunchKernelGGL(bnpool_bwd_apply_kernel, dim3((unsigned)nnl_cdiv(total, kBlock)), dim3(kBlock), 0, s, dpool, idx, x, scale, shift, coef, dx, (int)N, (int)C, g);
+  NNL_CHECK_LAUNCH();
+  NNL_TRY(launch_bwd_finalize(ws.part, (int)grid, gamma, mean, invstd, dgamma, dbeta, ws.coef, rows, C, training, s));
+  hipLaunchKernelGGL(bnpool_bwd_apply_kernel, dim3((unsigned)nnl_cdiv(total, kBlock)), dim3(kBlock), 0, s, dpool, idx, x, scale, shift,
+                     ws.coef, dx, (int)N, (int)C, g);
   NNL_CHECK_LAUNCH();
   return NNL_OK;
 }
 
 // ---- SyncBN entry points (split-phase: the host runs the collective between the two halves) -------------------------
-namespace {
-int launch_stats(const float* x, float* part, long rows, long C, hipStream_t s, Shape& sh) {
-  const int VEC = (C % 4 == 0) ? 4 : 1;
-  sh = make_shape(rows, C / VEC);
-  if (VEC == 4)
-    hipLaunchKernelGGL(bn_stats_kernel<4>, dim3(sh.gx, sh.gy), dim3(kBlock), 0, s, x, part, rows, (int)C, sh.L);
-  else
-    hipLaunchKernelGGL(bn_stats_kernel<1>, dim3(sh.gx, sh.gy), dim3(kBlock), 0, s, x, part, rows, (int)C, sh.L);
-  NNL_CHECK_LAUNCH();
-  return NNL_OK;
-}
-}  // namespace
-
 extern "C" int nnl_bn_sync_stats(const float* x, float* stats, int64_t rows, int64_t C, void* workspace,
                                  size_t workspace_bytes, void* stream) {
   NNL_CHECK_ARG(rows > 0 && C > 0 && C < (1 << 24) && x && stats, "bn_sync_stats: bad arguments");
-  if (workspace == nullptr || workspace_bytes < nnl_bn_workspace_bytes(rows, C))
-    return nnl_set_error(NNL_ERR_WORKSPACE, "bn_sync_stats: workspace too small");
+  Workspace ws;
+  NNL_TRY(bind_workspace(workspace, workspace_bytes, rows, C, "bn_sync_stats", ws));
   hipStream_t s = (hipStream_t)stream;
   NnlProfScope prof(NNL_PROF_ELEMENTWISE, s, (double)rows * C * 4.0);
-  Shape sh;
-  int rc = launch_stats(x, (float*)workspace, rows, C, s, sh);
-  if (rc != NNL_OK) return rc;
-  hipLaunchKernelGGL(bn_sync_local_kernel, dim3((unsigned)nnl_cdiv(C, 4)), dim3(256), 0, s, x, (const float*)workspace, sh.gx,
-                     stats, (long)rows, (int)C);
+  int nparts;
+  NNL_TRY(launch_stats(x, ws.part, rows, C, s, nparts));
+  hipLaunchKernelGGL(bn_sync_local_kernel, dim3((unsigned)nnl_cdiv(C, 4)), dim3(256), 0, s, x, (const float*)ws.part, nparts, stats,
+                     (long)rows, (int)C);
   NNL_CHECK_LAUNCH();
   return NNL_OK;
 }
@@ -968,27 +980,15 @@ extern "C" int nnl_bn_sync_fwd(const float* x, const float* all_stats, int world
                                void* stream) {
   NNL_CHECK_ARG(rows > 0 && C > 0 && C < (1 << 24) && world > 0, "bn_sync_fwd: bad sizes");
   NNL_CHECK_ARG(x && y && all_stats && save_mean && save_invstd, "bn_sync_fwd: null pointer");
-  if (workspace == nullptr || workspace_bytes < nnl_bn_workspace_bytes(rows, C))
-    return nnl_set_error(NNL_ERR_WORKSPACE, "bn_sync_fwd: workspace too small");
+  Workspace ws;
+  NNL_TRY(bind_workspace(workspace, workspace_bytes, rows, C, "bn_sync_fwd", ws));
   hipStream_t s = (hipStream_t)stream;
-  float* scale = (float*)workspace + (long)kMaxRowBlocks * C * 2;
-  float* shift = scale + C;
-  float* apv = shift + C;
   NnlProfScope prof(NNL_PROF_ELEMENTWISE, s, (double)rows * C * 8.0 + (residual ? 4.0 * rows * C : 0.0));
   hipLaunchKernelGGL(bn_sync_merge_kernel, dim3((unsigned)nnl_cdiv(C, 256)), dim3(256), 0, s, all_stats, world, gamma, beta,
-                     save_mean, save_invstd, running_mean, running_var, scale, shift, (int)C, eps, momentum,
-                     (long long*)num_batches_tracked, apv);
+                     save_mean, save_invstd, running_mean, running_var, ws.scale, ws.shift, (int)C, eps, momentum,
+                     (long long*)num_batches_tracked, ws.apply_pivot);
   NNL_CHECK_LAUNCH();
-  const int VEC = (C % 4 == 0) ? 4 : 1;
-  const long CG = C / VEC, total_v = rows * CG;
-  if (VEC == 4)
-    hipLaunchKernelGGL(bn_apply_kernel<4>, dim3(ew_grid(total_v, CG)), dim3(kBlock), 0, s, x, apv, scale, shift, residual, y, total_v,
-                       (int)CG, relu, relu ? relu_mask : nullptr);
-  else
-    hipLaunchKernelGGL(bn_apply_kernel<1>, dim3(ew_grid(total_v, CG)), dim3(kBlock), 0, s, x, apv, scale, shift, residual, y, total_v,
-                       (int)CG, relu, relu ? relu_mask : nullptr);
-  NNL_CHECK_LAUNCH();
-  return NNL_OK;
+  return launch_apply(x, ws, residual, y, rows, C, relu, relu_mask, s);
 }
 
 extern "C" int nnl_bn_sync_bwd_reduce(const float* dy, const float* y, const uint32_t* relu_mask, const float* x,
@@ -996,22 +996,13 @@ extern "C" int nnl_bn_sync_bwd_reduce(const float* dy, const float* y, const uin
                                       void* workspace, size_t workspace_bytes, void* stream) {
   NNL_CHECK_ARG(rows > 0 && C > 0 && C < (1 << 24), "bn_sync_bwd_reduce: bad sizes");
   NNL_CHECK_ARG(dy && x && mean && invstd && sums && (y || relu_mask || !relu), "bn_sync_bwd_reduce: null pointer");
-  if (workspace == nullptr || workspace_bytes < nnl_bn_workspace_bytes(rows, C))
-    return nnl_set_error(NNL_ERR_WORKSPACE, "bn_sync_bwd_reduce: workspace too small");
+  Workspace ws;
+  NNL_TRY(bind_workspace(workspace, workspace_bytes, rows, C, "bn_sync_bwd_reduce", ws));
   hipStream_t s = (hipStream_t)stream;
-  float* part = (float*)workspace;
-  const int VEC = (C % 4 == 0) ? 4 : 1;
-  const Shape sh = make_shape(rows, C / VEC);
   NnlProfScope prof(NNL_PROF_ELEMENTWISE, s, (double)rows * C * (relu ? 12.0 : 8.0));
-  if (VEC == 4)
-    hipLaunchKernelGGL(bn_bwd_reduce_kernel<4>, dim3(sh.gx, sh.gy), dim3(kBlock), 0, s, dy, y, x, mean, invstd, part, (long)rows,
-                       (int)C, sh.L, relu, relu_mask);
-  else
-    hipLaunchKernelGGL(bn_bwd_reduce_kernel<1>, dim3(sh.gx, sh.gy), dim3(kBlock), 0, s, dy, y, x, mean, invstd, part, (long)rows,
-                       (int)C, sh.L, relu, relu_mask);
-  NNL_CHECK_LAUNCH();
-  hipLaunchKernelGGL(bn_sync_bwd_sums_kernel, dim3((unsigned)nnl_cdiv(C, 4)), dim3(256), 0, s, (const float*)part, sh.gx, sums,
-                     (int)C);
+  int nparts;
+  NNL_TRY(launch_bwd_reduce(dy, y, relu_mask, x, mean, invstd, ws.part, rows, C, relu, s, nparts));
+  hipLaunchKernelGGL(bn_sync_bwd_sums_kernel, dim3((unsigned)nnl_cdiv(C, 4)), dim3(256), 0, s, (const float*)ws.part, nparts, sums, (int)C);
   NNL_CHECK_LAUNCH();
   return NNL_OK;
 }
@@ -1024,30 +1015,20 @@ extern "C" int nnl_bn_sync_bwd(const float* dy, const float* y, const uint32_t* 
   NNL_CHECK_ARG(rows > 0 && C > 0 && C < (1 << 24) && world > 0, "bn_sync_bwd: bad sizes");
   NNL_CHECK_ARG(dy && x && mean && invstd && dx && local_sums && global_sums && all_stats && (y || relu_mask || !relu),
                 "bn_sync_bwd: null pointer");
-  if (workspace == nullptr || workspace_bytes < nnl_bn_workspace_bytes(rows, C))
-    return nnl_set_error(NNL_ERR_WORKSPACE, "bn_sync_bwd: workspace too small");
+  Workspace ws;
+  NNL_TRY(bind_workspace(workspace, workspace_bytes, rows, C, "bn_sync_bwd", ws));
   hipStream_t s = (hipStream_t)stream;
-  float* coef = (float*)workspace + (long)kMaxRowBlocks * C * 2 + 2 * C;
   NnlProfScope prof(NNL_PROF_ELEMENTWISE, s, (double)rows * C * (relu ? 16.0 : 12.0) + (dres ? 4.0 * rows * C : 0.0));
   hipLaunchKernelGGL(bn_sync_bwd_coef_kernel, dim3((unsigned)nnl_cdiv(C, 256)), dim3(256), 0, s, local_sums, global_sums, all_stats,
-                     world, gamma, mean, invstd, dgamma, dbeta, coef, (int)C);
+                     world, gamma, mean, invstd, dgamma, dbeta, ws.coef, (int)C);
   NNL_CHECK_LAUNCH();
-  const int VEC = (C % 4 == 0) ? 4 : 1;
-  const long CG = C / VEC, total_v = rows * CG;
-  if (VEC == 4)
-    hipLaunchKernelGGL(bn_bwd_apply_kernel<4>, dim3(ew_grid(total_v, CG)), dim3(kBlock), 0, s, dy, y, x, coef, dx, dres, total_v,
-                       (int)CG, (int)C, relu, relu_mask);
-  else
-    hipLaunchKernelGGL(bn_bwd_apply_kernel<1>, dim3(ew_grid(total_v, CG)), dim3(kBlock), 0, s, dy, y, x, coef, dx, dres, total_v,
-                       (int)CG, (int)C, relu, relu_mask);
-  NNL_CHECK_LAUNCH();
-  return NNL_OK;
+  return launch_bwd_apply(dy, y, relu_mask, x, ws.coef, dx, dres, rows, C, relu, s);
 }
 
 // ---- planner query (debug, host only: no HIP call) ---------------------------------------------------------------------
 extern "C" int nnl_debug_bn_plan(int64_t rows, int64_t C, int64_t N, int64_t H, int64_t W, int64_t P, int64_t Q, int32_t* out10) {
   if (rows <= 0 || C <= 0 || C >= (1 << 24) || out10 == nullptr) return 0;
-  const int VEC = (C % 4 == 0) ? 4 : 1;
+  const int VEC = vec_of(C);
   const long CG = C / VEC;
   const Shape sh = make_shape(rows, CG);
   out10[0] = VEC; out10[1] = sh.L; out10[2] = sh.rpb; out10[3] = sh.gx; out10[4] = sh.gy; out10[5] = sh.capped ? 1 : 0;

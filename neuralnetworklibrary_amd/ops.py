@@ -896,6 +896,22 @@ def _relu_mask(rows, C, device):
     return torch.empty((rows * C + 31) // 32 + 2, dtype=torch.int32, device=device)
 
 
+def _bn_grad_buffers(ctx, xm, gamma, has_res):
+    "dx, dres (only when the residual wants a gradient), dgamma, dbeta for a BatchNorm backward to fill"
+    dx = torch.empty_like(xm)
+    dres = torch.empty_like(xm) if (has_res and ctx.needs_input_grad[1]) else None
+    dgamma = torch.empty(xm.shape[1], dtype=torch.float32, device=xm.device) if gamma is not None else None
+    dbeta = torch.empty(xm.shape[1], dtype=torch.float32, device=xm.device) if gamma is not None else None
+    return dx, dres, dgamma, dbeta
+
+
+def _bn_grads(ctx, back, dx, dres, dgamma, dbeta):
+    "the gradients of (x, residual, gamma, beta); with a GradSlot the residual's goes to the block's first conv, which adds it to its dx"
+    if ctx.slot is not None and dres is not None:
+        ctx.slot.tensor, dres = dres, None
+    return back(dx), None if dres is None else back(dres), dgamma, dbeta
+
+
 class _BNAct(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, residual, gamma, beta, running_mean, running_var, training, momentum, eps, relu, nbt, slot=None, ext=None,
@@ -925,22 +941,12 @@ class _BNAct(torch.autograd.Function):
         training, relu, has_res, back = ctx.cfg
         dym = _rows_view(dy)[0]
         rows, C = xm.shape
-        dx = torch.empty_like(xm)
-        dres = torch.empty_like(xm) if (has_res and ctx.needs_input_grad[1]) else None
-        dgamma = torch.empty(C, dtype=torch.float32, device=xm.device) if gamma is not None else None
-        dbeta = torch.empty(C, dtype=torch.float32, device=xm.device) if gamma is not None else None
+        dx, dres, dgamma, dbeta = _bn_grad_buffers(ctx, xm, gamma, has_res)
         wsb = int(lib.nnl_bn_workspace_bytes(rows, C))
         ws = _workspace(wsb, xm.device)
         check(lib.nnl_bn_bwd(ptr(dym), None, ptr(mask), ptr(xm), ptr(gamma), ptr(mean), ptr(invstd), ptr(dx), ptr(dres),
                              ptr(dgamma), ptr(dbeta), rows, C, int(training), int(relu), ptr(ws), wsb, stream()))
-        if ctx.slot is not None and dres is not None:
-            ctx.slot.tensor, dres = dres, None              # the block's first conv adds it to its dx (GradSlot)
-        return (back(dx), None if dres is None else back(dres), dgamma, dbeta) + (None,) * 10
-
-
-def _sync_group_size(group):
-    import torch.distributed as dist
-    return dist.get_world_size(group)
+        return _bn_grads(ctx, back, dx, dres, dgamma, dbeta) + (None,) * 10
 
 
 class _SyncBNAct(torch.autograd.Function):
@@ -986,16 +992,11 @@ class _SyncBNAct(torch.autograd.Function):
         check(lib.nnl_bn_sync_bwd_reduce(ptr(dym), None, ptr(mask), ptr(xm), ptr(mean), ptr(invstd), ptr(sums), rows, C, int(relu),
                                          ptr(ws), wsb, stream()))
         total = comm.all_reduce_sum(sums, group)                   # a new tensor; `sums` keeps the local values
-        dx = torch.empty_like(xm)
-        dres = torch.empty_like(xm) if (has_res and ctx.needs_input_grad[1]) else None
-        dgamma = torch.empty(C, dtype=torch.float32, device=dev) if gamma is not None else None
-        dbeta = torch.empty(C, dtype=torch.float32, device=dev) if gamma is not None else None
+        dx, dres, dgamma, dbeta = _bn_grad_buffers(ctx, xm, gamma, has_res)
         check(lib.nnl_bn_sync_bwd(ptr(dym), None, ptr(mask), ptr(xm), ptr(gamma), ptr(mean), ptr(invstd), ptr(sums), ptr(total),
                                   ptr(all_stats), int(all_stats.shape[0]), ptr(dx), ptr(dres), ptr(dgamma), ptr(dbeta), rows, C,
                                   int(relu), ptr(ws), wsb, stream()))
-        if ctx.slot is not None and dres is not None:
-            ctx.slot.tensor, dres = dres, None
-        return (back(dx), None if dres is None else back(dres), dgamma, dbeta) + (None,) * 9
+        return _bn_grads(ctx, back, dx, dres, dgamma, dbeta) + (None,) * 9
 
 
 class DistComm:

@@ -460,6 +460,28 @@ def test_stem_refuses_c12():
     assert bool(torch.isnan(y.t).all()) and bool(torch.isnan(v.t).all()) and bool(torch.isnan(ws.t).all())
 
 
+def test_stem_backward_refuses_geometry_the_forward_refuses():
+    """nnl_bn_relu_maxpool_bwd indexes idx and dpool by P and Q as the caller states them: a Q one larger than the pooling yields, or a
+    window of 16 x 16 (kh*ks + kw no longer fits idx's byte), is refused on the host like in the forward: nothing is launched."""
+    from neuralnetworklibrary_amd._lib import lib, ptr, stream
+    N, H, W, C = 2, 15, 13, 16
+    P, Q = bc.pool_out(H, 3, 2, 1), bc.pool_out(W, 3, 2, 1)
+    npool = N * P * (Q + 1) * C
+    x, dpool = torch.zeros(N * H * W * C, device=DEV), torch.zeros(npool, device=DEV)
+    idx, v = torch.zeros(npool, dtype=torch.uint8, device=DEV), torch.ones(C, device=DEV)
+    dx, dg, db = _nan(N * H * W * C), _nan(C), _nan(C)
+    ws, wsb = _workspace(lib, N * H * W, C)
+    for q, ks in ((Q + 1, 3), (Q, 16)):
+        st = lib.nnl_bn_relu_maxpool_bwd(ptr(dpool), None, ptr(idx), ptr(x), ptr(v), ptr(v), ptr(v), ptr(v), ptr(v), ptr(v), ptr(dx.t), ptr(dg.t),
+                                         ptr(db.t), N, H, W, C, P, q, ks, 2, 1, 1, ptr(ws.t), wsb, stream())
+        err = lib.nnl_last_error()
+        assert st == -1 and (b'bad geometry' in err or b'P/Q do not match' in err), 'Q=%d ks=%d: status %d: %s' % (q, ks, st, err.decode())
+        assert b'bn_relu_maxpool_bwd' in err
+    torch.cuda.synchronize()
+    for g in (dx, dg, db, ws):
+        assert bool(torch.isnan(g.t).all()) and g.intact()
+
+
 STEM_SWEEP = [(c, t) for c in bc.STEM_CASES for t in ((1, 0) if c[3] == 16 else (1,))]
 
 
