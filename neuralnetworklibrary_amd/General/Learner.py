@@ -16,6 +16,7 @@ What is new (MI355X-first, not in the reference):
     prints / saves;
   * plotting is imported lazily (matplotlib is UI, out of scope for the hot path).
 """
+import contextlib
 import copy
 import os
 import time
@@ -177,6 +178,14 @@ class _PendingLoss:
         return float(self.host[self.slot])
 
 
+def _filter_window(model):
+    "the prepared-filter window of one training step (ops.filter_window): `with ... as backward:` forward, loss, backward(loss)"
+    if default_device().type != 'cuda':                   # host-logic tests: the HIP library is never loaded; a plain loss.backward()
+        return contextlib.nullcontext(torch.Tensor.backward)
+    from .. import ops
+    return ops.filter_window(model)
+
+
 class _GraphedStep:
     """One captured training step for one input signature (Learner.use_graphs)."""
 
@@ -218,13 +227,12 @@ class _GraphedStep:
                 with torch.cuda.graph(graph, capture_error_mode='thread_local' if dp else 'global'):   # records; nothing executes until replay()
                     if dp:
                         gs.capture_begin()            # the replay counter's bump: the first node of the graph
-                    if dev.type == 'cuda':
-                        from .. import ops
-                        ops.prepare_forward(learner.model)   # all Winograd filters in ONE captured launch (the eager steps built the batch;
-                                                             # round 4 captured one filter-transform launch per convolution instead)
-                    y_pred = learner.predict1minibatch(self.x)
-                    self.loss = learner.loss_func(y_pred, self.y)
-                    learner._backward(self.loss)
+                    # entering the window: all Winograd filters in ONE captured launch (the eager steps built the batch; round 4
+                    # captured one filter-transform launch per convolution instead)
+                    with _filter_window(learner.model) as backward:
+                        y_pred = learner.predict1minibatch(self.x)
+                        self.loss = learner.loss_func(y_pred, self.y)
+                        backward(self.loss)
                     if not dp:
                         opt.step()
             finally:
@@ -658,11 +666,7 @@ class Learner(object):
         opt.opt.zero_grad()
         if self.grad_sync is not None:
             self.grad_sync.begin(self._dp_weight)
-        on_gpu = default_device().type == 'cuda'
-        if on_gpu:
-            from .. import ops
-            ops.prepare_forward(self.model)              # the Winograd filters of all conv layers in one launch (ops.prepare_forward)
-        try:
+        with _filter_window(self.model) as backward:     # the Winograd filters of all conv layers in one launch; closed whatever happens
             y_pred = self.predict1minibatch(x_batch)
             loss = self.loss_func(y_pred, y_batch)
             early = loss.is_cuda and loss.numel() == 1 and not torch.cuda.is_current_stream_capturing()
@@ -672,28 +676,12 @@ class Learner(object):
                     self._loss_event = torch.cuda.Event()
                 self._loss_host.copy_(loss.detach().reshape(()).float(), non_blocking=True)
                 self._loss_event.record()
-            self._backward(loss)                         # (closes the prepared-filter window in its own `finally`)
-        except BaseException:
-            if on_gpu:
-                ops.finish_backward()                    # the window must not outlive a failed step: the next forward may follow a weight change
-            raise
+            backward(loss)                               # (after all conv filter transposes, in one launch)
         opt.step()
         if early:
             self._loss_event.synchronize()
             return float(self._loss_host)
         return loss.item()
-
-    def _backward(self, loss):
-        "loss.backward() with the per-pass preparation of the HIP layers (all conv filter transposes in one launch)"
-        if loss.is_cuda:
-            from .. import ops
-            ops.prepare_backward(self.model)
-            try:
-                loss.backward()
-            finally:
-                ops.finish_backward()
-        else:
-            loss.backward()
 
     def _graphed_step(self, x_batch, y_batch, defer=False):
         "use_graphs(): replay (or first capture) the step for this input signature; None -> run it eagerly"

@@ -5,6 +5,7 @@ cited per class).  Tensors are handed over as raw device pointers + sizes on tor
 is no CPU fallback — a non-CUDA tensor raises NnlError.
 """
 import collections
+import contextlib
 import ctypes
 import os
 import weakref
@@ -251,51 +252,14 @@ def _pad_c4(t_nhwc):
     return torch.nn.functional.pad(t_nhwc, (0, 4 - C % 4))
 
 
-# ---- all filter transposes of a backward pass in one launch --------------------------------------------------------------
-_WT_ACTIVE = {}       # weight data_ptr -> W^T tensor [C,R,S,K]; valid ONLY between prepare_backward() and finish_backward()
-_WT_PADDED = {}       # (weight data_ptr, shape, pad) -> transposed, channel-padded filter of a K % 16 != 0 dgrad; same window
-
-
-# Prepared Winograd filters (include/nnl.h: nnl_wino_filter_multi).  The transformed filter of a 3x3 / stride 1 / pad 1 layer depends
-# on its weights only; transforming it inside every convolution call costs one extra launch per call (58 per ResNet-34 step).
-# `prepare_forward(model)` (Learner, before the forward of a training step) and `prepare_backward(model)` transform the filters of all
-# layers that took the Winograd kernel at their LAST call (`_WINO_PREF`) in one launch each; the convolutions pick them up by weight
-# address.  The window closes in finish_backward() (Learner: in a `finally`), before the optimizer touches the weights.
-_WINO_U_FWD, _WINO_U_BWD = {}, {}     # (weight data_ptr, kernel mode) -> U [K,4|16,3|1,C] (forward) / U' [C,...,K] (dgrad) in that kernel's layout
-_WINO_GEN = [0]                       # training-step counter (prepare_forward): the recorded modes of a weight are those of its LAST step
-_WINO_IN_STEP = [False]               # True from prepare_forward to finish_backward: only the forward calls of a training step are recorded
-_WINO_PREF = {}                       # weight data_ptr -> [modes the forward calls took, modes the dgrad calls took] (sets; 1 = 1-D, 2 = 2-D kernel):
-                                      # a weight shared between geometries (RetinaNet's heads: five pyramid levels) may need BOTH layouts
-
-
-class _WinoBatch:
-    """persistent U buffers + device descriptor tables for nnl_wino_filter_multi: items = [(key_ptr, src tensor [rows,3,3,ch], flip, mode)],
-    mode as nnl_conv2d_wino_preferred: 1 -> U [rows,12,ch] (1-D kernel), 2 -> U [rows,16,ch] (2-D kernel)"""
-
-    def __init__(self, items):
-        dev = items[0][1].device
-        self.key = _wino_batch_key(items)
-        total = sum(_wino_u_numel(t.shape[0], t.shape[3], mode) for _, t, _, mode in items)
-        self.flat = torch.empty(total, dtype=torch.float32, device=dev)
-        desc = np.zeros(len(items), dtype=np.dtype([('src', '<u8'), ('dst', '<u8'), ('rows', '<i4'), ('ch', '<i4'), ('flip', '<i4'), ('first', '<i4'),
-                                                    ('two_d', '<i4'), ('reserved', '<i4')]))
-        block_desc, self.views, off, first = [], {}, 0, 0
-        for i, (k, t, flip, mode) in enumerate(items):
-            rows, ch = t.shape[0], t.shape[3]
-            n = _wino_u_numel(rows, ch, mode)
-            u = self.flat[off:off + n]
-            off += n
-            nb = (rows * ch + 255) // 256 if mode == 2 else (rows * 3 * ch + 255) // 256
-            desc[i] = (t.data_ptr(), u.data_ptr(), rows, ch, flip, first, 1 if mode == 2 else 0, 0)
-            block_desc += [i] * nb
-            first += nb
-            self.views[(k, mode)] = u
-        self.n_blocks = first
-        self.desc = torch.from_numpy(desc.view(np.uint8).copy()).to(dev)
-        self.block_desc = torch.tensor(block_desc, dtype=torch.int32, device=dev)
-
-    def run(self):
-        check(lib.nnl_wino_filter_multi(ptr(self.desc), ptr(self.block_desc), self.n_blocks, stream()))
+# ---- prepared conv filters: one window object per model --------------------------------------------------------------------------
+# The transformed filter of a 3x3 / stride 1 / pad 1 layer (include/nnl.h: nnl_wino_filter_multi) and the transpose W^T of a dgrad depend
+# on the weights only; producing them inside every convolution call costs one extra launch per call (58 + 37 per ResNet-34 step).  A
+# training step opens a WINDOW on its model instead (`filter_window`: prepare_forward .. prepare_backward .. finish_backward): all
+# filters of the layers that took a Winograd kernel in the LAST step are transformed in one launch per pass, all transposes in one, and
+# the convolutions pick them up by weight address.  The window closes before the optimizer touches the weights, so a filter modified
+# later can never meet a stale transform: the views exist only in the open object, and nothing is handed out through a closed one.
+_OPEN = None          # the _Filters whose window is open (at most one), or None
 
 
 def _wino_u_numel(rows, ch, mode):
@@ -303,145 +267,200 @@ def _wino_u_numel(rows, ch, mode):
     return rows * 16 * ch if mode == 2 else rows * 12 * ch
 
 
-def _wino_batch_key(items):
-    return tuple((k, t.data_ptr(), tuple(t.shape), mode) for k, t, _, mode in items)
+class _FilterBatch:
+    """persistent output buffers (one flat allocation) + device descriptor table + block -> descriptor table of one *_multi entry.
+    items = [(view key, view shape, blocks of the launch, f(dst pointer, first block) -> descriptor row)]; `extra`: the entry's
+    arguments between the block count and the stream.  (`entry` is the symbol's NAME: the model, and this with it, must stay deep-copyable.)"""
+
+    def __init__(self, key, dev, entry, desc_dtype, items, extra=()):
+        self.key, self.entry, self.extra = key, entry, extra
+        sizes = [int(np.prod(shape)) for _, shape, _, _ in items]
+        self.flat = torch.empty(sum(sizes), dtype=torch.float32, device=dev)
+        desc = np.zeros(len(items), dtype=desc_dtype)
+        block_desc, self.views, off = [], {}, 0
+        for i, ((k, shape, nb, row), n) in enumerate(zip(items, sizes)):
+            v = self.views[k] = self.flat[off:off + n].view(shape)
+            off += n
+            desc[i] = row(v.data_ptr(), len(block_desc))
+            block_desc += [i] * nb
+        self.n_blocks = len(block_desc)
+        self.desc = torch.from_numpy(desc.view(np.uint8).copy()).to(dev)
+        self.block_desc = torch.tensor(block_desc, dtype=torch.int32, device=dev)
+
+    def run(self):
+        check(getattr(lib, self.entry)(ptr(self.desc), ptr(self.block_desc), self.n_blocks, *self.extra, stream()))
 
 
-def _conv_mods(model):
-    mods = getattr(model, '_nnl_conv_mods', None)
-    if mods is None:                # the module walk costs ~0.1 ms per step on a host-bound model: done once.  A conv added
-        mods = [m for m in model.modules() if getattr(m, 'nnl_hip_conv', False)]     # later transforms its own filter (slower, correct)
-        object.__setattr__(model, '_nnl_conv_mods', mods)
-    return mods
+def _wino_batch(key, srcs):
+    """nnl_wino_filter_multi over srcs = [(key_ptr, src tensor [rows,3,3,ch], flip, mode)], mode as nnl_conv2d_wino_preferred:
+    1 -> U [rows,12,ch] (1-D kernel), 2 -> U [rows,16,ch] (2-D kernel); views by (key_ptr, mode)"""
+    def item(k, t, flip, mode):
+        rows, ch = t.shape[0], t.shape[3]
+        nb = (rows * ch + 255) // 256 if mode == 2 else (rows * 3 * ch + 255) // 256
+        return (k, mode), (_wino_u_numel(rows, ch, mode),), nb, lambda dst, first: (t.data_ptr(), dst, rows, ch, flip, first, 1 if mode == 2 else 0, 0)
+    dtype = np.dtype([('src', '<u8'), ('dst', '<u8'), ('rows', '<i4'), ('ch', '<i4'), ('flip', '<i4'), ('first', '<i4'), ('two_d', '<i4'), ('reserved', '<i4')])
+    return _FilterBatch(key, srcs[0][1].device, 'nnl_wino_filter_multi', dtype, [item(*s) for s in srcs])
 
 
-def prepared_batches(model):
-    """the persistent filter batches (_WinoBatch / _WtBatch) the last prepare_forward / prepare_backward of `model` ran.  A captured
-    step bakes raw pointers to their buffers and descriptor tables into its graph and must keep them alive (Learner._GraphedStep):
-    the next step at another batch size may replace the model's batch when the layers' Winograd modes change."""
-    return tuple(b for b in (getattr(model, a, None) for a in ('_nnl_wino_fwd_batch', '_nnl_wino_bwd_batch', '_nnl_wt_batch')) if b is not None)
+def _wt_batch(key, weights):
+    "nnl_conv2d_weight_transpose_multi over the conv filters [K,C,R,S] of one model; views W^T [C,R,S,K] by weight address"
+    def item(w):
+        K, C, R, S = w.shape
+        return w.data_ptr(), (C, R, S, K), R * S * ((K + 31) // 32) * ((C + 31) // 32), lambda dst, first: (w.data_ptr(), dst, K, R * S, C, first)
+    dtype = np.dtype([('w', '<u8'), ('wt', '<u8'), ('K', '<i4'), ('RS', '<i4'), ('C', '<i4'), ('first', '<i4')])
+    return _FilterBatch(key, weights[0].device, 'nnl_conv2d_weight_transpose_multi', dtype, [item(w) for w in weights],
+                        (float(sum(w.numel() for w in weights)),))
 
 
-def _run_wino_batch(model, attr, items, out):
-    if not items:
-        return
-    key = _wino_batch_key(items)
-    batch = getattr(model, attr, None)
-    if batch is None or batch.key != key:
-        if torch.cuda.is_current_stream_capturing():
-            return                                      # (buffers are built during eager steps)
-        batch = _WinoBatch(items)
-        object.__setattr__(model, attr, batch)
-    batch.run()
-    out.update(batch.views)
+class _Filters:
+    "the prepared-filter state of ONE model (model._nnl_filters; it dies with the model)"
+
+    def __init__(self, model):
+        # the module walk costs ~0.1 ms per step on a host-bound model: done once.  A conv added later transforms its own filter (slower, correct)
+        self.mods = [m for m in model.modules() if getattr(m, 'nnl_hip_conv', False)]
+        self.step = 0         # training-step counter (open): the recorded modes of a weight are those of its LAST step
+        self.modes = {}       # weight data_ptr -> [[step stamp, modes the forward calls took], [stamp, modes the dgrad calls took]] (sets; 1 = 1-D,
+                              # 2 = 2-D kernel): a weight shared between geometries (RetinaNet's heads: five pyramid levels) may need BOTH layouts
+        self.batches = {}     # 'fwd' / 'bwd' / 'wt' -> the persistent forward U / dgrad U' / W^T batch (_FilterBatch)
+        # the views the convolutions read, filled ONLY while the window is open:
+        self.u = ({}, {})     # [0] forward, [1] dgrad: (weight data_ptr, kernel mode) -> U [K,4|16,3|1,C] / U' [C,...,K] in that kernel's layout
+        self.wt = {}          # weight data_ptr -> W^T tensor [C,R,S,K]
+        self.wt_padded = {}   # (weight data_ptr, shape, pad) -> transposed, channel-padded filter of a K % 16 != 0 dgrad
+
+    def open(self):
+        global _OPEN
+        finish_backward()                # (whichever model's window was left open)
+        self.step += 1                   # a new training step: the modes recorded from here on replace the previous step's
+        _OPEN = self
+
+    def recorded(self, key_ptr, which):
+        return self.modes[key_ptr][which][1] if key_ptr in self.modes else ()
+
+    def _run(self, slot, key, build, *args):
+        """the persistent batch `slot` after its launch, rebuilt first when its key (the weights' pointers, shapes and modes) changed; None
+        when that happens while the stream is capturing (buffers are built during the eager warm-up steps): nothing is published then"""
+        batch = self.batches.get(slot)
+        if batch is None or batch.key != key:
+            if torch.cuda.is_current_stream_capturing():
+                return None
+            batch = self.batches[slot] = build(key, *args)
+        batch.run()
+        return batch
+
+    def _run_wino(self, which, srcs):
+        if srcs and os.environ.get('NNL_WINO_PREPARE', '1') != '0':
+            batch = self._run(('fwd', 'bwd')[which], tuple((k, t.data_ptr(), tuple(t.shape), mode) for k, t, _, mode in srcs), _wino_batch, srcs)
+            if batch is not None:
+                self.u[which].update(batch.views)
+
+    def prepare_forward(self):
+        self.open()
+        srcs = []
+        for m in self.mods:
+            w = m.weight
+            modes = self.recorded(w.data_ptr(), 0)
+            if (modes and w.is_cuda and w.dim() == 4 and w.shape[2] == 3 and w.shape[3] == 3 and w.dtype == torch.float32
+                    and w.is_contiguous(memory_format=torch.channels_last)):
+                srcs += [(w.data_ptr(), w.permute(0, 2, 3, 1), 0, mode) for mode in sorted(modes)]    # KRSC view of the same memory
+        self._run_wino(0, srcs)
+
+    def prepare_backward(self):
+        if _OPEN is not self:
+            self.open()
+        ws = [m.weight for m in self.mods
+              if m.weight.is_cuda and m.weight.dim() == 4 and m.weight.shape[1] % 4 == 0
+              and m.weight.shape[0] % 4 == 0 and m.weight.dtype == torch.float32
+              and m.weight.is_contiguous(memory_format=torch.channels_last)]
+        if len(ws) < 2 or sum(w.requires_grad for w in ws) * 2 < len(ws):
+            return
+        batch = self._run('wt', tuple((w.data_ptr(), tuple(w.shape)) for w in ws), _wt_batch, ws)
+        if batch is not None:
+            self.wt.update(batch.views)
+            # the dgrad Winograd filters U' [C,4,3,K] of the layers whose last dgrad took the Winograd kernel, from the transposes above
+            self._run_wino(1, [(w.data_ptr(), batch.views[w.data_ptr()], 1, mode) for w in ws if w.shape[2] == 3 and w.shape[3] == 3
+                               for mode in sorted(self.recorded(w.data_ptr(), 1))])
+
+    def wino(self, key_ptr, which, g):
+        """the prepared filter, or None, for the forward (which = 0) / dgrad (1) call of geometry g on the weight at key_ptr.  Inside the
+        window the call's kernel mode (nnl_conv2d_wino_preferred: 0 direct, 1 Winograd 1-D, 2 Winograd 2-D) is remembered per weight
+        for the next step's batch, and the prepared buffer is handed over only when its size is that of the mode's layout.  key_ptr 0
+        (a channel-padded dgrad: it transforms its own filter) records and finds nothing.  Neither does any call outside the window —
+        evaluation, no_grad, other batch sizes, a bare loss.backward() with neither prepare call (the first bracketed step after it
+        transforms per call, the second uses the batch: same bits): an evaluation forward must not change the next training step's
+        batch (a rebuild would free buffers a captured step still reads), and grad mode cannot tell the two apart here: autograd runs
+        every Function's forward with it off."""
+        if _OPEN is not self or not key_ptr:
+            return None
+        mode = int(lib.nnl_conv2d_wino_preferred(g, which)) if (g.R == 3 and g.S == 3 and g.stride == 1) else 0
+        if mode or key_ptr in self.modes:
+            e = self.modes.setdefault(key_ptr, [[-1, set()], [-1, set()]])[which]
+            if e[0] != self.step:                        # first call of this training step: forget the old modes
+                e[0], e[1] = self.step, set()
+            if mode:
+                e[1].add(mode)
+        u = self.u[which].get((key_ptr, mode)) if mode else None
+        rows, ch = (g.C, g.K) if which else (g.K, g.C)
+        return u if u is not None and u.numel() == _wino_u_numel(rows, ch, mode) else None
 
 
-def _wino_modes(key_ptr, which):
-    e = _WINO_PREF.get(key_ptr)
-    return e[which][1] if e is not None else ()
+_CLOSED = _Filters(torch.nn.Module())     # never opened, so never written: what a convolution outside every window asks (nothing recorded, nothing found)
+
+
+def _filters(model):
+    if getattr(model, '_nnl_filters', None) is None:
+        object.__setattr__(model, '_nnl_filters', _Filters(model))
+    return model._nnl_filters
 
 
 def prepare_forward(model):
-    """Call right before the forward of a TRAINING step (Learner does): the Winograd filters of every HipConv2d whose last forward
-    took the Winograd kernel, in one launch; valid until finish_backward()."""
-    _WINO_U_FWD.clear()
-    _WINO_GEN[0] += 1                                    # a new training step: the modes recorded from here on replace the previous step's
-    _WINO_IN_STEP[0] = True
-    if os.environ.get('NNL_WINO_PREPARE', '1') == '0':
-        return
-    items = []
-    for m in _conv_mods(model):
-        w = m.weight
-        modes = _wino_modes(w.data_ptr(), 0)
-        if (modes and w.is_cuda and w.dim() == 4 and w.shape[2] == 3 and w.shape[3] == 3 and w.dtype == torch.float32
-                and w.is_contiguous(memory_format=torch.channels_last)):
-            for mode in sorted(modes):
-                items.append((w.data_ptr(), w.permute(0, 2, 3, 1), 0, mode))    # KRSC view of the same memory
-    _run_wino_batch(model, '_nnl_wino_fwd_batch', items, _WINO_U_FWD)
-
-
-class _WtBatch:
-    "persistent W^T buffers + device descriptor tables for the conv filters of one model (nnl_conv2d_weight_transpose_multi)"
-
-    def __init__(self, weights):
-        dev = weights[0].device
-        self.key = tuple((w.data_ptr(), tuple(w.shape)) for w in weights)
-        total = sum(w.numel() for w in weights)
-        self.flat = torch.empty(total, dtype=torch.float32, device=dev)
-        desc = np.zeros(len(weights), dtype=np.dtype([('w', '<u8'), ('wt', '<u8'), ('K', '<i4'), ('RS', '<i4'), ('C', '<i4'), ('first', '<i4')]))
-        tile_tensor, self.views, off, first = [], {}, 0, 0
-        for i, w in enumerate(weights):
-            K, C, R, S = w.shape
-            wt = self.flat[off:off + w.numel()].view(C, R, S, K)
-            off += w.numel()
-            n_tiles = R * S * ((K + 31) // 32) * ((C + 31) // 32)
-            desc[i] = (w.data_ptr(), wt.data_ptr(), K, R * S, C, first)
-            tile_tensor += [i] * n_tiles
-            first += n_tiles
-            self.views[w.data_ptr()] = wt
-        self.n_tiles, self.total = first, float(total)
-        self.desc = torch.from_numpy(desc.view(np.uint8).copy()).to(dev)
-        self.tile_tensor = torch.tensor(tile_tensor, dtype=torch.int32, device=dev)
-
-    def run(self):
-        check(lib.nnl_conv2d_weight_transpose_multi(ptr(self.desc), ptr(self.tile_tensor), self.n_tiles, self.total, stream()))
+    """Call right before the forward of a TRAINING step (filter_window does): opens the window and transforms the Winograd filters of
+    every HipConv2d whose forward took a Winograd kernel in the last step, in one launch; valid until finish_backward()."""
+    _filters(model).prepare_forward()
 
 
 def prepare_backward(model):
-    """Call right before `loss.backward()` (Learner does): transposes the filters of every HipConv2d of `model` in ONE launch
-    (one small launch per layer otherwise) and exposes them to the convolutions' backward until finish_backward().  The
-    window is deliberately that short: a filter modified later can never meet a stale transpose."""
-    mods = _conv_mods(model)
-    ws = [m.weight for m in mods
-          if m.weight.is_cuda and m.weight.dim() == 4 and m.weight.shape[1] % 4 == 0
-          and m.weight.shape[0] % 4 == 0 and m.weight.dtype == torch.float32
-          and m.weight.is_contiguous(memory_format=torch.channels_last)]
-    if len(ws) < 2 or sum(w.requires_grad for w in ws) * 2 < len(ws):
-        return
-    key = tuple((w.data_ptr(), tuple(w.shape)) for w in ws)
-    batch = getattr(model, '_nnl_wt_batch', None)
-    if batch is None or batch.key != key:
-        if torch.cuda.is_current_stream_capturing():
-            return                                      # (buffers are built during the eager warm-up steps)
-        batch = _WtBatch(ws)
-        object.__setattr__(model, '_nnl_wt_batch', batch)
-    batch.run()
-    _WT_ACTIVE.clear()
-    _WT_ACTIVE.update(batch.views)
-    # the dgrad Winograd filters U' [C,4,3,K] of the layers whose last dgrad took the Winograd kernel, from the transposes above
-    _WINO_U_BWD.clear()
-    if os.environ.get('NNL_WINO_PREPARE', '1') != '0':
-        items = [(w.data_ptr(), batch.views[w.data_ptr()], 1, mode) for w in ws if w.shape[2] == 3 and w.shape[3] == 3
-                 for mode in sorted(_wino_modes(w.data_ptr(), 1))]
-        _run_wino_batch(model, '_nnl_wino_bwd_batch', items, _WINO_U_BWD)
+    """Call right before `loss.backward()` (filter_window's backward does; opens the window itself when prepare_forward did not):
+    transposes the filters of every HipConv2d of `model` in ONE launch (one small launch per layer otherwise), transforms the dgrad
+    Winograd filters from them, and exposes both to the convolutions' backward until finish_backward()."""
+    _filters(model).prepare_backward()
 
 
 def finish_backward():
     "closes the window of everything prepare_forward / prepare_backward exposed (the optimizer is about to change the weights)"
-    _WT_ACTIVE.clear()
-    _WT_PADDED.clear()
-    _WINO_U_FWD.clear()
-    _WINO_U_BWD.clear()
-    _WINO_IN_STEP[0] = False
+    global _OPEN
+    if _OPEN is not None:
+        for views in (*_OPEN.u, _OPEN.wt, _OPEN.wt_padded):
+            views.clear()
+        _OPEN = None
 
 
-def _wino_pref(key_ptr, which, g):
-    """which kernel nnl_conv2d_fwd (which = 0) / nnl_conv2d_dgrad (1) takes for g: 0 direct, 1 Winograd 1-D, 2 Winograd 2-D.  Remembered
-    per weight for the next step's batch (a weight shared between geometries keeps the mode of its LAST call; calls whose mode
-    differs transform their own filter: the prepared buffer is only handed over when its size is that of the mode's layout)"""
-    pref = int(lib.nnl_conv2d_wino_preferred(g, which)) if (g.R == 3 and g.S == 3 and g.stride == 1) else 0
-    # a forward is recorded only inside a training step (prepare_forward .. finish_backward): an evaluation forward at another batch size
-    # must not change the next training step's batch (a rebuild would free buffers a captured step still reads).  Grad mode cannot tell
-    # them apart here: autograd runs every Function's forward with it off.  A dgrad only runs in a backward pass: it always records.
-    if (pref or key_ptr in _WINO_PREF) and (which == 1 or _WINO_IN_STEP[0]):
-        if len(_WINO_PREF) > 8192:
-            _WINO_PREF.clear()
-        e = _WINO_PREF.setdefault(key_ptr, [[-1, set()], [-1, set()]])[which]
-        if e[0] != _WINO_GEN[0]:                         # first call of this training step (prepare_forward opens a new one): forget the old modes
-            e[0], e[1] = _WINO_GEN[0], set()
-        if pref:
-            e[1].add(pref)
-    return pref
+def prepared_batches(model):
+    """the persistent filter batches (_FilterBatch) the last prepare_forward / prepare_backward of `model` ran.  A captured step bakes
+    raw pointers to their buffers and descriptor tables into its graph and must keep them alive (Learner._GraphedStep): the next step
+    at another batch size may replace the model's batch when the layers' Winograd modes change."""
+    return tuple(_filters(model).batches.values())
+
+
+def prepared_filter_counts():
+    "(forward U, dgrad U', W^T) views the open window exposes to the convolutions; zeros when none is open"
+    f = _OPEN or _CLOSED
+    return len(f.u[0]), len(f.u[1]), len(f.wt)
+
+
+@contextlib.contextmanager
+def filter_window(model):
+    """with ops.filter_window(model) as backward: loss = loss_func(model(x), y); backward(loss)
+    One training step's prepared-filter window: entering is prepare_forward, backward(loss) is prepare_backward + loss.backward(), and
+    leaving — also by an exception anywhere in the body — is finish_backward: the window never outlives a failed step, whose next
+    forward may follow a weight change."""
+    def backward(loss):
+        prepare_backward(model)
+        loss.backward()
+    prepare_forward(model)
+    try:
+        yield backward
+    finally:
+        finish_backward()
 
 
 # Gradient buffers whose rows are ALREADY padded with zeros to the GEMM granularity (the softmax-CE backward at V % 16 != 0, the
@@ -651,23 +670,24 @@ def _conv_dgrad_operands(dy4, w4, g4, K):
     transpose comes from the caches of prepare_backward's window where it can"""
     ktail = g4.R == 1 and g4.S == 1 and g4.K % 4 == 0 and os.environ.get('NNL_IGEMM_KTAIL', '1') != '0'     # the tap kernel masks the k tail itself
     dyd, gd, padk, wkey = dy4, g4, 0, None
+    f = _OPEN or _CLOSED                     # (f.wt is non-empty only inside the backward window, after the batched transposes)
     if g4.K % 16 != 0 and g4.K >= 32 and not ktail:
         # dgrad reduces over K: the tap-table kernel needs K % 16 == 0 (RetinaNet's 36- / 180-channel output convs would
         # fall back to the first-generation kernel, ~2.5x slower); zero channels cost one copy of dy
         padk = 16 - g4.K % 16
         dyd, gd = torch.nn.functional.pad(dy4, (0, padk)), _with_k(g4, g4.K + padk)
         wkey = (w4.data_ptr(), tuple(w4.shape), padk)
-        wt = _WT_PADDED.get(wkey) if _WT_ACTIVE else None      # a shared filter (RetinaNet's output convs on five levels): padded + transposed ONCE per backward pass
+        wt = f.wt_padded.get(wkey) if f.wt else None           # a shared filter (RetinaNet's output convs on five levels): padded + transposed ONCE per backward pass
     else:
-        wt = _WT_ACTIVE.get(w4.data_ptr()) if g4.K == K else None
+        wt = f.wt.get(w4.data_ptr()) if g4.K == K else None
         if wt is not None and tuple(wt.shape) != (g4.C, g4.R, g4.S, g4.K):
             wt = None
     if wt is None:
         wd = torch.nn.functional.pad(w4, (0, 0, 0, 0, 0, 0, 0, padk)) if padk else w4
         wt = torch.empty((gd.C, gd.R, gd.S, gd.K), dtype=torch.float32, device=dy4.device)
         check(lib.nnl_conv2d_weight_transpose(ptr(wd), ptr(wt), gd.K, gd.R, gd.S, gd.C, stream()))
-        if wkey is not None and _WT_ACTIVE:                   # (only inside the prepare_backward .. finish_backward window: weights are fixed there)
-            _WT_PADDED[wkey] = wt
+        if wkey is not None and f.wt:                         # (only inside the prepare_backward .. finish_backward window: weights are fixed there)
+            f.wt_padded[wkey] = wt
     return dyd, wt, gd
 
 
@@ -685,10 +705,7 @@ def _conv_dgrad(st, dy4, w4, g4, K):
     fuse = shortcut is not None and g.K % 16 == 0 and g.R * g.S <= 49 and shortcut.numel() == dxn.numel() \
         and ((g.stride == 1 and (g.S <= 32 or g.pad <= 127)) or (g.stride == 2 and g.R == 3 and g.S == 3 and g.pad == 1))
     # a channel-padded dgrad transforms its own filter: not recorded under the weight (key 0; a 1x1 filter's mode 0 records nothing)
-    wmode = _wino_pref(w4.data_ptr() if g.K == K else 0, 1, g)
-    u = _WINO_U_BWD.get((w4.data_ptr(), wmode)) if (wmode and g.K == K) else None
-    if u is not None and u.numel() != _wino_u_numel(g.C, g.K, wmode):
-        u = None
+    u = (_OPEN or _CLOSED).wino(w4.data_ptr() if g.K == K else 0, 1, g)
     check(lib.nnl_conv2d_dgrad_pre(ptr(dyd), ptr(wt), ptr(dxn), g, ptr(shortcut) if fuse else None, ptr(dws), wsb,
                                    ptr(_tile_counters(dyd.device) if wsb else None), ptr(u), stream()))
     if shortcut is not None and not fuse:
@@ -742,17 +759,14 @@ class _Conv2d(torch.autograd.Function):
     def forward(ctx, x, weight, bias, stride, pad, relu, slot=None, bn_pivot=None, give_slot=None):
         require_cuda(x, weight, bias)
         xn, wn, b, g, y = _conv_operands(x, weight, bias, stride, pad)
-        N, K, C = g.N, g.K, g.C
+        N, K = g.N, g.K
         ctx.st = _conv_state(x, weight, bias, g, relu, slot, give_slot)
         wsb = int(lib.nnl_conv2d_fwd_workspace_bytes(g))         # balanced-schedule slabs (0 when the plain launch is used)
         ws = _workspace(wsb, x.device)                           # None at 0 bytes: no Winograd kernel without a workspace
         part, rows = None, _lib.i32(0)
         if bn_pivot is not None:                                  # BatchNorm statistics from the conv epilogue (include/nnl.h)
             part = torch.empty(((N * g.P * g.Q + 63) // 64) * K * 2, dtype=torch.float32, device=x.device)
-        wmode = _wino_pref(wn.data_ptr(), 0, g)
-        u = _WINO_U_FWD.get((wn.data_ptr(), wmode)) if wmode else None   # the filter prepared for this step, if any — in THIS call's layout
-        if u is not None and u.numel() != _wino_u_numel(K, C, wmode):
-            u = None
+        u = (_OPEN or _CLOSED).wino(wn.data_ptr(), 0, g)                   # the filter prepared for this step, if any — in THIS call's layout
         check(lib.nnl_conv2d_fwd_pre(ptr(xn), ptr(wn), ptr(b), ptr(y), g, int(relu), ptr(ws), wsb, ptr(_tile_counters(x.device) if wsb else None),
                                      ptr(part), ptr(bn_pivot), ctypes.byref(rows) if part is not None else None, ptr(u), stream()))
         if part is None or rows.value == 0:

@@ -403,24 +403,65 @@ def test_prepared_winograd_filters_match_per_call_transform(mode, monkeypatch):
         for p in net.parameters():
             p.grad = None
         ops.prepare_forward(net)
-        n_fwd = len(ops._WINO_U_FWD)
+        n_fwd = ops.prepared_filter_counts()[0]
         y = net(xg)
         ops.prepare_backward(net)
-        n_bwd = len(ops._WINO_U_BWD)
+        n_bwd = ops.prepared_filter_counts()[1]
         try:
             y.backward(dy)
         finally:
             ops.finish_backward()
-        assert not ops._WINO_U_FWD and not ops._WINO_U_BWD and not ops._WT_ACTIVE, 'the prepared-filter window stayed open'
+        assert ops.prepared_filter_counts() == (0, 0, 0), 'the prepared-filter window stayed open'
         return y.detach(), xg.grad, [p.grad.clone() for p in net.parameters()], n_fwd, n_bwd
 
-    ref = step(False)                       # also teaches _WINO_PREF which layers take the Winograd kernel
+    ref = step(False)                       # also teaches the net's filter object which layers take the Winograd kernel
     assert ref[3] == 0 and ref[4] == 0
     got = step(True)
     assert got[3] == 2 and got[4] == 2, 'prepared filters were not built for both layers (fwd %d, dgrad %d)' % (got[3], got[4])
     assert torch.equal(got[0], ref[0]) and torch.equal(got[1], ref[1])
     for a, b in zip(got[2], ref[2]):
         assert torch.equal(a, b)
+    monkeypatch.delenv('NNL_CONV_WINO'); lib.nnl_reload_env()
+
+
+@pytest.mark.parametrize('mode', ['2', '3'], ids=['winograd', 'winograd2d'])
+def test_failed_step_leaves_no_prepared_filter_behind(mode, monkeypatch):
+    """A step that raises between its forward and its backward (here: from the loss, in Python) must leave the prepared-filter window
+    closed (ops.filter_window): the weights are then changed in place — same data_ptr, as load_state_dict does — and a no_grad forward
+    must compute with the NEW weights, bitwise as with NNL_WINO_PREPARE=0.  A transformed filter left behind from the failed step
+    would be found by address and give the result of the old weights."""
+    from neuralnetworklibrary_amd import ops
+    from neuralnetworklibrary_amd._lib import lib
+    import torch.nn as nn
+    from neuralnetworklibrary_amd.Applications.VisionModels.retinanet import HipConv2d
+    monkeypatch.setenv('NNL_CONV_WINO', mode); lib.nnl_reload_env()
+    monkeypatch.setenv('NNL_WINO_PREPARE', '1')
+    torch.manual_seed(3)
+    net = nn.Sequential(HipConv2d(64, 128, 3, padding=1), nn.ReLU(), HipConv2d(128, 64, 3, padding=1)).to(DEV)
+    x = torch.randn(4, 64, 20, 18, device=DEV)
+    dy = torch.randn(4, 64, 20, 18, device=DEV)
+
+    def raising_loss(y):
+        raise RuntimeError('the loss failed')
+
+    with ops.filter_window(net) as backward:             # one full step teaches the modes
+        backward((net(x) * dy).sum())
+    with pytest.raises(RuntimeError, match='the loss failed'):
+        with ops.filter_window(net) as backward:
+            y = net(x)
+            assert ops.prepared_filter_counts()[0] == 2, 'the failed step ran without prepared filters: the test checks nothing'
+            backward(raising_loss(y))
+    assert ops.prepared_filter_counts() == (0, 0, 0) and ops._OPEN is None, 'the failed step left the prepared-filter window open'
+    ptrs = [p.data_ptr() for p in net.parameters()]
+    with torch.no_grad():
+        for m in (net[0], net[2]):
+            m.weight.mul_(1.5)
+        assert [p.data_ptr() for p in net.parameters()] == ptrs
+        got = net(x)
+        monkeypatch.setenv('NNL_WINO_PREPARE', '0')
+        want = net(x)
+    assert not torch.equal(got, y.detach()), 'scaling the weights did not change the output'
+    assert torch.equal(got, want), 'the forward after the failed step did not use the modified weights'
     monkeypatch.delenv('NNL_CONV_WINO'); lib.nnl_reload_env()
 
 

@@ -475,7 +475,7 @@ def test_fit_loop_runs_ahead_of_the_gpu_with_per_step_schedules():
 class _TwoConvNet(nn.Module):
     """two 3x3 128 -> 128 HipConv2d + BatchNorm + ReLU at 28 x 28, concat pooling, a linear head.  At 28 x 28 the dispatcher takes the
     2-D Winograd kernel at 32 images, the 1-D kernel at 24 and the direct kernel at 5 (pinned on the CPU by
-    test_conv_planner_cpu.py::test_modes_the_graph_rebuild_test_relies_on), so the prepared-filter batch (ops._WinoBatch) changes
+    test_conv_planner_cpu.py::test_modes_the_graph_rebuild_test_relies_on), so the prepared-filter batch (ops._FilterBatch) changes
     with the batch size."""
 
     def __init__(self, n_classes=10):
@@ -566,18 +566,18 @@ def test_replay_across_batch_sizes_keeps_captured_filter_buffers():
                         assert r() is not None, ('epoch %d, %d images: the %s Winograd filter batch captured with this signature\'s graph '
                                                  'was freed (a rebuild at another batch size replaced it); its replay would read freed '
                                                  'buffers' % (epoch + 1, n, what))
-                stale = replay and model._nnl_wino_fwd_batch is not captured[n][0]()
+                stale = replay and model._nnl_filters.batches['fwd'] is not captured[n][0]()
                 before = {k: v.detach().cpu().clone() for k, v in model.named_parameters()} if stale else None
                 n_before = _n_captured(learner)
                 losses.append(learner.train1minibatch(x, y, lr, mom_batch=0.9))
                 if graphs and _n_captured(learner) > n_before:
-                    fwd, bwd = getattr(model, '_nnl_wino_fwd_batch', None), getattr(model, '_nnl_wino_bwd_batch', None)
+                    fwd, bwd = model._nnl_filters.batches.get('fwd'), model._nnl_filters.batches.get('bwd')
                     assert fwd is not None and bwd is not None, 'the captured step ran no prepared Winograd filter batch'
                     captured[n] = (weakref.ref(fwd), weakref.ref(bwd))
                     del fwd, bwd
                     if first_fwd is None:
                         first_fwd = captured[n][0]
-                if first_fwd is not None and model._nnl_wino_fwd_batch is not first_fwd():
+                if first_fwd is not None and model._nnl_filters.batches['fwd'] is not first_fwd():
                     rebuilt = True
                 if stale:
                     checks.append((epoch + 1, n, losses[-1], _two_conv_loss_fp64(before, x, y)))
@@ -609,7 +609,7 @@ def test_eval_forward_does_not_rebuild_the_training_filter_batches():
         model = learner.model
         for i in range(3):
             learner.train1minibatch(*batches[32][i], lr, mom_batch=0.9)
-        fwd, bwd = model._nnl_wino_fwd_batch, model._nnl_wino_bwd_batch
+        fwd, bwd = model._nnl_filters.batches['fwd'], model._nnl_filters.batches['bwd']
         if evals:
             model.eval()
             with torch.no_grad():
@@ -617,7 +617,7 @@ def test_eval_forward_does_not_rebuild_the_training_filter_batches():
                     learner.predict1minibatch(batches[n][0][0])
             model.train()
         loss = learner.train1minibatch(*batches[32][0], lr, mom_batch=0.9)
-        same = (model._nnl_wino_fwd_batch is fwd, model._nnl_wino_bwd_batch is bwd)
+        same = (model._nnl_filters.batches['fwd'] is fwd, model._nnl_filters.batches['bwd'] is bwd)
         return loss, [p.detach().cpu().clone() for p in model.parameters()], same
 
     l0, p0, same0 = run(())
