@@ -199,8 +199,8 @@ int nnl_debug_conv_plan_times(int N, int H, int W, int C, int K, double* out);
  *   nnl_debug_route_record(enable): start (1) or stop (0) recording on the CALLING THREAD; either way the buffer is cleared.
  *   nnl_debug_route_collect(out, n): copies the notes recorded since ("name;name;...", NUL-terminated) into out[n] and clears the buffer;
  *     returns the number of notes, or NNL_ERR_INVALID_ARG when out is NULL or too small (the buffer is kept then).
- * A name is `kernel<template arguments>:plan flags` and maps to one launch in conv2d.hip / wino.hip / wino2.hip; text after an `@`
- * is a numeric detail of the plan (slice counts).  Recording changes no launch; when it is off a note costs one branch. */
+ * A name is `kernel<template arguments>:plan flags` and maps to one launch in conv2d.hip / wino.hip / wino2.hip (lstm_*: to one call
+ * of nnl_lstm_fwd / nnl_lstm_bwd, see nnl_debug_lstm_plan); text after an `@` is a numeric detail of the plan (slice counts).  Recording changes no launch; when it is off a note costs one branch. */
 int nnl_debug_route_record(int enable);
 int nnl_debug_route_collect(char* out, size_t n);
 /* dw[K,R,S,C] = sum_{n,p,q} dy[n,p,q,k] * x[n,p*stride-pad+r,q*stride-pad+s,c]; split-K partial slabs are
@@ -477,6 +477,21 @@ int nnl_lstm_bwd(const float* dy, const float* dhT, const float* dcT, const floa
 /* The partition (KG x NG workgroups, k-slice Ks, column slice Ns, NT column tiles -> out5) the 2-D persistent BPTT kernel
  * (csrc/lstm_bptt2.hip) would use for this shape; returns 0 when the shape does not fit it.  Host-only. */
 int nnl_debug_lstm_bptt2_plan(int64_t B, int64_t H, int32_t* out5);
+/* What the host code of csrc/lstm.hip, lstm_persist.hip and lstm_bptt2.hip decides for batch B and hidden size H (tests/lstm_cases.py
+ * derives from it which loops and template instantiations a case reaches).  Host only: no HIP call, works without a device.  It calls
+ * the functions the entry points call (make_plan, shape_of, plan2).  out14:
+ *   [0] Hp    padded hidden size                                    [1] Gp   padded gate columns
+ *   [2] tf    tiles of a per-timestep forward launch                [3] tb   tiles of a per-timestep backward GEMM
+ *   [4] sf    k slices of the per-timestep forward                  [5] sb   k slices (slabs) of the per-timestep backward
+ *   [6] 1 when the persistent kernels (lstm_persist.hip) take the shape, else 0
+ *   [7] U     hidden units per workgroup = their template argument  [8] NWG  their workgroups   (both reported also where [6] is 0)
+ *   [9] 1 when the 2-D partitioned BPTT (lstm_bptt2.hip) takes the shape, else 0; then
+ *   [10] NT, [11] PB  its template arguments                        [12] KG, [13] NG  its partition   (all four 0 where [9] is 0)
+ * Which of these kernels a call runs depends further on NNL_LSTM_PERSIST, NNL_LSTM_FUSED_BWD and err_flag; the route notes
+ * (nnl_debug_route_record) name the one that ran: lstm_persist_fwd<U>@NWG, lstm_step_fwd@sf, lstm_bptt2<NT,PB>@KGxNG,
+ * lstm_persist_bwd<U>@NWG, lstm_step_bwd@sb, lstm_step_bwd:fused@sb — one per call, written after its launches were issued.
+ * Returns 1, or 0 (out14 untouched) for sizes the entry points refuse, B >= 2^24 or out14 == NULL. */
+int nnl_debug_lstm_plan(int64_t B, int64_t H, int32_t* out14);
 
 /* nn.MSELoss(reduction='mean') — `loss_func_dict['cont']` (General/Learner.py:20), the loss of the collaborative-filtering and
  * structured-data heads: *loss = mean((pred - target)^2) over n fp32 elements (one launch up to 65 536 samples, fixed-order sum);

@@ -21,6 +21,7 @@
 
 // the persistent (one cooperative launch per layer and direction) path: lstm_persist.hip
 bool nnl_lstm_persist_ok(long B, long H, long Kp, long Gp);
+bool nnl_lstm_persist_shape(long B, long H, long Kp, long Gp, int* U, int* NWG);
 size_t nnl_lstm_persist_ws_floats(long T, long Kp, long Gp);
 hipError_t nnl_lstm_persist_fwd(const float* gx, const float* w_hh_pad, const float* h0, const float* c0, float* y, float* cy,
                                 float* gates, long T, long B, long H, long Kp, long Gp, float* ws, int* err, hipStream_t s);
@@ -30,6 +31,7 @@ hipError_t nnl_lstm_persist_bwd(const float* dy, const float* dhT, const float* 
 
 // the 2-D partitioned persistent BPTT (round 4): lstm_bptt2.hip
 bool nnl_lstm_bptt2_ok(long B, long H, long Gp);
+bool nnl_lstm_bptt2_shape(long B, long H, long Gp, int* NT, int* PB, int* KG, int* NG);
 size_t nnl_lstm_bptt2_ws_floats(long T, long B, long H, long Gp);
 hipError_t nnl_lstm_bptt2(const float* dy, const float* dhT, const float* dcT, const float* gates, const float* cy, const float* c0,
                           const float* w_hh_t_pad, float* dgates_pad, float* dh0, float* dc0, long T, long B, long H, long Gp,
@@ -197,6 +199,18 @@ extern "C" size_t nnl_lstm_workspace_bytes(int64_t T, int64_t B, int64_t H) {
   return lstm_ws_floats(make_plan(B, H), T, B, H) * sizeof(float);
 }
 
+// for tools / tests: what make_plan, shape_of (lstm_persist.hip) and plan2 (lstm_bptt2.hip) decide for a shape; no HIP call
+extern "C" int nnl_debug_lstm_plan(int64_t B, int64_t H, int32_t* out14) {
+  if (out14 == nullptr || B <= 0 || H <= 0 || 4 * H >= (1 << 24) || B >= (1 << 24)) return 0;
+  const Plan p = make_plan(B, H);
+  int U = 0, NWG = 0, NT = 0, PB = 0, KG = 0, NG = 0;
+  const bool pok = nnl_lstm_persist_shape(B, H, p.Hp, p.Gp, &U, &NWG);
+  const bool ok2 = nnl_lstm_bptt2_shape(B, H, p.Gp, &NT, &PB, &KG, &NG);
+  const int32_t v[14] = {p.Hp, p.Gp, p.tf, p.tb, p.sf, p.sb, pok ? 1 : 0, U, NWG, ok2 ? 1 : 0, NT, PB, KG, NG};
+  memcpy(out14, v, sizeof(v));
+  return 1;
+}
+
 extern "C" int nnl_lstm_fwd(const float* gx, const float* w_hh_pad, const float* h0, const float* c0, float* y, float* cy,
                             float* gates, int64_t T, int64_t B, int64_t H, void* workspace, size_t workspace_bytes,
                             int32_t* err_flag, void* stream) {
@@ -236,6 +250,7 @@ extern "C" int nnl_lstm_fwd(const float* gx, const float* w_hh_pad, const float*
     int st = nnl_internal_lstm_step(q, 1, s);
     if (st) return st;
   }
+  NNL_ROUTE("lstm_step_fwd@%d", p.sf);
   return NNL_OK;
 }
 
@@ -308,5 +323,6 @@ extern "C" int nnl_lstm_bwd(const float* dy, const float* dhT, const float* dcT,
   }
   hipLaunchKernelGGL(sum_slabs_kernel, dim3(ew_grid(BH)), dim3(kBlock), 0, s, (const float*)slabs, p.sb, BH, dh0, BH);
   NNL_CHECK_LAUNCH();
+  NNL_ROUTE("lstm_step_bwd%s@%d", fused_bwd ? ":fused" : "", p.sb);
   return NNL_OK;
 }

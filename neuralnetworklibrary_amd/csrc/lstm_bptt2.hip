@@ -368,6 +368,10 @@ hipError_t launch2(Bptt2& p, size_t lds, hipStream_t s) {
   return hipLaunchCooperativeKernel(reinterpret_cast<const void*>(kernel), dim3(p.NWG), dim3(kBlock), args, (unsigned)lds, s);
 }
 
+// partial polls of phase B in batches of 8 or 16 granules (measured: KG = 16 -> 2 x 8: 15.9 vs 16.3 us per step at H = 1150;
+// KG = 10 -> one batch of 16: 9.5 vs 10.1 at H = 400)
+int poll_batch(const Plan2& pl) { return pl.KG % 8 == 0 ? 8 : 16; }
+
 size_t xp_granules(const Plan2& pl) { return (size_t)kSlots * pl.NG * pl.KG * kRows * 16 * pl.NT; }
 size_t xt_granules(long Gp) { return (size_t)kSlots * kRows * Gp; }
 
@@ -391,6 +395,14 @@ extern "C" int nnl_debug_lstm_bptt2_plan(int64_t B, int64_t H, int32_t* out5) {
   return 1;
 }
 
+// for nnl_debug_lstm_plan: the template arguments the launch below picks, and the partition
+bool nnl_lstm_bptt2_shape(long B, long H, long Gp, int* NT, int* PB, int* KG, int* NG) {
+  const Plan2 pl = plan2(B, H, Gp);
+  if (!pl.ok) return false;
+  *NT = pl.NT; *PB = poll_batch(pl); *KG = pl.KG; *NG = pl.NG;
+  return true;
+}
+
 // returns hipSuccess when the cooperative launch was issued; any other value: nothing was launched, take another path
 hipError_t nnl_lstm_bptt2(const float* dy, const float* dhT, const float* dcT, const float* gates, const float* cy, const float* c0,
                           const float* w_hh_t_pad, float* dgates_pad, float* dh0, float* dc0, long T, long B, long H, long Gp,
@@ -407,17 +419,19 @@ hipError_t nnl_lstm_bptt2(const float* dy, const float* dhT, const float* dcT, c
   p.KG = pl.KG; p.NG = pl.NG; p.Ks = pl.Ks; p.Ns = pl.Ns; p.NWG = pl.KG * pl.NG; p.chunk = pl.chunk;
   hipError_t e = hipMemsetAsync(p.xp, 0, sizeof(u64) * (xp_granules(pl) + xt_granules(Gp)), s);     // tag 0 = nothing yet
   if (e != hipSuccess) return e;
-  // partial polls of phase B in batches of 8 or 16 granules (measured: KG = 16 -> 2 x 8: 15.9 vs 16.3 us per step at H = 1150;
-  // KG = 10 -> one batch of 16: 9.5 vs 10.1 at H = 400)
-  const int pb = pl.KG % 8 == 0 ? 8 : 16;
-#define NNL_BPTT2_CASE(N) case N: return pb == 8 ? launch2<N, 8>(p, pl.lds, s) : launch2<N, 16>(p, pl.lds, s)
+  const int pb = poll_batch(pl);
+  hipError_t st;
+#define NNL_BPTT2_CASE(N) case N: st = pb == 8 ? launch2<N, 8>(p, pl.lds, s) : launch2<N, 16>(p, pl.lds, s); break
   switch (pl.NT) {
     NNL_BPTT2_CASE(1);
     NNL_BPTT2_CASE(2);
     NNL_BPTT2_CASE(3);
     NNL_BPTT2_CASE(4);
     NNL_BPTT2_CASE(5);
-    default: return pb == 8 ? launch2<6, 8>(p, pl.lds, s) : launch2<6, 16>(p, pl.lds, s);
+    // NT = 6 comes only with KG % 8 == 0 (tests/test_lstm_cases_cpu.py holds that against plan2 for H <= 4096); otherwise: not taken
+    default: static_assert(kMaxNT == 6, "one case per NT"); st = pb == 8 ? launch2<6, 8>(p, pl.lds, s) : hipErrorInvalidValue; break;
   }
 #undef NNL_BPTT2_CASE
+  if (st == hipSuccess) NNL_ROUTE("lstm_bptt2<%d,%d>@%dx%d", pl.NT, pb, pl.KG, pl.NG);
+  return st;
 }

@@ -44,7 +44,8 @@ namespace {
 
 constexpr int kBlock = 256;
 constexpr int kLanes = 64;         // batch rows per workgroup = lanes of a wave
-constexpr int kMaxU = 8;           // units per workgroup: 4U <= 32 gate columns (8 MFMA column groups)
+constexpr int kMaxU = 5;           // units per workgroup: shape_of's LDS bound (16 U (Kp + 512) bytes <= 150 KiB) admits nothing above H = 1280
+                                   // (tests/test_lstm_cases_cpu.py holds that against the planner)
 constexpr int kSpinLimit = 1 << 22;
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
@@ -107,7 +108,7 @@ __device__ __forceinline__ void panel(const float* __restrict__ xs, const float*
     for (int kk = 0; kk < 4; ++kk) {
       const float a = a4[kk], b = b4[kk];
 #define NNL_MFMA_G(G) if constexpr (NG > G) acc[G] = __builtin_amdgcn_mfma_f32_4x4x1f32(a, b, acc[G], 4, G, 0);
-      NNL_MFMA_G(0) NNL_MFMA_G(1) NNL_MFMA_G(2) NNL_MFMA_G(3) NNL_MFMA_G(4) NNL_MFMA_G(5) NNL_MFMA_G(6) NNL_MFMA_G(7)
+      NNL_MFMA_G(0) NNL_MFMA_G(1) NNL_MFMA_G(2) NNL_MFMA_G(3) NNL_MFMA_G(4)      // NG <= kMaxU
 #undef NNL_MFMA_G
     }
   };
@@ -165,7 +166,7 @@ __device__ __forceinline__ void panel_single(const float* __restrict__ xs, const
     for (int kk = 0; kk < 4; ++kk) {
       const float a = a4[kk], b = xb_[j][kk];
 #define NNL_MFMA_G(G) if constexpr (NG > G) acc[G] = __builtin_amdgcn_mfma_f32_4x4x1f32(a, b, acc[G], 4, G, 0);
-      NNL_MFMA_G(0) NNL_MFMA_G(1) NNL_MFMA_G(2) NNL_MFMA_G(3) NNL_MFMA_G(4) NNL_MFMA_G(5) NNL_MFMA_G(6) NNL_MFMA_G(7)
+      NNL_MFMA_G(0) NNL_MFMA_G(1) NNL_MFMA_G(2) NNL_MFMA_G(3) NNL_MFMA_G(4)      // NG <= kMaxU
 #undef NNL_MFMA_G
     }
   }
@@ -446,6 +447,13 @@ hipError_t coop_launch(K kernel, int nwg, size_t lds, P& p, hipStream_t s, int b
 // ---- entry points used by lstm.hip ----------------------------------------------------------------------------------
 bool nnl_lstm_persist_ok(long B, long H, long Kp, long Gp) { return shape_of(B, H, Kp, Gp).ok; }
 
+// for nnl_debug_lstm_plan: units per workgroup and workgroups as shape_of computes them (also where it refuses the shape)
+bool nnl_lstm_persist_shape(long B, long H, long Kp, long Gp, int* U, int* NWG) {
+  const Shape sh = shape_of(B, H, Kp, Gp);
+  *U = sh.U; *NWG = sh.NWG;
+  return sh.ok;
+}
+
 // extra workspace of the persistent path (floats): forward [T+1][Kp][64] + T ints; backward [T][Gp][64] + T ints
 size_t nnl_lstm_persist_ws_floats(long T, long Kp, long Gp) {
   const size_t f = (size_t)(T + 1) * Kp * kLanes + (size_t)T + 16;
@@ -468,16 +476,16 @@ hipError_t nnl_lstm_persist_fwd(const float* gx, const float* w_hh_pad, const fl
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(exchange_prologue_kernel, dim3((unsigned)nnl_cdiv(H * kLanes, 256)), dim3(256), 0, s, h0, p.xT, (int)B, (int)H,
                      (int)Kp, (int)(T + 1));
+  hipError_t st;
   switch (sh.U) {
-    case 1: return coop_launch(lstm_persist_fwd_kernel<1>, sh.NWG, sh.lds_fwd, p, s, kFwdBlock);
-    case 2: return coop_launch(lstm_persist_fwd_kernel<2>, sh.NWG, sh.lds_fwd, p, s, kFwdBlock);
-    case 3: return coop_launch(lstm_persist_fwd_kernel<3>, sh.NWG, sh.lds_fwd, p, s, kFwdBlock);
-    case 4: return coop_launch(lstm_persist_fwd_kernel<4>, sh.NWG, sh.lds_fwd, p, s, kFwdBlock);
-    case 5: return coop_launch(lstm_persist_fwd_kernel<5>, sh.NWG, sh.lds_fwd, p, s, kFwdBlock);
-    case 6: return coop_launch(lstm_persist_fwd_kernel<6>, sh.NWG, sh.lds_fwd, p, s, kFwdBlock);
-    case 7: return coop_launch(lstm_persist_fwd_kernel<7>, sh.NWG, sh.lds_fwd, p, s, kFwdBlock);
-    default: return coop_launch(lstm_persist_fwd_kernel<8>, sh.NWG, sh.lds_fwd, p, s, kFwdBlock);
+    case 1: st = coop_launch(lstm_persist_fwd_kernel<1>, sh.NWG, sh.lds_fwd, p, s, kFwdBlock); break;
+    case 2: st = coop_launch(lstm_persist_fwd_kernel<2>, sh.NWG, sh.lds_fwd, p, s, kFwdBlock); break;
+    case 3: st = coop_launch(lstm_persist_fwd_kernel<3>, sh.NWG, sh.lds_fwd, p, s, kFwdBlock); break;
+    case 4: st = coop_launch(lstm_persist_fwd_kernel<4>, sh.NWG, sh.lds_fwd, p, s, kFwdBlock); break;
+    default: static_assert(kMaxU == 5, "one case per U"); st = coop_launch(lstm_persist_fwd_kernel<5>, sh.NWG, sh.lds_fwd, p, s, kFwdBlock); break;
   }
+  if (st == hipSuccess) NNL_ROUTE("lstm_persist_fwd<%d>@%d", sh.U, sh.NWG);
+  return st;
 }
 
 hipError_t nnl_lstm_persist_bwd(const float* dy, const float* dhT, const float* dcT, const float* gates, const float* cy,
@@ -495,14 +503,14 @@ hipError_t nnl_lstm_persist_bwd(const float* dy, const float* dhT, const float* 
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(exchange_prologue_kernel, dim3(64), dim3(256), 0, s, (const float*)nullptr, p.dgT, (int)B, (int)(4 * H), (int)Gp,
                      (int)T);
+  hipError_t st;
   switch (sh.U) {
-    case 1: return coop_launch(lstm_persist_bwd_kernel<1>, sh.NWG, sh.lds_bwd, p, s);
-    case 2: return coop_launch(lstm_persist_bwd_kernel<2>, sh.NWG, sh.lds_bwd, p, s);
-    case 3: return coop_launch(lstm_persist_bwd_kernel<3>, sh.NWG, sh.lds_bwd, p, s);
-    case 4: return coop_launch(lstm_persist_bwd_kernel<4>, sh.NWG, sh.lds_bwd, p, s);
-    case 5: return coop_launch(lstm_persist_bwd_kernel<5>, sh.NWG, sh.lds_bwd, p, s);
-    case 6: return coop_launch(lstm_persist_bwd_kernel<6>, sh.NWG, sh.lds_bwd, p, s);
-    case 7: return coop_launch(lstm_persist_bwd_kernel<7>, sh.NWG, sh.lds_bwd, p, s);
-    default: return coop_launch(lstm_persist_bwd_kernel<8>, sh.NWG, sh.lds_bwd, p, s);
+    case 1: st = coop_launch(lstm_persist_bwd_kernel<1>, sh.NWG, sh.lds_bwd, p, s); break;
+    case 2: st = coop_launch(lstm_persist_bwd_kernel<2>, sh.NWG, sh.lds_bwd, p, s); break;
+    case 3: st = coop_launch(lstm_persist_bwd_kernel<3>, sh.NWG, sh.lds_bwd, p, s); break;
+    case 4: st = coop_launch(lstm_persist_bwd_kernel<4>, sh.NWG, sh.lds_bwd, p, s); break;
+    default: st = coop_launch(lstm_persist_bwd_kernel<5>, sh.NWG, sh.lds_bwd, p, s); break;
   }
+  if (st == hipSuccess) NNL_ROUTE("lstm_persist_bwd<%d>@%d", sh.U, sh.NWG);
+  return st;
 }

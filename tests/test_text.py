@@ -213,9 +213,30 @@ def test_embedding_rowmask_bit_exact_and_grad():
     assert float(Wg.grad[1].abs().sum()) == 0.0                            # padding row gets no gradient
 
 
+@pytest.fixture
+def lstm_switches():
+    """setenv for the NNL_LSTM_* switches; afterwards the variables are restored and the library reads them again, so that the value
+    it caches per call site never outlives the test"""
+    import os
+    from neuralnetworklibrary_amd._lib import lib
+    names = ('NNL_LSTM_PERSIST', 'NNL_LSTM_FUSED_BWD')
+    saved = {k: os.environ.get(k) for k in names}
+
+    def setenv(name, value):
+        assert name in names
+        os.environ[name] = value
+    yield setenv
+    for k, v in saved.items():
+        if v is None:
+            os.environ.pop(k, None)
+        else:
+            os.environ[k] = v
+    lib.nnl_reload_env()
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize('fused_bwd,persist', [('0', '1'), ('1', '0'), ('0', '3'), ('0', '0'), ('0', '5')])
-def test_lstm_full_size_recurrence_vs_torch_and_bitwise_repeatable(fused_bwd, persist, monkeypatch):
+def test_lstm_full_size_recurrence_vs_torch_and_bitwise_repeatable(fused_bwd, persist, lstm_switches):
     """BASELINE-size layer (bs 64, bptt 70, 1150 -> 1150) on every recurrence path: the persistent cooperative kernels
     (lstm_persist.hip: 230 workgroups exchange h_t / dgates_t through per-timestep slots and meet at a grid barrier per step —
     a stale read or a missed arrival would show as a run-to-run difference, a large error or the time-out flag) and the
@@ -224,8 +245,8 @@ def test_lstm_full_size_recurrence_vs_torch_and_bitwise_repeatable(fused_bwd, pe
     run-to-run difference or a large error.  Checked bitwise over repeated runs and against torch's LSTM in fp64."""
     from neuralnetworklibrary_amd import ops_text
     from neuralnetworklibrary_amd._lib import lib
-    monkeypatch.setenv('NNL_LSTM_FUSED_BWD', fused_bwd)       # '1': the (slower) fused backward step is kept tested too
-    monkeypatch.setenv('NNL_LSTM_PERSIST', persist)           # 1: persistent forward; 3: + first persistent BPTT; 5: + 2-D partitioned BPTT (lstm_bptt2.hip); 0: per-timestep
+    lstm_switches('NNL_LSTM_FUSED_BWD', fused_bwd)        # '1': the (slower) fused backward step is kept tested too
+    lstm_switches('NNL_LSTM_PERSIST', persist)            # 1: persistent forward; 3: + first persistent BPTT; 5: + 2-D partitioned BPTT (lstm_bptt2.hip); 0: per-timestep
     lib.nnl_reload_env()
     T, B, I, H = 70, 64, 1150, 1150
     g = torch.Generator().manual_seed(3)
@@ -260,7 +281,7 @@ def test_lstm_full_size_recurrence_vs_torch_and_bitwise_repeatable(fused_bwd, pe
 @pytest.mark.gpu
 @pytest.mark.parametrize('persist', ['5'])
 @pytest.mark.parametrize('T,B,I,H', [(12, 20, 48, 100), (70, 64, 1150, 400), (9, 64, 32, 32), (5, 33, 64, 256), (6, 7, 40, 37)])
-def test_lstm_bptt2_partition_shapes_vs_torch_fp64(T, B, I, H, persist, monkeypatch):
+def test_lstm_bptt2_partition_shapes_vs_torch_fp64(T, B, I, H, persist, lstm_switches):
     """The 2-D partitioned persistent BPTT (lstm_bptt2.hip, NNL_LSTM_PERSIST bit 2) on other shapes than the headline's: the
     last AWD-LSTM layer (1150 -> 400), ragged batches (B < 64: masked rows), H not a multiple of the column tile, a k range
     that leaves the padded gate columns to the last slice.  Against torch's LSTM in fp64, bitwise repeatable, and the planner's
@@ -273,7 +294,7 @@ def test_lstm_bptt2_partition_shapes_vs_torch_fp64(T, B, I, H, persist, monkeypa
     KG, NG, Ks, Ns, NT = list(out5)
     Gp = int(lib.nnl_lstm_padded_gates(H))
     assert KG * NG <= 256 and KG * Ks == Gp and NG * Ns >= H and (NG - 1) * Ns < H and 16 * NT >= Ns
-    monkeypatch.setenv('NNL_LSTM_PERSIST', persist)
+    lstm_switches('NNL_LSTM_PERSIST', persist)
     lib.nnl_reload_env()
     g = torch.Generator().manual_seed(T + H)
     x = torch.randn(T, B, I, generator=g) * 0.5
