@@ -551,6 +551,30 @@ int nnl_seq_reg_bwd(const float* h, const float* grad_out, float* dh, int64_t T,
 int nnl_weight_drop(const float* src, int64_t ld_src, const float* mask, float* out, int64_t ld_out, int64_t rows, int64_t H,
                     uint64_t seed, float p, void* stream);
 
+/* ---- K5d: text generation, LanguageModelNet.predict_from_string (Text.py:655-676): batch 1, one timestep, fp32 --------------
+ * One LSTM layer for one token (Text.py:655-676, the T = 1 / B = 1 case of the layer its loop runs): gates = w_ih x + w_hh h + bias
+ * (bias [4H] = b_ih + b_hh, pre-summed), torch's gate order i, f, g, o, c_out = f c + i g, h_out = o tanh(c_out).  One wave per hidden
+ * unit streams its four gate rows with 16-byte loads; a plain launch, no synchronisation between workgroups.  w_ih [4H, ldi] and
+ * w_hh [4H, ldh] hold zeros in columns >= I / >= H; ldi and ldh must be multiples of 4 floats (a 1150-float row is not 16-byte
+ * aligned on odd rows) and cover I / H, and w_ih, w_hh, x, h must be 16-byte aligned: anything else is NNL_ERR_INVALID_ARG and
+ * nothing is launched.  x [ldi] and h [ldh] are zero-padded vectors; h_out [>= H] and c_out [>= H]: only entries < H are written.
+ * h_out must not alias h (every wave reads all of h); c_out may alias c.  x == NULL: the input is row tokens[pos] of emb [V, ld_emb]
+ * (entries < I; ld_emb >= I, any alignment), the id read on the device; an id outside [0, V) reads as a zero row. */
+int nnl_lstm_cell_b1(const float* w_ih, int64_t ldi, const float* w_hh, int64_t ldh, const float* bias, const float* x,
+                     const float* emb, int64_t ld_emb, const int64_t* tokens, int64_t pos, int64_t V, const float* h,
+                     const float* c, float* h_out, float* c_out, int64_t I, int64_t H, void* stream);
+/* The rest of one generated token (Text.py:655-676, lines 667-672): logits l = emb [V, ld_emb] h (the tied decoder; h [E], ld_emb
+ * a multiple of 4 floats, emb 16-byte aligned), p = softmax(l) over ALL V entries, entries < n_special excluded from the choice,
+ * the k largest p in descending order (ties: lower index), fp32 partial sums c_1 .. c_k taken sequentially, and the seeded draw
+ * slot j = #{ m in 1..k-1 : c_m <= u[step] * c_k }: tokens[pos + 1] = index of slot j.  Optional outputs: top_probs [*, k] and
+ * top_indices [*, k] get row `step`; logits_out [V] (debug) gets the logits, which otherwise never leave LDS.  Two launches (slices
+ * of 64 vocabulary rows, then one workgroup that merges them); fixed-order sums, bitwise repeatable.  1 <= k <= 64,
+ * k <= V - n_special; V <= 262 144 and ld_emb <= 8192 (NNL_ERR_UNSUPPORTED above). */
+size_t nnl_lm_next_token_workspace_bytes(int64_t V, int64_t k);
+int nnl_lm_next_token(const float* emb, int64_t ld_emb, const float* h, int64_t V, int64_t E, int64_t k, int64_t n_special,
+                      const float* u, int64_t step, int64_t* tokens, int64_t pos, float* top_probs, int64_t* top_indices,
+                      float* logits_out, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- K5c: attention pooling of TextClassificationDecoder (Text.py:575-609), everything after attn1 ----------------------
  * h = relu(attn1(enc_out)) [T,B,A], w2 [A] and b2 [1] (device: attn2's weight and bias), enc_out [T,B,E], x [B,T] int64 tokens:
  *   s[t,b] = h[t,b,:].w2 + b2;  attn[:,b] = softmax of s[:,b] over the positions with x[b,t] != pad_token (the reference's

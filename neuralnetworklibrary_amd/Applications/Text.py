@@ -7,7 +7,9 @@ decoder GEMM (ops.linear) and the fused softmax-cross-entropy over the vocabular
 Same classes, constructor arguments, state_dict keys (enc.word_embed.embed.weight, enc.lstms.{l}.lstm.{weight_ih_l0,
 bias_ih_l0,bias_hh_l0,weight_hh_l0_raw}, dec.lin.weight tied) and quirks as the reference: hidden dropout is applied
 after EVERY LSTM layer including the last (Text.py:546), hidden state is carried (detached) across batches and never
-reset by the Learner (Text.py:547-550).  spaCy tokenisation / numericalisation (:19-229) is CPU text preparation and
+reset by the Learner (Text.py:547-550).  Text generation (K5d, Text.py:655-676): LanguageModelNet.predict_from_tokens /
+predict_from_string on ops_text.LstmCellB1 and ops_text.LmNextToken (batch 1, one timestep, nothing read back inside the loop).
+spaCy tokenisation / numericalisation (:19-229) is CPU text preparation and
 out of scope.
 """
 import math
@@ -430,6 +432,115 @@ class LanguageModelNet(nn.Module):
 
     def forward(self, x):
         return self.dec(self.enc(x))
+
+    # ---- text generation (Text.py:655-676) -------------------------------------------------------------------------------------
+
+    N_SPECIAL = 4          # the special tokens the reference never generates (`probs_next_token[:4] = 0`, Text.py:668)
+
+    def predict_from_tokens(self, ids, n, k=5, seed=0, refeed=True, return_probs=False):
+        """The next `n` token ids after the prompt `ids` (a list of token ids); returns the prompt plus the n new ids — the loop of
+        the reference's predict_from_string (Text.py:660-676) on HIP kernels: eval(), enc.reset(bs=1) once, then per step softmax
+        over the last position, entries [:4] (special tokens) zeroed, topk(k), one of the k drawn with probabilities
+        top_probs / top_probs.sum(), appended; at the end enc.reset(bs=self.bs).  The model stays in eval mode.
+
+        refeed=True (default) keeps the reference's quirk: EVERY iteration feeds the WHOLE sequence so far through the encoder with
+        the hidden state carried over from the previous iteration.  refeed=False is the usual incremental decoder: the prompt goes
+        through the encoder once, then each step feeds only the newest token through ops_text.lstm_cell_b1 (T = 1, B = 1).  Both end
+        in ops_text.lm_next_token; the token buffer stays on the device and nothing is read back until all n steps are enqueued
+        (one upload of prompt + uniforms, one copy back).
+
+        Two deliberate differences from the reference: (1) the draw is SEEDED instead of coming from torch's global generator:
+        step i uses u_i = float32(np.random.RandomState(seed).random_sample(n)[i]) and picks slot
+        j = #{ m in 1..k-1 : c_m <= u_i * c_k }, c_m the sequential fp32 partial sums of the top probabilities in descending order;
+        (2) tokenisation stays out of scope (as in TextDataset): this method takes ids, predict_from_string a `tokenize` callable.
+
+        return_probs=True: also the per-step top_probs [n, k] (float32) and top_indices [n, k] (int64) as numpy arrays."""
+        ids = [int(v) for v in ids]
+        V = len(self.stoi)
+        n, k = int(n), int(k)
+        if len(ids) == 0:
+            raise ValueError('predict_from_tokens: empty prompt')
+        if n < 1:
+            raise ValueError('predict_from_tokens: n must be at least 1')
+        if k < 1 or k > 64:
+            raise ValueError('predict_from_tokens: k must be in [1, 64]')
+        if k > V - self.N_SPECIAL:
+            raise ValueError('predict_from_tokens: k exceeds the %d tokens that are not special' % (V - self.N_SPECIAL))
+        if min(ids) < 0 or max(ids) >= V:
+            raise ValueError('predict_from_tokens: token id outside [0, %d)' % V)
+        self.eval()
+        self.enc.reset(1)
+        dev = self.enc.word_embed.embed.weight.device
+        L, nk = len(ids), n * k
+        # ONE int64 buffer both ways: tokens [L + n] | uniforms (fp32 view) | top_indices [n, k] | top_probs (fp32 view)
+        o_u = L + n
+        o_idx = o_u + (n + 1) // 2
+        o_p = o_idx + nk
+        host = np.zeros(o_p + (nk + 1) // 2, dtype=np.int64)
+        host[:L] = ids
+        host[o_u:o_idx].view(np.float32)[:n] = np.random.RandomState(seed).random_sample(n).astype(np.float32)
+        try:
+            with torch.no_grad():
+                buf = torch.from_numpy(host).to(dev)
+                tokens, u = buf[:o_u], buf[o_u:o_idx].view(torch.float32)
+                top_idx, top_p = buf[o_idx:o_p], buf[o_p:].view(torch.float32)
+                self._generate_steps(tokens, u, top_p, top_idx, L, n, k, refeed)
+                host = buf.cpu().numpy()
+        finally:
+            self.enc.reset(self.bs)
+        out = [int(v) for v in host[:o_u]]
+        if return_probs:
+            return out, host[o_p:].view(np.float32)[:nk].reshape(n, k).copy(), host[o_idx:o_p].reshape(n, k).copy()
+        return out
+
+    def _generate_steps(self, tokens, u, top_p, top_idx, L, n, k, refeed):
+        "enqueues the n steps of predict_from_tokens on device buffers; no host read (runs under torch.cuda.set_sync_debug_mode('error'))"
+        emb = self.enc.word_embed.embed.weight.detach()
+        V, E = emb.shape
+        emb4 = ops_text.padded_rows(emb)                       # 16-byte rows for the decoder (emb itself when E % 4 == 0)
+        pick = ops_text.LmNextToken(emb4, k, u, tokens, top_p, top_idx, self.N_SPECIAL, E)
+        on = ops_text.stream()
+        x = tokens.view(1, -1)
+
+        def next_token(h, step):
+            pick(h, step, L + step - 1, on)
+
+        if refeed:
+            for i in range(n):
+                next_token(self.enc(x[:, :L + i])[-1, 0], i)
+            return
+        next_token(self.enc(x[:, :L])[-1, 0], 0)
+        if n == 1:
+            return
+        # the padded weight copies, once per call; (h, c) of the prompt into zero-padded ping-pong buffers
+        hbufs = []
+        cells = [[], []]                                        # cells[q][l]: layer l reading its h buffer q, writing buffer 1 - q
+        for l, lstm in enumerate(self.enc.lstms):
+            p = lstm.lstm
+            H = p.hidden_size
+            hb = [torch.zeros((H + 3) // 4 * 4, dtype=torch.float32, device=emb.device) for _ in range(2)]
+            hb[0][:H] = self.enc.h[l].reshape(-1)
+            hbufs.append(hb)
+            w_ih, w_hh = ops_text.padded_rows(p.weight_ih_l0), ops_text.padded_rows(p.weight_hh_l0_raw, w_hh=True)
+            bias = (p.bias_ih_l0 + p.bias_hh_l0).detach().float().contiguous()
+            c = self.enc.c[l].reshape(-1).float().clone()
+            for q in (0, 1):                                    # every layer flips once per step: all read q, all write 1 - q
+                below = hbufs[l - 1][1 - q] if l else None
+                cells[q].append(ops_text.LstmCellB1(w_ih, w_hh, bias, hb[q], c, hb[1 - q], c, p.input_size, H, x=below,
+                                                    emb=None if l else emb, tokens=None if l else tokens))
+        for i in range(1, n):
+            q = (i - 1) & 1
+            for cell in cells[q]:
+                cell(L + i - 1, on)
+            next_token(hbufs[-1][1 - q], i)
+
+    def predict_from_string(self, s, n, k=5, seed=0, refeed=True, tokenize=str.split):
+        """The next n tokens after the string s, as a new string (Text.py:655-676).  `tokenize` (default str.split) stands in for the
+        reference's spaCy tokeniser, which is not part of this package; tokens go through self.stoi, unknown ones to id 0 as
+        numericalize does, then through predict_from_tokens (see there for k, seed, refeed and the two differences from the
+        reference), and back through self.itos joined with spaces."""
+        ids = [self.stoi.get(t, 0) for t in tokenize(s)]
+        return ' '.join(self.itos[i] for i in self.predict_from_tokens(ids, n, k=k, seed=seed, refeed=refeed))
 
 
 class TextClassificationNet(nn.Module):

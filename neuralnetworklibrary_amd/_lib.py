@@ -128,6 +128,9 @@ SIGNATURES = {
     'nnl_seq_reg_fwd': (C.c_int, [c_p, c_p, i64, i64, C.c_float, C.c_float, c_p, sz, c_p]),
     'nnl_seq_reg_bwd': (C.c_int, [c_p, c_p, c_p, i64, i64, C.c_float, C.c_float, c_p]),
     'nnl_weight_drop': (C.c_int, [c_p, i64, c_p, c_p, i64, i64, i64, C.c_uint64, C.c_float, c_p]),
+    'nnl_lstm_cell_b1': (C.c_int, [c_p, i64, c_p, i64, c_p, c_p, c_p, i64, c_p, i64, i64, c_p, c_p, c_p, c_p, i64, i64, c_p]),
+    'nnl_lm_next_token_workspace_bytes': (sz, [i64, i64]),
+    'nnl_lm_next_token': (C.c_int, [c_p, i64, c_p, i64, i64, i64, i64, c_p, i64, c_p, i64, c_p, c_p, c_p, c_p, sz, c_p]),
     'nnl_attn_pool_workspace_bytes': (sz, [i64, i64, i64, i64]),
     'nnl_attn_pool_fwd': (C.c_int, [c_p, c_p, c_p, c_p, c_p, i64, c_p, c_p, i64, i64, i64, i64, c_p, sz, c_p, i64, c_p]),
     'nnl_attn_pool_bwd': (C.c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, i64, i64, i64, i64, c_p, sz, c_p, i64, c_p]),

@@ -1,5 +1,6 @@
 """Language-model ops on the C ABI (K5 / K5b): LSTM layer, embedding with vocabulary-row dropout, fused softmax-CE.
-Imported into `ops` (use `ops.lstm_layer`, `ops.embedding_rowmask`, `ops.softmax_cross_entropy`)."""
+Imported into `ops` (use `ops.lstm_layer`, `ops.embedding_rowmask`, `ops.softmax_cross_entropy`).  Text generation (K5d):
+`LstmCellB1` / `lstm_cell_b1` and `LmNextToken` / `lm_next_token`, the batch-1 decode kernels of csrc/lm_generate.hip."""
 import torch
 import torch.nn.functional as F
 
@@ -294,3 +295,76 @@ def attention_pool(h, w2, b2, enc_out, x, pad_token=1):
     (attn [T,B], pooled [B,E]) of TextClassificationDecoder (reference Text.py:597-605; pad token 1 is hard-coded there).
     A column without a non-pad token gives NaN, as the reference's 0/0 does."""
     return _AttentionPool.apply(h, w2, b2, enc_out, x, pad_token)
+
+
+# ---- text generation (K5d): batch 1, one timestep; no autograd ---------------------------------------------------------------------
+
+def padded_rows(w, w_hh=False):
+    """w [R, C] fp32 with rows padded with zeros to a multiple of 4 floats (16-byte rows for nnl_lstm_cell_b1 / nnl_lm_next_token);
+    w itself when C already is one.  w_hh=True pads through nnl_weight_drop (p = 0, no mask), as the LSTM layer does."""
+    require_cuda(w)
+    w = _f32c(w.detach())
+    R, Cc = w.shape
+    Cp = _ceil4(Cc)
+    if Cp == Cc:
+        return w
+    out = torch.empty(R, Cp, dtype=torch.float32, device=w.device)
+    if w_hh:
+        check(lib.nnl_weight_drop(ptr(w), Cc, None, ptr(out), Cp, R, Cc, 0, 0.0, stream()))
+    else:
+        check(lib.nnl_pad_cols(ptr(w), ptr(out), R, Cc, Cp, stream()))
+    return out
+
+
+class LstmCellB1:
+    """One LSTM layer, one timestep, batch 1 (nnl_lstm_cell_b1; reference Text.py:655-676 runs it through nn.LSTM) on fixed buffers:
+    w_ih [4H, ldi] and w_hh [4H, ldh] with zero-padded rows (`padded_rows`), bias = b_ih + b_hh [4H], h [ldh] and x [ldi] zero-padded
+    vectors, c [H].  A call writes h_out[:H] (must not be h) and c_out[:H] (may be c).  x=None: the input is row tokens[pos] of emb,
+    read on the device.  Every argument is converted once here, so that a decode loop pays one foreign call per launch."""
+
+    def __init__(self, w_ih, w_hh, bias, h, c, h_out, c_out, I, H, x=None, emb=None, tokens=None):
+        require_cuda(w_ih, w_hh, bias, h, c, h_out, c_out, x, emb, tokens)
+        self._keep = (w_ih, w_hh, bias, h, c, h_out, c_out, x, emb, tokens)
+        ld_emb, V = (emb.stride(0), emb.shape[0]) if emb is not None else (0, 0)
+        self._head = (ptr(w_ih), w_ih.stride(0), ptr(w_hh), w_hh.stride(0), ptr(bias), ptr(x), ptr(emb), ld_emb, ptr(tokens))
+        self._tail = (V, ptr(h), ptr(c), ptr(h_out), ptr(c_out), int(I), int(H))
+
+    def __call__(self, pos=0, on_stream=None):
+        check(lib.nnl_lstm_cell_b1(*self._head, int(pos), *self._tail, on_stream or stream()))
+
+
+def lstm_cell_b1(w_ih, w_hh, bias, h, c, h_out, c_out, I, H, x=None, emb=None, tokens=None, pos=0):
+    "one call of LstmCellB1 (see there); returns (h_out, c_out)"
+    LstmCellB1(w_ih, w_hh, bias, h, c, h_out, c_out, I, H, x, emb, tokens)(pos)
+    return h_out, c_out
+
+
+def lm_next_token_workspace(V, k, device):
+    return torch.empty(max(int(lib.nnl_lm_next_token_workspace_bytes(V, k)) // 4, 1), dtype=torch.float32, device=device)
+
+
+class LmNextToken:
+    """The rest of a generated token (nnl_lm_next_token; reference Text.py:667-672) on fixed buffers: tied decoder emb [V, ld] . h [E],
+    softmax over all V, the first n_special entries excluded, top-k, and the draw with the uniform u[step].  A call (h, step, pos)
+    writes tokens[pos + 1] (int64, on the device) and, if given, row `step` of top_probs / top_indices [*, k].  Nothing is read back."""
+
+    def __init__(self, emb, k, u, tokens, top_probs=None, top_indices=None, n_special=4, E=None, logits_out=None, workspace=None):
+        require_cuda(emb, u, tokens, top_probs, top_indices, logits_out, workspace)
+        V = emb.shape[0]
+        ws = lm_next_token_workspace(V, k, emb.device) if workspace is None else workspace
+        self._keep = (emb, u, tokens, top_probs, top_indices, logits_out, ws)
+        self._emb = (ptr(emb), emb.stride(0))
+        self._mid = (V, emb.shape[1] if E is None else int(E), int(k), int(n_special), ptr(u))
+        self._tokens = ptr(tokens)
+        self._tail = (ptr(top_probs), ptr(top_indices), ptr(logits_out), ptr(ws), ws.numel() * 4)
+
+    def __call__(self, h, step, pos, on_stream=None):
+        require_cuda(h)
+        check(lib.nnl_lm_next_token(*self._emb, ptr(h), *self._mid, int(step), self._tokens, int(pos), *self._tail, on_stream or stream()))
+
+
+def lm_next_token(emb, h, k, u, step, tokens, pos, top_probs=None, top_indices=None, n_special=4, E=None, logits_out=None,
+                  workspace=None):
+    "one call of LmNextToken (see there); returns tokens"
+    LmNextToken(emb, k, u, tokens, top_probs, top_indices, n_special, E, logits_out, workspace)(h, step, pos)
+    return tokens
