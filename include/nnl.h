@@ -435,7 +435,13 @@ int nnl_linear_small_bwd(const float* dy, const float* x, const float* w, float*
  * match_anchors_objects :1474-1511, jaccard :234-256, focal_loss_retina :1513-1530, smoothL1_loss_retina :1532-1566).
  * anchors [A,4]; reg [bs,A,4]; clas [bs,A,K] (probabilities); boxes [bs,M,4], cats int64 [bs,M], both padded with -1
  * (Vision.py:798-809), M <= 128.  Outputs: out[3] = {(1-beta)*reg + beta*clas, reg_loss, clas_loss} (batch means),
- * state int32 [bs,A] (>=0 matched object, -1 negative, -2 ignored) and npos float [bs] are kept for backward. */
+ * state int32 [bs,A] (>=0 matched object, -1 negative, -2 ignored) and npos float [bs] are kept for backward.
+ * Preconditions (relied on, not checked): every anchor has positive area — a zero-area anchor against a zero-area object gives
+ * IoU 0/0, which the kernel's comparisons file as negative where torch's max makes the anchor ignored; generated anchors never
+ * have zero area; cats are in [0, K) or negative (any negative value = padding row, anywhere in the list); anchors, reg and boxes
+ * are 16-byte aligned (clas and dclas too when K % 4 == 0).  M = 0 may come with boxes = cats = NULL; with M > 0 both calls
+ * refuse NULL.  Sizes: 0 < bs < 65536, 0 < A < 2^30, 0 < K <= 4096, 0 <= M <= 128, else NNL_ERR_INVALID_ARG; a workspace that is
+ * NULL or smaller than nnl_retina_loss_workspace_bytes(bs, A) = bs * ceil(A / 256) * 12 bytes is NNL_ERR_WORKSPACE. */
 size_t nnl_retina_loss_workspace_bytes(int64_t bs, int64_t A);
 int nnl_retina_loss_fwd(const float* anchors, const float* reg, const float* clas, const float* boxes,
                         const int64_t* cats, int32_t* state, float* npos, float* out, int64_t bs, int64_t A,

@@ -374,8 +374,10 @@ extern "C" int nnl_retina_loss_bwd(const float* anchors, const float* reg, const
                                    const int64_t* cats, const int32_t* state, const float* npos, const float* grad_out,
                                    float* dreg, float* dclas, int64_t bs, int64_t A, int64_t K, int64_t M, float beta,
                                    float alpha, float gamma, void* stream) {
-  NNL_CHECK_ARG(bs > 0 && A > 0 && K > 0 && M >= 0 && M <= kMaxObj && bs < 65536 && K <= 4096, "retina_loss_bwd: bad sizes");
-  NNL_CHECK_ARG(anchors && reg && clas && state && npos && grad_out && dreg && dclas, "retina_loss_bwd: null pointer");
+  NNL_CHECK_ARG(bs > 0 && A > 0 && K > 0 && M >= 0 && A < (1L << 30) && bs < 65536 && K <= 4096, "retina_loss_bwd: bad sizes");
+  NNL_CHECK_ARG(M <= kMaxObj, "retina_loss_bwd: at most %d objects per image (got %ld)", kMaxObj, (long)M);
+  NNL_CHECK_ARG(anchors && reg && clas && state && npos && grad_out && dreg && dclas && (M == 0 || (boxes && cats)),
+                "retina_loss_bwd: null pointer");
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid(chunks_per_image(A), (unsigned)bs);
   NnlProfScope prof(NNL_PROF_RETINA_LOSS, s, (double)bs * A * (16 + 32 + 8.0 * K + 4));
