@@ -694,6 +694,33 @@ int nnl_optim_patch(nnl_optim_tensor_t* tensors, float* hyper, const float* dyn,
 int nnl_optim_step(const nnl_optim_tensor_t* tensors, const int32_t* chunk_tensor, const int64_t* chunk_off,
                    int64_t n_chunks, int kind, const float* hyper, int use_clip, float* clip_workspace, void* stream);
 
+/* ---- K12: time-series features of the structured-data workflow ------------------------------------------------------
+ * Both entries read n rows ALREADY SORTED by (group, time ascending), 1 <= n < 2^31: t int64 [n] (nanoseconds of a timestamp, or a
+ * plain integer index), head uint8 [n] = 1 on the first row of every group (row 0 counts as one whatever it holds).  Outputs are
+ * float64.  Arguments are validated before any HIP call.
+ *
+ * nnl_seg_event_gaps replaces the per-row Python loops of get_TimeBeforeAfter (Applications/StructuredData.py:482-519, once per
+ * group and direction): before[i] = (double)(t[i] - t[j]) / timescale with j the last row strictly before i in i's group with
+ * event[j] == 1, NaN if there is none; after[i] = (double)(t[j] - t[i]) / timescale with j the next such row strictly after i.  A
+ * row's own event does not count for that row (:499-502 append before they update last_event).  It also writes seg_start[i] and
+ * seg_end[i], int32 [n]: the first and the last row of i's group, which nnl_seg_rolling reads.  Three launches, no workspace: the
+ * scan's tile carries (NNL_SEG_SCAN_TILE rows per tile) pass through the output arrays.
+ *
+ * nnl_seg_rolling replaces the per-group pandas rolling calls of get_RollingStats (:556-607): x float64 [C, n] (column c at
+ * x + c n), out float64 [popcount(stat_mask), C, n], the requested statistics in the fixed order of the NNL_ROLL_* bits.  Exactly one
+ * of count_window > 0 (rows) and span > 0 (in t's units) is given.  The window of row i never leaves i's group [seg_start[i],
+ * seg_end[i]] and is, backward (forward == 0): rows j <= i with t[j] > t[i] - span (pandas' closed='right'), or rows
+ * [max(seg_start, i - w + 1), i]; forward (forward == 1): rows j >= i with t[j] < t[i] + span (the reference's reverse_datetime,
+ * :521-528, :572-574), or rows [i, min(seg_end, i + w - 1)].  NaN entries are skipped; Count is the number of non-NaN entries; Sum,
+ * Min, Max and Mean are NaN when Count < 1; Std has ddof = 1 and is NaN when Count < 2 (min_periods of :580-596).  One thread per
+ * (row, column) adds its window oldest to newest in fp64 (Std: a second walk over (x - mean)^2): O(window) per output. */
+#define NNL_SEG_SCAN_TILE 1024
+enum { NNL_ROLL_SUM = 1, NNL_ROLL_MIN = 2, NNL_ROLL_MAX = 4, NNL_ROLL_MEAN = 8, NNL_ROLL_STD = 16, NNL_ROLL_COUNT = 32 };
+int nnl_seg_event_gaps(const int64_t* t, const uint8_t* head, const uint8_t* event, int64_t n, double timescale, double* before,
+                       double* after, int32_t* seg_start, int32_t* seg_end, void* stream);
+int nnl_seg_rolling(const int64_t* t, const int32_t* seg_start, const int32_t* seg_end, const double* x, int64_t n, int64_t C,
+                    int64_t count_window, int64_t span, int forward, int stat_mask, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,14 +1,17 @@
-"""Structured (tabular) data application of the drop-in API: model side of Applications/StructuredData.py §2
-(StructuredDataset :803, StructuredDataCollater :849, StructuredDataObj :871, embedding_dim :970,
-StructuredDataNet :979-1096, StructuredDataEnsembleNet :1098).
+"""Structured (tabular) data application of the drop-in API: Applications/StructuredData.py §1.3 (feature engineering: add_datepart
+:432, get_TimeBeforeAfter :460, get_RollingStats :530) and §2 (ProcessDataFrame :614, StructuredDataset :803, StructuredDataCollater
+:849, StructuredDataObj :871 with from_dataframes :913, embedding_dim :970, StructuredDataNet :979-1096, StructuredDataEnsembleNet :1098).
 
-HIP-backed hot path: the categorical front end (per-column max_norm renorm + gather + per-sample dropout + both
-torch.cat calls) is ONE fused gather kernel (ops.tab_embed_concat, K3) and one scatter-add kernel in backward; the
-FC head runs on the fp32-MFMA GEMM (ops.linear) and the fused BatchNorm kernels (ops.bn_act).
-Out of scope (offline pandas feature engineering / EDA plots, never inside fit(): SURVEY.md §2.1 rows 7-8):
-ProcessDataFrame and the §1 helpers — `StructuredDataObj` is built from ready arrays / StructuredDatasets.
+HIP-backed hot paths.  Model: the categorical front end (per-column max_norm renorm + gather + per-sample dropout + both torch.cat
+calls) is ONE fused gather kernel (ops.tab_embed_concat, K3) and one scatter-add kernel in backward; the FC head runs on the fp32-MFMA
+GEMM (ops.linear) and the fused BatchNorm kernels (ops.bn_act).  Data: the two slow cells of the Rossmann notebook, the per-row Python
+loop of get_TimeBeforeAfter and the per-group pandas rolling of get_RollingStats, are scans over rows sorted by (group, time) on the
+device (ops.seg_event_gaps, ops.seg_rolling, K12); like every op they need a GPU and have no CPU fallback.  add_datepart and
+ProcessDataFrame are host pandas: calendar fields pandas already has, and string work that runs once, offline.
+Still out of scope: the EDA plots, the associations_* / entropy / correlation-ratio helpers, missing_value_counts and CSV reading.
 """
 import numpy as np
+import pandas as pd
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -23,6 +26,235 @@ from ..General.Core import TEN, separate_bn_layers
 from ..General.Layers import EmbeddingDrop, Flatten1d, FullyConnectedNet
 from .. import ops
 from ..dist import keyed_mask
+
+
+# ---- §1.3 feature engineering ------------------------------------------------------------------------------------------
+
+def add_datepart(df, date_column='Date', start=None):
+    """Adds 'week', 'month', 'year', 'dayofweek', 'dayofmonth', 'dayofyear', 'is_month_end/start', 'is_quarter_end/start',
+    'is_year_end/start' (integer columns) and 'days_elapsed' (days since `start`, default the earliest date) to df, in place
+    (StructuredData.py:432-458).  Host pandas: one pass over calendar fields pandas already has.  'week' is the ISO week
+    (.dt.isocalendar().week: the reference's .dt.week, which current pandas no longer has)."""
+    df[date_column] = pd.to_datetime(df[date_column])
+    d = df[date_column].dt
+    df['week'] = d.isocalendar().week.astype('int64')
+    df['month'], df['year'] = d.month, d.year
+    df['dayofweek'], df['dayofmonth'], df['dayofyear'] = d.dayofweek, d.day, d.dayofyear
+    for name in ('is_month_end', 'is_month_start', 'is_quarter_end', 'is_quarter_start', 'is_year_end', 'is_year_start'):
+        df[name] = getattr(d, name).astype(int)
+    if start is None:
+        start = df[date_column].min()
+    df['days_elapsed'] = (df[date_column] - pd.to_datetime(start)) / np.timedelta64(1, 'D')
+
+
+def _time_values(values, what):
+    "times as int64: nanoseconds of a datetime column / index, or the integer index itself -> (t [n], is_datetime)"
+    values = pd.Series(np.asarray(values) if not isinstance(values, (pd.Series, pd.Index)) else values).reset_index(drop=True)
+    if values.isna().any():
+        raise ValueError('%s holds NaT / NaN: every row needs a time' % what)
+    if pd.api.types.is_datetime64_any_dtype(values):
+        if getattr(values.dt, 'tz', None) is not None:
+            values = values.dt.tz_convert('UTC').dt.tz_localize(None)
+        return values.to_numpy().astype('datetime64[ns]').view('int64'), True
+    if pd.api.types.is_integer_dtype(values):
+        return values.to_numpy().astype('int64'), False
+    if pd.api.types.is_float_dtype(values) and (values == np.floor(values)).all():
+        return values.to_numpy().astype('int64'), False
+    raise ValueError('%s must hold timestamps or integers (got dtype %s)' % (what, values.dtype))
+
+
+def _sorted_rows(df, index_col, groupby_col):
+    """The host half of the scans: `order` = positions of df's rows sorted by (group label, time) — groups in sorted label order, rows
+    of a missing label dropped, as groupby does —, t int64 and head uint8 in that order.  Duplicate times inside a group raise."""
+    what = repr(index_col) if index_col is not None else 'the index'
+    t, is_dt = _time_values(df[index_col] if index_col is not None else df.index, what)
+    if len(t) == 0:
+        raise ValueError('the frame has no rows')
+    if groupby_col is None:
+        codes, order = np.zeros(len(t), dtype='int64'), np.argsort(t, kind='stable')
+    else:
+        # the order of np.lexsort((t, codes)), by ONE integer key where it fits: group code x number of distinct times + rank of the time
+        # (two hash factorisations and one sort of int64 keys: a third of the lexsort's time at a million rows)
+        codes = pd.factorize(df[groupby_col], sort=True)[0].astype('int64')
+        ranks, distinct = pd.factorize(t, sort=True)
+        if (int(codes.max()) + 1) * len(distinct) < 2 ** 62:
+            order = np.argsort(codes * len(distinct) + ranks)       # equal keys are duplicate times: they raise below
+        else:
+            order = np.lexsort((t, codes))
+    codes = codes[order]
+    if codes[0] < 0:                                                # rows without a group label sort first: dropped
+        order, codes = order[codes >= 0], codes[codes >= 0]
+        if len(order) == 0:
+            raise ValueError('no row of the frame has a group label')
+    t = t[order]
+    head = np.ones(len(t), dtype='uint8')
+    head[1:] = codes[1:] != codes[:-1]
+    if ((t[1:] == t[:-1]) & (head[1:] == 0)).any():
+        raise ValueError('duplicate times in %s inside a group: the rows of a group need distinct times' % what)
+    return order, np.ascontiguousarray(t), head, is_dt
+
+
+def _to_device(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(default_device())
+
+
+def get_TimeBeforeAfter(df, event_col, index_col=None, groupby_col=None, keep_cols=[], timescale=1):
+    """Time since the last and until the next event (event_col == 1) for every row, per label of groupby_col if given, in units of
+    `timescale` (a number, or an np.timedelta64 / pd.Timedelta for timestamps); NaN where there is no such event; a row's own event does
+    not count (StructuredData.py:460-519).  Returns the reference's frame: columns [index_col or 'index', *keep_cols, (groupby_col),
+    event_col + 'Before', event_col + 'After'], groups in sorted label order, time ascending inside a group, df's index kept.
+    The host factorises and sorts by (group, time), the order of np.lexsort; the two scans are one ops.seg_event_gaps call on the device.
+    The times of a group must be distinct and none may be missing (ValueError; the reference's NOTE 2).  Unlike the reference, which
+    adds and drops an 'index' column on it, df is not modified."""
+    order, t, head, is_dt = _sorted_rows(df, index_col, groupby_col)
+    if isinstance(timescale, (np.timedelta64, pd.Timedelta)):
+        timescale = pd.Timedelta(timescale).value
+    event = (df[event_col].to_numpy()[order] == 1).astype('uint8')
+    before, after, _, _ = ops.seg_event_gaps(_to_device(t), _to_device(head), _to_device(event), float(timescale))
+    gaps = torch.stack([before, after]).cpu().numpy()
+    keep = list(keep_cols) + ([groupby_col] if groupby_col is not None else [])
+    if index_col is None:
+        out = pd.DataFrame({'index': df.index[order]}, index=df.index[order])
+        for c in keep:
+            out[c] = df[c].to_numpy()[order]
+    else:
+        out = df[[index_col] + keep].iloc[order].copy()
+    out[event_col + 'Before'], out[event_col + 'After'] = gaps[0], gaps[1]
+    return out
+
+
+def get_RollingStats(df, columns, window_size, stat_types, index_col=None, groupby_col=None, keep_cols=[]):
+    """Backward and forward rolling statistics ('Sum', 'Min', 'Max', 'Mean', 'Std', 'Count') of the numeric `columns`, per label of
+    groupby_col if given (StructuredData.py:530-607).  window_size: an int (rows), or anything pd.Timedelta parses ('8D': needs a
+    datetime index / index_col): backward the rows in (t - window, t], forward those in [t, t + window).  Returns the reference's
+    frame: indexed by time, for each statistic all c + 'RollBwd' + st columns, then all c + 'RollFwd' + st; when grouped, groupby_col
+    and 'index' are appended and the groups follow each other in sorted label order.  keep_cols is ignored (the reference uses it
+    only when it calls itself).  One upload, one ops.seg_event_gaps call for the group bounds, two ops.seg_rolling calls and one copy
+    back: each output costs O(window) on the device.  Restriction: the times of a group must be distinct and none may be missing
+    (ValueError).  df is not modified."""
+    order, t, head, is_dt = _sorted_rows(df, index_col, groupby_col)
+    stats = list(stat_types)
+    if isinstance(window_size, (int, np.integer)) and not isinstance(window_size, bool):
+        window = dict(count_window=int(window_size))
+    else:
+        if not is_dt:
+            raise ValueError('a time window (%r) needs a datetime index' % (window_size,))
+        window = dict(span=pd.Timedelta(window_size).value)
+    if min(window.values()) < 1:
+        raise ValueError('window_size must be positive (got %r)' % (window_size,))
+    x = np.stack([df[c].to_numpy(dtype='float64')[order] for c in columns])
+    td = _to_device(t)
+    _, _, seg_start, seg_end = ops.seg_event_gaps(td, _to_device(head), torch.zeros(len(t), dtype=torch.uint8, device=td.device))
+    xd = _to_device(x)
+    both = torch.stack([ops.seg_rolling(td, seg_start, seg_end, xd, stats, forward=fwd, **window) for fwd in (False, True)])
+    both = both.cpu().numpy()                                           # [direction, statistic, column, row]
+    times = (df[index_col] if index_col is not None else df.index).to_numpy()[order]
+    index = pd.Index(times, name=index_col if index_col is not None else df.index.name)
+    data = {}
+    for s, st in enumerate(stats):
+        for d, tag in enumerate(('RollBwd', 'RollFwd')):
+            for c, col in enumerate(columns):
+                data[col + tag + st] = both[d, s, c]
+    out = pd.DataFrame(data, index=index)
+    if groupby_col is not None:
+        out[groupby_col] = df[groupby_col].to_numpy()[order]
+        out['index'] = out.index
+    return out
+
+
+# ---- §2.1 data object construction ---------------------------------------------------------------------------------------
+
+_MISSING = 'nan'          # how the reference spells a missing categorical value (astype(str) of np.nan)
+
+
+def _category_strings(col):
+    "a categorical column as strings: float-coded integers through int (7.0 -> '7'), missing values (None, NaN) -> 'nan'"
+    missing = col.isna().to_numpy()
+    if pd.api.types.is_float_dtype(col):
+        s = col.fillna(0).astype('int64').astype(str).to_numpy(dtype=object)
+    else:
+        s = col.astype(str).to_numpy(dtype=object)
+    s[missing] = _MISSING
+    return s
+
+
+def ProcessDataFrame(df, cat_vars, cont_vars, output_var, scale_cont, fill_missing='median', category_labels=None, unknown_category=True):
+    """DataFrame -> (xcat_df, xcont_df, y, scaling_values, category_labels) with the reference's semantics (StructuredData.py:614-801).
+
+    cat_vars hold strings or (possibly float-coded) integers; the categories of a variable are the lexicographically sorted string
+    forms of its values.  unknown_category=True: missing values become 0 ('unknown') and the known categories 1, 2, ...; values not
+    in `category_labels` (unseen validation / test values) become 0 as well.  unknown_category=False: the categories become 0, 1, ...
+    (a missing value is then a category of its own, 'nan'; a value without a label raises).  A categorical output is numbered in
+    order of first appearance.  cont_vars are cast to float32, filled (fill_missing = 'median', 'mean' or a constant), then scaled:
+    scale_cont = 'No', 'by_df' (this frame's mean and std, returned as scaling_values[var] = [mean, std]) or such a dictionary.
+    category_labels: None for the training frame, otherwise what the call on the training frame returned.
+    Host code: this is string work and runs once, offline.  None and NaN both count as missing.  df is not modified (the reference
+    converts its columns in place)."""
+    xcat_vars = [v for v in cat_vars if v != output_var]
+    xcont_vars = [v for v in cont_vars if v != output_var]
+    need_labels = category_labels is None
+    category_labels = [] if need_labels else category_labels
+
+    def codes_of(strings, labels, var):
+        codes = pd.Series(strings).map(labels)
+        if unknown_category and 'unknown' in labels:
+            codes = codes.fillna(labels['unknown'])
+        if codes.isna().any():
+            raise ValueError('%r holds values without a category label: %s' % (var, sorted(set(strings[codes.isna().to_numpy()]))[:5]))
+        return codes.to_numpy().astype('int64')
+
+    y = None
+    y_labels = None
+    if output_var is not None and output_var in cont_vars:
+        y = df[output_var].to_numpy(dtype='float32')
+    elif output_var is not None and output_var in cat_vars:
+        s = _category_strings(df[output_var])
+        if need_labels:
+            y_labels = {c: i for i, c in enumerate(pd.unique(s))}
+        labels = y_labels if need_labels else category_labels[-1]
+        if not all(c in labels for c in pd.unique(s)):
+            raise ValueError('%r holds values without a category label' % output_var)
+        y = pd.Series(s).map(labels).to_numpy().astype('int64')
+
+    xcat_df = None
+    if xcat_vars:
+        cols = {}
+        for j, var in enumerate(xcat_vars):
+            s = _category_strings(df[var])
+            if need_labels:
+                cats = sorted(set(s) - {_MISSING}) if unknown_category else sorted(set(s))
+                labels = {c: i + 1 for i, c in enumerate(cats)} if unknown_category else {c: i for i, c in enumerate(cats)}
+                if unknown_category:
+                    labels['unknown'] = 0
+                category_labels.append(labels)
+            labels = category_labels[j]
+            cols[var] = codes_of(s, labels, var)
+        xcat_df = pd.DataFrame(cols, index=df.index, columns=xcat_vars)
+    if need_labels and y_labels is not None:
+        category_labels.append(y_labels)
+
+    scaling_values = None
+    if xcont_vars and isinstance(scale_cont, str) and scale_cont == 'by_df':
+        scaling_values = {}
+    elif xcont_vars and isinstance(scale_cont, dict):
+        scaling_values = scale_cont
+    xcont_df = None
+    if xcont_vars:
+        xcont_df = df[xcont_vars].astype('float32')
+        if isinstance(fill_missing, str) and fill_missing == 'median':
+            xcont_df = xcont_df.fillna(xcont_df.median())
+        elif isinstance(fill_missing, str) and fill_missing == 'mean':
+            xcont_df = xcont_df.fillna(xcont_df.mean())
+        else:
+            xcont_df = xcont_df.fillna(pd.Series(fill_missing, index=xcont_vars))
+        if scaling_values is not None:
+            for var in xcont_vars:
+                if not isinstance(scale_cont, dict):
+                    scaling_values[var] = [xcont_df[var].mean(), xcont_df[var].std()]
+                mean, std = scaling_values[var]
+                xcont_df[var] = (xcont_df[var] - mean) / std
+        xcont_df = xcont_df.astype('float32')
+    return xcat_df, xcont_df, y, scaling_values, category_labels
 
 
 class StructuredDataset(Dataset):
@@ -88,6 +320,29 @@ class StructuredDataObj(object):
         self.val_dl = DataLoader(val_ds, shuffle=False, **kw)
         if self.test_ds:
             self.test_dl = DataLoader(test_ds, shuffle=False, **kw)
+
+    @classmethod
+    def from_dataframes(cls, train_df, val_df, cat_vars, cont_vars, output_var, bs, fill_missing='median', scale_cont=True,
+                        unknown_category=True, num_workers=6, test_df=None, device_resident=False, seed=0):
+        """train / val / (test) DataFrames -> data object (StructuredData.py:913-965): ProcessDataFrame on the training frame, then on
+        the validation and test frames with the training frame's category labels and scaling values.  device_resident and seed go to
+        the constructor.  The frames are not modified."""
+        target_type = 'cat' if output_var in cat_vars else 'cont'
+        xcat_vars = [v for v in cat_vars if v != output_var]
+        xcont_vars = [v for v in cont_vars if v != output_var]
+        xcat, xcont, y, scaling_values, category_labels = ProcessDataFrame(
+            train_df, cat_vars, cont_vars, output_var, 'by_df' if scale_cont else 'No', fill_missing, None, unknown_category)
+        train_ds = StructuredDataset(xcat, xcont, y, target_type)
+        scale = scaling_values if scale_cont else 'No'
+        xcat, xcont, y, _, _ = ProcessDataFrame(val_df, cat_vars, cont_vars, output_var, scale, fill_missing, category_labels,
+                                                unknown_category)
+        val_ds = StructuredDataset(xcat, xcont, y, target_type)
+        test_ds = None
+        if isinstance(test_df, pd.DataFrame):
+            xcat, xcont, y, _, _ = ProcessDataFrame(test_df, xcat_vars, xcont_vars, None, scale, fill_missing, category_labels,
+                                                    unknown_category)
+            test_ds = StructuredDataset(xcat, xcont, y, target_type)
+        return cls(train_ds, val_ds, category_labels, scaling_values, bs, num_workers, test_ds, device_resident=device_resident, seed=seed)
 
 
 def embedding_dim(n):

@@ -152,6 +152,8 @@ SIGNATURES = {
     'nnl_bn_sync_bwd': (C.c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, C.c_int, c_p, c_p, c_p, c_p, i64, i64,
                                   C.c_int, c_p, sz, c_p]),
     'nnl_bn_bwd': (C.c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, i64, i64, C.c_int, C.c_int, c_p, sz, c_p]),
+    'nnl_seg_event_gaps': (C.c_int, [c_p, c_p, c_p, i64, f64, c_p, c_p, c_p, c_p, c_p]),
+    'nnl_seg_rolling': (C.c_int, [c_p, c_p, c_p, c_p, i64, i64, i64, i64, C.c_int, C.c_int, c_p, c_p]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

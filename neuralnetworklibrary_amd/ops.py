@@ -1548,5 +1548,61 @@ def tta_bbox_merge(boxes, classes, scores, counts, undo):
 
 __all__ += ['tta_bbox_merge', 'tta_undo_rows']
 
+
+# ---------------------------------------------------------------------------------------------------------
+# K12 time-series features of the structured-data workflow (include/nnl.h): rows sorted by (group, time).
+# ---------------------------------------------------------------------------------------------------------
+SEG_SCAN_TILE = 1024                     # NNL_SEG_SCAN_TILE: rows per scan tile (tests place group boundaries on its edges)
+ROLL_STATS = ['Sum', 'Min', 'Max', 'Mean', 'Std', 'Count']      # bit k of stat_mask, and the order of the output planes
+
+
+def _seg_rows(name, t, **others):
+    "t int64 [n] and every other array uint8 / int32 [n] as named, contiguous, on t's device"
+    require_cuda(t, *[a for a, _ in others.values()])
+    if t.dtype != torch.int64 or t.dim() != 1 or t.numel() < 1:
+        raise ValueError('%s: t must be a non-empty int64 vector' % name)
+    for key, (a, dtype) in others.items():
+        if a.dtype != dtype or tuple(a.shape) != tuple(t.shape) or a.device != t.device:
+            raise ValueError('%s: %s must be %s [%d] on %s' % (name, key, dtype, t.numel(), t.device))
+    return [t.contiguous()] + [a.contiguous() for a, _ in others.values()]
+
+
+def seg_event_gaps(t, head, event, timescale=1.0):
+    """Time since the last and until the next event inside each group, for rows sorted by (group, time): t int64 [n], head uint8 [n]
+    (1 on the first row of a group), event uint8 [n].  Returns (before, after, seg_start, seg_end): float64 [n] gaps in units of
+    `timescale` (NaN where the group has no such event; a row's own event does not count) and int32 [n] first / last row of the
+    row's group."""
+    t, head, event = _seg_rows('seg_event_gaps', t, head=(head, torch.uint8), event=(event, torch.uint8))
+    n, dev = t.numel(), t.device
+    before, after = torch.empty(n, dtype=torch.float64, device=dev), torch.empty(n, dtype=torch.float64, device=dev)
+    seg_start, seg_end = torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev)
+    check(lib.nnl_seg_event_gaps(ptr(t), ptr(head), ptr(event), n, float(timescale), ptr(before), ptr(after), ptr(seg_start), ptr(seg_end),
+                                 stream()))
+    return before, after, seg_start, seg_end
+
+
+def seg_rolling(t, seg_start, seg_end, x, stats, count_window=0, span=0, forward=False):
+    """Rolling statistics inside each group: x float64 [C, n], stats a list out of ROLL_STATS, exactly one of count_window (rows) and
+    span (t's units) positive; seg_start / seg_end as seg_event_gaps returns them.  Returns float64 [len(stats), C, n] in the order of
+    `stats`.  NaN entries are skipped (Std: ddof 1, NaN below two entries; Count 0 and the others NaN for an empty window)."""
+    t, seg_start, seg_end = _seg_rows('seg_rolling', t, seg_start=(seg_start, torch.int32), seg_end=(seg_end, torch.int32))
+    require_cuda(x)
+    n = t.numel()
+    if x.dtype != torch.float64 or x.dim() != 2 or x.shape[1] != n or x.device != t.device:
+        raise ValueError('seg_rolling: x must be float64 [C, %d] on %s' % (n, t.device))
+    unknown = [s for s in stats if s not in ROLL_STATS]
+    if unknown or not stats or len(set(stats)) != len(stats):
+        raise ValueError('seg_rolling: stats must be distinct names out of %s (got %r)' % (ROLL_STATS, list(stats)))
+    x = x.contiguous()
+    mask = sum(1 << ROLL_STATS.index(s) for s in stats)
+    planes = [s for s in ROLL_STATS if s in stats]
+    out = torch.empty(len(planes), x.shape[0], n, dtype=torch.float64, device=t.device)
+    check(lib.nnl_seg_rolling(ptr(t), ptr(seg_start), ptr(seg_end), ptr(x), n, x.shape[0], int(count_window), int(span), int(bool(forward)),
+                              mask, ptr(out), stream()))
+    return out if planes == list(stats) else out[[planes.index(s) for s in stats]]
+
+
+__all__ += ['seg_event_gaps', 'seg_rolling', 'SEG_SCAN_TILE', 'ROLL_STATS']
+
 from .ops_text import (lstm_layer, embedding_rowmask, softmax_cross_entropy, cross_entropy_nd, seq_activation_reg)  # noqa: E402,F401
 __all__ += ['lstm_layer', 'embedding_rowmask', 'softmax_cross_entropy', 'cross_entropy_nd', 'seq_activation_reg', 'conv_add_upsampled']
