@@ -721,6 +721,50 @@ int nnl_seg_event_gaps(const int64_t* t, const uint8_t* head, const uint8_t* eve
 int nnl_seg_rolling(const int64_t* t, const int32_t* seg_start, const int32_t* seg_end, const double* x, int64_t n, int64_t C,
                     int64_t count_window, int64_t span, int forward, int stat_mask, double* out, void* stream);
 
+/* ---- K13: association measures of the structured-data EDA (Applications/StructuredData.py:235-428) -------------------------
+ * Columns live on the device, one after another: codes int32 [V, n] (category codes in [0, card[v]), -1 = missing; a code outside
+ * that range counts as missing too), vals float64 [V, n] (NaN = missing; no +-inf) with shift float64 [V] on the device (the
+ * caller's centre of each column, its nanmean: every sum is taken over vals - shift).  1 <= n < 2^31.  card, pair_x, pair_y and
+ * offsets are HOST arrays: pair p associates column pair_x[p] with column pair_y[p].  Every entry validates its arguments before
+ * any HIP call (null pointers, n, P >= 1, pair indices inside [0, V), offsets against the cardinalities) and cuts the pair list
+ * into chunks that travel to the kernels as arguments; a workgroup stages a tile of NNL_ASSOC_ROW_TILE rows of a chunk's columns in
+ * LDS once and walks the chunk's pairs over it.
+ *
+ * nnl_assoc_contingency: tables uint32 [offsets[P]], the table of pair p row-major [card[x], card[y]] at offsets[p]
+ * (offsets[0] = 0, at most 2^26 cells per table): the number of rows with both codes present.  The entry zeroes the tables.
+ * Tables of at most NNL_ASSOC_LDS_CELLS cells are counted in LDS per workgroup and flushed once, larger ones with global atomics;
+ * the result is exact either way.  Route note: "assoc_contingency:lds=<pairs>,global=<pairs>,chunks=<launches>".
+ * nnl_assoc_table_stats: out float64 [P, 6] = n, non-empty rows, non-empty columns, H_X, H_Y (natural log, from the marginals) and
+ * H_XY, which adds -1e-20 log(1e-20) for every empty cell of the non-empty rows x non-empty columns (the reference's clamp).
+ * Fixed reduction order: the same table gives the same bits.
+ *
+ * nnl_assoc_cat_cont: x indexes codes [Vc, n], y indexes vals [Vy, n]; rows with a code and a non-NaN value count.
+ * out float64 [P, 6] = n, non-empty categories, correlation ratio sqrt((sum_c n_c (mean_c - mean)^2 / n) / var_ddof1(y)),
+ * max_c |mean_c - mean| / std_ddof1(y), min and max of y - shift.  Per-category sums are fp64 atomics (LDS for up to
+ * NNL_ASSOC_MOMENT_LDS_CELLS categories, else global): the last bits may differ between calls.  The workspace
+ * (nnl_assoc_cat_cont_workspace_bytes, 0 for invalid arguments) is zeroed by the entry.
+ *
+ * nnl_assoc_cont_cont: out float64 [P, 4] = n, degenerate (1.0 if n = 0 or either column holds one distinct value on the pair's
+ * rows, else 0.0), |corr(x, y)|, and, with_abs = 1, max |corr| over (x, y), (x, |y - my|), (|x - mx|, y), (|x - mx|, |y - my|) with
+ * mx, my the means over the pair's rows (a second pass over the rows), else NaN.  |x - mx| counts as constant, and its two
+ * correlations are skipped, when its centred sum of squares is at most n (2^-26 mean|x - mx|)^2.  Both values are NaN for a
+ * degenerate pair.  No atomics: at most NNL_ASSOC_MAX_GROUPS per-workgroup partial sums per pair, added in a fixed order. */
+#define NNL_ASSOC_ROW_TILE 1024
+#define NNL_ASSOC_LDS_CELLS 6144
+#define NNL_ASSOC_MOMENT_LDS_CELLS 1152
+#define NNL_ASSOC_MAX_GROUPS 256
+int nnl_assoc_contingency(const int32_t* codes, const int32_t* card, int64_t V, int64_t n, const int32_t* pair_x, const int32_t* pair_y,
+                          const int64_t* offsets, int64_t P, uint32_t* tables, void* stream);
+int nnl_assoc_table_stats(const uint32_t* tables, const int32_t* card, int64_t V, const int32_t* pair_x, const int32_t* pair_y,
+                          const int64_t* offsets, int64_t P, double* out, void* stream);
+size_t nnl_assoc_cat_cont_workspace_bytes(const int32_t* card, int64_t Vc, const int32_t* pair_x, int64_t P);
+int nnl_assoc_cat_cont(const int32_t* codes, const int32_t* card, int64_t Vc, const double* vals, const double* shift, int64_t Vy,
+                       int64_t n, const int32_t* pair_x, const int32_t* pair_y, int64_t P, void* workspace, size_t workspace_bytes,
+                       double* out, void* stream);
+size_t nnl_assoc_cont_cont_workspace_bytes(int64_t n, int64_t P);
+int nnl_assoc_cont_cont(const double* vals, const double* shift, int64_t V, int64_t n, const int32_t* pair_x, const int32_t* pair_y,
+                        int64_t P, int with_abs, void* workspace, size_t workspace_bytes, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

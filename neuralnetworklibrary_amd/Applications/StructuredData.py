@@ -7,8 +7,10 @@ calls) is ONE fused gather kernel (ops.tab_embed_concat, K3) and one scatter-add
 GEMM (ops.linear) and the fused BatchNorm kernels (ops.bn_act).  Data: the two slow cells of the Rossmann notebook, the per-row Python
 loop of get_TimeBeforeAfter and the per-group pandas rolling of get_RollingStats, are scans over rows sorted by (group, time) on the
 device (ops.seg_event_gaps, ops.seg_rolling, K12); like every op they need a GPU and have no CPU fallback.  add_datepart and
-ProcessDataFrame are host pandas: calendar fields pandas already has, and string work that runs once, offline.
-Still out of scope: the EDA plots, the associations_* / entropy / correlation-ratio helpers, missing_value_counts and CSV reading.
+ProcessDataFrame are host pandas: calendar fields pandas already has, and string work that runs once, offline.  EDA (§1.2, :235-428):
+missing_value_counts, the entropy / correlation-ratio / correlation helpers, get_association, associations_dependent and
+associations_pairs compute all pairs of a call on the device (ops.assoc_*, K13: contingency counts and fp64 moments).
+Still out of scope: the EDA plots (plot_distributions, plot_dependence, plot_pairs) and CSV reading.
 """
 import numpy as np
 import pandas as pd
@@ -26,6 +28,258 @@ from ..General.Core import TEN, separate_bn_layers
 from ..General.Layers import EmbeddingDrop, Flatten1d, FullyConnectedNet
 from .. import ops
 from ..dist import keyed_mask
+
+
+# ---- §1.2 EDA: numerical measures of association (StructuredData.py:235-428) --------------------------------------------------
+# One call = one upload of the distinct columns the requested pairs use (categorical columns factorised to int32 codes, -1 for
+# missing; continuous ones as float64 with NaN for missing and one shift, the column's nanmean), the K13 kernels over all pairs
+# (ops.assoc_*), and one small copy back of a few numbers per pair.  Contingency tables and per-category moments stay on the device.
+#
+# Deliberate differences from the reference: the six direct helpers raise ValueError on a missing value, naming the column (the
+# reference "assumes" there is none, and its entropy then divides by the wrong length); +-inf in a continuous column raises
+# ValueError before anything is uploaded; in abs_max_correlation |X - mean(X)| counts as constant, and its correlations are skipped
+# as pandas' NaN ones are, when its centred sum of squares is at most n (2^-26 mean|X - mean(X)|)^2 (our pair mean is not bit-equal to
+# pandas', so a column such as balanced +-1, exactly constant there, would otherwise yield a correlation of rounding noise; 2^-26
+# is the geometric middle between rounding noise, 2^-52, and a data-sized spread); an unknown Type raises ValueError; no frame is
+# modified; nothing is printed; plot=True is written fresh (a pandas bar plot, a seaborn heatmap with the diagonal zeroed).
+# correlation_ratio and max_correlation_ratio sum per category with fp64 atomics: their last bits may differ between calls; the
+# entropy- and correlation-based measures are bit-equal from call to call.
+
+ASSOCIATION_TYPES = {'abs_correlation': 'cont', 'abs_max_correlation': 'cont', 'correlation_ratio': 'cat_cont',
+                     'max_correlation_ratio': 'cat_cont', 'mutual_info_asymmetric': 'cat', 'mutual_info_symmetric': 'cat'}
+_ASSOC_CHUNK_CELLS = 2 ** 25             # contingency cells per ops call: bounds the table workspace at 128 MiB
+_ONE = object()                          # a stand-in column with one category: H_X alone is the table stats of (X, _ONE)
+
+
+def missing_value_counts(df):
+    "Counts of missing values in the columns of df that have any (StructuredData.py:235-238).  Host pandas."
+    counts = df.isnull().astype(int).sum()
+    return counts[counts > 0]
+
+
+def _assoc_device():
+    from .._lib import NnlError
+    if not torch.cuda.is_available():
+        raise NnlError('the association measures run on the GPU (ops.assoc_*): there is no CPU fallback')
+    return torch.device('cuda', torch.cuda.current_device())
+
+
+def _assoc_upload(df, cat_cols, cont_cols, strict):
+    """The host half: factorise / convert the distinct columns and upload them in ONE buffer.
+    -> (codes int32 [Vc, n] or None, card, vals float64 [Vy, n] or None, shift float64 [Vy] or None)"""
+    n = len(df)
+    if n < 1:
+        raise ValueError('the frame has no rows')
+    codes, card, vals = [], [], []
+    for col in cat_cols:
+        if col is _ONE:
+            codes.append(np.zeros(n, dtype=np.int32)), card.append(1)
+            continue
+        c, uniques = pd.factorize(df[col])
+        if strict and (c < 0).any():
+            raise ValueError('column %r holds missing values' % (col,))
+        codes.append(c.astype(np.int32)), card.append(max(len(uniques), 1))
+    for col in cont_cols:
+        v = df[col].to_numpy(dtype='float64', na_value=np.nan)
+        if np.isinf(v).any():
+            raise ValueError('column %r holds an infinite value' % (col,))
+        if strict and np.isnan(v).any():
+            raise ValueError('column %r holds missing values' % (col,))
+        vals.append(v)
+    shifts = [float(np.nanmean(v)) if not np.isnan(v).all() else 0.0 for v in vals]
+    dev = _assoc_device()
+    Vc, Vy = len(codes), len(vals)
+    buf = np.empty(8 * Vy * (n + 1) + 4 * Vc * n, dtype=np.uint8)
+    if Vy:
+        buf[:8 * Vy * n].view(np.float64).reshape(Vy, n)[:] = np.stack(vals)
+        buf[8 * Vy * n:8 * Vy * (n + 1)].view(np.float64)[:] = shifts
+    if Vc:
+        buf[8 * Vy * (n + 1):].view(np.int32).reshape(Vc, n)[:] = np.stack(codes)
+    d = torch.from_numpy(buf).to(dev)
+    d_vals = d[:8 * Vy * n].view(torch.float64).view(Vy, n) if Vy else None
+    d_shift = d[8 * Vy * n:8 * Vy * (n + 1)].view(torch.float64) if Vy else None
+    d_codes = d[8 * Vy * (n + 1):].view(torch.int32).view(Vc, n) if Vc else None
+    return d_codes, np.asarray(card, dtype=np.int64), d_vals, d_shift
+
+
+def _distinct(items):
+    seen = {}
+    for it in items:
+        seen.setdefault(it, len(seen))
+    return list(seen), seen
+
+
+def _assoc_prepare(df, pairs, family, strict=False):
+    "host half of one call: the distinct columns of `pairs` on the device and the pairs as column indices"
+    xs, ys = [p[0] for p in pairs], [p[1] for p in pairs]
+    if family == 'cat_cont':
+        ccols, cwhere = _distinct(xs)
+        ycols, ywhere = _distinct(ys)
+        codes, card, vals, shift = _assoc_upload(df, ccols, ycols, strict)
+        return codes, card, vals, shift, np.array([cwhere[x] for x in xs]), np.array([ywhere[y] for y in ys])
+    cols, where = _distinct(xs + ys)
+    codes, card, vals, shift = _assoc_upload(df, cols if family == 'cat' else [], cols if family == 'cont' else [], strict)
+    px, py = np.array([where[x] for x in xs]), np.array([where[y] for y in ys])
+    if family == 'cat':
+        cells = card[px] * card[py]
+        if cells.max() > ops.ASSOC_MAX_TABLE_CELLS:
+            k = int(cells.argmax())
+            raise ValueError('the contingency table of %r x %r has %d cells, above the limit of %d'
+                             % (xs[k], ys[k], cells[k], ops.ASSOC_MAX_TABLE_CELLS))
+    return codes, card, vals, shift, px, py
+
+
+def _assoc_run(prepared, family, with_abs=True):
+    "device half: the K13 kernels over all pairs -> float64 [P, K] on the device"
+    codes, card, vals, shift, px, py = prepared
+    if family == 'cat_cont':
+        return ops.assoc_cat_cont(codes, card, vals, shift, px, py)
+    if family == 'cont':
+        return ops.assoc_cont_cont(vals, shift, px, py, with_abs=with_abs)
+    cells = card[px] * card[py]
+    out, lo = [], 0
+    while lo < len(px):                         # chunks of the pair list: the table workspace stays bounded
+        hi = lo + 1
+        while hi < len(px) and cells[lo:hi + 1].sum() <= _ASSOC_CHUNK_CELLS:
+            hi += 1
+        tables, offsets = ops.assoc_contingency(codes, card, px[lo:hi], py[lo:hi])
+        out.append(ops.assoc_table_stats(tables, card, px[lo:hi], py[lo:hi], offsets))
+        lo = hi
+    return torch.cat(out)
+
+
+def _assoc_stats(df, pairs, family, with_abs=True, strict=False):
+    """Per-pair statistics of one family as a float64 numpy array [P, K] (see ops.assoc_table_stats, ops.assoc_cat_cont,
+    ops.assoc_cont_cont): one upload, the kernels, one copy back."""
+    return _assoc_run(_assoc_prepare(df, pairs, family, strict), family, with_abs).cpu().numpy()
+
+
+def _association_values(df, pairs, Type):
+    "get_association for every (X, Y) of `pairs`, as a list of floats: the reference's short-circuits, one device call for the rest"
+    if Type not in ASSOCIATION_TYPES:
+        raise ValueError('Type must be one of %s (got %r)' % (sorted(ASSOCIATION_TYPES), Type))
+    family = ASSOCIATION_TYPES[Type]
+    values = [1.0 if x == y else None for x, y in pairs]
+    todo = [k for k, v in enumerate(values) if v is None]
+    if not todo:
+        return values
+    if len(df) == 0:
+        return [0.0 if v is None else v for v in values]
+    st = _assoc_stats(df, [pairs[k] for k in todo], family, with_abs=(Type == 'abs_max_correlation'))
+    for k, s in zip(todo, st):
+        if family == 'cat':
+            n, rows, cols, hx, hy, hxy = s
+            if n == 0 or rows == 1 or cols == 1:
+                values[k] = 0.0
+            else:
+                i_xy = hx + hy - hxy
+                values[k] = float(i_xy / hy if Type == 'mutual_info_asymmetric' else 0.5 * (i_xy / hx + i_xy / hy))
+        elif family == 'cat_cont':
+            n, cats, ratio, max_ratio, ymin, ymax = s
+            if n == 0 or cats == 1 or ymin == ymax:
+                values[k] = 0.0
+            else:
+                values[k] = float(ratio if Type == 'correlation_ratio' else min(max_ratio / 3, 1.0))
+        else:
+            n, degenerate, c1, cmax = s
+            values[k] = 0.0 if degenerate else float(c1 if Type == 'abs_correlation' else cmax)
+    return values
+
+
+def _divide(a, b):
+    with np.errstate(divide='ignore', invalid='ignore'):
+        return float(np.float64(a) / np.float64(b))
+
+
+def entropy(df, X):
+    """Entropy (natural log) of the categorical column X of df (StructuredData.py:240-244).  Raises ValueError if X holds a missing
+    value (the reference assumes there is none and would divide by the wrong length)."""
+    return float(_assoc_stats(df, [(X, _ONE)], 'cat', strict=True)[0, 3])
+
+
+def joint_entropy(df, X, Y):
+    """Joint entropy of the categorical columns X, Y (:246-252), with the reference's clamp: every empty cell of the observed
+    categories' table adds -1e-20 log(1e-20).  Raises ValueError on a missing value."""
+    return float(_assoc_stats(df, [(X, Y)], 'cat', strict=True)[0, 5])
+
+
+def normed_mutual_info(df, X, Y, symmetric):
+    """I(X;Y)/H(Y), or symmetric: 0.5 (I(X;Y)/H(X) + I(X;Y)/H(Y)) (:254-262).  Raises ValueError on a missing value."""
+    _, _, _, hx, hy, hxy = _assoc_stats(df, [(X, Y)], 'cat', strict=True)[0]
+    i_xy = hx + hy - hxy
+    return 0.5 * (_divide(i_xy, hx) + _divide(i_xy, hy)) if symmetric else _divide(i_xy, hy)
+
+
+def correlation_ratio(df, X, Y):
+    """Correlation ratio of categorical X and numeric Y (:264-271): the between-category sum of squares is divided by n, the variance
+    of Y is the ddof=1 one.  Raises ValueError on a missing or infinite value.  Last bits may differ between calls (fp64 atomics)."""
+    return float(_assoc_stats(df, [(X, Y)], 'cat_cont', strict=True)[0, 2])
+
+
+def max_correlation_ratio(df, X, Y):
+    """max_i |mean(Y | X = x_i) - mean(Y)| / std(Y) (:273-287), raw: in [0, inf).  Raises ValueError on a missing or infinite value.
+    Last bits may differ between calls (fp64 atomics)."""
+    return float(_assoc_stats(df, [(X, Y)], 'cat_cont', strict=True)[0, 3])
+
+
+def abs_max_correlation(df, X, Y):
+    """max(|c1|, |c2|, |c3|, |c4|) with c1 = corr(X, Y), c2 = corr(X, Y2), c3 = corr(X2, Y), c4 = corr(X2, Y2), X2 = |X - mean(X)|,
+    Y2 = |Y - mean(Y)| (:289-309).  A correlation with a constant X2 or Y2 (NaN in pandas) is skipped; X2 counts as constant when its
+    centred sum of squares is at most n (2^-26 mean(X2))^2.  Raises ValueError on a missing or infinite value; NaN if X or Y is constant."""
+    return float(_assoc_stats(df, [(X, Y)], 'cont', strict=True)[0, 3])
+
+
+def get_association(df, X, Y, Type):
+    """Unsigned association strength of X and Y in [0, 1] (:311-338).  Type: 'abs_correlation' / 'abs_max_correlation' (both numeric),
+    'correlation_ratio' / 'max_correlation_ratio' (X categorical, Y numeric; the latter as min(ratio / 3, 1)),
+    'mutual_info_symmetric' / 'mutual_info_asymmetric' (both categorical).  X == Y gives 1.0; the rows are those where both are
+    present; no such row, or a single distinct value in either column on those rows, gives 0.0."""
+    return _association_values(df, [(X, Y)], Type)[0]
+
+
+def _need(module, what):
+    import importlib
+    try:
+        return importlib.import_module(module)
+    except ImportError as e:
+        raise ImportError('plot=True needs %s for %s, which is not installed (pass plot=False)' % (module.split('.')[0], what)) from e
+
+
+def associations_dependent(df, Type, variables, depend_var, reverse=False, plot=True):
+    """Association of each of `variables` with depend_var (reverse: of depend_var with each) as a pd.Series indexed by `variables`,
+    optionally as a bar plot (:340-359).  One device call for all variables."""
+    variables = list(variables)
+    pairs = [(depend_var, v) if reverse else (v, depend_var) for v in variables]
+    associations = pd.Series(_association_values(df, pairs, Type), index=variables, dtype='float64')
+    if plot:
+        _need('matplotlib.pyplot', 'the bar plot')
+        figsize = (len(associations) / 2, max(len(associations) / 4, 4))
+        associations.plot.bar(title='Associations with ' + str(depend_var), figsize=figsize)
+    return associations
+
+
+def associations_pairs(df, Type, cat_vars=None, cont_vars=None, plot=True):
+    """Associations between pairs of variables as a pd.DataFrame, optionally as a heatmap (:361-428).  cat_vars and cont_vars: rows
+    cat_vars, columns cont_vars; cat_vars alone or cont_vars alone: all ordered pairs of that list.  One device call for all pairs."""
+    if cat_vars and cont_vars:
+        rows, cols = list(cat_vars), list(cont_vars)
+    elif cont_vars is None:
+        rows = cols = list(cat_vars)
+    elif cat_vars is None:
+        rows = cols = list(cont_vars)
+    else:
+        raise ValueError('give cat_vars, cont_vars or both')
+    values = _association_values(df, [(x, y) for x in rows for y in cols], Type)
+    Assoc = pd.DataFrame(np.asarray(values, dtype='float64').reshape(len(rows), len(cols)), index=rows, columns=cols)
+    if plot:
+        _need('matplotlib.pyplot', 'the heatmap')
+        sns = _need('seaborn', 'the heatmap')
+        shown = Assoc if rows is not cols else Assoc - pd.DataFrame(np.identity(len(rows)), index=rows, columns=cols)
+        heatmap = sns.heatmap(shown, cbar_kws={'shrink': .5}, cmap='Reds', fmt='.2f', square=True, linewidths=.5, annot=True,
+                              xticklabels=cols, yticklabels=rows)
+        heatmap.figure.set_size_inches(len(rows), 1.5 * len(cols))
+        sns.despine()
+    return Assoc
 
 
 # ---- §1.3 feature engineering ------------------------------------------------------------------------------------------

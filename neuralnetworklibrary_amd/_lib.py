@@ -154,6 +154,12 @@ SIGNATURES = {
     'nnl_bn_bwd': (C.c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, i64, i64, C.c_int, C.c_int, c_p, sz, c_p]),
     'nnl_seg_event_gaps': (C.c_int, [c_p, c_p, c_p, i64, f64, c_p, c_p, c_p, c_p, c_p]),
     'nnl_seg_rolling': (C.c_int, [c_p, c_p, c_p, c_p, i64, i64, i64, i64, C.c_int, C.c_int, c_p, c_p]),
+    'nnl_assoc_contingency': (C.c_int, [c_p, c_p, i64, i64, c_p, c_p, c_p, i64, c_p, c_p]),
+    'nnl_assoc_table_stats': (C.c_int, [c_p, c_p, i64, c_p, c_p, c_p, i64, c_p, c_p]),
+    'nnl_assoc_cat_cont_workspace_bytes': (sz, [c_p, i64, c_p, i64]),
+    'nnl_assoc_cat_cont': (C.c_int, [c_p, c_p, i64, c_p, c_p, i64, i64, c_p, c_p, i64, c_p, sz, c_p, c_p]),
+    'nnl_assoc_cont_cont_workspace_bytes': (sz, [i64, i64]),
+    'nnl_assoc_cont_cont': (C.c_int, [c_p, c_p, i64, i64, c_p, c_p, i64, C.c_int, c_p, sz, c_p, c_p]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -1604,5 +1604,144 @@ def seg_rolling(t, seg_start, seg_end, x, stats, count_window=0, span=0, forward
 
 __all__ += ['seg_event_gaps', 'seg_rolling', 'SEG_SCAN_TILE', 'ROLL_STATS']
 
+
+# ---------------------------------------------------------------------------------------------------------
+# K13 association measures of the structured-data EDA (include/nnl.h): many column pairs per call.
+# codes int32 [V, n] (-1 missing), vals float64 [V, n] (NaN missing) and shift float64 [V] are device tensors; card and the pair
+# lists are host integer sequences.
+# ---------------------------------------------------------------------------------------------------------
+ASSOC_ROW_TILE = 1024                    # NNL_ASSOC_ROW_TILE: rows a workgroup stages at a time
+ASSOC_LDS_CELLS = 6144                   # NNL_ASSOC_LDS_CELLS: largest contingency table counted in LDS
+ASSOC_MOMENT_LDS_CELLS = 1152            # NNL_ASSOC_MOMENT_LDS_CELLS: most categories whose moments are summed in LDS
+ASSOC_MAX_GROUPS = 256                   # NNL_ASSOC_MAX_GROUPS: workgroups per launch
+ASSOC_CONTINGENCY_PAIRS = 32             # pairs one contingency launch takes (a longer list is cut into several launches)
+ASSOC_CONT_PAIRS = 16                    # pairs one cont x cont launch takes
+ASSOC_MAX_TABLE_CELLS = 2 ** 26          # per table
+ASSOC_MAX_CALL_CELLS = 2 ** 28           # all tables of one call (1 GiB of uint32): the caller chunks its pair list below this
+
+
+def _host_i32(a):
+    return np.ascontiguousarray(np.asarray(a, dtype=np.int64).astype(np.int32))
+
+
+def _hp(a):
+    return ctypes.c_void_p(a.ctypes.data)
+
+
+def _assoc_pairs(name, pair_x, pair_y, Vx, Vy):
+    px, py = _host_i32(pair_x), _host_i32(pair_y)
+    if px.ndim != 1 or px.shape != py.shape or len(px) < 1:
+        raise ValueError('%s: pair_x and pair_y must be equally long, non-empty lists' % name)
+    if px.min() < 0 or px.max() >= Vx or py.min() < 0 or py.max() >= Vy:
+        raise ValueError('%s: a pair names a column outside [0, %d) x [0, %d)' % (name, Vx, Vy))
+    return px, py
+
+
+def _assoc_columns(name, t, dtype, what):
+    require_cuda(t)
+    if t.dtype != dtype or t.dim() != 2 or t.shape[0] < 1 or not 1 <= t.shape[1] < 2 ** 31:
+        raise ValueError('%s: %s must be %s [V, n] with 1 <= n < 2^31' % (name, what, dtype))
+    return t.contiguous()
+
+
+def _assoc_card(name, card, V):
+    card = _host_i32(card)
+    if card.shape != (V,) or card.min() < 1:
+        raise ValueError('%s: card must hold %d cardinalities of at least 1' % (name, V))
+    return card
+
+
+def assoc_table_offsets(card, pair_x, pair_y):
+    "int64 [P+1]: where the row-major [card[x], card[y]] table of each pair starts in the tables vector"
+    card = np.asarray(card, dtype=np.int64)
+    cells = card[np.asarray(pair_x, dtype=np.int64)] * card[np.asarray(pair_y, dtype=np.int64)]
+    return np.concatenate([[0], np.cumsum(cells)]).astype(np.int64)
+
+
+def assoc_contingency(codes, card, pair_x, pair_y):
+    """Contingency tables of many column pairs: codes int32 [V, n] on the device, card [V], pair_x / pair_y [P] host integers.
+    Returns (tables, offsets): tables int32 [offsets[P]] on the device (exact counts of the rows where both codes are present; the
+    table of pair p is tables[offsets[p]:offsets[p+1]].view(card[x], card[y])) and offsets as assoc_table_offsets gives them."""
+    codes = _assoc_columns('assoc_contingency', codes, torch.int32, 'codes')
+    V, n = codes.shape
+    card = _assoc_card('assoc_contingency', card, V)
+    px, py = _assoc_pairs('assoc_contingency', pair_x, pair_y, V, V)
+    offsets = assoc_table_offsets(card, px, py)
+    cells = np.diff(offsets)
+    if cells.max() > ASSOC_MAX_TABLE_CELLS:
+        raise ValueError('assoc_contingency: a table of %d cells exceeds the limit of %d' % (cells.max(), ASSOC_MAX_TABLE_CELLS))
+    if offsets[-1] > ASSOC_MAX_CALL_CELLS:
+        raise ValueError('assoc_contingency: %d cells in one call exceed the limit of %d: pass fewer pairs per call'
+                         % (offsets[-1], ASSOC_MAX_CALL_CELLS))
+    tables = torch.empty(int(offsets[-1]), dtype=torch.int32, device=codes.device)
+    check(lib.nnl_assoc_contingency(ptr(codes), _hp(card), V, n, _hp(px), _hp(py), _hp(offsets), len(px), ptr(tables), stream()))
+    return tables, offsets
+
+
+def assoc_table_stats(tables, card, pair_x, pair_y, offsets):
+    """float64 [P, 6] on the device from assoc_contingency's tables: n, non-empty rows, non-empty columns, H_X, H_Y and H_XY (with
+    the reference's 1e-20 clamp term for every empty cell of the observed table).  Bit-equal from call to call."""
+    require_cuda(tables)
+    if tables.dtype != torch.int32 or tables.dim() != 1:
+        raise ValueError('assoc_table_stats: tables must be the int32 vector assoc_contingency returns')
+    card = _assoc_card('assoc_table_stats', card, len(card))
+    px, py = _assoc_pairs('assoc_table_stats', pair_x, pair_y, len(card), len(card))
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    if not np.array_equal(offsets, assoc_table_offsets(card, px, py)) or offsets[-1] != tables.numel():
+        raise ValueError('assoc_table_stats: offsets do not match the cardinalities of the pairs and the length of tables')
+    out = torch.empty(len(px), 6, dtype=torch.float64, device=tables.device)
+    check(lib.nnl_assoc_table_stats(ptr(tables.contiguous()), _hp(card), len(card), _hp(px), _hp(py), _hp(offsets), len(px), ptr(out),
+                                    stream()))
+    return out
+
+
+def _assoc_vals(name, vals, shift):
+    vals = _assoc_columns(name, vals, torch.float64, 'vals')
+    require_cuda(shift)
+    if shift.dtype != torch.float64 or tuple(shift.shape) != (vals.shape[0],) or shift.device != vals.device:
+        raise ValueError('%s: shift must be float64 [%d] on %s' % (name, vals.shape[0], vals.device))
+    return vals, shift.contiguous()
+
+
+def assoc_cat_cont(codes, card, vals, shift, pair_x, pair_y):
+    """Moments of a continuous column per category, many pairs at once: pair p = (codes[pair_x[p]], vals[pair_y[p]]).  Returns float64
+    [P, 6] on the device: n, non-empty categories, correlation ratio, raw max correlation ratio, min and max of vals - shift, over
+    the rows where the code is present and the value is not NaN.  The per-category sums are fp64 atomics: the last bits of the two
+    ratios may differ between calls (n, the category count, min and max do not)."""
+    codes = _assoc_columns('assoc_cat_cont', codes, torch.int32, 'codes')
+    vals, shift = _assoc_vals('assoc_cat_cont', vals, shift)
+    if vals.shape[1] != codes.shape[1] or vals.device != codes.device:
+        raise ValueError('assoc_cat_cont: codes and vals must hold the same rows on one device')
+    card = _assoc_card('assoc_cat_cont', card, codes.shape[0])
+    if card.max() > ASSOC_MAX_TABLE_CELLS:
+        raise ValueError('assoc_cat_cont: %d categories exceed the limit of %d' % (card.max(), ASSOC_MAX_TABLE_CELLS))
+    px, py = _assoc_pairs('assoc_cat_cont', pair_x, pair_y, codes.shape[0], vals.shape[0])
+    nbytes = int(lib.nnl_assoc_cat_cont_workspace_bytes(_hp(card), len(card), _hp(px), len(px)))
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=codes.device)
+    out = torch.empty(len(px), 6, dtype=torch.float64, device=codes.device)
+    check(lib.nnl_assoc_cat_cont(ptr(codes), _hp(card), codes.shape[0], ptr(vals), ptr(shift), vals.shape[0], codes.shape[1], _hp(px),
+                                 _hp(py), len(px), ptr(ws), nbytes, ptr(out), stream()))
+    return out
+
+
+def assoc_cont_cont(vals, shift, pair_x, pair_y, with_abs=True):
+    """Correlations of many pairs of continuous columns.  Returns float64 [P, 4] on the device: n, degenerate (1.0: no common row, or a
+    column with one distinct value on the pair's rows), |corr(x, y)| and, with_abs, the absolute maximum correlation (a second pass
+    about the pair's means), else NaN.  No atomics: bit-equal from call to call."""
+    vals, shift = _assoc_vals('assoc_cont_cont', vals, shift)
+    V, n = vals.shape
+    px, py = _assoc_pairs('assoc_cont_cont', pair_x, pair_y, V, V)
+    nbytes = int(lib.nnl_assoc_cont_cont_workspace_bytes(n, len(px)))
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=vals.device)
+    out = torch.empty(len(px), 4, dtype=torch.float64, device=vals.device)
+    check(lib.nnl_assoc_cont_cont(ptr(vals), ptr(shift), V, n, _hp(px), _hp(py), len(px), int(bool(with_abs)), ptr(ws), nbytes, ptr(out),
+                                  stream()))
+    return out
+
+
+__all__ += ['assoc_contingency', 'assoc_table_stats', 'assoc_table_offsets', 'assoc_cat_cont', 'assoc_cont_cont', 'ASSOC_ROW_TILE',
+            'ASSOC_LDS_CELLS', 'ASSOC_MOMENT_LDS_CELLS', 'ASSOC_MAX_GROUPS', 'ASSOC_CONTINGENCY_PAIRS', 'ASSOC_CONT_PAIRS',
+            'ASSOC_MAX_TABLE_CELLS', 'ASSOC_MAX_CALL_CELLS']
+
 from .ops_text import (lstm_layer, embedding_rowmask, softmax_cross_entropy, cross_entropy_nd, seq_activation_reg)  # noqa: E402,F401
 __all__ += ['lstm_layer', 'embedding_rowmask', 'softmax_cross_entropy', 'cross_entropy_nd', 'seq_activation_reg', 'conv_add_upsampled']

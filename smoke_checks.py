@@ -110,7 +110,41 @@ def check_lstm_lm(device):
         _close(p.grad, q.grad, 1e-3, 1e-5 * max(q.grad.abs().max().item(), 1e-3), 'LM grad ' + n)
 
 
-CHECKS = [check_collab, check_resnet_block, check_tabular, check_retina_loss, check_lstm_lm]
+def check_tabular_assoc(device):
+    """get_association of the three families on a 64-row frame with missing values (K13: contingency counts, per-category moments,
+    two-pass correlations), against numpy written out here."""
+    import pandas as pd
+    from neuralnetworklibrary_amd.Applications import StructuredData as SD
+    rs = np.random.RandomState(3)
+    n = 64
+    a, b = rs.randint(0, 4, n).astype('float64'), rs.randint(0, 3, n).astype('float64')
+    x = rs.standard_normal(n) + a
+    y = x * x + rs.standard_normal(n)
+    a[::9], x[1::7] = np.nan, np.nan
+    df = pd.DataFrame({'a': a, 'b': b, 'x': x, 'y': y})
+    ok = ~np.isnan(a)
+    t = np.bincount((a[ok] * 3 + b[ok]).astype(int), minlength=12).reshape(4, 3) / ok.sum()
+    h = lambda p: -(np.log(p[p > 0]) * p[p > 0]).sum()      # noqa: E731  (no empty cell here: no clamp term)
+    assert (t > 0).all()
+    i_ab = h(t.sum(1)) + h(t.sum(0)) - h(t.ravel())
+    want_mi = 0.5 * (i_ab / h(t.sum(1)) + i_ab / h(t.sum(0)))
+    ok = ~np.isnan(a) & ~np.isnan(x)
+    av, xv = a[ok], x[ok]
+    between = sum((av == k).sum() * (xv[av == k].mean() - xv.mean()) ** 2 for k in range(4)) / ok.sum()
+    want_ratio = np.sqrt(between / xv.var(ddof=1))
+    ok = ~np.isnan(x)
+    dx, dy = x[ok] - x[ok].mean(), y[ok] - y[ok].mean()
+    ax, ay = np.abs(dx) - np.abs(dx).mean(), np.abs(dy) - np.abs(dy).mean()
+    corr = lambda u, v: abs(u @ v) / np.sqrt((u @ u) * (v @ v))      # noqa: E731
+    want_corr = max(corr(dx, dy), corr(dx, ay), corr(ax, dy), corr(ax, ay))
+    for Type, X, Y, want in (('mutual_info_symmetric', 'a', 'b', want_mi), ('correlation_ratio', 'a', 'x', want_ratio),
+                             ('abs_max_correlation', 'x', 'y', want_corr)):
+        got = SD.get_association(df, X, Y, Type)
+        if not abs(got - want) <= 1e-12:
+            raise AssertionError(f'smoke: {Type} mismatch, got {got!r}, want {want!r}')
+
+
+CHECKS = [check_collab, check_resnet_block, check_tabular, check_retina_loss, check_lstm_lm, check_tabular_assoc]
 
 
 def run_all(device='cuda:0'):
