@@ -765,6 +765,56 @@ size_t nnl_assoc_cont_cont_workspace_bytes(int64_t n, int64_t P);
 int nnl_assoc_cont_cont(const double* vals, const double* shift, int64_t V, int64_t n, const int32_t* pair_x, const int32_t* pair_y,
                         int64_t P, int with_abs, void* workspace, size_t workspace_bytes, double* out, void* stream);
 
+/* ---- K14: detection evaluation (Applications/pycocotools/cocoeval.py:171-198, 243-428; Applications/Vision.py:1696-1747) ------
+ * A group is an (image, category) pair with at least one detection or one ground truth; groups are sorted by (category, image id),
+ * so group g owns detections [dt_off[g], dt_off[g+1]) and ground truths [gt_off[g], gt_off[g+1]) and category k owns groups
+ * [cat_grp_off[k], cat_grp_off[k+1]) and detections [cat_dt_off[k], cat_dt_off[k+1]).  Every array but the parameter lists
+ * (thresholds, area ranges, maxDets: HOST arrays, validated and passed to the kernels as arguments) is a DEVICE array.  The entries
+ * validate sizes and the parameter lists before any HIP call; the CALLER checks, before the upload, that every offset array is
+ * non-decreasing, starts at 0 and ends at the length of what it indexes, and that order / dt_rank are in range.
+ * Limits: T <= NNL_DET_EVAL_MAX_T thresholds, A <= NNL_DET_EVAL_MAX_A area ranges, M <= NNL_DET_EVAL_MAX_M maxDets entries,
+ * R <= NNL_DET_EVAL_MAX_R recall thresholds, fewer than 2^31 groups / detections / ground truths; none on the size of a group.
+ *
+ * nnl_det_coco_match (cocoeval.py:171-198 computeIoU, :243-321 evaluateImg): dt_box / gt_box float64 [., 4] = [x, y, w, h]; the
+ * detections of a group sorted by score descending (stable) and cut to maxDets[-1] by the caller; gt_area the annotation's area;
+ * gt_flags bit 0 = iscrowd, bit 1 = ignore.  area_rng float64 [A, 2].  The overlap of detection D and ground truth G, fp64, one
+ * operation at a time: w = min(D.x + D.w, G.x + G.w) - max(D.x, G.x), h likewise, 0 if w <= 0 or h <= 0, else
+ * w h / (crowd ? D.w D.h : D.w D.h + G.w G.h - w h); computed once per group for all A x T matchers, each of which runs the
+ * reference's greedy loop in a lane of its own (one wave per group).  A group needs D G + ceil((A T + A) G / 8) doubles: in LDS
+ * up to NNL_DET_EVAL_LDS_DOUBLES (scr_off[g] = -1), else at scratch + scr_off[g] doubles (scr_off int64 [NG]).  Outputs:
+ * dtm int32 [A, T, Nd] = position of the matched ground truth in its group + 1, or 0; dtig uint8 [A, T, Nd] the detection's
+ * ignore bit; npig int32 [A, NG] the group's ground truths that are not ignored in range a; status int32 [1] = 1 if a group's
+ * buffer did not fit where scr_off put it (the group is skipped: the caller must raise).
+ * nnl_det_coco_accumulate (cocoeval.py:323-428): one workgroup per (k, a, m, t).  order int32 [Nd]: the detections of each category
+ * in stable descending-score order over (group, rank); dt_rank int32 [Nd] the rank inside the group; entry m keeps rank <
+ * max_dets[m].  precision, scores float64 [T, R, K, A, M], recall float64 [T, K, A, M]; a (k, a) block without a group or without a
+ * counting ground truth is -1.  rec_thrs must ascend.
+ * nnl_det_map_match (Vision.py:1696-1728): pr_box / gt_box float32 [., 4] min-max boxes; fp32 jaccard in retinanet.jaccard's
+ * operation order; every ground truth marks its first arg-max prediction in correct uint8 [T, Np] (zeroed by the entry) where the
+ * overlap, widened to fp64, is > thrs[t].
+ * nnl_det_map_integrate (Vision.py:1730-1747): one workgroup per (category, threshold); order int32 [Np] the predictions of each
+ * category by descending score (ties in any order: the entry puts the correct ones of a run of equal scores first), score float64
+ * [Np], ntrue int64 [C].  out float64 [T, C] = sum of the max-smoothed precision at the correct positions / ntrue (0 / 0 = NaN).
+ * The workspace holds T Np doubles.  Fixed summation order: the same inputs give the same bits. */
+#define NNL_DET_EVAL_MAX_T 16
+#define NNL_DET_EVAL_MAX_A 8
+#define NNL_DET_EVAL_MAX_M 8
+#define NNL_DET_EVAL_MAX_R 128
+#define NNL_DET_EVAL_LDS_DOUBLES 2048
+int nnl_det_coco_match(const int32_t* dt_off, const int32_t* gt_off, const double* dt_box, const double* gt_box, const double* gt_area,
+                       const uint8_t* gt_flags, const int64_t* scr_off, int64_t NG, int64_t Nd, int64_t Ng, const double* iou_thrs, int64_t T,
+                       const double* area_rng, int64_t A, void* scratch, size_t scratch_bytes, int32_t* dtm, uint8_t* dtig, int32_t* npig,
+                       int32_t* status, void* stream);
+int nnl_det_coco_accumulate(const int32_t* cat_grp_off, const int32_t* cat_dt_off, const int32_t* order, const int32_t* dt_rank,
+                            const double* dt_score, const int32_t* dtm, const uint8_t* dtig, const int32_t* npig, int64_t K, int64_t NG,
+                            int64_t Nd, int64_t T, int64_t A, const int32_t* max_dets, int64_t M, const double* rec_thrs, int64_t R,
+                            double* precision, double* scores, double* recall, void* stream);
+int nnl_det_map_match(const int32_t* pr_off, const int32_t* gt_off, const float* pr_box, const float* gt_box, int64_t NG, int64_t Np,
+                      int64_t Ng, const double* thrs, int64_t T, uint8_t* correct, void* stream);
+size_t nnl_det_map_integrate_workspace_bytes(int64_t Np, int64_t T);
+int nnl_det_map_integrate(const int32_t* cat_pr_off, const int32_t* order, const double* score, const uint8_t* correct, const int64_t* ntrue,
+                          int64_t C, int64_t Np, int64_t T, void* workspace, size_t workspace_bytes, double* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,7 +13,8 @@ K9), replacing the per-image cv2 / numpy `Transform.__call__` (:449-507) in Data
 normalises, flips, resizes, jitters and pads the images and flips, scales and shifts their boxes in float64.
 Out of scope here: file decode and the csv / folder / json constructors (the data classes take decoded H x W x 3 uint8 arrays),
 `pad` and `max_noise` (cv2.GaussianBlur), TransformBBoxShowPreds, TTA_bbox and TransformBBox.get_values, and ImageLearner's
-display helpers (show_images, show_bbox_preds) and coco_pascal_eval.
+display helpers (show_images, show_bbox_preds).  Scoring a detector runs on the device too: coco_pascal_eval
+(the COCO / Pascal protocol of pycocotools' COCOeval for boxes) and mAP_device (ops.det_eval_coco / ops.det_map, K14).
 """
 import numpy as np
 import torch
@@ -688,8 +689,9 @@ class ImageLearner(Learner):
     With data = ImageDataObj(..., 'bbox', ..., get_transforms_bbox(...), ...) the whole detection workflow runs
     from the public API: fit trains from device_data.DetectionBatches minibatches (a new padded size runs the step eagerly),
     predict('val') divides each image's boxes by its 'scale', TTA_bbox('val', transforms) merges five passes over the resident set,
-    compute_mAP scores either.  The visualisation helpers (show_images, show_bbox_preds) and the pycocotools convenience of the
-    reference's ImageLearner are UI / external tooling (out of scope)."""
+    compute_mAP scores either (device=True: on the device) and coco_pascal_eval gives the twelve COCO / Pascal numbers without
+    pycocotools.  The visualisation helpers (show_images, show_bbox_preds) of the reference's ImageLearner are UI (out of scope,
+    SURVEY §2.1 row 12)."""
 
     def _transforms(self):
         "the Transform objects of the train, val and (if any) test datasets: the ones their loaders read at every minibatch"
@@ -860,9 +862,116 @@ class ImageLearner(Learner):
         return out
 
     def compute_mAP(self, predictions=None, thresh=0.05, max_overlap=0.5, rel_thresh=None, top_k=1000, max_boxes=20,
-                    dup=None, inc=None, mAP_thresholds=COCO_thresholds):
-        "mAP of the validation set, target_type 'bbox' only (Vision.py:2123-2140)"
+                    dup=None, inc=None, mAP_thresholds=COCO_thresholds, device=False):
+        """mAP of the validation set, target_type 'bbox' only (Vision.py:2123-2140).  device=True scores on the device (mAP_device:
+        the same numbers up to the summation order of each curve); the default is the host loop."""
         categories, targets = self.data.categories, self.data.val_ds.y
         if predictions is None:
             predictions = self.predict('val', True, thresh, max_overlap, rel_thresh, top_k, max_boxes, dup, inc)
+        if device:
+            return mAP_device(predictions, targets, categories, mAP_thresholds)
         return mAP(predictions, targets, categories, mAP_thresholds)
+
+    def coco_pascal_eval(self, val_json, predictions=None, thresh=0.05, max_overlap=0.5, rel_thresh=None, top_k=1000, max_boxes=20,
+                         dup=None, inc=None, cat2dscat=None, save_preds=False):
+        """The COCO / Pascal evaluation of the validation set's box predictions (Vision.py:2142-2177): what pycocotools'
+        COCOeval(coco_true, coco_pred, 'bbox') evaluate / accumulate / summarize compute with Params.setDetParams (iouThrs
+        linspace(.5, .95, 10), recThrs linspace(0, 1, 101), maxDets [1, 10, 100], the four area ranges), without pycocotools: the
+        per-(image, category) matching and the per-(category, area, maxDets, threshold) curves are HIP kernels (ops.det_eval_coco,
+        K14) and the twelve summary numbers are numpy means over the arrays that come back.  Only iouType 'bbox' with useCats = 1.
+        val_json: path of the annotation file, or the loaded dict.  predictions: as predict('val') returns them, or None to predict
+        with the other arguments.  Image ids are self.data.val_ds.images[i]['id']; the category map is `cat2dscat`, else
+        self.data.cat2dscat, else {i: categories[i]['id']} in the json's order (as from_json_bbox builds it, Vision.py:1120).
+        Deliberate differences from the reference:
+          * it RETURNS the twelve numbers (AP, AP50, AP75, AP small / medium / large, AR at 1 / 10 / 100 detections, AR small /
+            medium / large) as a float64 vector; the reference returns None.  They are printed in summarize's format when
+            Learner.verbose;
+          * precision [T, R, K, A, M], recall [T, K, A, M], scores and the parameters are kept in self.coco_eval;
+          * preds.json is written (to self.PATH) only with save_preds=True;
+          * ValueError, before anything is uploaded, for: an annotation id of 0 (COCOeval stores matched ids and tests `== 0` for
+            "unmatched", so such a ground truth matches and still counts as a false positive there; we store positions + 1), a
+            validation image without 'id', a prediction category absent from the map, and no prediction at all (the reference's
+            loadRes fails on anns[0])."""
+        import json
+        if self.target_type != 'bbox':
+            raise ValueError("coco_pascal_eval works only with target_type 'bbox' (got %r)" % (self.target_type,))
+        coco = val_json
+        if not isinstance(coco, dict):
+            with open(val_json) as f:
+                coco = json.load(f)
+        images = self.data.val_ds.images
+        missing = [i for i, im in enumerate(images) if not (isinstance(im, dict) and 'id' in im)]
+        if missing:
+            raise ValueError("coco_pascal_eval: validation image %d has no 'id'" % missing[0])
+        if cat2dscat is None:
+            cat2dscat = getattr(self.data, 'cat2dscat', None)
+        if cat2dscat is None:
+            cat2dscat = {i: c['id'] for i, c in enumerate(coco['categories'])}
+        if predictions is None:
+            predictions = self.predict('val', True, thresh, max_overlap, rel_thresh, top_k, max_boxes, dup, inc)
+        if len(predictions) != len(images):
+            raise ValueError('coco_pascal_eval: %d prediction lists for %d validation images' % (len(predictions), len(images)))
+        if sum(len(p[0]) for p in predictions) == 0:
+            raise ValueError('coco_pascal_eval: there is no prediction at all')
+        image_ids = [im['id'] for im in images]
+        iouThrs, recThrs, maxDets = np.linspace(.5, .95, 10), np.linspace(0, 1, 101), [1, 10, 100]      # Params.setDetParams
+        areaRng = [[0 ** 2, 1e5 ** 2], [0 ** 2, 32 ** 2], [32 ** 2, 96 ** 2], [96 ** 2, 1e5 ** 2]]
+        areaRngLbl = ['all', 'small', 'medium', 'large']
+        packed = ops.det_eval_pack(predictions, coco=coco, image_ids=image_ids, cat2dscat=cat2dscat, max_det=maxDets[-1])
+        if save_preds:
+            rows = []
+            for ID, (B, Cl, Sc) in zip(image_ids, predictions):
+                for box, cat, score in zip(B, Cl, Sc):
+                    rows.append({'image_id': ID, 'category_id': cat2dscat[int(cat)], 'score': float(score),
+                                 'bbox': [float(box[0]), float(box[1]), float(box[2] - box[0]), float(box[3] - box[1])]})
+            with open(self.PATH + 'preds.json', 'w') as f:
+                json.dump(rows, f, indent=4)
+        precision, recall, scores = ops.det_eval_coco(packed, iouThrs, recThrs, maxDets, areaRng, device=default_device())
+        self.coco_eval = {'precision': precision, 'recall': recall, 'scores': scores, 'iouThrs': iouThrs, 'recThrs': recThrs,
+                          'maxDets': maxDets, 'areaRng': areaRng, 'areaRngLbl': areaRngLbl, 'catIds': packed['cat_ids'],
+                          'imgIds': packed['img_ids']}
+        stats, lines = coco_summarize(precision, recall, iouThrs, maxDets, areaRngLbl)
+        self.coco_eval['stats'] = stats
+        if Learner.verbose:
+            print('\n'.join(lines))
+        return stats
+
+
+def coco_summarize(precision, recall, iouThrs, maxDets, areaRngLbl):
+    """The twelve numbers of COCOeval.summarize for detections (cocoeval.py:430-480) and their printed lines: each the mean of the
+    entries above -1 of a slice of precision [T, R, K, A, M] or recall [T, K, A, M], -1 if there is none."""
+    def one(ap, iouThr, area, max_det):
+        a, m = areaRngLbl.index(area), list(maxDets).index(max_det)
+        s = precision if ap else recall
+        if iouThr is not None:
+            s = s[np.where(iouThr == iouThrs)[0]]
+        s = s[..., a, m]
+        mean = -1 if len(s[s > -1]) == 0 else np.mean(s[s > -1])
+        iou = '{:0.2f}:{:0.2f}'.format(iouThrs[0], iouThrs[-1]) if iouThr is None else '{:0.2f}'.format(iouThr)
+        line = ' {:<18} {} @[ IoU={:<9} | area={:>6s} | maxDets={:>3d} ] = {:0.3f}'.format(
+            'Average Precision' if ap else 'Average Recall', '(AP)' if ap else '(AR)', iou, area, max_det, mean)
+        return mean, line
+    top = maxDets[2]
+    rows = [(1, None, 'all', top), (1, .5, 'all', top), (1, .75, 'all', top), (1, None, 'small', top), (1, None, 'medium', top),
+            (1, None, 'large', top), (0, None, 'all', maxDets[0]), (0, None, 'all', maxDets[1]), (0, None, 'all', top),
+            (0, None, 'small', top), (0, None, 'medium', top), (0, None, 'large', top)]
+    got = [one(*r) for r in rows]
+    return np.array([g[0] for g in got], dtype=np.float64), [g[1] for g in got]
+
+
+def mAP_device(predictions, targets, categories, thresholds=COCO_thresholds, verbose=True):
+    """`mAP` on the device: the per-(category, image) overlaps and arg-max marks and the per-(category, threshold) curves are HIP
+    kernels (ops.det_map, K14) instead of one Python iteration per (category, threshold, image).  Prints what mAP prints and returns
+    its mean; a value differs from mAP's only by the order in which a curve's non-negative terms are added.  ValueError for a
+    ground-truth box of non-positive area, whose 0 / 0 overlap the host path turns into a NaN arg-max."""
+    C = len(categories)
+    packed = ops.det_eval_pack(predictions, targets=targets, n_categories=C)
+    vals = ops.det_map(packed, thresholds, device=default_device())
+    if verbose:
+        for c in range(C):
+            for j, thresh in enumerate(thresholds):
+                print('cat =', c, ':', categories[c], ' thresh =', thresh)
+                print('cat-thresh mAP = ', vals[j, c])
+                print('')
+        print('Overall mAP = ', np.mean(vals))
+    return np.mean(vals)

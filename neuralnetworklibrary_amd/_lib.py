@@ -160,6 +160,11 @@ SIGNATURES = {
     'nnl_assoc_cat_cont': (C.c_int, [c_p, c_p, i64, c_p, c_p, i64, i64, c_p, c_p, i64, c_p, sz, c_p, c_p]),
     'nnl_assoc_cont_cont_workspace_bytes': (sz, [i64, i64]),
     'nnl_assoc_cont_cont': (C.c_int, [c_p, c_p, i64, i64, c_p, c_p, i64, C.c_int, c_p, sz, c_p, c_p]),
+    'nnl_det_coco_match': (C.c_int, [c_p] * 7 + [i64, i64, i64, c_p, i64, c_p, i64, c_p, sz, c_p, c_p, c_p, c_p, c_p]),
+    'nnl_det_coco_accumulate': (C.c_int, [c_p] * 8 + [i64, i64, i64, i64, i64, c_p, i64, c_p, i64, c_p, c_p, c_p, c_p]),
+    'nnl_det_map_match': (C.c_int, [c_p, c_p, c_p, c_p, i64, i64, i64, c_p, i64, c_p, c_p]),
+    'nnl_det_map_integrate_workspace_bytes': (sz, [i64, i64]),
+    'nnl_det_map_integrate': (C.c_int, [c_p, c_p, c_p, c_p, c_p, i64, i64, i64, c_p, sz, c_p, c_p]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

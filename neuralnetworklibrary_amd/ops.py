@@ -1743,5 +1743,345 @@ __all__ += ['assoc_contingency', 'assoc_table_stats', 'assoc_table_offsets', 'as
             'ASSOC_LDS_CELLS', 'ASSOC_MOMENT_LDS_CELLS', 'ASSOC_MAX_GROUPS', 'ASSOC_CONTINGENCY_PAIRS', 'ASSOC_CONT_PAIRS',
             'ASSOC_MAX_TABLE_CELLS', 'ASSOC_MAX_CALL_CELLS']
 
+
+# ---------------------------------------------------------------------------------------------------------
+# K14 detection evaluation (include/nnl.h): the COCO / Pascal protocol of COCOeval for boxes and the mAP of Vision.py:1696-1800.
+# det_eval_pack is pure numpy and needs no device; det_eval_coco / det_map upload its arrays in ONE buffer, launch, and copy ONE
+# buffer back, with no synchronisation in between.
+# ---------------------------------------------------------------------------------------------------------
+DET_EVAL_MAX_T, DET_EVAL_MAX_A, DET_EVAL_MAX_M, DET_EVAL_MAX_R = 16, 8, 8, 128      # NNL_DET_EVAL_MAX_*
+DET_EVAL_LDS_DOUBLES = 2048              # NNL_DET_EVAL_LDS_DOUBLES: a larger group's overlap matrix goes to the scratch buffer
+
+
+def _pred_arrays(pred, i):
+    "one image's [boxes, classes, scores] of predict('val') as (boxes [n, 4] in their own dtype, classes int64 [n], scores [n])"
+    boxes, classes, scores = pred
+    n = len(boxes)
+    if len(classes) != n or len(scores) != n:
+        raise ValueError('predictions[%d]: %d boxes, %d classes, %d scores' % (i, n, len(classes), len(scores)))
+    if n == 0:
+        return np.zeros((0, 4), np.float32), np.zeros(0, np.int64), np.zeros(0, np.float64)
+    B = np.stack([np.asarray(b.detach().cpu() if torch.is_tensor(b) else b) for b in boxes]) if not isinstance(boxes, np.ndarray) else boxes
+    if B.ndim != 2 or B.shape[1] != 4:
+        raise ValueError('predictions[%d]: boxes must be [n, 4] (got %r)' % (i, B.shape))
+    if isinstance(classes, np.ndarray) and isinstance(scores, np.ndarray):
+        return B, classes.astype(np.int64), scores.astype(np.float64)
+    return B, np.array([int(c) for c in classes], dtype=np.int64), np.array([float(s) for s in scores], dtype=np.float64)
+
+
+def _csr(sorted_keys, groups):
+    "offsets int32 [len(groups) + 1] of each group's span in a sorted key vector"
+    return np.concatenate([np.searchsorted(sorted_keys, groups, side='left'), [len(sorted_keys)]]).astype(np.int32)
+
+
+def _check_csr(name, off, n_groups, length):
+    off = np.asarray(off)
+    if off.shape != (n_groups + 1,) or off[0] != 0 or off[-1] != length or (np.diff(off.astype(np.int64)) < 0).any():
+        raise ValueError('det_eval: offsets %s must be non-decreasing, start at 0 and end at %d' % (name, length))
+
+
+def det_eval_pack(predictions, targets=None, coco=None, image_ids=None, cat2dscat=None, max_det=100, n_categories=None):
+    """Flat arrays and offsets of nnl_det_* from `predictions` (the predict('val') format: [boxes, classes, scores] per image, min-max
+    boxes) and the ground truth.  Pure numpy.  Two layouts:
+    coco=<annotation dict>, image_ids=[id of image i], cat2dscat={model category: dataset category id}: the COCOeval layout.  A
+      detection is [float(b0), float(b1), float(b2 - b0), float(b3 - b1)] with the subtraction in the dtype the box arrives in
+      (Vision.py:2166), float(score), cat2dscat[category]; groups are sorted by (sorted category id, ascending image id), a group's
+      detections by descending score (stable) and cut to `max_det`, its ground truths in annotation order with the annotation's
+      area, iscrowd and ignore ('ignore' key, else iscrowd, else 0: cocoeval.py:114-116).  Images are np.unique(image_ids), categories
+      the sorted ids of coco['categories']; annotations of other images and detections of other categories do not take part.
+    targets=<val_ds.y: [(box, category), ...] per image>, n_categories=C: the mAP layout (Vision.py:1749-1769): float32 min-max
+      boxes, groups sorted by (category, image), predictions and targets of a group in their own order.
+    Raises ValueError for a prediction category outside the map / [0, C), an annotation id of 0 (coco) and a ground-truth box of
+    non-positive area (targets)."""
+    if (coco is None) == (targets is None):
+        raise ValueError('det_eval_pack: give either coco= (with image_ids and cat2dscat) or targets= (with n_categories)')
+    N = len(predictions)
+    per = [_pred_arrays(p, i) for i, p in enumerate(predictions)]
+    counts = np.array([len(b) for b, _, _ in per], dtype=np.int64)
+    img_of = np.repeat(np.arange(N, dtype=np.int64), counts)
+    cls = np.concatenate([c for _, c, _ in per]) if N else np.zeros(0, np.int64)
+    score = np.concatenate([s for _, _, s in per]) if N else np.zeros(0, np.float64)
+    if coco is not None:
+        if image_ids is None or cat2dscat is None or len(image_ids) != N:
+            raise ValueError('det_eval_pack: the coco layout needs image_ids (one per prediction list) and cat2dscat')
+        cat_ids = np.unique(np.array([c['id'] for c in coco['categories']], dtype=np.int64))
+        img_ids = np.unique(np.asarray(image_ids, dtype=np.int64))
+        K, I = len(cat_ids), len(img_ids)
+        unknown = sorted(set(cls.tolist()) - set(cat2dscat))
+        if unknown:
+            raise ValueError('det_eval_pack: prediction categories %r are absent from the category map' % (unknown,))
+        lut = {c: int(cat2dscat[c]) for c in set(cls.tolist())}
+        dscat = np.array([lut[c] for c in cls.tolist()], dtype=np.int64)
+        xywh = [np.stack([b[:, 0], b[:, 1], b[:, 2] - b[:, 0], b[:, 3] - b[:, 1]], axis=1).astype(np.float64) for b, _, _ in per]
+        box = np.concatenate(xywh) if N else np.zeros((0, 4))
+        k_of = np.searchsorted(cat_ids, dscat)
+        known = cat_ids[np.minimum(k_of, K - 1)] == dscat if K else np.zeros(len(dscat), bool)
+        i_of = np.searchsorted(img_ids, np.asarray(image_ids, dtype=np.int64))[img_of]
+        key = (k_of * I + i_of)[known]
+        box, score = box[known], score[known]
+        srt = np.lexsort((-score, key))                                     # stable: by group, then descending score
+        key, box, score = key[srt], box[srt], score[srt]
+        anns = coco['annotations']
+        if any(a['id'] == 0 for a in anns):
+            raise ValueError("det_eval_pack: an annotation has id 0, which COCOeval cannot tell from 'unmatched' (cocoeval.py:303, 307)")
+        a_img = np.array([a['image_id'] for a in anns], dtype=np.int64)
+        a_cat = np.array([a['category_id'] for a in anns], dtype=np.int64)
+        gi, gk = np.searchsorted(img_ids, a_img), np.searchsorted(cat_ids, a_cat)
+        use = np.zeros(len(anns), bool)
+        if len(anns) and K and I:
+            use = (img_ids[np.minimum(gi, I - 1)] == a_img) & (cat_ids[np.minimum(gk, K - 1)] == a_cat)
+        sel = np.nonzero(use)[0]
+        gkey = (gk * I + gi)[sel]
+        gs = np.argsort(gkey, kind='stable')
+        sel, gkey = sel[gs], gkey[gs]
+        gt_box = np.array([[float(v) for v in anns[j]['bbox']] for j in sel], dtype=np.float64).reshape(-1, 4)
+        gt_area = np.array([float(anns[j]['area']) for j in sel], dtype=np.float64)
+        crowd = np.array([1 if anns[j].get('iscrowd', 0) else 0 for j in sel], dtype=np.uint8)
+        ignore = np.array([1 if (anns[j]['ignore'] if 'ignore' in anns[j] else anns[j].get('iscrowd', 0)) else 0 for j in sel], dtype=np.uint8)
+        groups = np.unique(np.concatenate([key, gkey]))
+        dt_off = _csr(key, groups)
+        rank = np.arange(len(key), dtype=np.int64) - np.repeat(dt_off[:-1].astype(np.int64), np.diff(dt_off))
+        keep = rank < int(max_det)                                          # dt[0:maxDets[-1]] (cocoeval.py:183-184)
+        key, box, score, rank = key[keep], box[keep], score[keep], rank[keep]
+        dt_off = _csr(key, groups)
+        grp_cat = groups // max(I, 1)
+        cat_grp_off = np.searchsorted(grp_cat, np.arange(K + 1), side='left').astype(np.int32)
+        return {'kind': 'coco', 'K': K, 'I': I, 'max_det': int(max_det), 'cat_ids': cat_ids, 'img_ids': img_ids,
+                'grp_cat': grp_cat.astype(np.int32), 'grp_img': (groups % max(I, 1)).astype(np.int32),
+                'dt_off': dt_off, 'gt_off': _csr(gkey, groups), 'cat_grp_off': cat_grp_off, 'cat_dt_off': dt_off[cat_grp_off],
+                'dt_box': np.ascontiguousarray(box), 'dt_score': score, 'dt_rank': rank.astype(np.int32),
+                'order': np.lexsort((-score, key // max(I, 1))).astype(np.int32),      # per category: stable descending score
+                'gt_box': gt_box, 'gt_area': gt_area, 'gt_flags': (crowd | (ignore << 1)).astype(np.uint8), 'gt_ann': sel.astype(np.int64)}
+    C = int(n_categories) if n_categories is not None else 0
+    if C < 1 or len(targets) != N:
+        raise ValueError('det_eval_pack: the mAP layout needs n_categories >= 1 and one target list per prediction list')
+    if len(cls) and (cls.min() < 0 or cls.max() >= C):
+        raise ValueError('det_eval_pack: prediction categories must lie in [0, %d) (got %d .. %d)' % (C, cls.min(), cls.max()))
+    box = np.concatenate([b.astype(np.float32) for b, _, _ in per]) if N else np.zeros((0, 4), np.float32)
+    key = cls * N + img_of
+    srt = np.argsort(key, kind='stable')
+    key, box, score = key[srt], box[srt], score[srt]
+    t_box = np.array([np.asarray(b, dtype=np.float32) for y in targets for b, _ in y], dtype=np.float32).reshape(-1, 4)
+    t_cls = np.array([int(c) for y in targets for _, c in y], dtype=np.int64)
+    t_img = np.repeat(np.arange(N, dtype=np.int64), [len(y) for y in targets])
+    if len(t_cls) and (t_cls.min() < 0 or t_cls.max() >= C):
+        raise ValueError('det_eval_pack: target categories must lie in [0, %d)' % C)
+    bad = ~((t_box[:, 2] - t_box[:, 0] > 0) & (t_box[:, 3] - t_box[:, 1] > 0))
+    if bad.any():
+        raise ValueError('det_eval_pack: ground-truth box %r of image %d has no positive area: its overlap with a degenerate prediction '
+                         'is 0 / 0' % (t_box[bad][0].tolist(), int(t_img[bad][0])))
+    gkey = t_cls * N + t_img
+    gs = np.argsort(gkey, kind='stable')
+    gkey, t_box = gkey[gs], t_box[gs]
+    groups = np.unique(np.concatenate([key, gkey]))
+    pr_off = _csr(key, groups)
+    cat_grp_off = np.searchsorted(groups // max(N, 1), np.arange(C + 1), side='left').astype(np.int32)
+    return {'kind': 'map', 'C': C, 'N': N, 'grp_cat': (groups // max(N, 1)).astype(np.int32), 'grp_img': (groups % max(N, 1)).astype(np.int32),
+            'pr_off': pr_off, 'gt_off': _csr(gkey, groups), 'cat_grp_off': cat_grp_off, 'cat_pr_off': pr_off[cat_grp_off],
+            'pr_box': np.ascontiguousarray(box), 'pr_score': score, 'order': np.lexsort((-score, key // max(N, 1))).astype(np.int32),
+            'gt_box': np.ascontiguousarray(t_box), 'ntrue': np.bincount(t_cls, minlength=C).astype(np.int64)}
+
+
+_NP2T = {np.dtype(np.float64): torch.float64, np.dtype(np.float32): torch.float32, np.dtype(np.int32): torch.int32,
+         np.dtype(np.int64): torch.int64, np.dtype(np.uint8): torch.uint8}
+
+
+def _det_upload(arrays, device):
+    "the named host arrays as views of ONE device buffer (one host-to-device copy)"
+    device = torch.device(device)
+    if device.type != 'cuda':
+        raise _lib.NnlError('nnl HIP op called for a non-CUDA device: the MI355X path has no CPU fallback')
+    spans, total = {}, 0
+    for name, a in arrays.items():
+        spans[name] = total
+        total += (a.nbytes + 15) // 16 * 16
+    host = np.zeros(max(total, 16), dtype=np.uint8)
+    for name, a in arrays.items():
+        host[spans[name]:spans[name] + a.nbytes] = np.ascontiguousarray(a).reshape(-1).view(np.uint8)
+    buf = torch.from_numpy(host).to(device)
+    out = {name: buf[spans[name]:spans[name] + a.nbytes].view(_NP2T[a.dtype]).view(a.shape) for name, a in arrays.items()}
+    out['_buffer'] = buf
+    return out
+
+
+def _det_params(iouThrs, areaRng=None):
+    thr = np.ascontiguousarray(np.asarray(iouThrs, dtype=np.float64).reshape(-1))
+    if not 1 <= len(thr) <= DET_EVAL_MAX_T or not np.isfinite(thr).all():
+        raise ValueError('det_eval: between 1 and %d finite thresholds (got %r)' % (DET_EVAL_MAX_T, thr.tolist()))
+    if areaRng is None:
+        return thr
+    rng = np.ascontiguousarray(np.asarray(areaRng, dtype=np.float64))
+    if rng.ndim != 2 or rng.shape[1] != 2 or not 1 <= len(rng) <= DET_EVAL_MAX_A or not np.isfinite(rng).all():
+        raise ValueError('det_eval: areaRng must be [A, 2] finite numbers, 1 <= A <= %d' % DET_EVAL_MAX_A)
+    return thr, rng
+
+
+def _coco_checked(packed):
+    if not isinstance(packed, dict) or packed.get('kind') != 'coco':
+        raise ValueError("det_eval_coco: `packed` must come from det_eval_pack(..., coco=...)")
+    p = packed
+    NG, Nd, Ng, K = len(p['grp_cat']), len(p['dt_score']), len(p['gt_area']), int(p['K'])
+    if NG < 1 or K < 1:
+        raise ValueError('det_eval_coco: nothing to evaluate (no detection and no ground truth in the evaluated images and categories)')
+    _check_csr('dt_off', p['dt_off'], NG, Nd)
+    _check_csr('gt_off', p['gt_off'], NG, Ng)
+    _check_csr('cat_grp_off', p['cat_grp_off'], K, NG)
+    _check_csr('cat_dt_off', p['cat_dt_off'], K, Nd)
+    if not np.array_equal(p['cat_dt_off'], np.asarray(p['dt_off'])[p['cat_grp_off']]):
+        raise ValueError('det_eval_coco: cat_dt_off does not match dt_off at cat_grp_off')
+    order = np.asarray(p['order'])
+    if order.shape != (Nd,) or p['dt_rank'].shape != (Nd,) or p['dt_box'].shape != (Nd, 4) or p['gt_box'].shape != (Ng, 4) \
+            or p['gt_flags'].shape != (Ng,):
+        raise ValueError('det_eval_coco: array lengths do not match the offsets')
+    if Nd:
+        seg = np.repeat(np.arange(K), np.diff(p['cat_dt_off']))
+        lo, hi = np.asarray(p['cat_dt_off'])[seg], np.asarray(p['cat_dt_off'])[seg + 1]
+        if (order < lo).any() or (order >= hi).any():
+            raise ValueError('det_eval_coco: order leaves its category')
+    return NG, Nd, Ng, K
+
+
+def _coco_scratch(packed, A, T):
+    "scr_off int64 [NG] (-1: the group's buffer fits LDS) and the scratch size in doubles"
+    D, G = np.diff(packed['dt_off']).astype(np.int64), np.diff(packed['gt_off']).astype(np.int64)
+    need = D * G + ((A * T + A) * G + 7) // 8
+    big = (need > DET_EVAL_LDS_DOUBLES) & (D > 0) & (G > 0)
+    off = np.full(len(D), -1, dtype=np.int64)
+    off[big] = np.cumsum(need[big]) - need[big]
+    return off, int(need[big].sum())
+
+
+def _coco_launch(packed, iouThrs, areaRng, device, recThrs=None, maxDets=None):
+    "upload, nnl_det_coco_match and, with recThrs, nnl_det_coco_accumulate; everything stays on the device"
+    NG, Nd, Ng, K = _coco_checked(packed)
+    thr, rng = _det_params(iouThrs, areaRng)
+    T, A = len(thr), len(rng)
+    if recThrs is not None:
+        rec = np.ascontiguousarray(np.asarray(recThrs, dtype=np.float64).reshape(-1))
+        md = np.ascontiguousarray(np.asarray(maxDets, dtype=np.int64).reshape(-1).astype(np.int32))
+        if not 1 <= len(rec) <= DET_EVAL_MAX_R or not np.isfinite(rec).all() or (np.diff(rec) < 0).any():
+            raise ValueError('det_eval_coco: recThrs must be 1 to %d ascending finite numbers' % DET_EVAL_MAX_R)
+        if not 1 <= len(md) <= DET_EVAL_MAX_M or md.min() < 1 or (np.diff(md) < 0).any() or md[-1] != packed['max_det']:
+            raise ValueError('det_eval_coco: maxDets must be 1 to %d ascending positive numbers ending at the %d the detections were cut to'
+                             % (DET_EVAL_MAX_M, packed['max_det']))
+    scr_off, scr_doubles = _coco_scratch(packed, A, T)
+    names = ['dt_off', 'gt_off', 'cat_grp_off', 'cat_dt_off', 'order', 'dt_rank', 'dt_score', 'dt_box', 'gt_box', 'gt_area', 'gt_flags']
+    dev = _det_upload(dict({n: np.ascontiguousarray(packed[n]) for n in names}, scr_off=scr_off), device)
+    device = dev['_buffer'].device
+    scratch = torch.empty(max(scr_doubles, 1), dtype=torch.float64, device=device)
+    dtm = torch.empty(A, T, Nd, dtype=torch.int32, device=device)
+    dtig = torch.empty(A, T, Nd, dtype=torch.uint8, device=device)
+    npig = torch.empty(A, NG, dtype=torch.int32, device=device)
+    res = {'dtm': dtm, 'dtig': dtig, 'npig': npig, '_keep': (dev, scratch)}
+    if recThrs is None:
+        status = torch.empty(2, dtype=torch.int32, device=device)
+    else:
+        R, M = len(rec), len(md)
+        n_pr, n_rc = T * R * K * A * M, T * K * A * M
+        out = torch.empty(2 * n_pr + n_rc + 1, dtype=torch.float64, device=device)         # one buffer: one copy back
+        status = out[-1:].view(torch.int32)
+        res.update(out=out, shape_pr=(T, R, K, A, M), shape_rc=(T, K, A, M))
+    res['status'] = status
+    check(lib.nnl_det_coco_match(ptr(dev['dt_off']), ptr(dev['gt_off']), ptr(dev['dt_box']), ptr(dev['gt_box']), ptr(dev['gt_area']),
+                                 ptr(dev['gt_flags']), ptr(dev['scr_off']), NG, Nd, Ng, _hp(thr), T, _hp(rng), A, ptr(scratch),
+                                 scr_doubles * 8, ptr(dtm), ptr(dtig), ptr(npig), ptr(status), stream()))
+    if recThrs is not None:
+        o = res['out']
+        check(lib.nnl_det_coco_accumulate(ptr(dev['cat_grp_off']), ptr(dev['cat_dt_off']), ptr(dev['order']), ptr(dev['dt_rank']),
+                                          ptr(dev['dt_score']), ptr(dtm), ptr(dtig), ptr(npig), K, NG, Nd, T, A, _hp(md), M, _hp(rec), R,
+                                          ptr(o[:n_pr]), ptr(o[n_pr:2 * n_pr]), ptr(o[2 * n_pr:2 * n_pr + n_rc]), stream()))
+    return res
+
+
+def _coco_status(flag):
+    if int(flag) != 0:
+        raise _lib.NnlError('nnl_det_coco_match skipped a group whose overlap matrix did not fit the buffer it was given (status %d)' % int(flag))
+
+
+def det_eval_coco_match(packed, iouThrs, areaRng, device='cuda'):
+    """evaluateImg of every group (cocoeval.py:243-321) for all area ranges and thresholds: host arrays (dtm int32 [A, T, Nd], the
+    matched ground truth's position in its group + 1 or 0; dtig uint8 [A, T, Nd]; npig int32 [A, NG], the group's ground truths not
+    ignored in the range).  Nd and NG count det_eval_pack's detections and groups."""
+    res = _coco_launch(packed, iouThrs, areaRng, device)
+    status = res['status'].cpu()
+    _coco_status(status[0])
+    return res['dtm'].cpu().numpy(), res['dtig'].cpu().numpy(), res['npig'].cpu().numpy()
+
+
+def det_eval_coco(packed, iouThrs, recThrs, maxDets, areaRng, device='cuda'):
+    """COCOeval.evaluate + accumulate for boxes with useCats=1 (cocoeval.py:129-428) on det_eval_pack(..., coco=...)'s arrays: returns
+    host arrays (precision [T, R, K, A, M], recall [T, K, A, M], scores [T, R, K, A, M]) as COCOeval.eval holds them.  One upload, two
+    launches, one copy back.  maxDets must ascend and end at the max_det the detections were cut to; recThrs must ascend."""
+    res = _coco_launch(packed, iouThrs, areaRng, device, recThrs, maxDets)
+    host = res['out'].cpu().numpy()
+    _coco_status(host[-1:].view(np.int32)[0])
+    n_pr, n_rc = int(np.prod(res['shape_pr'])), int(np.prod(res['shape_rc']))
+    return (host[:n_pr].reshape(res['shape_pr']), host[2 * n_pr:2 * n_pr + n_rc].reshape(res['shape_rc']),
+            host[n_pr:2 * n_pr].reshape(res['shape_pr']))
+
+
+def _map_launch(packed, thresholds, device, integrate):
+    if not isinstance(packed, dict) or packed.get('kind') != 'map':
+        raise ValueError("det_map: `packed` must come from det_eval_pack(..., targets=...)")
+    p = packed
+    NG, Np, Ng, C = len(p['grp_cat']), len(p['pr_score']), len(p['gt_box']), int(p['C'])
+    _det_params(thresholds)
+    # `jaccard > thresh` of Vision.py:1727 compares a float32 with the threshold under numpy's promotion rules (a Python float is
+    # taken to float32 by numpy >= 2): the kernel compares in fp64 against the threshold as that comparison sees it
+    thr = np.array([float((np.float32(0) + t).dtype.type(t)) for t in (thresholds if np.ndim(thresholds) else [thresholds])], dtype=np.float64)
+    T = len(thr)
+    if NG < 1:
+        if torch.device(device).type != 'cuda':
+            raise _lib.NnlError('nnl HIP op called for a non-CUDA device: the MI355X path has no CPU fallback')
+        return {'empty': True, 'T': T, 'C': C, 'ntrue': p['ntrue']}
+    _check_csr('pr_off', p['pr_off'], NG, Np)
+    _check_csr('gt_off', p['gt_off'], NG, Ng)
+    _check_csr('cat_grp_off', p['cat_grp_off'], C, NG)
+    _check_csr('cat_pr_off', p['cat_pr_off'], C, Np)
+    order = np.asarray(p['order'])
+    if order.shape != (Np,) or p['pr_box'].shape != (Np, 4) or p['gt_box'].shape != (Ng, 4) or p['ntrue'].shape != (C,):
+        raise ValueError('det_map: array lengths do not match the offsets')
+    if Np:
+        seg = np.repeat(np.arange(C), np.diff(p['cat_pr_off']))
+        if (order < np.asarray(p['cat_pr_off'])[seg]).any() or (order >= np.asarray(p['cat_pr_off'])[seg + 1]).any():
+            raise ValueError('det_map: order leaves its category')
+    names = ['pr_off', 'gt_off', 'cat_pr_off', 'order', 'pr_score', 'pr_box', 'gt_box', 'ntrue']
+    dev = _det_upload({n: np.ascontiguousarray(p[n]) for n in names}, device)
+    device = dev['_buffer'].device
+    correct = torch.empty(T, Np, dtype=torch.uint8, device=device)
+    check(lib.nnl_det_map_match(ptr(dev['pr_off']), ptr(dev['gt_off']), ptr(dev['pr_box']), ptr(dev['gt_box']), NG, Np, Ng, _hp(thr), T,
+                                ptr(correct), stream()))
+    res = {'correct': correct, '_keep': dev}
+    if integrate:
+        nbytes = int(lib.nnl_det_map_integrate_workspace_bytes(Np, T))
+        ws = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=device)
+        out = torch.empty(T, C, dtype=torch.float64, device=device)
+        check(lib.nnl_det_map_integrate(ptr(dev['cat_pr_off']), ptr(dev['order']), ptr(dev['pr_score']), ptr(correct), ptr(dev['ntrue']), C,
+                                        Np, T, ptr(ws), nbytes, ptr(out), stream()))
+        res.update(out=out, _ws=ws)
+    return res
+
+
+def det_map_match(packed, thresholds, device='cuda'):
+    "the is_correct flags of mAP1 (Vision.py:1696-1728) for every threshold: host uint8 [T, Np] over det_eval_pack's prediction order"
+    res = _map_launch(packed, thresholds, device, False)
+    if res.get('empty'):
+        return np.zeros((res['T'], 0), dtype=np.uint8)
+    return res['correct'].cpu().numpy()
+
+
+def det_map(packed, thresholds, device='cuda'):
+    """mAP1 of every (threshold, category) (Vision.py:1696-1747) on det_eval_pack(..., targets=...)'s arrays: host float64 [T, C], 0.0
+    for a category without predictions and nan for one without ground truth, as the host code gives.  One upload, two launches, one
+    copy back; the same inputs give the same bits."""
+    res = _map_launch(packed, thresholds, device, True)
+    if res.get('empty'):                                  # no prediction and no ground truth at all: 0.0 / 0
+        return np.full((res['T'], res['C']), np.nan)
+    return res['out'].cpu().numpy()
+
+
+__all__ += ['det_eval_pack', 'det_eval_coco', 'det_eval_coco_match', 'det_map', 'det_map_match', 'DET_EVAL_LDS_DOUBLES', 'DET_EVAL_MAX_T',
+            'DET_EVAL_MAX_A', 'DET_EVAL_MAX_M', 'DET_EVAL_MAX_R']
+
 from .ops_text import (lstm_layer, embedding_rowmask, softmax_cross_entropy, cross_entropy_nd, seq_activation_reg)  # noqa: E402,F401
 __all__ += ['lstm_layer', 'embedding_rowmask', 'softmax_cross_entropy', 'cross_entropy_nd', 'seq_activation_reg', 'conv_add_upsampled']

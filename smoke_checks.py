@@ -144,7 +144,30 @@ def check_tabular_assoc(device):
             raise AssertionError(f'smoke: {Type} mismatch, got {got!r}, want {want!r}')
 
 
-CHECKS = [check_collab, check_resnet_block, check_tabular, check_retina_loss, check_lstm_lm, check_tabular_assoc]
+def check_det_eval(device):
+    """two images, two detections and two ground truths of one category through the COCO protocol and the mAP (K14): the perfect
+    detection scores above the one that overlaps 7 / 8, so AP is 1 up to t = 0.85 and 1 / 2 above."""
+    from neuralnetworklibrary_amd import ops
+    f = lambda *v: np.array(v, dtype=np.float32)      # noqa: E731
+    coco = {'images': [{'id': 2}, {'id': 1}], 'categories': [{'id': 6}],
+            'annotations': [{'id': 1, 'image_id': 2, 'category_id': 6, 'bbox': [10., 10., 50., 40.], 'area': 2000., 'iscrowd': 0},
+                            {'id': 2, 'image_id': 1, 'category_id': 6, 'bbox': [0., 0., 20., 20.], 'area': 400., 'iscrowd': 0}]}
+    preds = [[[f(10, 10, 60, 45)], [0], [np.float32(0.5)]], [[f(0, 0, 20, 20)], [0], [np.float32(0.75)]]]
+    packed = ops.det_eval_pack(preds, coco=coco, image_ids=[2, 1], cat2dscat={0: 6})
+    thr = np.linspace(.5, .95, 10)
+    rec = np.linspace(0, 1, 101)
+    precision, recall, _ = ops.det_eval_coco(packed, thr, rec, [1, 10, 100], [[0, 1e10]], device=device)
+    half = np.where(rec <= 0.5, 1 / (1 + np.spacing(1)), 0.0).mean()      # one hit, then one miss: precision 1 / (1 + eps) up to recall 1 / 2
+    want = np.where(thr <= 0.875, 1.0, half)
+    if not np.array_equal(precision[:, :, 0, 0, 2].mean(axis=1), want) or not np.array_equal(recall[:, 0, 0, 2], np.where(thr <= 0.875, 1.0, 0.5)):
+        raise AssertionError(f'smoke: det_eval_coco mismatch, got {precision[:, :, 0, 0, 2].mean(axis=1)!r}, want {want!r}')
+    targets = [[(np.array([10., 10., 60., 50.]), 0)], [(np.array([0., 0., 20., 20.]), 0)]]
+    vals = ops.det_map(ops.det_eval_pack(preds, targets=targets, n_categories=1), [0.5, 0.9], device=device)
+    if vals.tolist() != [[1.0], [0.5]]:
+        raise AssertionError(f'smoke: det_map mismatch, got {vals!r}')
+
+
+CHECKS = [check_collab, check_resnet_block, check_tabular, check_retina_loss, check_lstm_lm, check_tabular_assoc, check_det_eval]
 
 
 def run_all(device='cuda:0'):
