@@ -4,6 +4,7 @@
 // Layout: activations NHWC, filters KRSC (see include/nnl.h).  MFMA-bound: 2*N*P*Q*K*R*S*C flops per pass.
 #include "igemm_kernels.h"
 #include "igemm_taps.h"
+#include "split_plan.h"
 #include "wino.h"
 #include "igemm_wgrad.h"
 #include "igemm_wgrad2d.h"
@@ -105,72 +106,27 @@ int launch_taps_ktail(IgemmTapsParams p, hipStream_t s) {
   return NNL_OK;
 }
 
-// ---- balanced schedule for the 64x64 taps kernel (see IgemmTapsParams::bal) --------------------------------------------
-// The plan is a pure function of the GEMM shape, so the *_workspace_bytes() query and the launch agree.
-struct BalPlan {
-  int on, bk, main_ks, n_main_tiles, tail_slices, tail_row0;
-  size_t main_floats, tail_floats;        // workspace: [main slabs][tail slabs]
-  double t_us;                            // predicted time of the chosen plan
-};
-
-constexpr int kCUs = 256;
+// ---- balanced schedule for the 64x64 taps kernel (see IgemmTapsParams::bal; the plan and its search: split_plan.h) -----
 constexpr long kTileCounters = 65536;   // ints in the caller's persistent tile-counter buffer (nnl_conv2d_tile_counters())
 
 // (a 128x64 tile under this schedule was measured 10-12 % slower on the 56x56 and 14x14 stages and removed: profiles/README.md)
-BalPlan plan_balance(long M, int Nc, int C, int ntaps) {
-  BalPlan best{};
+SplitPlan plan_balance(long M, int Nc, int C, int ntaps) {
   const int e_bal = NNL_ENV_INT("NNL_IGEMM_BALANCE", 1);
-  if (e_bal == 0 || Nc % 4 != 0) return best;
-  const long gm = nnl_cdiv(M, 64), gn = nnl_cdiv(Nc, 64), T = gm * gn;
-  const int bk = ((T < 1200 || C >= 256 || C == 64) && C % 32 == 0) ? 32 : 16;
-  const long I = (long)ntaps * (C / bk);                               // k iterations of a whole tile
-  const double c_it = bk == 32 ? 0.60 : 0.30;                          // us per k iteration per CU-resident workgroup set (measured ~113 TF/s ceiling)
-  const double occ = bk == 32 ? 4 : 6;                                 // resident workgroups per CU (LDS- / VGPR-limited)
-  auto wave_iters = [&](long blocks, long iters) {                     // busiest CU's iterations for `blocks` equal workgroups
-    if (blocks <= 0) return 0.0;
-    const long cap = (long)occ * kCUs;                                 // full residency waves, then the remainder on top
-    const long full = blocks / cap, rem = blocks - full * cap;         // (measured: 1568 workgroups at occupancy 6 take 7 units)
-    return (double)(full * (long)occ + nnl_cdiv(rem, kCUs)) * iters;
-  };
-  const double plain = wave_iters(T, I) * c_it;
-  best.t_us = plain;
-  double best_t = plain * (e_bal == 2 ? 1.25 : 0.99);         // need a >= 1 % predicted win (2 = force, for A/B runs)
-  const int plan_extra = 2;                                            // k iterations' worth of fix-up cost per sliced workgroup
-  const double plan_bw = 16000 * 1.0e3;                                // slab traffic bandwidth, bytes per us
-  for (int ks = 1; ks <= 4; ks *= 2) {
-    if (I / ks < 8) break;
-    const long units = T * ks;
-    long n_main = ((units / kCUs) * kCUs / ks / gn) * gn;              // main tiles: whole multiples of 256 workgroups, whole tile rows
-    if (n_main > T) n_main = T;
-    const long tail = T - n_main;
-    const long it_main = nnl_cdiv(I, ks);
-    static const int kSlices[] = {1, 2, 3, 4, 6, 8, 9, 12, 16, 18, 24, 32, 36, 48};
-    for (int S : kSlices) {
-      if (tail == 0 && S > 1) break;
-      if (S > 1 && I / S < 4) break;
-      const long it_tail = nnl_cdiv(I, S);
-      const long tail_blocks = tail * S;
-      double t = (wave_iters(n_main * ks, it_main) + wave_iters(tail_blocks, it_tail + (S > 1 ? plan_extra : 0))) * c_it;
-      const long row0 = (n_main / gn) * 64 < M ? (n_main / gn) * 64 : M;
-      const double main_b = ks > 1 ? (2.0 * ks + 1) * row0 * Nc * 4 : 0;
-      const double tail_b = S > 1 ? (2.0 * S + 1) * (M - row0) * Nc * 4 : 0;
-      t += (main_b + tail_b) / plan_bw + (ks > 1 ? 1 : 0) + (S > 1 && tail ? 1 : 0);      // slab traffic (write + re-read) + fix-up latency
-      if (t < best_t) {
-        best_t = t;
-        best.t_us = t;
-        best.on = 1; best.bk = bk; best.main_ks = ks; best.n_main_tiles = (int)n_main; best.tail_slices = tail ? S : 1;
-        best.tail_row0 = (int)row0;
-        best.main_floats = ks > 1 ? (size_t)ks * row0 * Nc : 0;
-        best.tail_floats = (S > 1 && tail) ? (size_t)S * (M - row0) * Nc : 0;
-      }
-    }
-  }
-  if (best.on && best.main_ks == 1 && best.tail_slices == 1) best.on = 0;
-  return best;
+  if (e_bal == 0 || Nc % 4 != 0) return SplitPlan{};
+  const long T = nnl_cdiv(M, 64) * nnl_cdiv(Nc, 64);
+  SplitKernel k{};
+  k.bk = ((T < 1200 || C >= 256 || C == 64) && C % 32 == 0) ? 32 : 16;
+  k.iters = (long)ntaps * (C / k.bk);
+  k.us_per_iter = k.bk == 32 ? 0.60 : 0.30;
+  k.occ = k.bk == 32 ? 4 : 6;
+  k.row_factor = 1;
+  k.balance = true;
+  k.accept = e_bal == 2 ? 1.25 : 0.99;                      // (2 = force, for A/B runs)
+  return split_search(k, M, Nc);
 }
 
 size_t balance_workspace_bytes(long M, int Nc, int C, int ntaps) {
-  const BalPlan pl = plan_balance(M, Nc, C, ntaps);
+  const SplitPlan pl = plan_balance(M, Nc, C, ntaps);
   return pl.on ? (pl.main_floats + pl.tail_floats) * sizeof(float) : 0;
 }
 
@@ -189,15 +145,10 @@ __global__ __launch_bounds__(256) void slab_reduce_kernel(const float* __restric
   reinterpret_cast<f32x4*>(out)[i] = acc;
 }
 
-int launch_balanced(IgemmTapsParams p, const BalPlan& pl, float* ws, int* counters, hipStream_t s) {
+int launch_balanced(IgemmTapsParams p, const SplitPlan& pl, float* ws, int* counters, hipStream_t s) {
   p.grid_m = (int)nnl_cdiv(p.M, 64);
   p.grid_n = (int)nnl_cdiv(p.Nc, 64);
-  const int T = p.grid_m * p.grid_n;
-  p.bal = 1; p.main_ks = pl.main_ks; p.n_main_tiles = pl.n_main_tiles; p.tail_slices = pl.tail_slices; p.tail_row0 = pl.tail_row0;
-  p.main_out = ws; p.main_slab_stride = (long)pl.tail_row0 * p.Nc;
-  p.tail_out = ws + pl.main_floats; p.tail_slab_stride = (long)(p.M - pl.tail_row0) * p.Nc;
-  p.tile_counters = counters;                                // in-kernel fix-up of the split tiles
-  const unsigned grid = (unsigned)(pl.n_main_tiles * pl.main_ks + (T - pl.n_main_tiles) * pl.tail_slices);
+  const unsigned grid = split_bind(p, pl, ws, p.M, 1, counters);
   NNL_ROUTE("balanced<%d>%s%s%s%s:%s@main_ks=%d,tail_slices=%d", pl.bk == 32 ? 32 : 16, p.ktail ? ":ktail" : "",
             (!p.ktail && taps_dma(pl.bk == 32 ? 32 : 16)) ? ":dma" : "", pl.main_ks > 1 ? ":main_ks" : "", pl.tail_slices > 1 ? ":tail_slices" : "",
             p.tile_counters != nullptr ? "counters" : "reduce", pl.main_ks, pl.tail_slices);
@@ -256,9 +207,9 @@ int dispatch_taps(const IgemmTapsParams& p_in, hipStream_t s, void* ws = nullptr
   if (ws != nullptr && dense) {
     // KTAIL: the planner sees C rounded up to the 32-wide k block (few, long tiles — 1024 x 500 x 1000: 128 workgroups of 32 k steps —
     // are what the balanced schedule's k slices fill the chip with)
-    const BalPlan pl = plan_balance(p.M, p.Nc, p.ktail ? (int)nnl_cdiv(p.C, 32) * 32 : p.C, p.ntaps);
-    if (pl.on && ws_bytes >= (pl.main_floats + pl.tail_floats) * sizeof(float)) {
-      int* const cnt = rows64 * nnl_cdiv(p.Nc, 64) <= kTileCounters ? counters : nullptr;
+    const SplitPlan pl = plan_balance(p.M, p.Nc, p.ktail ? (int)nnl_cdiv(p.C, 32) * 32 : p.C, p.ntaps);
+    int* cnt = counters;
+    if (pl.on && split_plan_fits(pl, rows64 * nnl_cdiv(p.Nc, 64), &cnt, kTileCounters, ws_bytes, 0, true)) {
       if (bn_part && cnt != nullptr) {              // split tiles are finished in-kernel: stats too
         p.bn_part = bn_part;
         if (bn_rows) *bn_rows = rows64;
@@ -933,11 +884,11 @@ static int wino_mode(int N, int H, int W, int Cin, int Nc, int R, int S, int str
   return 1;
 }
 static size_t wino_mode_workspace(int mode, int N, int H, int W, int Cin, int Nc) {
-  return mode == 2 ? nnl_wino2_workspace_bytes(N, H, W, Cin, Nc) : nnl_wino_workspace_bytes(N, H, W, Cin, Nc);
+  return kWinoFamily[mode - 1].workspace_bytes(N, H, W, Cin, Nc);
 }
 static int wino_mode_launch(int mode, const WinoProblem& q, void* ws, size_t ws_bytes, int* counters, long n_counters, hipStream_t s) {
   nnl_prof_exec_frac(mode >= 2 ? 1.0 / 2.25 : 1.0 / 1.5);                  // multiplies issued per algorithmic multiply (bench.py: roofline.executed_frac)
-  return mode == 2 ? nnl_wino2_launch(q, ws, ws_bytes, counters, n_counters, s) : nnl_wino_launch(q, ws, ws_bytes, counters, n_counters, s);
+  return kWinoFamily[mode - 1].launch(q, ws, ws_bytes, counters, n_counters, s);
 }
 
 // debug / tuning: the planners' predicted launch times (us) for a 3x3 / stride 1 / pad 1 problem: out[0] direct, out[1] Winograd 1-D, out[2] 2-D,
@@ -1019,7 +970,7 @@ extern "C" int nnl_conv2d_fwd_pre(const float* x, const float* w, const float* b
     wq.bn_part = stats ? bn_partials : nullptr; wq.bn_pivot = bn_pivot;
     wq.u_pre = u;
     st = wino_mode_launch(wmode, wq, workspace, workspace_bytes, tile_counters, kTileCounters, s);
-    if (st == NNL_OK && stats) *bn_rows = wmode >= 2 ? nnl_wino2_bn_rows(g->N, g->H, g->W) : nnl_wino_bn_rows(g->N, g->H, g->W);
+    if (st == NNL_OK && stats) *bn_rows = kWinoFamily[wmode - 1].bn_rows(g->N, g->H, g->W);
     return st;
   }
   if (const int tk = taps_kind(a_elems, b_elems, g->C, g->R * g->S)) {

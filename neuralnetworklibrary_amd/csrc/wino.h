@@ -26,3 +26,16 @@ bool nnl_wino2_plan_is_pos(int N, int H, int W, int Cin, int Nc);      // the pl
 size_t nnl_wino2_workspace_bytes(int N, int H, int W, int Cin, int Nc);
 int nnl_wino2_bn_rows(int N, int H, int W);
 int nnl_wino2_launch(const WinoProblem& q, void* ws, size_t ws_bytes, int* tile_counters, long n_counters, hipStream_t s);
+
+// the two families as data: kWinoFamily[mode - 1], mode as conv2d.hip's wino_mode() returns it (1: 1-D, 2: 2-D)
+struct WinoFamily {
+  const char* name;
+  bool (*ok)(int N, int H, int W, int Cin, int Nc, int R, int S, int stride, int pad);
+  double (*plan_time_us)(int N, int H, int W, int Cin, int Nc);
+  size_t (*workspace_bytes)(int N, int H, int W, int Cin, int Nc);
+  int (*bn_rows)(int N, int H, int W);
+  int (*launch)(const WinoProblem& q, void* ws, size_t ws_bytes, int* tile_counters, long n_counters, hipStream_t s);
+};
+inline constexpr WinoFamily kWinoFamily[2] = {
+    {"wino", nnl_wino_ok, nnl_wino_plan_time_us, nnl_wino_workspace_bytes, nnl_wino_bn_rows, nnl_wino_launch},
+    {"wino2", nnl_wino2_ok, nnl_wino2_plan_time_us, nnl_wino2_workspace_bytes, nnl_wino2_bn_rows, nnl_wino2_launch}};

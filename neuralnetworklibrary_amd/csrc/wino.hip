@@ -18,10 +18,9 @@
 #include "wino.h"
 #include "wino_filter.h"
 #include "igemm_taps.h"
+#include "split_plan.h"
 
 namespace {
-
-constexpr int kCUs = 256;
 
 struct WinoParams {
   const float* a;      // in [N][H][W][C]
@@ -401,72 +400,22 @@ __global__ __launch_bounds__(256, 4) void wino_kernel(const WinoParams p) {
   }
 }
 
-// ---- schedule: the balanced plan of conv2d.hip (plan_balance) for I = 12 * C / BK iterations per tile ----
-struct WPlan {
-  int bk, on, main_ks, n_main_tiles, tail_slices, tail_row0;
-  size_t main_floats, tail_floats;
-  double t_us;                           // predicted launch time (same cost model as conv2d.hip's plan_balance)
-};
-
-WPlan wino_plan(long M2, int Nc, int C) {
-  WPlan best{};
-  const long gm = nnl_cdiv(M2, 64), gn = nnl_cdiv(Nc, 64), T = gm * gn;
+// ---- schedule: the shared balanced plan (split_plan.h) for I = 12 * C / BK iterations per tile, two output rows per pair row ----
+SplitPlan wino_plan(long M2, int Nc, int C) {
+  const long T = nnl_cdiv(M2, 64) * nnl_cdiv(Nc, 64);
+  SplitKernel k{};
   // BK 32 where the per-tap channel loop is short (C = 64: 134.5 -> 137.5 TF/s) or the grid small (7x7 stage: 116 -> 125); BK 16
   // otherwise (28x28 / 14x14 stages: 144 / 151 against 141 / 147) — tools/bench_conv.py
-  best.bk = (C % 32 == 0 && (C == 64 || T < 300)) ? 32 : 16;
-  if (C % best.bk != 0) best.bk = 16;
-  const int bk = best.bk;
-  const long I = 12L * (C / bk);
-  const double c_it = bk == 32 ? 0.60 : 0.30;
-  const long occ = 4;                                               // 108-127 VGPRs: four workgroups per CU
-  auto wave_iters = [&](long blocks, long iters) {
-    if (blocks <= 0) return 0.0;
-    const long cap = occ * kCUs;
-    const long full = blocks / cap, rem = blocks - full * cap;
-    return (double)(full * occ + nnl_cdiv(rem, (long)kCUs)) * iters;
-  };
-  const double plain = wave_iters(T, I) * c_it;
-  best.t_us = plain;
-  if (NNL_ENV_INT("NNL_WINO_BALANCE", 1) == 0) return best;
-  double best_t = plain * 0.99;
-  const int plan_extra = 2;
-  const double plan_bw = 16000.0e3;
-  const int f_ks = NNL_ENV_INT("NNL_WINO_PLAN_KS", 0), f_S = NNL_ENV_INT("NNL_WINO_PLAN_S", 0);
-  if (f_ks > 0 || f_S > 0) best_t = 1e300;
-  for (int ks = 1; ks <= 4; ks *= 2) {
-    if (f_ks > 0 && ks != f_ks) continue;
-    if (I / ks < 8) break;
-    const long units = T * ks;
-    long n_main = ((units / kCUs) * kCUs / ks / gn) * gn;
-    if (n_main > T) n_main = T;
-    const long tail = T - n_main;
-    const long it_main = nnl_cdiv(I, (long)ks);
-    static const int kSlices[] = {1, 2, 3, 4, 6, 8, 9, 12, 16, 18, 24, 32, 36, 48};
-    for (int S : kSlices) {
-      if (tail == 0 && S > 1) break;
-      if (S > 1 && I / S < 4) break;
-      if (f_S > 0 && tail > 0 && S != f_S) continue;
-      const long it_tail = nnl_cdiv(I, (long)S);
-      double t = (wave_iters(n_main * ks, it_main) + wave_iters(tail * S, it_tail + (S > 1 ? plan_extra : 0))) * c_it;
-      const long row0 = (n_main / gn) * 64 < M2 ? (n_main / gn) * 64 : M2;
-      const double main_b = ks > 1 ? (2.0 * ks + 1) * row0 * 2 * Nc * 4 : 0;
-      const double tail_b = S > 1 ? (2.0 * S + 1) * (M2 - row0) * 2 * Nc * 4 : 0;
-      t += (main_b + tail_b) / plan_bw + (ks > 1 ? 1 : 0) + (S > 1 && tail ? 1 : 0);
-      if (t < best_t) {
-        best_t = t;
-        best.t_us = t;
-        best.on = 1; best.main_ks = ks; best.n_main_tiles = (int)n_main; best.tail_slices = tail ? S : 1;
-        best.tail_row0 = (int)row0;
-        best.main_floats = ks > 1 ? (size_t)ks * row0 * 2 * Nc : 0;
-        best.tail_floats = (S > 1 && tail) ? (size_t)S * (M2 - row0) * 2 * Nc : 0;
-      }
-    }
-  }
-  if (best.on && best.main_ks == 1 && best.tail_slices == 1) best.on = 0;
-  return best;
+  k.bk = (C % 32 == 0 && (C == 64 || T < 300)) ? 32 : 16;
+  k.iters = 12L * (C / k.bk);
+  k.us_per_iter = k.bk == 32 ? 0.60 : 0.30;
+  k.occ = 4;                                                        // 108-127 VGPRs: four workgroups per CU
+  k.row_factor = 2;
+  k.balance = NNL_ENV_INT("NNL_WINO_BALANCE", 1) != 0;
+  k.accept = 0.99;
+  k.force_ks = NNL_ENV_INT("NNL_WINO_PLAN_KS", 0); k.force_S = NNL_ENV_INT("NNL_WINO_PLAN_S", 0);
+  return split_search(k, M2, Nc);
 }
-
-size_t align4(size_t floats) { return (floats + 3) & ~(size_t)3; }
 
 }  // namespace
 
@@ -479,13 +428,13 @@ bool nnl_wino_ok(int N, int H, int W, int Cin, int Nc, int R, int S, int stride,
 
 // the plan's predicted time x the measured cost of a Winograd k iteration relative to the direct kernel's (BK 16: 1.18, BK 32: 1.08)
 double nnl_wino_plan_time_us(int N, int H, int W, int Cin, int Nc) {
-  const WPlan pl = wino_plan((long)N * H * ((W + 1) / 2), Nc, Cin);
+  const SplitPlan pl = wino_plan((long)N * H * ((W + 1) / 2), Nc, Cin);
   return pl.t_us * (pl.bk == 32 ? 1.08 : 1.18);
 }
 
 size_t nnl_wino_workspace_bytes(int N, int H, int W, int Cin, int Nc) {
   const long M2 = (long)N * H * ((W + 1) / 2);
-  const WPlan pl = wino_plan(M2, Nc, Cin);
+  const SplitPlan pl = wino_plan(M2, Nc, Cin);
   return (align4((size_t)Nc * 12 * Cin) + (pl.on ? pl.main_floats + pl.tail_floats : 0)) * sizeof(float);
 }
 
@@ -509,18 +458,9 @@ int nnl_wino_launch(const WinoProblem& q, void* ws, size_t ws_bytes, int* tile_c
   p.grid_m = (int)nnl_cdiv(M2, 64L); p.grid_n = (int)nnl_cdiv(q.Nc, 64);
   p.bn_part = q.bn_part; p.bn_pivot = q.bn_pivot;
   const long T = (long)p.grid_m * p.grid_n;
-  WPlan pl = wino_plan(M2, q.Nc, q.Cin);
-  if (pl.on && (tile_counters == nullptr || T > n_counters || ws_bytes < (u_floats + pl.main_floats + pl.tail_floats) * sizeof(float) ||
-                pl.main_floats * sizeof(float) >= (1UL << 31) || pl.tail_floats * sizeof(float) >= (1UL << 31)))
-    pl.on = 0;                                       // split tiles are finished in-kernel only; a slab region is one 2 GB buffer resource
-  unsigned grid = (unsigned)T;
-  if (pl.on) {
-    p.bal = 1; p.main_ks = pl.main_ks; p.n_main_tiles = pl.n_main_tiles; p.tail_slices = pl.tail_slices; p.tail_row0 = pl.tail_row0;
-    p.main_out = u + u_floats; p.main_slab_stride = (long)pl.tail_row0 * 2 * q.Nc;
-    p.tail_out = p.main_out + pl.main_floats; p.tail_slab_stride = (long)(M2 - pl.tail_row0) * 2 * q.Nc;
-    p.tile_counters = tile_counters;
-    grid = (unsigned)(pl.n_main_tiles * pl.main_ks + (T - pl.n_main_tiles) * pl.tail_slices);
-  }
+  SplitPlan pl = wino_plan(M2, q.Nc, q.Cin);
+  if (pl.on && !split_plan_fits(pl, T, &tile_counters, n_counters, ws_bytes, u_floats, false)) pl.on = 0;
+  const unsigned grid = pl.on ? split_bind(p, pl, u + u_floats, M2, 2, tile_counters) : (unsigned)T;
   NNL_ROUTE("wino1d<%d>:%s:%s@main_ks=%d,tail_slices=%d", pl.bk == 32 ? 32 : 16, pl.on ? "ksliced" : "plain", q.u_pre ? "u_pre" : "own_u",
             pl.on ? pl.main_ks : 1, pl.on ? pl.tail_slices : 1);
   if (pl.bk == 32) hipLaunchKernelGGL(wino_kernel<32>, dim3(grid), dim3(256), 0, s, p);
@@ -536,14 +476,26 @@ extern "C" int nnl_wino_filter_multi(const nnl_wino_desc_t* desc, const int32_t*
   return NNL_OK;
 }
 
-// debug / A-B entry (tools/bench_wino.py): ws as nnl_wino_workspace_bytes; counters: >= tiles zeroed int32 or null
-extern "C" size_t nnl_debug_conv_wino_workspace_bytes(int N, int H, int W, int C, int K) { return nnl_wino_workspace_bytes(N, H, W, C, K); }
-extern "C" int nnl_debug_conv_wino_fwd(const float* x, const float* w, const float* bias, const float* add, float* y, void* ws,
-                                       size_t ws_bytes, int32_t* counters, long n_counters, float* bn_part, const float* bn_pivot, int N,
-                                       int H, int W, int C, int K, int relu, int flip, void* stream) {
-  NNL_CHECK_ARG(nnl_wino_ok(N, H, W, C, K, 3, 3, 1, 1), "wino: unsupported shape");
+// debug / A-B entries (tools/bench_wino.py, --two-d for the 2-D family): ws as nnl_debug_conv_wino[2]_workspace_bytes; counters: >= tiles
+// zeroed int32 or null
+static int debug_wino_fwd(const WinoFamily& f, const float* x, const float* w, const float* bias, const float* add, float* y, void* ws,
+                          size_t ws_bytes, int32_t* counters, long n_counters, float* bn_part, const float* bn_pivot, int N, int H, int W,
+                          int C, int K, int relu, int flip, void* stream) {
+  NNL_CHECK_ARG(f.ok(N, H, W, C, K, 3, 3, 1, 1), "%s: unsupported shape", f.name);
   WinoProblem q{};
   q.in = x; q.filt = w; q.out = y; q.bias = bias; q.add = add; q.N = N; q.H = H; q.W = W; q.Cin = C; q.Nc = K; q.relu = relu; q.flip = flip;
   q.bn_part = bn_part; q.bn_pivot = bn_pivot;
-  return nnl_wino_launch(q, ws, ws_bytes, counters, n_counters, (hipStream_t)stream);
+  return f.launch(q, ws, ws_bytes, counters, n_counters, (hipStream_t)stream);
+}
+extern "C" size_t nnl_debug_conv_wino_workspace_bytes(int N, int H, int W, int C, int K) { return nnl_wino_workspace_bytes(N, H, W, C, K); }
+extern "C" size_t nnl_debug_conv_wino2_workspace_bytes(int N, int H, int W, int C, int K) { return nnl_wino2_workspace_bytes(N, H, W, C, K); }
+extern "C" int nnl_debug_conv_wino_fwd(const float* x, const float* w, const float* bias, const float* add, float* y, void* ws,
+                                       size_t ws_bytes, int32_t* counters, long n_counters, float* bn_part, const float* bn_pivot, int N,
+                                       int H, int W, int C, int K, int relu, int flip, void* stream) {
+  return debug_wino_fwd(kWinoFamily[0], x, w, bias, add, y, ws, ws_bytes, counters, n_counters, bn_part, bn_pivot, N, H, W, C, K, relu, flip, stream);
+}
+extern "C" int nnl_debug_conv_wino2_fwd(const float* x, const float* w, const float* bias, const float* add, float* y, void* ws,
+                                        size_t ws_bytes, int32_t* counters, long n_counters, float* bn_part, const float* bn_pivot, int N,
+                                        int H, int W, int C, int K, int relu, int flip, void* stream) {
+  return debug_wino_fwd(kWinoFamily[1], x, w, bias, add, y, ws, ws_bytes, counters, n_counters, bn_part, bn_pivot, N, H, W, C, K, relu, flip, stream);
 }

@@ -22,11 +22,10 @@
 #include "wino.h"
 #include "wino_filter.h"
 #include "igemm_taps.h"
+#include "split_plan.h"
 #include <algorithm>
 
 namespace {
-
-constexpr int kCUs = 256;
 
 // sc1 (device-scope) 16-B load with the wave-uniform part of the address in the scalar offset operand (no VGPR per distinct slab)
 template <int POL>
@@ -528,13 +527,8 @@ __global__ __launch_bounds__(256, OCC) void wino2_kernel(const Wino2Params p) {
   }
 }
 
-// ---- schedule: the balanced plan of conv2d.hip (plan_balance) for I = 16 * C / BK iterations per tile ----
-struct W2Plan {
-  int bk, on, main_ks, n_main_tiles, tail_slices, tail_row0;
-  size_t main_floats, tail_floats;
-  double t_us;
-  int pos_cs;          // > 0: the position-split instantiation with that many channel slices per position (main_floats = its M slabs)
-};
+// ---- schedule: the shared split plan (split_plan.h) for I = 16 * C / BK iterations per tile, four output rows per quad row, with this
+// kernel's own cost model and search; SplitPlan::pos_cs > 0: the position-split instantiation (main_floats = its M slabs) ----
 
 // Cost of the position-split schedule (us): T tiles x 16 positions x cs channel slices, every workgroup runs C / 32 / cs iterations of the
 // BK 32 loop with one accumulator; a CU's nb workgroups, c of them co-resident, cost nb * I * (b + a / c) like the plan above (same loop,
@@ -558,30 +552,23 @@ double w2_pos_cost(long T, long M4, int Nc, int C, int cs) {
 // the co-resident count; `a` is the per-iteration latency a lone workgroup cannot hide (five loads, one barrier), `b` the MFMA / LDS
 // share that co-resident workgroups divide.  Plus a fixed cost per workgroup generation (prologue, 16 folds, four-tile epilogue),
 // the slab round trips at a fitted 11.7 TB/s and 10 us of launch + filter pre-pass.
-double w2_cost(long T, long gn, long M4, int Nc, long I, int bk, int ks, int S, W2Plan* out) {
+double w2_cost(long T, long gn, long M4, int Nc, long I, int bk, int ks, int S, SplitPlan* out) {
   const double a = bk == 32 ? 0.363 : 0.226, b = bk == 32 ? 0.490 : 0.243, tfix = bk == 32 ? 12.3 : 15.0;
   const long occ = bk == 16 ? 4 : 3;
-  long n_main = ((T * ks / kCUs) * kCUs / ks / gn) * gn;
-  if (n_main > T) n_main = T;
-  const long tail = T - n_main;
+  const long tail = split_geometry(T, gn, M4, 4L * Nc, ks, S, out);
   if (tail == 0 && S > 1) return -1.0;
+  const long n_main = T - tail, row0 = out->tail_row0;
+  out->bk = bk; out->on = (ks > 1 || (S > 1 && tail)) ? 1 : 0;
   const long m = nnl_cdiv(n_main * ks, (long)kCUs), q = nnl_cdiv(tail * S, (long)kCUs);
   const long W = m * nnl_cdiv(I, (long)ks) + q * nnl_cdiv(I, (long)S), nb = m + q;
   const double c = (double)(nb < occ ? nb : occ);
-  const long row0 = (n_main / gn) * 64 < M4 ? (n_main / gn) * 64 : M4;
   const double main_b = ks > 1 ? (2.0 * ks + 1) * row0 * 4 * Nc * 4 : 0;
   const double tail_b = (S > 1 && tail) ? (2.0 * S + 1) * (M4 - row0) * 4 * Nc * 4 : 0;
-  if (out) {
-    out->bk = bk; out->on = (ks > 1 || (S > 1 && tail)) ? 1 : 0;
-    out->main_ks = ks; out->n_main_tiles = (int)n_main; out->tail_slices = tail ? S : 1; out->tail_row0 = (int)row0;
-    out->main_floats = ks > 1 ? (size_t)ks * row0 * 4 * Nc : 0;
-    out->tail_floats = (S > 1 && tail) ? (size_t)S * (M4 - row0) * 4 * Nc : 0;
-  }
   return W * (b + a / c) + tfix * nb / c + (main_b + tail_b) / 11.7e6 + 10.0;
 }
 
-W2Plan wino2_plan(long M4, int Nc, int C) {
-  W2Plan best{};
+SplitPlan wino2_plan(long M4, int Nc, int C) {
+  SplitPlan best{};
   const long gm = nnl_cdiv(M4, 64), gn = nnl_cdiv(Nc, 64), T = gm * gn;
   const int f_ks = NNL_ENV_INT("NNL_WINO_PLAN_KS", 0), f_S = NNL_ENV_INT("NNL_WINO_PLAN_S", 0);
   const bool balance = NNL_ENV_INT("NNL_WINO_BALANCE", 1) != 0;
@@ -595,7 +582,7 @@ W2Plan wino2_plan(long M4, int Nc, int C) {
       if (f_ks > 0 && ks != f_ks && balance) continue;
       for (int S : kSlices) {
         if (S > 1 && (!balance || I / S < 4)) break;
-        W2Plan cand{};
+        SplitPlan cand{};
         const double t = w2_cost(T, gn, M4, Nc, I, bk, ks, S, &cand);
         if (t < 0) break;                                                  // no tail tiles: S is meaningless beyond 1
         if (f_S > 0 && balance && cand.n_main_tiles < T && S != f_S) continue;
@@ -621,15 +608,13 @@ W2Plan wino2_plan(long M4, int Nc, int C) {
       if (t < pt) { pt = t; pcs = cs; }
     }
     if (pcs && (e_pos > 0 || pt < best_t)) {
-      best = W2Plan{};
+      best = SplitPlan{};
       best.bk = 32; best.on = 1; best.main_ks = 16 * pcs; best.n_main_tiles = (int)T; best.tail_slices = 1; best.tail_row0 = (int)M4;
       best.main_floats = (size_t)16 * pcs * M4 * Nc; best.tail_floats = 0; best.t_us = pt; best.pos_cs = pcs;
     }
   }
   return best;
 }
-
-size_t align4(size_t floats) { return (floats + 3) & ~(size_t)3; }
 
 long quads(int N, int H, int W) { return (long)N * ((H + 1) / 2) * ((W + 1) / 2); }
 
@@ -646,7 +631,7 @@ double nnl_wino2_plan_time_us(int N, int H, int W, int Cin, int Nc) { return win
 bool nnl_wino2_plan_is_pos(int N, int H, int W, int Cin, int Nc) { return wino2_plan(quads(N, H, W), Nc, Cin).pos_cs > 0; }
 
 size_t nnl_wino2_workspace_bytes(int N, int H, int W, int Cin, int Nc) {
-  const W2Plan pl = wino2_plan(quads(N, H, W), Nc, Cin);
+  const SplitPlan pl = wino2_plan(quads(N, H, W), Nc, Cin);
   return (align4((size_t)Nc * 16 * Cin) + (pl.on ? pl.main_floats + pl.tail_floats : 0)) * sizeof(float);
 }
 
@@ -679,9 +664,8 @@ int nnl_wino2_launch(const WinoProblem& q, void* ws, size_t ws_bytes, int* tile_
   p.grid_m = (int)nnl_cdiv(M4, 64L); p.grid_n = (int)nnl_cdiv(q.Nc, 64);
   p.bn_part = q.bn_part; p.bn_pivot = q.bn_pivot;
   const long T = (long)p.grid_m * p.grid_n;
-  W2Plan pl = wino2_plan(M4, q.Nc, q.Cin);
-  if (pl.on && (tile_counters == nullptr || T > n_counters || ws_bytes < (u_floats + pl.main_floats + pl.tail_floats) * sizeof(float) ||
-                pl.main_floats * sizeof(float) >= (1UL << 31) || pl.tail_floats * sizeof(float) >= (1UL << 31))) {
+  SplitPlan pl = wino2_plan(M4, q.Nc, q.Cin);
+  if (pl.on && !split_plan_fits(pl, T, &tile_counters, n_counters, ws_bytes, u_floats, false)) {
     if (pl.pos_cs) {                                                       // (no counters / workspace for the slabs: the unsplit plan)
       const int bk = q.Cin % 32 == 0 ? 32 : 16;
       w2_cost(T, p.grid_n, M4, q.Nc, 16L * (q.Cin / bk), bk, 1, 1, &pl);
@@ -689,39 +673,19 @@ int nnl_wino2_launch(const WinoProblem& q, void* ws, size_t ws_bytes, int* tile_
     }
     pl.on = 0;
   }
-  unsigned grid = (unsigned)T;
-  if (pl.pos_cs) {
-    p.bal = 1; p.main_ks = pl.main_ks; p.n_main_tiles = pl.n_main_tiles; p.tail_slices = 1; p.tail_row0 = (int)M4;
-    p.main_out = u + u_floats; p.main_slab_stride = M4 * q.Nc; p.tile_counters = tile_counters; p.pos_cs = pl.pos_cs;
-    grid = (unsigned)(T * pl.main_ks);
+  if (pl.pos_cs) {                                                         // one slab of M4 x Nc per position and channel slice
+    const unsigned grid = split_bind(p, pl, u + u_floats, M4, 1, tile_counters);
+    p.pos_cs = pl.pos_cs;
     NNL_ROUTE("wino2d<32,4,pos>:%s@slices=%d,pos_cs=%d", q.u_pre ? "u_pre" : "own_u", pl.main_ks, pl.pos_cs);
     hipLaunchKernelGGL((wino2_kernel<32, 4, true>), dim3(grid), dim3(256), 0, s, p);
     NNL_CHECK_LAUNCH();
     return NNL_OK;
   }
-  if (pl.on) {
-    p.bal = 1; p.main_ks = pl.main_ks; p.n_main_tiles = pl.n_main_tiles; p.tail_slices = pl.tail_slices; p.tail_row0 = pl.tail_row0;
-    p.main_out = u + u_floats; p.main_slab_stride = (long)pl.tail_row0 * 4 * q.Nc;
-    p.tail_out = p.main_out + pl.main_floats; p.tail_slab_stride = (long)(M4 - pl.tail_row0) * 4 * q.Nc;
-    p.tile_counters = tile_counters;
-    grid = (unsigned)(pl.n_main_tiles * pl.main_ks + (T - pl.n_main_tiles) * pl.tail_slices);
-  }
+  const unsigned grid = pl.on ? split_bind(p, pl, u + u_floats, M4, 4, tile_counters) : (unsigned)T;
   NNL_ROUTE("wino2d<%s>:%s:%s@main_ks=%d,tail_slices=%d", pl.bk == 32 ? "32,3" : "16,4", pl.on ? "ksliced" : "plain", q.u_pre ? "u_pre" : "own_u",
             pl.on ? pl.main_ks : 1, pl.on ? pl.tail_slices : 1);
   if (pl.bk == 32) hipLaunchKernelGGL((wino2_kernel<32, 3>), dim3(grid), dim3(256), 0, s, p);
   else hipLaunchKernelGGL((wino2_kernel<16, 4>), dim3(grid), dim3(256), 0, s, p);
   NNL_CHECK_LAUNCH();
   return NNL_OK;
-}
-
-// debug / A-B entry (tools/bench_wino.py --two-d): ws as nnl_debug_conv_wino2_workspace_bytes; counters: >= tiles zeroed int32 or null
-extern "C" size_t nnl_debug_conv_wino2_workspace_bytes(int N, int H, int W, int C, int K) { return nnl_wino2_workspace_bytes(N, H, W, C, K); }
-extern "C" int nnl_debug_conv_wino2_fwd(const float* x, const float* w, const float* bias, const float* add, float* y, void* ws,
-                                        size_t ws_bytes, int32_t* counters, long n_counters, float* bn_part, const float* bn_pivot, int N,
-                                        int H, int W, int C, int K, int relu, int flip, void* stream) {
-  NNL_CHECK_ARG(nnl_wino2_ok(N, H, W, C, K, 3, 3, 1, 1), "wino2: unsupported shape");
-  WinoProblem q{};
-  q.in = x; q.filt = w; q.out = y; q.bias = bias; q.add = add; q.N = N; q.H = H; q.W = W; q.Cin = C; q.Nc = K; q.relu = relu; q.flip = flip;
-  q.bn_part = bn_part; q.bn_pivot = bn_pivot;
-  return nnl_wino2_launch(q, ws, ws_bytes, counters, n_counters, (hipStream_t)stream);
 }

@@ -25,7 +25,7 @@ pytestmark = pytest.mark.skipif(torch.cuda.is_available(), reason='fake pointers
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'conv_routes.txt')
 SWITCHES = ('NNL_CONV_WINO', 'NNL_CONV_WINO2', 'NNL_WINO2_POS', 'NNL_WINO_PLAN_KS', 'NNL_WINO_PLAN_S', 'NNL_IGEMM_BALANCE', 'NNL_IGEMM_KTAIL',
-            'NNL_IGEMM_DMA', 'NNL_WGRAD_WINO', 'NNL_WGRAD_WINO2D')
+            'NNL_IGEMM_DMA', 'NNL_WGRAD_WINO', 'NNL_WGRAD_WINO2D', 'NNL_WINO_BALANCE', 'NNL_WINO2_CHUNK')
 CALL_MODES = ('ws+cnt', 'ws', 'none')
 
 
