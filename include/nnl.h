@@ -318,7 +318,9 @@ int nnl_bn_sync_bwd(const float* dy, const float* y, const uint32_t* relu_mask, 
  * nn.MaxPool2d(ksize, stride, pad) of the ResNet stem (Applications/VisionModels/retinanet.py:307,374; torchvision
  * resnet.maxpool) with torch's tie rule — `if ((val > max) || isnan(val))` in (kh, kw) scan order.  idx [N,P,Q,C] uint8 =
  * kh*ksize + kw of the winning tap, kept for the backward, which GATHERS (each input pixel sums dy over the windows whose
- * arg-max it is): no atomics, bitwise reproducible. */
+ * arg-max it is): no atomics, bitwise reproducible.  (P, Q) is the module's output size: floor mode, or ceil_mode=True (the pool of
+ * the SENet stem, Applications/VisionModels/senet.py:314-315) by torch's rule — round up, then drop a last window that would start
+ * beyond the input plus its left padding; taps outside the input are skipped on every side.  Any other P / Q is an invalid argument. */
 int nnl_maxpool2d_fwd(const float* x, float* y, uint8_t* idx, int64_t N, int64_t H, int64_t W, int64_t C, int64_t P,
                       int64_t Q, int ksize, int stride, int pad, void* stream);
 int nnl_maxpool2d_bwd(const float* dy, const uint8_t* idx, float* dx, int64_t N, int64_t H, int64_t W, int64_t C,
@@ -328,6 +330,38 @@ int nnl_maxpool2d_bwd(const float* dy, const uint8_t* idx, float* dx, int64_t N,
  * dout[:, :C] to that pixel and dout[:, C:]/HW to every pixel. */
 int nnl_concat_pool_fwd(const float* x, float* out, int32_t* argmax, int64_t N, int64_t HW, int64_t C, void* stream);
 int nnl_concat_pool_bwd(const float* dout, const int32_t* argmax, float* dx, int64_t N, int64_t HW, int64_t C, void* stream);
+
+/* ---- K15: grouped convolution, nn.Conv2d(groups = G) (Applications/VisionModels/senet.py:178-180, 205-206, 229-230) --------------
+ * Activations NHWC fp32; the filter is the parameter's own channels_last memory: logical [K, C/G, R, R] stored [K, R, R, Cg], and dw
+ * comes back in that layout.  Output channel k reads the input channels [g Cg, (g + 1) Cg) of its group g = k / (K / G).
+ * Domain: G divides C and K (any Cg = C/G >= 1, Kg = K/G >= 1), R in {1, 3}, stride in {1, 2}, 0 <= pad <= R / 2, N < 65536, every
+ * tensor below 2^31 elements; anything else is NNL_ERR_INVALID_ARG and nothing is launched.  P = (H + 2 pad - R) / stride + 1, Q likewise.
+ * Direct kernels (csrc/gconv.hip), every sum in a fixed order and no atomics: two calls on the same inputs give the same bits.
+ * nnl_gconv2d_fwd (Applications/VisionModels/senet.py:178-180, 205-206, 229-230): y = conv(x, w) + bias (bias may be NULL), ReLU when relu != 0. */
+int nnl_gconv2d_fwd(const float* x, const float* w, const float* bias, float* y, int64_t N, int64_t H, int64_t W, int64_t C, int64_t K,
+                    int64_t G, int R, int stride, int pad, int relu, void* stream);
+/* nnl_gconv2d_dgrad (backward of senet.py:178-180, 205-206, 229-230): dx [N,H,W,C] from dy [N,P,Q,K] taken at the convolution's output;
+ * every element of dx is written. */
+int nnl_gconv2d_dgrad(const float* dy, const float* w, float* dx, int64_t N, int64_t H, int64_t W, int64_t C, int64_t K, int64_t G,
+                      int R, int stride, int pad, void* stream);
+/* nnl_gconv2d_wgrad (backward of senet.py:178-180, 205-206, 229-230): dw [K, R, R, Cg].  The N*P*Q pixels are cut into slices whose
+ * partial sums go to the workspace (nnl_gconv2d_workspace_bytes; 0 = one slice, ws may be NULL) and are added in slice order by a second
+ * launch; a workspace that is too small is NNL_ERR_WORKSPACE. */
+size_t nnl_gconv2d_workspace_bytes(int64_t N, int64_t H, int64_t W, int64_t C, int64_t K, int64_t G, int R, int stride, int pad);
+int nnl_gconv2d_wgrad(const float* x, const float* dy, float* dw, void* ws, size_t ws_bytes, int64_t N, int64_t H, int64_t W, int64_t C,
+                      int64_t K, int64_t G, int R, int stride, int pad, void* stream);
+
+/* ---- K15: squeeze-and-excitation tail of a SENet block (Applications/VisionModels/senet.py:118-137 SEModule, :161-162) -------------
+ *   out = relu( x * sigmoid(z[n, c]) + residual ),  z = fc2(relu(fc1(m))),  m[n, c] = mean over the HW pixels of x   (x NHWC = [N, HW, C])
+ * nnl_se_squeeze: m [N, C], summed in a fixed order.  nnl_se_excite_fwd: one pass; z holds the PRE-sigmoid logits; residual may be NULL;
+ * C % 4 == 0.  nnl_se_excite_bwd: g = dy * [out > 0]; dres = g (dres may be NULL); dx = g * sigmoid(z); dz[n, c] = sigmoid'(z) *
+ * sum_h g * x, accumulated in fp64 in a fixed order and rounded once.  nnl_se_squeeze_bwd: dx += dm[n, c] / HW, the gradient of the mean
+ * (C % 4 == 0).  No atomics: bitwise repeatable.  N < 65536, HW < 2^30, C < 2^22. */
+int nnl_se_squeeze(const float* x, float* m, int64_t N, int64_t HW, int64_t C, void* stream);
+int nnl_se_excite_fwd(const float* x, const float* z, const float* residual, float* out, int64_t N, int64_t HW, int64_t C, void* stream);
+int nnl_se_excite_bwd(const float* dy, const float* out, const float* x, const float* z, float* dx, float* dres, float* dz, int64_t N,
+                      int64_t HW, int64_t C, void* stream);
+int nnl_se_squeeze_bwd(const float* dm, float* dx, int64_t N, int64_t HW, int64_t C, void* stream);
 
 /* ---- detection inference: the device half of BBoxPredictor.__call__ / nms (Applications/VisionModels/retinanet.py:523-812)
  * nnl_bbox_decode: per (image, anchor) best class (first maximum) and its score; keep score > thresh; decode the box

@@ -18,7 +18,7 @@ import torch.nn as nn
 from ... import ops
 from ...General.Core import default_device
 
-__all__ = ['HipConv2d', 'conv3x3', 'BasicBlock', 'Bottleneck', 'PyramidFeatures', 'RegressionModel',
+__all__ = ['HipConv2d', 'HipGroupedConv2d', 'conv3x3', 'BasicBlock', 'Bottleneck', 'PyramidFeatures', 'RegressionModel',
            'ClassificationModel', 'RetinaNet', 'retinanet18', 'retinanet34', 'retinanet50', 'retinanet101',
            'retinanet152', 'get_anchor_set', 'get_anchor_shifts', 'AnchorGenerator', 'intersections', 'jaccard', 'nms',
            'BBoxPredictor']
@@ -44,14 +44,37 @@ class HipConv2d(nn.Conv2d):
                           grad_slot=grad_slot, give_slot=give_slot)
 
 
+class HipGroupedConv2d(nn.Conv2d):
+    """nn.Conv2d(groups=G) (same parameters / state_dict) computed by the direct grouped kernels of csrc/gconv.hip (ops.grouped_conv2d):
+    the 3x3 of the SENet / SE-ResNeXt bottlenecks (senet.py:178-180, 229-230).  The weight keeps its logical [K, C/G, R, R] shape and is
+    STORED channels_last (= [K, R, R, C/G], the kernels' filter layout).  Deliberately not marked `nnl_hip_conv`: the prepared-filter
+    window (ops._Filters) transposes the weights of the marked modules as dense [K, C, R, S] filters."""
+    fuse_relu = False
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.weight.data = self.weight.data.contiguous(memory_format=torch.channels_last)
+
+    def forward(self, x):
+        if self.dilation != (1, 1):
+            raise NotImplementedError('HipGroupedConv2d: dilation %r is not supported' % (self.dilation,))
+        if self.padding_mode != 'zeros' or isinstance(self.padding, str):
+            raise NotImplementedError('HipGroupedConv2d: padding_mode %r / padding %r is not supported' % (self.padding_mode, self.padding))
+        if self.stride[0] != self.stride[1]:
+            raise NotImplementedError('HipGroupedConv2d: stride %r must be the same in both directions' % (self.stride,))
+        if self.padding[0] != self.padding[1]:
+            raise NotImplementedError('HipGroupedConv2d: padding %r must be the same in both directions' % (self.padding,))
+        return ops.grouped_conv2d(x, self.weight, self.bias, self.stride[0], self.padding[0], self.groups, relu=self.fuse_relu)
+
+
 class HipMaxPool2d(nn.MaxPool2d):
-    "nn.MaxPool2d (floor mode, no dilation) on the NHWC HIP kernels of csrc/pool.hip (same tie rule as torch)"
+    "nn.MaxPool2d (floor or ceil mode, no dilation) on the NHWC HIP kernels of csrc/pool.hip (same tie rule as torch)"
 
     def forward(self, x):
         k, s, p = self.kernel_size, self.stride, self.padding
-        if self.dilation != 1 or self.ceil_mode or self.return_indices or not all(isinstance(v, int) for v in (k, s, p)):
-            raise NotImplementedError('HipMaxPool2d: only the square floor-mode pooling the reference uses')
-        return ops.maxpool2d(x, k, s, p)
+        if self.dilation != 1 or self.return_indices or not all(isinstance(v, int) for v in (k, s, p)):
+            raise NotImplementedError('HipMaxPool2d: only the square pooling the reference uses')
+        return ops.maxpool2d(x, k, s, p, ceil_mode=self.ceil_mode)
 
 
 class _ConvReLU(HipConv2d):

@@ -83,6 +83,14 @@ SIGNATURES = {
                                           C.c_int, C.c_int, C.c_int, C.c_int, c_p, sz, c_p]),
     'nnl_concat_pool_fwd': (C.c_int, [c_p, c_p, c_p, i64, i64, i64, c_p]),
     'nnl_concat_pool_bwd': (C.c_int, [c_p, c_p, c_p, i64, i64, i64, c_p]),
+    'nnl_gconv2d_fwd': (C.c_int, [c_p, c_p, c_p, c_p, i64, i64, i64, i64, i64, i64, C.c_int, C.c_int, C.c_int, C.c_int, c_p]),
+    'nnl_gconv2d_dgrad': (C.c_int, [c_p, c_p, c_p, i64, i64, i64, i64, i64, i64, C.c_int, C.c_int, C.c_int, c_p]),
+    'nnl_gconv2d_workspace_bytes': (sz, [i64, i64, i64, i64, i64, i64, C.c_int, C.c_int, C.c_int]),
+    'nnl_gconv2d_wgrad': (C.c_int, [c_p, c_p, c_p, c_p, sz, i64, i64, i64, i64, i64, i64, C.c_int, C.c_int, C.c_int, c_p]),
+    'nnl_se_squeeze': (C.c_int, [c_p, c_p, i64, i64, i64, c_p]),
+    'nnl_se_excite_fwd': (C.c_int, [c_p, c_p, c_p, c_p, i64, i64, i64, c_p]),
+    'nnl_se_excite_bwd': (C.c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, i64, i64, i64, c_p]),
+    'nnl_se_squeeze_bwd': (C.c_int, [c_p, c_p, i64, i64, i64, c_p]),
     'nnl_bbox_decode': (C.c_int, [c_p, c_p, c_p, i64, i64, i64, c_p, c_p, f32, f32, f32, c_p, c_p, c_p, c_p, c_p, c_p]),
     'nnl_bbox_decode_window': (C.c_int, [c_p, c_p, c_p, i64, i64, i64, c_p, c_p, f32, f32, f32, f32, f32, c_p, c_p, c_p, c_p, c_p, c_p]),
     'nnl_nms_workspace_bytes': (sz, [i64, i64]),

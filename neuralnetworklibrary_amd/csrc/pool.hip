@@ -137,13 +137,21 @@ int ew_blocks(long total) {
   return (int)(b < 1 ? 1 : b);
 }
 
+// P is nn.MaxPool2d's output size for H: floor mode, or ceil_mode=True (torch's rule: round up, then drop a last window that would
+// start beyond the input plus its left padding).  Both kernels skip the taps outside the input and clamp their window range to P.
+bool pool_out_ok(int64_t H, int64_t P, int ksize, int stride, int pad) {
+  int64_t ceil = (H + 2 * pad - ksize + stride - 1) / stride + 1;
+  if ((ceil - 1) * stride >= H + pad) --ceil;
+  return P == (H + 2 * pad - ksize) / stride + 1 || P == ceil;
+}
+
 }  // namespace
 
 extern "C" int nnl_maxpool2d_fwd(const float* x, float* y, uint8_t* idx, int64_t N, int64_t H, int64_t W, int64_t C, int64_t P,
                                  int64_t Q, int ksize, int stride, int pad, void* stream) {
   NNL_CHECK_ARG(x && y && idx && N > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0, "maxpool2d_fwd: bad argument (C %% 4 == 0)");
   NNL_CHECK_ARG(ksize >= 1 && ksize <= 15 && stride >= 1 && pad >= 0 && 2 * pad <= ksize, "maxpool2d_fwd: bad window");
-  NNL_CHECK_ARG(P == (H + 2 * pad - ksize) / stride + 1 && Q == (W + 2 * pad - ksize) / stride + 1, "maxpool2d_fwd: bad P/Q");
+  NNL_CHECK_ARG(pool_out_ok(H, P, ksize, stride, pad) && pool_out_ok(W, Q, ksize, stride, pad), "maxpool2d_fwd: bad P/Q");
   NNL_CHECK_ARG(N * H * W * C < (1L << 40), "maxpool2d_fwd: tensor too large");
   hipStream_t s = (hipStream_t)stream;
   const long total = N * P * Q * (C / 4);
@@ -158,7 +166,7 @@ extern "C" int nnl_maxpool2d_bwd(const float* dy, const uint8_t* idx, float* dx,
                                  int64_t P, int64_t Q, int ksize, int stride, int pad, void* stream) {
   NNL_CHECK_ARG(dy && dx && idx && N > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0, "maxpool2d_bwd: bad argument (C %% 4 == 0)");
   NNL_CHECK_ARG(ksize >= 1 && ksize <= 15 && stride >= 1 && pad >= 0 && 2 * pad <= ksize, "maxpool2d_bwd: bad window");
-  NNL_CHECK_ARG(P == (H + 2 * pad - ksize) / stride + 1 && Q == (W + 2 * pad - ksize) / stride + 1, "maxpool2d_bwd: bad P/Q");
+  NNL_CHECK_ARG(pool_out_ok(H, P, ksize, stride, pad) && pool_out_ok(W, Q, ksize, stride, pad), "maxpool2d_bwd: bad P/Q");
   hipStream_t s = (hipStream_t)stream;
   const long total = N * H * W * (C / 4);
   NnlProfScope prof(NNL_PROF_ELEMENTWISE, s, 4.0 * N * H * W * C + 5.0 * N * P * Q * C);

@@ -16,7 +16,7 @@ import torch
 from . import _lib
 from ._lib import check, lib, ptr, require_cuda, stream
 
-__all__ = ['mse_loss', 'bce_with_logits', 'fbeta', 'scaled_sigmoid', 'embdotbias', 'index_error_flag', 'raise_if_index_error', 'conv2d', 'to_nhwc', 'from_nhwc', 'linear', 'bn_act', 'concat_pool2d', 'TabularPlan', 'tab_embed_concat', 'embedding_renorm_drop', 'retina_loss', 'image_aug']
+__all__ = ['mse_loss', 'bce_with_logits', 'fbeta', 'scaled_sigmoid', 'embdotbias', 'index_error_flag', 'raise_if_index_error', 'conv2d', 'to_nhwc', 'from_nhwc', 'linear', 'bn_act', 'concat_pool2d', 'TabularPlan', 'tab_embed_concat', 'embedding_renorm_drop', 'retina_loss', 'image_aug', 'grouped_conv2d', 'se_excite']
 
 _ERR_FLAGS = {}
 
@@ -1134,13 +1134,22 @@ def concat_pool2d(x):
     return _ConcatPool.apply(x)
 
 
+def pool_out_size(H, ksize, stride, pad, ceil_mode=False):
+    """nn.MaxPool2d's output size along one axis.  ceil_mode (the SENet stem pool, senet.py:314-315): torch's rule — round up, then drop
+    a last window that would start beyond the input plus its left padding."""
+    if not ceil_mode:
+        return (H + 2 * pad - ksize) // stride + 1
+    out = -((H + 2 * pad - ksize) // -stride) + 1
+    return out - 1 if (out - 1) * stride >= H + pad else out
+
+
 class _MaxPool2d(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, ksize, stride, pad):
+    def forward(ctx, x, ksize, stride, pad, ceil_mode=False):
         require_cuda(x)
         xn = to_nhwc(x.float())
         N, H, W, C = xn.shape
-        P, Q = (H + 2 * pad - ksize) // stride + 1, (W + 2 * pad - ksize) // stride + 1
+        P, Q = pool_out_size(H, ksize, stride, pad, ceil_mode), pool_out_size(W, ksize, stride, pad, ceil_mode)
         y = torch.empty(N, P, Q, C, dtype=torch.float32, device=x.device)
         idx = torch.empty(N, P, Q, C, dtype=torch.uint8, device=x.device)
         check(lib.nnl_maxpool2d_fwd(ptr(xn), ptr(y), ptr(idx), N, H, W, C, P, Q, ksize, stride, pad, stream()))
@@ -1155,7 +1164,7 @@ class _MaxPool2d(torch.autograd.Function):
         dyn = to_nhwc(dy.float())
         dx = torch.empty(N, H, W, C, dtype=torch.float32, device=dy.device)
         check(lib.nnl_maxpool2d_bwd(ptr(dyn), ptr(idx), ptr(dx), N, H, W, C, P, Q, ksize, stride, pad, stream()))
-        return from_nhwc(dx), None, None, None
+        return from_nhwc(dx), None, None, None, None
 
 
 class _BNReLUMaxPool(torch.autograd.Function):
@@ -1218,10 +1227,134 @@ def conv_bn_relu_maxpool(conv, bn, pool, x):
     return _BNReLUMaxPool.apply(y, bn.weight, bn.bias, rmean, rvar, training, momentum, bn.eps, nbt, k, s, p)
 
 
-def maxpool2d(x, ksize=3, stride=2, pad=1):
-    """nn.MaxPool2d(ksize, stride, pad) (floor mode, no dilation) — the ResNet stem pool (retinanet.py:307,374) — NHWC,
-    channel count a multiple of 4; torch's first-maximum tie rule, deterministic gather-style backward (pool.hip)."""
-    return _MaxPool2d.apply(x, int(ksize), int(stride), int(pad))
+def maxpool2d(x, ksize=3, stride=2, pad=1, ceil_mode=False):
+    """nn.MaxPool2d(ksize, stride, pad, ceil_mode=ceil_mode) (no dilation) — the ResNet stem pool (retinanet.py:307,374), in ceil
+    mode the SENet one (senet.py:314-315) — NHWC, channel count a multiple of 4; torch's first-maximum tie rule, deterministic
+    gather-style backward (pool.hip).  ceil_mode changes the output size only: the kernels skip the taps outside the input."""
+    return _MaxPool2d.apply(x, int(ksize), int(stride), int(pad), bool(ceil_mode))
+
+
+# ---------------------------------------------------------------------------------------------------------
+# K15 grouped convolution and squeeze-excite (the SENet family, Applications/VisionModels/senet.py)
+# ---------------------------------------------------------------------------------------------------------
+def _gconv_check(x_shape, w_shape, stride, pad, groups):
+    "the domain of csrc/gconv.hip, checked before any launch (and before any device is needed): names the offending argument"
+    if len(x_shape) != 4 or len(w_shape) != 4:
+        raise NotImplementedError('grouped_conv2d: x %s and weight %s must be 4-D' % (tuple(x_shape), tuple(w_shape)))
+    C, (K, Cg, R, S) = x_shape[1], w_shape
+    if R != S or R not in (1, 3):
+        raise NotImplementedError('grouped_conv2d: kernel_size %dx%d is not supported (1x1 or 3x3)' % (R, S))
+    if stride not in (1, 2):
+        raise NotImplementedError('grouped_conv2d: stride %r is not supported (1 or 2)' % (stride,))
+    if pad not in (0, 1) or pad > R // 2:
+        raise NotImplementedError('grouped_conv2d: padding %r is not supported (0 .. kernel_size // 2)' % (pad,))
+    if groups < 1 or C % groups or K % groups or C // groups != Cg:
+        raise NotImplementedError('grouped_conv2d: groups %r must divide the %d input and %d output channels (weight holds %d inputs per group)'
+                                  % (groups, C, K, Cg))
+
+
+class _GroupedConv2d(torch.autograd.Function):
+    """nn.Conv2d(groups=G) forward / backward (reference Applications/VisionModels/senet.py:178-180, 205-206, 229-230) on the direct
+    kernels of csrc/gconv.hip; optional fused bias + ReLU epilogue.  Plain autograd: no GradSlot, no prepared filters."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, stride, pad, groups, relu):
+        _gconv_check(x.shape, weight.shape, stride, pad, groups)
+        require_cuda(x, weight, bias)
+        xn, wn = to_nhwc(x.float()), to_nhwc(weight.float())                 # (no copy: both are stored channels_last)
+        b = None if bias is None else _f32c(bias)
+        N, H, W, C = xn.shape
+        K, R = wn.shape[0], wn.shape[1]
+        g = _geom(N, H, W, C, K, R, R, stride, pad)
+        y = torch.empty((N, g.P, g.Q, K), dtype=torch.float32, device=x.device)
+        check(lib.nnl_gconv2d_fwd(ptr(xn), ptr(wn), ptr(b), ptr(y), N, H, W, C, K, groups, R, stride, pad, int(relu), stream()))
+        ctx.cfg = (g, groups, bool(relu), bias is not None)
+        ctx.save_for_backward(xn, wn, y if relu else None)
+        return from_nhwc(y)
+
+    @staticmethod
+    def backward(ctx, dy):
+        xn, wn, y = ctx.saved_tensors
+        g, groups, relu, has_bias = ctx.cfg
+        dims = (g.N, g.H, g.W, g.C, g.K, groups, g.R, g.stride, g.pad)
+        want_db = has_bias and ctx.needs_input_grad[2]
+        dyn, db = to_nhwc(dy.float()), None
+        if relu:
+            dyn, db = _conv_act_gate(y, dyn, g, 1, want_db)
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty_like(xn)
+            check(lib.nnl_gconv2d_dgrad(ptr(dyn), ptr(wn), ptr(dx), *dims, stream()))
+            dx = from_nhwc(dx)
+        if ctx.needs_input_grad[1]:
+            dw = torch.empty_like(wn)                                        # [K, R, R, Cg]: the parameter's own layout
+            wsb = int(lib.nnl_gconv2d_workspace_bytes(*dims))
+            ws = _workspace(wsb, dyn.device)
+            check(lib.nnl_gconv2d_wgrad(ptr(xn), ptr(dyn), ptr(dw), ptr(ws), wsb, *dims, stream()))
+            dw = from_nhwc(dw)
+        if db is None and want_db:
+            db = _conv_bias_grad(dyn, g, g.K)
+        return dx, dw, db, None, None, None, None
+
+
+def grouped_conv2d(x, weight, bias, stride, pad, groups, relu=False):
+    """y = [relu](conv2d(x, weight, bias, stride, padding=pad, groups=groups)); x logical [N,C,H,W], weight [K, C/groups, R, R] stored
+    channels_last.  Domain: R in {1, 3}, stride in {1, 2}, pad in {0, 1} and <= R // 2, groups divides C and K; anything else raises
+    NotImplementedError naming the argument."""
+    return _GroupedConv2d.apply(x, weight, bias, int(stride), int(pad), int(groups), bool(relu))
+
+
+class _SEExcite(torch.autograd.Function):
+    """relu(x * sigmoid(fc2(relu(fc1(mean_hw(x))))) + residual): SEModule plus the block's closing add and ReLU (reference
+    Applications/VisionModels/senet.py:118-137, 161-162) — squeeze, the scaling pass and their backward in csrc/se.hip, the two FCs
+    through `linear` on the [N, C] matrix (their backward is the recorded graph of those two calls)."""
+
+    @staticmethod
+    def forward(ctx, x, residual, w1, b1, w2, b2):
+        require_cuda(x, residual, w1, b1, w2, b2)
+        xn = to_nhwc(x.float())
+        rn = None if residual is None else to_nhwc(residual.float())
+        N, H, W, C = xn.shape
+        if rn is not None and rn.shape != xn.shape:
+            raise _lib.NnlError('se_excite: residual %s does not match x %s' % (tuple(residual.shape), tuple(x.shape)))
+        m = torch.empty(N, C, dtype=torch.float32, device=x.device)
+        check(lib.nnl_se_squeeze(ptr(xn), ptr(m), N, H * W, C, stream()))
+        track = any(ctx.needs_input_grad)
+        with torch.enable_grad() if track else contextlib.nullcontext():
+            if track:
+                m.requires_grad_(True)
+            z = linear(linear(m, w1.reshape(w1.shape[0], C), b1, relu=True), w2.reshape(C, w2.shape[1]), b2)
+        zd = _f32c(z.detach())
+        out = torch.empty_like(xn)
+        check(lib.nnl_se_excite_fwd(ptr(xn), ptr(zd), ptr(rn), ptr(out), N, H * W, C, stream()))
+        ctx.fc = (m, z, (w1, b1, w2, b2)) if track else None
+        ctx.has_res = rn is not None
+        ctx.save_for_backward(xn, zd, out)
+        return from_nhwc(out)
+
+    @staticmethod
+    def backward(ctx, dy):
+        xn, zd, out = ctx.saved_tensors
+        N, H, W, C = xn.shape
+        dyn = to_nhwc(dy.float())
+        dx, dz = torch.empty_like(xn), torch.empty_like(zd)
+        dres = torch.empty_like(xn) if (ctx.has_res and ctx.needs_input_grad[1]) else None
+        check(lib.nnl_se_excite_bwd(ptr(dyn), ptr(out), ptr(xn), ptr(zd), ptr(dx), ptr(dres), ptr(dz), N, H * W, C, stream()))
+        m, z, params = ctx.fc
+        ctx.fc = None
+        live = [p is not None and p.requires_grad for p in params]
+        grads = iter(torch.autograd.grad(z, [m] + [p for p, on in zip(params, live) if on], dz, allow_unused=True))
+        dm = next(grads)
+        if ctx.needs_input_grad[0]:
+            check(lib.nnl_se_squeeze_bwd(ptr(_f32c(dm)), ptr(dx), N, H * W, C, stream()))
+        dparams = tuple(next(grads) if on else None for on in live)
+        return ((from_nhwc(dx) if ctx.needs_input_grad[0] else None), (None if dres is None else from_nhwc(dres))) + dparams
+
+
+def se_excite(x, fc1, fc2, residual=None):
+    """relu(x * sigmoid(fc2(relu(fc1(avg_pool(x))))) + residual) for the 1x1 convolutions fc1 [C/r, C, 1, 1] and fc2 [C, C/r, 1, 1]
+    (with bias) of an SEModule; residual None = no shortcut term.  x logical [N,C,H,W], C a multiple of 4."""
+    return _SEExcite.apply(x, residual, fc1.weight, fc1.bias, fc2.weight, fc2.bias)
 
 
 # ---------------------------------------------------------------------------------------------------------
