@@ -710,8 +710,9 @@ int nnl_detect_aug(const uint8_t* arena, int64_t arena_bytes, const nnl_image_de
  * 1-beta1 (Adam), beta1, beta2, eps, bc1 = 1-beta1^t, sqrt(bc2) = sqrt(1-beta2^t), clip max_norm, 1-beta2} (1-beta rounded once from
  * double by the caller, as torch.optim.Adam's scalar arguments are): hyper-parameters are read from
  * memory so that a captured hipGraph of the whole step can be replayed with new values.  use_clip != 0: gradients are
- * scaled by min(1, max_norm/(||g||_2 + 1e-6)) (also written back to .grad, as clip_grad_norm_ does); clip_workspace:
- * n_chunks + 2 floats, [0] = coefficient, [1] = total norm on return. */
+ * scaled by min(1, max_norm/(||g||_2 + 1e-6)) (also written back to .grad, as clip_grad_norm_ does; a NaN norm gives a NaN
+ * coefficient, an Inf norm the coefficient 0, as there); clip_workspace: n_chunks + 2 floats, [0] = coefficient, [1] = total norm on
+ * return. */
 typedef struct {
   float* param;
   float* grad;

@@ -110,6 +110,8 @@ class Optimizer(object):
             lrs, decays = self._fused_args()
             fused.step(lrs, decays, self.clip)
             return
+        if fused is not None:
+            fused.unshare_steps()
         if self.wd:
             reg_groups = self.opt.param_groups[:self.NL]
             bn_groups = self.opt.param_groups[self.NL:]

@@ -32,7 +32,8 @@ __global__ __launch_bounds__(kBlock) void sqnorm_partial_kernel(const nnl_optim_
   if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-// coef[0] = min(1, max_norm / (sqrt(sum partial) + 1e-6))   (torch.nn.utils.clip_grad_norm_), fixed summation order
+// coef[0] = min(1, max_norm / (sqrt(sum partial) + 1e-6))   (torch.nn.utils.clip_grad_norm_), fixed summation order.  A NaN norm gives a
+// NaN coefficient, as torch's clamp does: every gradient of a diverged step becomes NaN, not only the elements that already were
 __global__ void clip_coef_kernel(const float* __restrict__ partial, int n, const float* __restrict__ hyper, float* __restrict__ coef) {
   const float max_norm = hyper[6];
   __shared__ double red[kBlock];
@@ -47,7 +48,7 @@ __global__ void clip_coef_kernel(const float* __restrict__ partial, int n, const
   if (threadIdx.x == 0) {
     const float total = (float)sqrt(red[0]);
     const float c = max_norm / (total + 1e-6f);
-    coef[0] = c < 1.f ? c : 1.f;
+    coef[0] = c >= 1.f ? 1.f : c;
     coef[1] = total;
   }
 }

@@ -51,10 +51,13 @@ class FusedStep:
         self.chunk_tensor = torch.tensor(ct, dtype=torch.int32, device=self.device)
         self.chunk_off = torch.tensor(co, dtype=torch.int64, device=self.device)
         n = len(self.params)
-        # one upload per step: [n descriptors | 8 floats of hyper-parameters]; two pinned staging buffers alternate so that
-        # step t+1 can be prepared while step t's copy is still in flight
+        # one upload per step: [n descriptors | 8 floats of hyper-parameters] from a ring of pinned staging buffers, so that step t+1 can
+        # be prepared while step t's copy is still in flight.  The copy is asynchronous: a slot is rewritten only after the event recorded
+        # behind its last copy has completed (a caller that enqueues steps ahead of the GPU — nothing in Optimizer.step() waits for it —
+        # otherwise hands step t+2's lr / decay / bias corrections / gradient pointers to step t)
         self.table_bytes = n * _DESC.itemsize
-        self.host = [torch.empty(self.table_bytes + 32, dtype=torch.uint8).pin_memory() for _ in range(2)]
+        self.host = [torch.empty(self.table_bytes + 32, dtype=torch.uint8).pin_memory() for _ in range(8)]
+        self.host_ev = [None] * len(self.host)
         self.dev = torch.empty(self.table_bytes + 32, dtype=torch.uint8, device=self.device)
         # replayed steps: the per-step values (lr, decay per tensor + 8 hyper floats) reach the device through `dyn`, uploaded eagerly
         # from a ring of pinned buffers before each replay and patched into the table by a captured kernel (nnl_optim_patch)
@@ -88,6 +91,23 @@ class FusedStep:
         if self.kind == 0:
             return len({g['momentum'] for g in gs}) == 1
         return len({(tuple(g['betas']), g['eps']) for g in gs}) == 1
+
+    def unshare_steps(self):
+        """Before torch.optim.Adam itself steps on states created here (the param groups stopped sharing betas / eps): torch bumps the counter of
+        every parameter, so the ONE counter tensor fresh states share would advance once per parameter and step."""
+        if self.kind != 1:
+            return
+        seen = set()
+        for p in self.params:
+            st = self.opt.state[p]
+            t = st.get('step')
+            if t is not None:
+                if id(t) in seen:
+                    st['step'] = t.clone()
+                seen.add(id(t))
+        self._step_cache = None                             # _advance() walks the states again
+        if hasattr(self, '_shared_step'):
+            del self._shared_step
 
     def _advance(self):
         "bump the step counters; returns the hyper-parameter vector the kernel reads (include/nnl.h, nnl_optim_step)"
@@ -151,13 +171,21 @@ class FusedStep:
             h, self._capture_buf = self._capture_buf, None
             self.last_capture = (h, keep)
         else:
-            h = self.host[self.flip]
-            self.flip ^= 1
+            k = self.flip
+            self.flip = (k + 1) % len(self.host)
+            ev = self.host_ev[k]
+            if ev is not None:
+                ev.synchronize()
+            else:
+                ev = self.host_ev[k] = torch.cuda.Event()
+            h = self.host[k]
         hn = h.numpy()
         hn[:self.table_bytes] = desc.view(np.uint8)
         hyper_vec = self._advance_hyper(clip)
         hn[self.table_bytes:].view(np.float32)[:] = hyper_vec
         self.dev.copy_(h, non_blocking=True)
+        if not capturing:
+            ev.record()
         hyper = self.dev.data_ptr() + self.table_bytes
         if capturing:
             # the captured upload re-reads the pinned image at every replay: the host never rewrites it again; what changes per step
