@@ -138,11 +138,7 @@ __global__ __launch_bounds__(256) void slab_reduce_kernel(const float* __restric
   if (i >= n4) return;
   f32x4 acc = reinterpret_cast<const f32x4*>(part)[i];
   for (int sl = 1; sl < nslabs; ++sl) acc += reinterpret_cast<const f32x4*>(part)[(long)sl * slab_stride4 + i];
-  if (bias) acc += reinterpret_cast<const f32x4*>(bias)[i % Nc4];
-  if (add) acc += reinterpret_cast<const f32x4*>(add)[i];
-  if (relu == 1) { acc[0] = fmaxf(acc[0], 0.f); acc[1] = fmaxf(acc[1], 0.f); acc[2] = fmaxf(acc[2], 0.f); acc[3] = fmaxf(acc[3], 0.f); }
-  else if (relu == 2) { acc[0] = nnl_sigmoid(acc[0]); acc[1] = nnl_sigmoid(acc[1]); acc[2] = nnl_sigmoid(acc[2]); acc[3] = nnl_sigmoid(acc[3]); }
-  reinterpret_cast<f32x4*>(out)[i] = acc;
+  reinterpret_cast<f32x4*>(out)[i] = finish4<true>(acc, bias, (i % Nc4) * 4, add, i * 4, relu);      // as the in-kernel fix-up (split_tile.h)
 }
 
 int launch_balanced(IgemmTapsParams p, const SplitPlan& pl, float* ws, int* counters, hipStream_t s) {

@@ -18,6 +18,7 @@
 // last tile instead of changing shape).
 #pragma once
 #include "igemm.h"
+#include "split_tile.h"
 
 #define IGEMM_MAX_TAPS 49
 
@@ -88,21 +89,10 @@ struct IgemmTapsParams {
   signed char tap_dh[IGEMM_MAX_TAPS], tap_dw[IGEMM_MAX_TAPS];
 };
 
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-
-template <int POL>
-__device__ __forceinline__ f32x4 buf_load4_policy(__amdgpu_buffer_rsrc_t rsrc, unsigned voff) {
-  const i32x4 v = __builtin_bit_cast(i32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)voff, 0, POL));
-  return __builtin_bit_cast(f32x4, v);
-}
-#define buf_load4_pol(rsrc, voff, pol) buf_load4_policy<pol>(rsrc, voff)
-
 __device__ __forceinline__ f32x4 buf_load4(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, unsigned soff) {
   const i32x4 v = __builtin_bit_cast(i32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)voff, (int)soff, 0));
   return __builtin_bit_cast(f32x4, v);
 }
-
-__device__ __forceinline__ float nnl_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
 
 // DMA = true (64x64 tile, EPI 0): the operand tiles go global -> LDS directly (`buffer_load_dwordx4 ... lds`, LDS-DMA) instead
 // of through VGPRs and ds_write_b128.  An LDS-DMA wave-instruction writes 64 x 16 B lane-linear (wave-uniform base + lane*16),
@@ -157,22 +147,10 @@ __global__ __launch_bounds__(256, (BM * BN >= 128 * 128 || (PF == 2 && BK == 32)
   int logical, kslice = 0, nslices = 1, row0 = 0, cls = 0;
   bool in_tail = false;
   float* yout = p.y;
-  if (p.bal) {
-    const int nmb = p.n_main_tiles * p.main_ks;
-    if ((int)blockIdx.x < nmb) {
-      const int u = nnl_xcd_remap(blockIdx.x, nmb);
-      logical = u / p.main_ks;
-      kslice = u - logical * p.main_ks;
-      nslices = p.main_ks;
-      if (nslices > 1) yout = p.main_out + (long)kslice * p.main_slab_stride;
-    } else {
-      const int tb = (int)blockIdx.x - nmb;
-      const int t = tb / p.tail_slices;
-      kslice = tb - t * p.tail_slices;
-      logical = p.n_main_tiles + t;
-      nslices = p.tail_slices;
-      if (nslices > 1) { yout = p.tail_out + (long)kslice * p.tail_slab_stride; row0 = p.tail_row0; in_tail = true; }
-    }
+  if (p.bal) {                                 // main / tail tiles and their k slices: split_tile.h
+    const SplitTile t = split_tile_decode(p);
+    logical = t.logical; kslice = t.kslice; nslices = t.nslices; row0 = t.row0; in_tail = t.in_tail;
+    if (nslices > 1) yout = in_tail ? p.tail_out + (long)kslice * p.tail_slab_stride : p.main_out + (long)kslice * p.main_slab_stride;
   } else if (p.ncls > 1) {
     // classes run one after the other in launch order (longest first); the XCD remap is applied INSIDE a class, so every XCD
     // gets its share of each class (a remap of the whole grid would hand the long classes to XCDs 0-1 and the short to 6-7)
@@ -532,42 +510,24 @@ __global__ __launch_bounds__(256, (BM * BN >= 128 * 128 || (PF == 2 && BK == 32)
     // ---- fused LSTM cell ----------------------------------------------------------------------------------------------
     constexpr int LDT = 68;
     float* tl = &lds[0][0];                          // 64 x 68 floats: the k loop is over (it ended with a barrier)
-    __shared__ int ticket;
     const int Nlog = p.grid_n * 64;
     const int cl = wn * 32 + (lane & 31);
     if (nslices > 1) {
-      // Cross-workgroup hand-over WITHOUT cache-wide fences: a device-scope __threadfence() writes back and invalidates the
-      // whole L2 of the XCD (measured: 4x slower steps, W_hh loses its L2 residency).  Instead the slab is written with
-      // agent-scope (write-through) atomic stores, every wave drains its stores (vmcnt 0) before the workgroup takes its
-      // ticket, and the finishing workgroup reads the slabs with agent-scope loads that bypass its own L2.
+      // hand-over of the k slices without cache-wide fences (split_tile.h): sc1 stores of the slab, drain, ticket; the last arriver
+      // sums the slabs with sc1 loads.  The host zeroes these counters before the launch: no reset here.
       const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(p.y, 0, (int)((long)nslices * p.slab_stride * 4), 0x00020000);
-      constexpr int kSc1 = 1 << 4;                   // gfx940+ cache policy bit: device (agent) scope — write-through / L2 bypass
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
         const int rl = wm * 32 + (e & 3) + 8 * (e >> 2) + (lane >> 5) * 4;
         const long off = (long)kslice * p.slab_stride + (long)(m0 + rl) * Nlog + n0 + cl;
         __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(acc[0][0][e]), rs, (m0 + rl < p.M) ? (int)(off * 4) : -1, 0, kSc1);
       }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      if (tid == 0) ticket = __hip_atomic_fetch_add(&p.lstm.counters[logical], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __syncthreads();
-      if (ticket != nslices - 1) return;             // someone else finishes this tile
-      // sum the slices in slice order (deterministic whoever is last): 4 float4 per thread, all loads in flight together
+      if (!split_tile_handover<false>(&p.lstm.counters[logical], nslices, tid)) return;      // someone else finishes this tile
+      // sum the slices in slice order (deterministic whoever is last): 4 float4 per thread
       for (int k4 = 0; k4 < 4; ++k4) {
         const int idx4 = tid + k4 * 256, rl = idx4 >> 4, c4 = (idx4 & 15) * 4;
         f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (m0 + rl < p.M) {
-          for (int sl0 = 0; sl0 < nslices; sl0 += 8) {
-            f32x4 part[8];
-#pragma unroll
-            for (int sl = 0; sl < 8; ++sl)
-              if (sl0 + sl < nslices) part[sl] = buf_load4_pol(rs, (unsigned)(((long)(sl0 + sl) * p.slab_stride + (long)(m0 + rl) * Nlog + n0 + c4) * 4), kSc1);
-#pragma unroll
-            for (int sl = 0; sl < 8; ++sl)
-              if (sl0 + sl < nslices) v += part[sl];
-          }
-        }
+        if (m0 + rl < p.M) v = slab_sum4(rs, (long)(m0 + rl) * Nlog + n0 + c4, p.slab_stride, nslices);
         *reinterpret_cast<f32x4*>(tl + rl * LDT + c4) = v;
       }
     } else {
@@ -620,12 +580,10 @@ __global__ __launch_bounds__(256, (BM * BN >= 128 * 128 || (PF == 2 && BK == 32)
   const int col_l = lane & 31, row_h = (lane >> 5) * 4;
   const bool dense_out = (p.out_stride == 1) && (p.OH == p.P) && (p.OW == p.Q) && (oh0 == 0) && (ow0 == 0);
   if (EPI == 0 && BM == 64 && BN == 64 && p.bal && partial && p.tile_counters != nullptr) {
-    // ---- in-kernel fix-up of a split tile (same hand-over as the fused LSTM step: sc1 stores, drain, ticket, sc1 loads) ----
-    __shared__ int ticket;
+    // ---- in-kernel fix-up of a split tile (split_tile.h: sc1 stores, hand-over to the last arriver, slab sum, finish) ----
     float* const base = in_tail ? p.tail_out : p.main_out;
     const long sstride = in_tail ? p.tail_slab_stride : p.main_slab_stride;
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(base, 0, (int)((long)nslices * sstride * 4), 0x00020000);
-    constexpr int kSc1 = 1 << 4;
     const int cl = n0 + wn * 32 + col_l;
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
@@ -633,55 +591,17 @@ __global__ __launch_bounds__(256, (BM * BN >= 128 * 128 || (PF == 2 && BK == 32)
       const long off = (long)kslice * sstride + (long)(row - row0) * p.Nc + cl;
       __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(acc[0][0][e]), rs, (row < p.M && cl < p.Nc) ? (int)(off * 4) : -1, 0, kSc1);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) ticket = __hip_atomic_fetch_add(&p.tile_counters[logical], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    if (ticket != nslices - 1) return;
-    if (tid == 0) __hip_atomic_store(&p.tile_counters[logical], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // zero at rest
+    if (!split_tile_handover<true>(&p.tile_counters[logical], nslices, tid)) return;
     float fs1[4] = {0.f, 0.f, 0.f, 0.f}, fs2[4] = {0.f, 0.f, 0.f, 0.f};
     for (int k4 = 0; k4 < 4; ++k4) {
       const int idx4 = tid + k4 * 256, rl = idx4 >> 4, c4 = n0 + (idx4 & 15) * 4;
       const int row = m0 + rl;
       if (row >= p.M || c4 >= p.Nc) continue;
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      for (int sl0 = 0; sl0 < nslices; sl0 += 8) {     // eight slab loads in flight per trip, added in slice order (the loop that
-        f32x4 part[8];                                 // followed the first eight used to wait for every single load)
-#pragma unroll
-        for (int sl = 0; sl < 8; ++sl)
-          if (sl0 + sl < nslices) part[sl] = buf_load4_pol(rs, (unsigned)(((long)(sl0 + sl) * sstride + (long)(row - row0) * p.Nc + c4) * 4), kSc1);
-#pragma unroll
-        for (int sl = 0; sl < 8; ++sl)
-          if (sl0 + sl < nslices) v += part[sl];
-      }
+      const f32x4 v = slab_sum4(rs, (long)(row - row0) * p.Nc + c4, sstride, nslices);
       const long o = (long)row * p.Nc + c4;
-      if (p.bias) v += *reinterpret_cast<const f32x4*>(p.bias + c4);
-      if (p.add) v += *reinterpret_cast<const f32x4*>(p.add + o);
-      if (p.relu == 1) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
-      else if (p.relu == 2) { v[0] = nnl_sigmoid(v[0]); v[1] = nnl_sigmoid(v[1]); v[2] = nnl_sigmoid(v[2]); v[3] = nnl_sigmoid(v[3]); }
-      *reinterpret_cast<f32x4*>(p.y + o) = v;
-      if (p.bn_part) {
-        const f32x4 pv = *reinterpret_cast<const f32x4*>(p.bn_pivot + c4);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { const float d = v[e] - pv[e]; fs1[e] += d; fs2[e] += d * d; }
-      }
+      finish_piece<true>(p, v, c4, o, fs1, fs2);
     }
-    if (p.bn_part) {                              // thread t owns columns (t & 15)*4..+3 of rows t>>4, +16, +32, +48
-      __syncthreads();
-      float* red = &lds[0][0];                      // [16 row lanes][64 cols][2]
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        red[(((tid >> 4) * 64) + (tid & 15) * 4 + e) * 2 + 0] = fs1[e];
-        red[(((tid >> 4) * 64) + (tid & 15) * 4 + e) * 2 + 1] = fs2[e];
-      }
-      __syncthreads();
-      if (tid < 64 && n0 + tid < p.Nc) {
-        float a = 0.f, b = 0.f;
-        for (int r = 0; r < 16; ++r) { a += red[(r * 64 + tid) * 2]; b += red[(r * 64 + tid) * 2 + 1]; }
-        p.bn_part[((long)tile_m * p.Nc + n0 + tid) * 2 + 0] = a;
-        p.bn_part[((long)tile_m * p.Nc + n0 + tid) * 2 + 1] = b;
-      }
-    }
+    bn_partials_write(p, fs1, fs2, &lds[0][0], tid, tile_m, n0);
     return;
   }
   if constexpr (EPI == 0 && BM == 64 && BN == 64) {
@@ -703,33 +623,9 @@ __global__ __launch_bounds__(256, (BM * BN >= 128 * 128 || (PF == 2 && BK == 32)
         if (row >= p.M || c4 >= p.Nc) continue;
         f32x4 v = *reinterpret_cast<const f32x4*>(tl + rl * LDT + (idx4 & 15) * 4);
         const long o = (long)row * p.Nc + c4;
-        if (p.bias) v += *reinterpret_cast<const f32x4*>(p.bias + c4);
-        if (p.add) v += *reinterpret_cast<const f32x4*>(p.add + o);
-        if (p.relu == 1) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
-        else if (p.relu == 2) { v[0] = nnl_sigmoid(v[0]); v[1] = nnl_sigmoid(v[1]); v[2] = nnl_sigmoid(v[2]); v[3] = nnl_sigmoid(v[3]); }
-        *reinterpret_cast<f32x4*>(p.y + o) = v;
-        if (p.bn_part) {
-          const f32x4 pv = *reinterpret_cast<const f32x4*>(p.bn_pivot + c4);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) { const float d = v[e] - pv[e]; fs1[e] += d; fs2[e] += d * d; }
-        }
+        finish_piece<true>(p, v, c4, o, fs1, fs2);
       }
-      if (p.bn_part) {                              // thread t owns columns (t & 15)*4..+3 of rows t>>4, +16, +32, +48
-        __syncthreads();
-        float* red = &lds[0][0];                      // [16 row lanes][64 cols][2]
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          red[(((tid >> 4) * 64) + (tid & 15) * 4 + e) * 2 + 0] = fs1[e];
-          red[(((tid >> 4) * 64) + (tid & 15) * 4 + e) * 2 + 1] = fs2[e];
-        }
-        __syncthreads();
-        if (tid < 64 && n0 + tid < p.Nc) {
-          float a = 0.f, b = 0.f;
-          for (int r = 0; r < 16; ++r) { a += red[(r * 64 + tid) * 2]; b += red[(r * 64 + tid) * 2 + 1]; }
-          p.bn_part[((long)tile_m * p.Nc + n0 + tid) * 2 + 0] = a;
-          p.bn_part[((long)tile_m * p.Nc + n0 + tid) * 2 + 1] = b;
-        }
-      }
+      bn_partials_write(p, fs1, fs2, &lds[0][0], tid, tile_m, n0);
       return;
     }
   }

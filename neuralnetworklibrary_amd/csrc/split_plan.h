@@ -1,5 +1,6 @@
 // The split schedule of the three 64x64-tile conv kernels (igemm_taps_kernel, wino_kernel, wino2_kernel), host side: the plan, its
-// geometry, the cost model and search the direct and 1-D Winograd kernels share, and the binding of a plan to a launch.
+// geometry, the cost model and search the direct and 1-D Winograd kernels share, and the binding of a plan to a launch.  The device side
+// (a workgroup's tile and slice, the hand-over to the last arriver, the slab sum and the finish of the output) is split_tile.h.
 //
 // T = grid_m x grid_n tiles of 64 schedule rows (output pixels, pairs or quads) x 64 channels.  The first n_main_tiles ("main": whole
 // multiples of 256 workgroups, whole tile rows) are cut into main_ks k slices, the leftover tail tiles into tail_slices; a slice writes

@@ -84,26 +84,9 @@ __global__ __launch_bounds__(256, 4) void wino_kernel(const WinoParams p) {
   constexpr int BM = 64, BN = 64, BKP = BK + 4, KC = BK / 4, RPP = 256 / KC, PA = BM / RPP, PB = BN / RPP;
   __shared__ __attribute__((aligned(16))) float lds[2][(BM + BN) * BKP];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
-  int logical, kslice = 0, nslices = 1, row0 = 0;
-  bool in_tail = false;
-  if (p.bal) {
-    const int nmb = p.n_main_tiles * p.main_ks;
-    if ((int)blockIdx.x < nmb) {
-      const int u = nnl_xcd_remap(blockIdx.x, nmb);
-      logical = u / p.main_ks;
-      kslice = u - logical * p.main_ks;
-      nslices = p.main_ks;
-    } else {
-      const int tb = (int)blockIdx.x - nmb;
-      const int t = tb / p.tail_slices;
-      kslice = tb - t * p.tail_slices;
-      logical = p.n_main_tiles + t;
-      nslices = p.tail_slices;
-      if (nslices > 1) { row0 = p.tail_row0; in_tail = true; }
-    }
-  } else {
-    logical = nnl_xcd_remap(blockIdx.x, gridDim.x);
-  }
+  const SplitTile st = split_tile_decode(p);         // this workgroup's tile and k slice (split_tile.h)
+  const int logical = st.logical, kslice = st.kslice, nslices = st.nslices, row0 = st.row0;
+  const bool in_tail = st.in_tail;
   const bool partial = nslices > 1;
   const int tile_m = logical / p.grid_n, tile_n = logical - tile_m * p.grid_n;
   const int m0 = tile_m * BM, n0 = tile_n * BN;
@@ -244,12 +227,10 @@ __global__ __launch_bounds__(256, 4) void wino_kernel(const WinoParams p) {
   // ---- epilogue: pair row -> pixels (line * W + 2j) and, when 2j + 1 < W, the next one ----
   const int col_l = lane & 31, row_h = (lane >> 5) * 4;
   if (partial) {
-    // split tile: sc1 stores of the partial pair sums, drain, ticket; the last slice sums the slabs in slice order and finishes
-    __shared__ int ticket;
+    // split tile (split_tile.h): sc1 stores of the partial pair sums, hand-over; the last slice sums the slabs in slice order and finishes
     float* const base = in_tail ? p.tail_out : p.main_out;
     const long sstride = in_tail ? p.tail_slab_stride : p.main_slab_stride;
     const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(base, 0, (int)((long)nslices * sstride * 4), 0x00020000);
-    constexpr int kSc1 = 1 << 4;
     const int cl = n0 + wn * 32 + col_l;
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
@@ -259,12 +240,7 @@ __global__ __launch_bounds__(256, 4) void wino_kernel(const WinoParams p) {
       __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(y0[e]), rs, ok ? (int)(off * 4) : -1, 0, kSc1);
       __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(y1[e]), rs, ok ? (int)((off + p.Nc) * 4) : -1, 0, kSc1);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) ticket = __hip_atomic_fetch_add(&p.tile_counters[logical], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __syncthreads();
-    if (ticket != nslices - 1) return;
-    if (tid == 0) __hip_atomic_store(&p.tile_counters[logical], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // zero at rest
+    if (!split_tile_handover<true>(&p.tile_counters[logical], nslices, tid)) return;
     float fs1[4] = {0.f, 0.f, 0.f, 0.f}, fs2[4] = {0.f, 0.f, 0.f, 0.f};
     for (int k8 = 0; k8 < 8; ++k8) {                 // 128 slab rows x 16 float4 columns = 8 float4 per thread
       const int idx4 = tid + k8 * 256, srow = idx4 >> 4, c4 = n0 + (idx4 & 15) * 4;
@@ -272,43 +248,11 @@ __global__ __launch_bounds__(256, 4) void wino_kernel(const WinoParams p) {
       if (row >= p.M2 || c4 >= p.Nc) continue;
       const int line = row / p.W2, j = row - line * p.W2;
       if (2 * j + h >= p.W) continue;                // the missing second output of an odd line
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      for (int sl0 = 0; sl0 < nslices; sl0 += 8) {
-        f32x4 part[8];
-#pragma unroll
-        for (int sl = 0; sl < 8; ++sl)
-          if (sl0 + sl < nslices) part[sl] = buf_load4_pol(rs, (unsigned)(((long)(sl0 + sl) * sstride + ((long)(row - row0) * 2 + h) * p.Nc + c4) * 4), kSc1);
-#pragma unroll
-        for (int sl = 0; sl < 8; ++sl)
-          if (sl0 + sl < nslices) v += part[sl];
-      }
+      const f32x4 v = slab_sum4(rs, ((long)(row - row0) * 2 + h) * p.Nc + c4, sstride, nslices);
       const long o = ((long)line * p.W + 2 * j + h) * p.Nc + c4;
-      if (p.bias) v += *reinterpret_cast<const f32x4*>(p.bias + c4);
-      if (p.add) v += *reinterpret_cast<const f32x4*>(p.add + o);
-      if (p.relu == 1) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
-      *reinterpret_cast<f32x4*>(p.y + o) = v;
-      if (p.bn_part) {
-        const f32x4 pv = *reinterpret_cast<const f32x4*>(p.bn_pivot + c4);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) { const float d = v[e] - pv[e]; fs1[e] += d; fs2[e] += d * d; }
-      }
+      finish_piece<false>(p, v, c4, o, fs1, fs2);
     }
-    if (p.bn_part) {                                 // thread t owns columns (t & 15)*4..+3 of slab rows t>>4, +16, ...
-      __syncthreads();
-      float* red = &lds[0][0];                       // [16 row lanes][64 cols][2]
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        red[(((tid >> 4) * 64) + (tid & 15) * 4 + e) * 2 + 0] = fs1[e];
-        red[(((tid >> 4) * 64) + (tid & 15) * 4 + e) * 2 + 1] = fs2[e];
-      }
-      __syncthreads();
-      if (tid < 64 && n0 + tid < p.Nc) {
-        float a = 0.f, b = 0.f;
-        for (int r = 0; r < 16; ++r) { a += red[(r * 64 + tid) * 2]; b += red[(r * 64 + tid) * 2 + 1]; }
-        p.bn_part[((long)tile_m * p.Nc + n0 + tid) * 2 + 0] = a;
-        p.bn_part[((long)tile_m * p.Nc + n0 + tid) * 2 + 1] = b;
-      }
-    }
+    bn_partials_write(p, fs1, fs2, &lds[0][0], tid, tile_m, n0);
     return;
   }
   if (p.Nc % 4 == 0) {
@@ -333,33 +277,10 @@ __global__ __launch_bounds__(256, 4) void wino_kernel(const WinoParams p) {
         if (2 * j + h >= p.W) continue;                    // the missing second output of an odd line
         f32x4 v = *reinterpret_cast<const f32x4*>(tl + rl * LDT + (idx4 & 15) * 4);
         const long o = ((long)line * p.W + 2 * j + h) * p.Nc + c4;
-        if (p.bias) v += *reinterpret_cast<const f32x4*>(p.bias + c4);
-        if (p.add) v += *reinterpret_cast<const f32x4*>(p.add + o);
-        if (p.relu == 1) { v[0] = fmaxf(v[0], 0.f); v[1] = fmaxf(v[1], 0.f); v[2] = fmaxf(v[2], 0.f); v[3] = fmaxf(v[3], 0.f); }
-        *reinterpret_cast<f32x4*>(p.y + o) = v;
-        if (p.bn_part) {
-          const f32x4 pv = *reinterpret_cast<const f32x4*>(p.bn_pivot + c4);
-#pragma unroll
-          for (int e = 0; e < 4; ++e) { const float d = v[e] - pv[e]; fs1[e] += d; fs2[e] += d * d; }
-        }
+        finish_piece<false>(p, v, c4, o, fs1, fs2);
       }
     }
-    if (p.bn_part) {                                       // thread t owns columns (t & 15)*4..+3 of rows t>>4, +16, +32, +48 (both halves)
-      __syncthreads();
-      float* red = &lds[0][0];                             // [16 row lanes][64 cols][2]
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        red[(((tid >> 4) * 64) + (tid & 15) * 4 + e) * 2 + 0] = fs1[e];
-        red[(((tid >> 4) * 64) + (tid & 15) * 4 + e) * 2 + 1] = fs2[e];
-      }
-      __syncthreads();
-      if (tid < 64 && n0 + tid < p.Nc) {
-        float a = 0.f, b = 0.f;
-        for (int r = 0; r < 16; ++r) { a += red[(r * 64 + tid) * 2]; b += red[(r * 64 + tid) * 2 + 1]; }
-        p.bn_part[((long)tile_m * p.Nc + n0 + tid) * 2 + 0] = a;
-        p.bn_part[((long)tile_m * p.Nc + n0 + tid) * 2 + 1] = b;
-      }
-    }
+    bn_partials_write(p, fs1, fs2, &lds[0][0], tid, tile_m, n0);
     return;
   }
   const int col = n0 + wn * 32 + col_l;
