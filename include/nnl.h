@@ -561,20 +561,28 @@ int nnl_scaled_sigmoid_bwd(const float* dy, const float* sig, float* dx, int64_t
 /* ---- K5b: embedding with per-vocabulary-row dropout mask, fused softmax + cross-entropy -----------------------
  * nnl_embedding_rowmask_*: EmbeddingDropout.forward, F.embedding(x, W * mask[V,1], pad) (Text.py:465-475):
  * out[i,:] = W[x[i],:] * rowmask[x[i]] (rowmask NULL = ones); backward zero-fills dW [V,D] and scatter-adds
- * dout[i,:]*rowmask[x[i]] except for x[i] == padding_idx (pass -1 for none). */
+ * dout[i,:]*rowmask[x[i]] except for x[i] == padding_idx (pass -1 for none).  The backward adds the samples of a row in a fixed order
+ * (route note emb_rowmask_bwd<det>) when it has its workspace, n <= 32768 and NNL_SCATTER_ATOMIC is not 1; else with fp32 atomics
+ * (emb_rowmask_bwd<atomic>), which is not bitwise reproducible. */
 int nnl_embedding_rowmask_fwd(const int64_t* x, const float* W, const float* rowmask, float* out, int64_t n,
                               int64_t V, int64_t D, int32_t* err_flag, void* stream);
 size_t nnl_embedding_rowmask_bwd_workspace_bytes(int64_t n);               /* deterministic scatter: see nnl_embdotbias_bwd */
 int nnl_embedding_rowmask_bwd(const int64_t* x, const float* rowmask, const float* dout, float* dW, int64_t n,
                               int64_t V, int64_t D, int64_t padding_idx, void* workspace, size_t workspace_bytes, void* stream);
 /* F.cross_entropy(logits [rows,V], target [rows], reduction='mean') (Text.py:773; also nn.CrossEntropyLoss of
- * General/Learner.py:20): lse[r] = logsumexp, loss_rows[r] = lse[r] - logits[r,target[r]], *loss_mean = mean.
- * Backward: dlogits = (softmax - onehot) * (*grad_out) / rows. */
-int nnl_softmax_ce_fwd(const float* logits, const int64_t* target, float* lse, float* loss_rows, float* loss_mean,
+ * General/Learner.py:20).  row_stats [rows][2] (8-byte aligned) = {m, log s} per row, m = max_v logits[r,v] and s = sum_v exp(logits[r,v] - m): the two
+ * halves of logsumexp are stored apart from forward to backward.  For |m| > 16 they are never added: loss_rows[r] = log s -
+ * (logits[r,target[r]] - m), so that no rounding is relative to |m| (softmax is shift-invariant, and so are the results up to rounding).
+ * For |m| <= 16 the kernels form lse = m + log s, loss_rows[r] = lse - logits[r,target[r]] and p = exp(logits - lse), bit for bit what
+ * they formed while they stored lse alone; that sum rounds by at most (16 + log s) 2^-24.  *loss_mean = mean over all rows.
+ * A -inf logit (a masked class) has probability and gradient exactly 0; a row of nothing but -inf, or one holding NaN or +inf, gives
+ * NaN as F.cross_entropy does.  A target outside [0, V): loss_rows[r] = 0 and *err_flag = 1 (err_flag may be NULL).
+ * Backward: dlogits = (p - onehot) * (*grad_out) / rows, p = exp((logits - m) - log s) (|m| <= 16: exp(logits - lse)). */
+int nnl_softmax_ce_fwd(const float* logits, const int64_t* target, float* row_stats, float* loss_rows, float* loss_mean,
                        int64_t rows, int64_t V, int32_t* err_flag, void* stream);
 /* ld_dlogits >= V: row stride of dlogits; columns [V, ld_dlogits) are written as zeros (a gradient buffer whose rows are already
  * padded to the GEMM granularity saves the consumer an 848 MB pad copy at V = 47 343). */
-int nnl_softmax_ce_bwd(const float* logits, const int64_t* target, const float* lse, const float* grad_out,
+int nnl_softmax_ce_bwd(const float* logits, const int64_t* target, const float* row_stats, const float* grad_out,
                        float* dlogits, int64_t rows, int64_t V, int64_t ld_dlogits, void* stream);
 /* AR / TAR regularisers of RegSeqCrossEntropyLoss (Text.py:765-777) on h = enc_out [T, R] (R = bs * emb_dim, contiguous):
  * out3[0] = alpha * mean(h^2) + beta * mean((h[1:] - h[:-1])^2), out3[1] = mean(h^2), out3[2] = the second mean; fixed-order

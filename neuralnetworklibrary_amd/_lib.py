@@ -120,7 +120,7 @@ SIGNATURES = {
     'nnl_embedding_rowmask_fwd': (C.c_int, [c_p, c_p, c_p, c_p, i64, i64, i64, c_p, c_p]),
     'nnl_embedding_rowmask_bwd_workspace_bytes': (sz, [i64]),
     'nnl_embedding_rowmask_bwd': (C.c_int, [c_p, c_p, c_p, c_p, i64, i64, i64, i64, c_p, sz, c_p]),
-    'nnl_softmax_ce_fwd': (C.c_int, [c_p, c_p, c_p, c_p, c_p, i64, i64, c_p, c_p]),
+    'nnl_softmax_ce_fwd': (C.c_int, [c_p, c_p, c_p, c_p, c_p, i64, i64, c_p, c_p]),      # third pointer: row_stats [rows][2] = {max, log s}
     'nnl_softmax_ce_bwd': (C.c_int, [c_p, c_p, c_p, c_p, c_p, i64, i64, i64, c_p]),
     'nnl_mse_workspace_bytes': (sz, [i64]),
     'nnl_mse_fwd': (C.c_int, [c_p, c_p, c_p, i64, c_p, sz, c_p]),

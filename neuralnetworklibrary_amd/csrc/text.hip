@@ -2,7 +2,7 @@
 //  * embedding gather with a per-vocabulary-row dropout mask (EmbeddingDropout.forward :465-475:
 //    F.embedding(x, W * mask[V,1], pad)) and its dense scatter-add backward (padding row gets no gradient);
 //  * fused softmax + cross-entropy over the vocabulary (F.cross_entropy inside RegSeqCrossEntropyLoss :773):
-//    one online-softmax pass per row forward (max and sum-exp together), one pass backward.
+//    one online-softmax pass per row forward (max and sum-exp together, kept apart as {max, log s} per row), one pass backward.
 // Both are HBM-bound: CE reads 4*V B per token forward and reads+writes 8*V B backward (V = 47 343: 848 MB of
 // logits per 4 480-token step).
 #include "scatter_det.h"
@@ -53,10 +53,20 @@ __device__ __forceinline__ MS ms_merge(MS a, MS b) {
   return r;
 }
 
-// one block per row: lse[r] = log sum exp(logits[r,:]); loss[r] = lse[r] - logits[r, target[r]]
+// one block per row: stats[r] = {m, log s}, m = max(logits[r,:]), s = sum exp(logits[r,:] - m).  m and log s are STORED apart and
+// joined only where that costs nothing: for |m| <= kLseJoin the loss is (m + log s) - x_t and the backward forms exp(x - (m + log s)),
+// the expressions (and so the bits) of the kernels that stored lse = m + log s in one float; the rounding of m + log s is then at most
+// (kLseJoin + log s) 2^-24.  Beyond it — logits that carry a large common offset — loss = log s - (x_t - m) and p = exp((x - m) - log s):
+// every rounding is relative to log s or to x - m, never to |m|, as softmax's shift invariance wants.
+// A lane whose running maximum is still -inf (masked columns) shifts by 0 instead of by -inf, so that exp(-inf - shift) is 0 and not
+// exp(NaN); a row of nothing but -inf ends with s = 0 and a NaN loss, as F.cross_entropy's.
+constexpr float kLseJoin = 16.f;
+__device__ __forceinline__ float ms_shift(float m) { return m == -INFINITY ? 0.f : m; }
+__device__ __forceinline__ bool lse_joined(float m) { return fabsf(m) <= kLseJoin; }        // false for NaN and +-inf
+
 __global__ __launch_bounds__(kBlock) void softmax_ce_fwd_kernel(const float* __restrict__ logits,
                                                                  const int64_t* __restrict__ target,
-                                                                 float* __restrict__ lse, float* __restrict__ loss, int V,
+                                                                 float2* __restrict__ stats, float* __restrict__ loss, int V,
                                                                  int32_t* __restrict__ err_flag) {
   __shared__ float sm[4], ss[4];
   const long r = blockIdx.x;
@@ -66,13 +76,15 @@ __global__ __launch_bounds__(kBlock) void softmax_ce_fwd_kernel(const float* __r
   for (; v + 3 * kBlock < V; v += 4 * kBlock) {          // 4 independent loads in flight per lane
     const float a = row[v], b = row[v + kBlock], c = row[v + 2 * kBlock], d = row[v + 3 * kBlock];
     const float m = fmaxf(fmaxf(fmaxf(a, b), fmaxf(c, d)), acc.m);
-    acc.s = acc.s * expf(acc.m - m) + ((expf(a - m) + expf(b - m)) + (expf(c - m) + expf(d - m)));
+    const float z = ms_shift(m);
+    acc.s = acc.s * expf(acc.m - z) + ((expf(a - z) + expf(b - z)) + (expf(c - z) + expf(d - z)));
     acc.m = m;
   }
   for (; v < V; v += kBlock) {
     const float a = row[v];
     const float m = fmaxf(a, acc.m);
-    acc.s = acc.s * expf(acc.m - m) + expf(a - m);
+    const float z = ms_shift(m);
+    acc.s = acc.s * expf(acc.m - z) + expf(a - z);
     acc.m = m;
   }
 #pragma unroll
@@ -86,10 +98,10 @@ __global__ __launch_bounds__(kBlock) void softmax_ce_fwd_kernel(const float* __r
   if (threadIdx.x == 0) {
     MS t = {sm[0], ss[0]};
     for (int w = 1; w < 4; ++w) t = ms_merge(t, MS{sm[w], ss[w]});
-    const float l = t.m + logf(t.s);
-    lse[r] = l;
+    const float ls = logf(t.s);
+    stats[r] = make_float2(t.m, ls);
     const int64_t tg = target[r];
-    if (tg >= 0 && tg < V) loss[r] = l - row[tg];
+    if (tg >= 0 && tg < V) loss[r] = lse_joined(t.m) ? (t.m + ls) - row[tg] : ls - (row[tg] - t.m);
     else { loss[r] = 0.f; if (err_flag) *err_flag = 1; }
   }
 }
@@ -108,19 +120,22 @@ __global__ void mean_kernel(const float* __restrict__ v, float* __restrict__ out
   if (threadIdx.x == 0) out[0] = red[0] / (float)n;
 }
 
-// dlogits[r,v] = (exp(logits[r,v] - lse[r]) - [v == target[r]]) * gup / rows
+// dlogits[r,v] = (p - [v == target[r]]) * gup / rows, p = exp((logits[r,v] - m[r]) - log s[r]), or exp(logits[r,v] - (m[r] + log s[r])) for
+// |m[r]| <= kLseJoin (see the forward)
 __global__ __launch_bounds__(kBlock) void softmax_ce_bwd_kernel(const float* __restrict__ logits,
                                                                  const int64_t* __restrict__ target,
-                                                                 const float* __restrict__ lse, const float* __restrict__ gup,
+                                                                 const float2* __restrict__ stats, const float* __restrict__ gup,
                                                                  float* __restrict__ dlogits, int V, long rows, long ld) {
   const long r = blockIdx.x;
   const float* __restrict__ row = logits + r * V;
   float* __restrict__ drow = dlogits + r * ld;
-  const float l = lse[r];
+  const float2 st = stats[r];
+  const bool joined = lse_joined(st.x);
+  const float l = st.x + st.y;
   const float g = gup[0] / (float)rows;
   const int64_t tg = target[r];
   for (int v = threadIdx.x; v < V; v += kBlock) {
-    float p = expf(row[v] - l);
+    float p = expf(joined ? row[v] - l : (row[v] - st.x) - st.y);
     if (v == tg) p -= 1.f;
     drow[v] = p * g;
   }
@@ -162,6 +177,7 @@ extern "C" int nnl_embedding_rowmask_bwd(const int64_t* x, const float* rowmask,
   NNL_CHECK_ARG(x && dout, "embedding_rowmask_bwd: null pointer");
   NnlProfScope prof(NNL_PROF_ELEMENTWISE, s, (double)n * (8 + 8.0 * D) + 4.0 * V * D);
   if (nnl_det::use_det(n, workspace) && workspace_bytes >= nnl_embedding_rowmask_bwd_workspace_bytes(n)) {
+    NNL_ROUTE("emb_rowmask_bwd<det>");
     int* order = (int*)workspace;                 // deterministic: the tokens of a vocabulary row are added in token order
     int st = nnl_det::sort_rows(x, 1, n, 1, order, s);
     if (st) return st;
@@ -170,32 +186,33 @@ extern "C" int nnl_embedding_rowmask_bwd(const int64_t* x, const float* rowmask,
     q.scale_row = rowmask; q.skip_row = padding_idx;
     return nnl_det::segsum(q, 1, s);
   }
+  NNL_ROUTE("emb_rowmask_bwd<atomic>");      // no or short workspace, n > kMaxSamples, or NNL_SCATTER_ATOMIC=1
   hipLaunchKernelGGL(emb_rowmask_bwd_kernel, dim3(grid_for(n * D)), dim3(kBlock), 0, s, x, rowmask, dout, dW, (long)n, (int)V, (int)D,
                      (long)padding_idx);
   NNL_CHECK_LAUNCH();
   return NNL_OK;
 }
 
-extern "C" int nnl_softmax_ce_fwd(const float* logits, const int64_t* target, float* lse, float* loss_rows, float* loss_mean,
+extern "C" int nnl_softmax_ce_fwd(const float* logits, const int64_t* target, float* row_stats, float* loss_rows, float* loss_mean,
                                   int64_t rows, int64_t V, int32_t* err_flag, void* stream) {
   NNL_CHECK_ARG(rows > 0 && V > 0 && V < (1L << 31) && rows < (1L << 31), "softmax_ce_fwd: bad sizes");
-  NNL_CHECK_ARG(logits && target && lse && loss_rows && loss_mean, "softmax_ce_fwd: null pointer");
+  NNL_CHECK_ARG(logits && target && row_stats && loss_rows && loss_mean, "softmax_ce_fwd: null pointer");
   hipStream_t s = (hipStream_t)stream;
   NnlProfScope prof(NNL_PROF_SOFTMAX_CE, s, 4.0 * rows * V);
-  hipLaunchKernelGGL(softmax_ce_fwd_kernel, dim3((unsigned)rows), dim3(kBlock), 0, s, logits, target, lse, loss_rows, (int)V, err_flag);
+  hipLaunchKernelGGL(softmax_ce_fwd_kernel, dim3((unsigned)rows), dim3(kBlock), 0, s, logits, target, (float2*)row_stats, loss_rows, (int)V, err_flag);
   NNL_CHECK_LAUNCH();
   hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(kBlock), 0, s, (const float*)loss_rows, loss_mean, (long)rows);
   NNL_CHECK_LAUNCH();
   return NNL_OK;
 }
 
-extern "C" int nnl_softmax_ce_bwd(const float* logits, const int64_t* target, const float* lse, const float* grad_out,
+extern "C" int nnl_softmax_ce_bwd(const float* logits, const int64_t* target, const float* row_stats, const float* grad_out,
                                   float* dlogits, int64_t rows, int64_t V, int64_t ld_dlogits, void* stream) {
   NNL_CHECK_ARG(rows > 0 && V > 0 && V < (1L << 31) && rows < (1L << 31) && ld_dlogits >= V, "softmax_ce_bwd: bad sizes");
-  NNL_CHECK_ARG(logits && target && lse && grad_out && dlogits, "softmax_ce_bwd: null pointer");
+  NNL_CHECK_ARG(logits && target && row_stats && grad_out && dlogits, "softmax_ce_bwd: null pointer");
   hipStream_t s = (hipStream_t)stream;
   NnlProfScope prof(NNL_PROF_SOFTMAX_CE, s, 8.0 * rows * V);
-  hipLaunchKernelGGL(softmax_ce_bwd_kernel, dim3((unsigned)rows), dim3(kBlock), 0, s, logits, target, lse, grad_out, dlogits, (int)V,
+  hipLaunchKernelGGL(softmax_ce_bwd_kernel, dim3((unsigned)rows), dim3(kBlock), 0, s, logits, target, (const float2*)row_stats, grad_out, dlogits, (int)V,
                      (long)rows, (long)ld_dlogits);
   NNL_CHECK_LAUNCH();
   return NNL_OK;

@@ -161,17 +161,17 @@ class _SoftmaxCE(torch.autograd.Function):
         target = target.contiguous().long()
         rows, V = logits.shape
         dev = logits.device
-        lse = torch.empty(rows, dtype=torch.float32, device=dev)
+        stats = torch.empty(rows, 2, dtype=torch.float32, device=dev)      # {max, log sum exp(x - max)} per row, kept apart
         loss_rows = torch.empty(rows, dtype=torch.float32, device=dev)
         loss = torch.empty((), dtype=torch.float32, device=dev)
-        check(lib.nnl_softmax_ce_fwd(ptr(logits), ptr(target), ptr(lse), ptr(loss_rows), ptr(loss), rows, V,
+        check(lib.nnl_softmax_ce_fwd(ptr(logits), ptr(target), ptr(stats), ptr(loss_rows), ptr(loss), rows, V,
                                      ptr(index_error_flag(dev)), stream()))
-        ctx.save_for_backward(logits, target, lse)
+        ctx.save_for_backward(logits, target, stats)
         return loss
 
     @staticmethod
     def backward(ctx, dloss):
-        logits, target, lse = ctx.saved_tensors
+        logits, target, stats = ctx.saved_tensors
         from .ops import register_padded_grad
         g = _f32c(dloss).view(1)
         rows, V = logits.shape
@@ -179,7 +179,7 @@ class _SoftmaxCE(torch.autograd.Function):
         # rows padded to the GEMM granularity (zeros in the pad columns): the producing linear layer's backward uses the buffer as
         # is instead of re-padding it (V = 47 343: an 848 MB fill + copy per step)
         buf = torch.empty(rows, Vp, dtype=torch.float32, device=logits.device)
-        check(lib.nnl_softmax_ce_bwd(ptr(logits), ptr(target), ptr(lse), ptr(g), ptr(buf), rows, V, Vp, stream()))
+        check(lib.nnl_softmax_ce_bwd(ptr(logits), ptr(target), ptr(stats), ptr(g), ptr(buf), rows, V, Vp, stream()))
         if Vp == V:
             return buf, None
         register_padded_grad(buf, Vp)
