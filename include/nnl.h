@@ -200,7 +200,13 @@ int nnl_debug_conv_plan_times(int N, int H, int W, int C, int K, double* out);
  *   nnl_debug_route_collect(out, n): copies the notes recorded since ("name;name;...", NUL-terminated) into out[n] and clears the buffer;
  *     returns the number of notes, or NNL_ERR_INVALID_ARG when out is NULL or too small (the buffer is kept then).
  * A name is `kernel<template arguments>:plan flags` and maps to one launch in conv2d.hip / wino.hip / wino2.hip (lstm_*: to one call
- * of nnl_lstm_fwd / nnl_lstm_bwd, see nnl_debug_lstm_plan); text after an `@` is a numeric detail of the plan (slice counts).  Recording changes no launch; when it is off a note costs one branch. */
+ * of nnl_lstm_fwd / nnl_lstm_bwd, see nnl_debug_lstm_plan); text after an `@` is a numeric detail of the plan (slice counts).  Recording changes no launch; when it is off a note costs one branch.
+ * The tabular / collab / small-linear calls leave ONE note per successful call that launched something (none for an error return or an
+ * early return at bs / n / M = 0):
+ *   tab_renorm, tab_gather, tab_scatter_bwd<det>, tab_scatter_bwd<atomic>, tab_scan_bwd@blocks=<n_scan_blocks>+<blocks of the continuous part>;
+ *   embdot_fwd, embdot_bwd<scan>, embdot_bwd<det>:one_block | :four_fills, embdot_bwd<atomic>:one_block | :four_fills (one_block: the
+ *   four gradients are adjacent, [dU | dM | dbu | dbi], and were zero-filled by one memset; four_fills: four memsets);
+ *   linear_small_fwd, linear_small_bwd:<the outputs asked for, of dx dw db, run together>@slabs=<64-row slabs of the dw / db reduction, 0 without one>. */
 int nnl_debug_route_record(int enable);
 int nnl_debug_route_collect(char* out, size_t n);
 /* dw[K,R,S,C] = sum_{n,p,q} dy[n,p,q,k] * x[n,p*stride-pad+r,q*stride-pad+s,c]; split-K partial slabs are
@@ -418,7 +424,11 @@ int nnl_tta_bbox_merge(const float* boxes, const int32_t* classes, const float* 
  * tables[j] (pointer to W_j [card[j], dim[j]]), card, dim, col_off (first output column of column j);
  * col_table[c] = column owning output column c (c < cat_width = sum dim); row_off[j] = first global row id of
  * table j, row_table[r] = table owning global row r (r < total_rows = sum card); flags: int32[total_rows], zero
- * on entry and on exit. */
+ * on entry and on exit.
+ * Indices outside [0, card[j]) — negative, card[j] and above, and 64-bit values whose low 32 bits would be in range — are SKIPPED by
+ * every call below: zero output columns in the forward, no gradient from that sample to column j in all three backward routes.  Only
+ * nnl_tab_renorm reports them (*err_flag = 1); nnl_tab_gather_fwd and the backward calls take no flag and stay silent, so a caller that
+ * does not renorm (max_norm = None) and cannot vouch for its indices has to check them itself. */
 /* In-place max_norm renormalisation of every row looked up by xcat [bs, ncat] (each distinct row exactly once):
  * rows with L2 norm > max_norm are scaled by max_norm/(norm+1e-7)  (torch embedding_renorm_). */
 int nnl_tab_renorm(const int64_t* xcat, float* const* tables, const int32_t* card, const int32_t* dim,
@@ -456,7 +466,8 @@ int nnl_keep_masks(const float* u, float* a, int64_t na, float keep_a, float* b,
 
 /* nn.Linear with 1 - 4 output features (the last layer of FullyConnectedNet, General/Layers.py:146 — the tabular regression head):
  * y [M,N] = x [M,K] (row stride ldx) w[N,K]^T + bias.  Backward: dx [M,K] dense, dw [N,K], db [N] (any may be NULL), fixed-order
- * sums (csrc/linear_small.hip). */
+ * sums (csrc/linear_small.hip); M = 0 zero-fills dw and db.  A workspace that is NULL or smaller than
+ * nnl_linear_small_bwd_workspace_bytes (needed for dw or db) is NNL_ERR_WORKSPACE, and no output is written. */
 int nnl_linear_small_supported(int64_t N);
 int nnl_linear_small_fwd(const float* x, const float* w, const float* bias, float* y, int64_t M, int64_t K, int64_t ldx, int64_t N,
                          void* stream);

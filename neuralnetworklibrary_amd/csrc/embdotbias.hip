@@ -173,6 +173,7 @@ extern "C" int nnl_embdotbias_fwd(const int64_t* x, const float* U, const float*
   hipLaunchKernelGGL(embdotbias_fwd_kernel, dim3(grid_for(n)), dim3(kBlock), 0, s, x, U, M, bu, bi, y, z,
                      n, n_user, n_item, (int)D, has_range, lo, hi, err_flag);
   NNL_CHECK_LAUNCH();
+  NNL_ROUTE("embdot_fwd");
   return NNL_OK;
 }
 
@@ -199,6 +200,7 @@ extern "C" int nnl_embdotbias_bwd(const int64_t* x, const float* U, const float*
     hipLaunchKernelGGL(embdot_scan_bwd_kernel, dim3((unsigned)nnl_cdiv(total, 256)), dim3(256), 0, s, x, U, M, z, dy, dU, (int)n, (long)n_user,
                        (long)n_item, (int)D, has_range, lo, hi);
     NNL_CHECK_LAUNCH();
+    NNL_ROUTE("embdot_bwd<scan>");
     return NNL_OK;
   }
   if (one_block) {
@@ -237,10 +239,13 @@ extern "C" int nnl_embdotbias_bwd(const int64_t* x, const float* U, const float*
     ps.q[2] = b;
     b.idx = x + 1; b.order = order + n; b.card = n_item; b.dst = dbi;
     ps.q[3] = b;
-    return nnl_det::segsum4(ps, 4, s);
+    if ((st = nnl_det::segsum4(ps, 4, s))) return st;
+    NNL_ROUTE("embdot_bwd<det>:%s", one_block ? "one_block" : "four_fills");
+    return NNL_OK;
   }
   hipLaunchKernelGGL(embdotbias_bwd_kernel, dim3(grid_for(n)), dim3(kBlock), 0, s, x, U, M, z, dy, dU, dM,
                      dbu, dbi, n, n_user, n_item, (int)D, has_range, lo, hi);
   NNL_CHECK_LAUNCH();
+  NNL_ROUTE("embdot_bwd<atomic>:%s", one_block ? "one_block" : "four_fills");
   return NNL_OK;
 }

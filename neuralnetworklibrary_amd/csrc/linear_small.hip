@@ -121,6 +121,7 @@ extern "C" int nnl_linear_small_fwd(const float* x, const float* w, const float*
   NnlProfScope prof(NNL_PROF_ELEMENTWISE, s, 4.0 * M * (double)(K + N));
   hipLaunchKernelGGL(lin_small_fwd_kernel, dim3((unsigned)nnl_cdiv(M, 4)), dim3(256), 0, s, x, w, bias, y, (long)M, (int)K, (long)ldx, (int)N);
   NNL_CHECK_LAUNCH();
+  NNL_ROUTE("linear_small_fwd");
   return NNL_OK;
 }
 
@@ -133,19 +134,25 @@ extern "C" size_t nnl_linear_small_bwd_workspace_bytes(int64_t M, int64_t K, int
 extern "C" int nnl_linear_small_bwd(const float* dy, const float* x, const float* w, float* dx, float* dw, float* db, int64_t M,
                                     int64_t K, int64_t ldx, int64_t N, void* workspace, size_t workspace_bytes, void* stream) {
   NNL_CHECK_ARG(M >= 0 && K > 0 && K < (1 << 24) && ldx >= K && N >= 1 && N <= kMaxN, "linear_small_bwd: bad sizes");
-  if (M == 0) return NNL_OK;
-  NNL_CHECK_ARG(dy && x && w, "linear_small_bwd: null pointer");
   hipStream_t s = (hipStream_t)stream;
+  if (M == 0) {                                              // an empty batch: empty sums, so dw and db are zero (they used to stay unwritten)
+    if (dw) NNL_CHECK_HIP(hipMemsetAsync(dw, 0, sizeof(float) * N * K, s));
+    if (db) NNL_CHECK_HIP(hipMemsetAsync(db, 0, sizeof(float) * N, s));
+    return NNL_OK;
+  }
+  NNL_CHECK_ARG(dy && x && w, "linear_small_bwd: null pointer");
   NnlProfScope prof(NNL_PROF_ELEMENTWISE, s, 4.0 * M * (double)(2 * K + N));
+  // (checked before the dx launch: an error return leaves every output untouched)
+  if ((dw || db) && (workspace == nullptr || workspace_bytes < nnl_linear_small_bwd_workspace_bytes(M, K, N)))
+    return nnl_set_error(NNL_ERR_WORKSPACE, "linear_small_bwd: workspace too small");
   if (dx) {
     long b = nnl_cdiv(M * K, 256);
     if (b > 2048) b = 2048;
     hipLaunchKernelGGL(lin_small_dx_kernel, dim3((unsigned)b), dim3(256), 0, s, dy, w, dx, (long)M, (int)K, (int)N);
     NNL_CHECK_LAUNCH();
   }
+  int nslab_note = 0;
   if (dw || db) {
-    if (workspace == nullptr || workspace_bytes < nnl_linear_small_bwd_workspace_bytes(M, K, N))
-      return nnl_set_error(NNL_ERR_WORKSPACE, "linear_small_bwd: workspace too small");
     const int nslab = (int)nnl_cdiv(M, kSlabRows);
     float* part = (float*)workspace;
     hipLaunchKernelGGL(lin_small_dw_part_kernel, dim3((unsigned)nnl_cdiv(K + 1, 64), (unsigned)nslab), dim3(256), 0, s, dy, x, part, (long)M,
@@ -154,6 +161,8 @@ extern "C" int nnl_linear_small_bwd(const float* dy, const float* x, const float
     hipLaunchKernelGGL(lin_small_dw_final_kernel, dim3((unsigned)nnl_cdiv(N * (K + 1), 256)), dim3(256), 0, s, (const float*)part, nslab, dw,
                        db, (int)K, (int)N);
     NNL_CHECK_LAUNCH();
+    nslab_note = nslab;
   }
+  NNL_ROUTE("linear_small_bwd:%s%s%s@slabs=%d", dx ? "dx" : "", dw ? "dw" : "", db ? "db" : "", nslab_note);
   return NNL_OK;
 }

@@ -157,7 +157,9 @@ __global__ __launch_bounds__(256) void tab_scan_bwd_kernel(const int64_t* __rest
   const unsigned magic = dj > 1 ? (unsigned)((0x100000000ull + dj - 1) / dj) : 0u;       // e / dj for e < 2^13 (exact: e * dj < 2^32 / dj ... checked by the test shapes)
   for (long s0 = 0; s0 < bs; s0 += 256) {
     const long sb = s0 + t;
-    s_idx[t] = sb < bs ? (int)xcat[sb * ncat + j] : -1;
+    // range check BEFORE narrowing: an index of 2^32 + r must not alias row r (tab_gather_kernel and the scatter kernels skip it)
+    const int64_t ix = sb < bs ? xcat[sb * ncat + j] : -1;
+    s_idx[t] = (ix >= 0 && ix < card[j]) ? (int)ix : -1;
     const float mk = (sb < bs && row_mask) ? row_mask[(long)j * bs + sb] : 1.f;     // this thread's SAMPLE (sl = t): its mask, then its
     // share of the 256 x dj gradient slice — all dj (<= 32) loads of a thread in flight at once (batches of 8 cost a ~1.5 us round
     // trip each: 24 of the first version's 38 us); element e = t + 256 u lives at sample e / dj (multiply-high by ceil(2^32 / dj))
@@ -245,6 +247,7 @@ extern "C" int nnl_tab_renorm(const int64_t* xcat, float* const* tables, const i
   hipLaunchKernelGGL(tab_renorm_kernel, dim3((unsigned)nnl_cdiv((long)total_rows * 16, kBlock)), dim3(kBlock), 0, s, tables, dim,
                      row_off, row_table, flags, total_rows, max_norm);
   NNL_CHECK_LAUNCH();
+  NNL_ROUTE("tab_renorm");
   return NNL_OK;
 }
 
@@ -262,6 +265,7 @@ extern "C" int nnl_tab_gather_fwd(const int64_t* xcat, const float* const* table
   hipLaunchKernelGGL(tab_gather_kernel, dim3(grid_for(bs * ld_out)), dim3(kBlock), 0, s, xcat, tables, card, dim, col_off,
                      col_table, row_mask, cont, cont_mask, out, (long)bs, ncat, cat_width, n_cont, ld_out);
   NNL_CHECK_LAUNCH();
+  NNL_ROUTE("tab_gather");
   return NNL_OK;
 }
 
@@ -298,11 +302,13 @@ extern "C" int nnl_tab_scatter_bwd(const int64_t* xcat, const int32_t* card, con
                          n_cont, ld_out);
       NNL_CHECK_LAUNCH();
     }
+    NNL_ROUTE("tab_scatter_bwd<det>");
     return NNL_OK;
   }
   hipLaunchKernelGGL(tab_scatter_kernel, dim3(grid_for(bs * (cat_width + n_cont))), dim3(kBlock), 0, s, xcat, card, dim, col_off,
                      col_table, grad_off, row_mask, cont_mask, dout, dtab_flat, dcont, (long)bs, ncat, cat_width, n_cont, ld_out);
   NNL_CHECK_LAUNCH();
+  NNL_ROUTE("tab_scatter_bwd<atomic>");      // no or short workspace, bs > kMaxSamples, ncat == 0, or NNL_SCATTER_ATOMIC=1
   return NNL_OK;
 }
 
@@ -321,6 +327,7 @@ extern "C" int nnl_tab_scan_bwd(const int64_t* xcat, const int32_t* card, const 
   hipLaunchKernelGGL(tab_scan_bwd_kernel, dim3((unsigned)(n_scan_blocks + cont_blocks)), dim3(256), 0, s, xcat, card, dim, col_off, grad_off,
                      row_mask, cont_mask, dout, dtab_flat, dcont, blk_col, blk_first, n_scan_blocks, (long)bs, ncat, cat_width, n_cont, ld_out);
   NNL_CHECK_LAUNCH();
+  NNL_ROUTE("tab_scan_bwd@blocks=%d+%ld", n_scan_blocks, cont_blocks);
   return NNL_OK;
 }
 
