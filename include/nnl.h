@@ -377,7 +377,20 @@ int nnl_se_squeeze_bwd(const float* dm, float* dx, int64_t N, int64_t HW, int64_
  * nnl_nms: top_k candidates by (score descending, order ascending), then greedy non-maximum suppression inside a class with
  *   IoU > max_overlap (retinanet.py:581-604; IoU in the reference's fp32 operation order).  cand_order may be NULL (= position).
  *   kept_* [bs][top_k] in descending score order, kept_count [bs].  The remaining list filters of nms() (relative
- *   thresholds, inclusions, cross-class duplicates, max_boxes) act on the few survivors and stay on the host. */
+ *   thresholds, inclusions, cross-class duplicates, max_boxes) act on the few survivors and stay on the host.
+ * The contracts in full (tests/detect_cases.py pins each of them):
+ *   decode   the class is the FIRST maximum of the K scores; a NaN among them drops the anchor.  The compare is strict: a score equal
+ *            to thresh is dropped.  A box is dropped when its clipped width or height is not > 0.  Written: cand_count [bs], and of
+ *            cand_boxes / cand_classes / cand_scores / cand_order the slots [0, cand_count) of every image; no other slot is touched.
+ *            The order of the slots is not defined (atomic append): cand_order identifies them.
+ *   nms      The candidates of an image are the slots [0, min(cand_count, cap)): a cand_count above cap is read as cap.  They are
+ *            ranked by the TOTAL order (score descending, cand_order ascending; the slot position when cand_order is NULL), so the
+ *            result does not depend on the order of the slots; cand_order values of one image must differ.  -0.0 and +0.0 are one
+ *            score.  The first min(n, top_k) of the ranking enter the suppression — the cut comes BEFORE it.  In rank order a box is
+ *            kept unless an earlier KEPT box of the same class has IoU > max_overlap (strict; a suppressed box suppresses nothing; an
+ *            IoU of 0/0 = NaN suppresses nothing).  Written: kept_count [bs] and the slots [0, kept_count) of kept_boxes /
+ *            kept_classes / kept_scores, bitwise copies of the candidates; no other slot is touched.  top_k may exceed cap.
+ *            workspace: nnl_nms_workspace_bytes(bs, top_k) bytes (0 for non-positive sizes), 16-byte aligned, contents irrelevant. */
 int nnl_bbox_decode(const float* anchors, const float* reg, const float* clas, int64_t bs, int64_t A, int64_t K,
                     const float* mean4, const float* std4, float thresh, float width, float height, float* cand_boxes,
                     int32_t* cand_classes, float* cand_scores, int32_t* cand_order, int32_t* cand_count, void* stream);

@@ -26,6 +26,7 @@ typedef unsigned long long u64;
 
 __device__ __forceinline__ unsigned desc_key(float s) {        // larger score -> smaller key
   unsigned u = __float_as_uint(s);
+  if (u == 0x80000000u) u = 0;                                  // -0.0 ranks as +0.0 (they compare equal): the order breaks the tie
   u ^= (u >> 31) ? 0xFFFFFFFFu : 0x80000000u;                   // ascending-sortable
   return ~u;
 }
