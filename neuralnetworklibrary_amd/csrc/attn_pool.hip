@@ -100,26 +100,6 @@ __device__ __forceinline__ bool arrive_last(int32_t* counter, int n, int* ticket
   return last;
 }
 
-// block-wide reductions in a fixed tree (the wave's shuffle tree, then the waves in order)
-__device__ __forceinline__ float block_max(float v, float* red) {
-  v = nnl_wave_max(v);
-  __syncthreads();
-  if ((threadIdx.x & (NNL_WAVE - 1)) == 0) red[threadIdx.x / NNL_WAVE] = v;
-  __syncthreads();
-  float r = red[0];
-  for (int w = 1; w < kWaves; ++w) r = fmaxf(r, red[w]);
-  return r;
-}
-__device__ __forceinline__ float block_sum(float v, float* red) {
-  v = nnl_wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & (NNL_WAVE - 1)) == 0) red[threadIdx.x / NNL_WAVE] = v;
-  __syncthreads();
-  float r = red[0];
-  for (int w = 1; w < kWaves; ++w) r += red[w];
-  return r;
-}
-
 // threads over the `nu` units of a row, G = 256 / min(nu, 256) row groups (group gi takes rows gi, gi + G, ...)
 struct Cols {
   int cpp, G, gi, c;
@@ -162,7 +142,7 @@ __global__ __launch_bounds__(kBlock) void attn_pool_fwd_kernel(FwdArgs p) {
   __syncthreads();
   float mloc = -INFINITY;
   for (int i = tid; i < L; i += kBlock) mloc = fmaxf(mloc, s_e[i]);
-  const float m = block_max(mloc, s_red);
+  const float m = nnl_block_reduce<kWaves>(mloc, NnlMax(), s_red);
   float* scol = p.sc + (long)b * p.T;
   for (int i = tid; i < L; i += kBlock) {
     const float s = s_e[i];
@@ -172,7 +152,7 @@ __global__ __launch_bounds__(kBlock) void attn_pool_fwd_kernel(FwdArgs p) {
   __syncthreads();
   float sloc = 0.f;
   for (int i = tid; i < L; i += kBlock) sloc += s_e[i];
-  const float ssum = block_sum(sloc, s_red);
+  const float ssum = nnl_block_reduce<kWaves>(sloc, NnlSum(), s_red);
 
   // 2. weighted sum of the enc_out rows; row groups combined in order through LDS
   const int nu = p.E / VW;
@@ -223,13 +203,13 @@ __global__ __launch_bounds__(kBlock) void attn_pool_fwd_kernel(FwdArgs p) {
   const float* msb = p.ms + 2 * (long)b * p.nch;
   float ml = -INFINITY;
   for (int k = tid; k < p.nch; k += kBlock) ml = fmaxf(ml, msb[2 * k]);
-  const float M = block_max(ml, s_red);
+  const float M = nnl_block_reduce<kWaves>(ml, NnlMax(), s_red);
   float sl = 0.f;
   for (int k = tid; k < p.nch; k += kBlock) {
     const float mk = msb[2 * k];
     sl += mk == -INFINITY ? 0.f : msb[2 * k + 1] * expf(mk - M);
   }
-  const float S = block_sum(sl, s_red);           // 0 only when the column holds no non-pad token
+  const float S = nnl_block_reduce<kWaves>(sl, NnlSum(), s_red);           // 0 only when the column holds no non-pad token
   const float* accb = p.acc + (long)b * p.nch * p.E;
   for (int j = tid; j < p.E; j += kBlock) {
     float a = 0.f;

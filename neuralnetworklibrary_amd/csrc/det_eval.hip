@@ -66,8 +66,7 @@ __global__ __launch_bounds__(NNL_WAVE) void coco_match_kernel(const int32_t* __r
       const double ar = gt_area[q0 + j];
       cnt += !((gt_flags[q0 + j] & 2) || ar < P.lo[a] || ar > P.hi[a]);
     }
-#pragma unroll
-    for (int o = NNL_WAVE / 2; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o, NNL_WAVE);
+    cnt = nnl_wave_sum(cnt);
     if (lane == 0) npig[(int64_t)a * NG + g] = cnt;
   }
   if (D == 0) return;
@@ -157,80 +156,9 @@ __global__ __launch_bounds__(NNL_WAVE) void coco_match_kernel(const int32_t* __r
 // ---- workgroup scans ---------------------------------------------------------------------------------------------------------
 
 struct I3 { int k, t, f; };
+__device__ __forceinline__ I3 i3_add(I3 a, I3 b) { return I3{a.k + b.k, a.t + b.t, a.f + b.f}; }
 
-// inclusive sums over the workgroup in thread order; total = the sum of all
-__device__ __forceinline__ I3 block_scan3(I3 v, int* lds, I3& total) {
-  const int lane = threadIdx.x & (NNL_WAVE - 1), w = threadIdx.x / NNL_WAVE;
-#pragma unroll
-  for (int o = 1; o < NNL_WAVE; o <<= 1) {
-    const int k = __shfl_up(v.k, o, NNL_WAVE), t = __shfl_up(v.t, o, NNL_WAVE), f = __shfl_up(v.f, o, NNL_WAVE);
-    if (lane >= o) { v.k += k; v.t += t; v.f += f; }
-  }
-  if (lane == NNL_WAVE - 1) { lds[w * 3] = v.k; lds[w * 3 + 1] = v.t; lds[w * 3 + 2] = v.f; }
-  __syncthreads();
-  I3 pre{0, 0, 0};
-  total = I3{0, 0, 0};
-#pragma unroll
-  for (int j = 0; j < kWaves; ++j) {
-    const int k = lds[j * 3], t = lds[j * 3 + 1], f = lds[j * 3 + 2];
-    if (j < w) { pre.k += k; pre.t += t; pre.f += f; }
-    total.k += k; total.t += t; total.f += f;
-  }
-  __syncthreads();
-  v.k += pre.k; v.t += pre.t; v.f += pre.f;
-  return v;
-}
-
-// inclusive maximum over the workgroup in thread order (keys: unsigned 64 bit)
-__device__ __forceinline__ unsigned long long block_scan_max(unsigned long long v, unsigned long long* lds, unsigned long long& total) {
-  const int lane = threadIdx.x & (NNL_WAVE - 1), w = threadIdx.x / NNL_WAVE;
-#pragma unroll
-  for (int o = 1; o < NNL_WAVE; o <<= 1) {
-    const unsigned long long u = __shfl_up(v, o, NNL_WAVE);
-    if (lane >= o && u > v) v = u;
-  }
-  if (lane == NNL_WAVE - 1) lds[w] = v;
-  __syncthreads();
-  unsigned long long pre = 0;
-  total = 0;
-#pragma unroll
-  for (int j = 0; j < kWaves; ++j) {
-    const unsigned long long u = lds[j];
-    if (j < w && u > pre) pre = u;
-    if (u > total) total = u;
-  }
-  __syncthreads();
-  return pre > v ? pre : v;
-}
-
-// maximum of the values at this thread and every later one of the workgroup
-__device__ __forceinline__ double block_suffix_max(double v, double* lds) {
-  const int lane = threadIdx.x & (NNL_WAVE - 1), w = threadIdx.x / NNL_WAVE;
-#pragma unroll
-  for (int o = 1; o < NNL_WAVE; o <<= 1) {
-    const double u = __shfl_down(v, o, NNL_WAVE);
-    if (lane + o < NNL_WAVE) v = fmax(v, u);
-  }
-  if (lane == 0) lds[w] = v;
-  __syncthreads();
-#pragma unroll
-  for (int j = 1; j < kWaves; ++j)
-    if (j > w) v = fmax(v, lds[j]);
-  __syncthreads();
-  return v;
-}
-
-__device__ __forceinline__ double block_sum(double v, double* lds) {
-#pragma unroll
-  for (int o = NNL_WAVE / 2; o > 0; o >>= 1) v += __shfl_down(v, o, NNL_WAVE);
-  if ((threadIdx.x & (NNL_WAVE - 1)) == 0) lds[threadIdx.x / NNL_WAVE] = v;
-  __syncthreads();
-  double r = lds[0];
-#pragma unroll
-  for (int k = 1; k < kWaves; ++k) r += lds[k];
-  __syncthreads();
-  return r;
-}
+constexpr I3 kZero3 = {0, 0, 0};
 
 // ---- b. COCO accumulation ------------------------------------------------------------------------------------------------------
 
@@ -254,7 +182,7 @@ __global__ __launch_bounds__(kThreads) void coco_accumulate_kernel(const int32_t
                                                                    double* __restrict__ recall) {
   __shared__ double rec[NNL_DET_EVAL_MAX_R];
   __shared__ int pos[NNL_DET_EVAL_MAX_R];
-  __shared__ int lds_i[3 * kWaves];
+  __shared__ I3 lds_i[kWaves];
   __shared__ double lds_d[kWaves];
   __shared__ double tile[kThreads];
   const int tid = threadIdx.x;
@@ -272,7 +200,7 @@ __global__ __launch_bounds__(kThreads) void coco_accumulate_kernel(const int32_t
   const int g0 = cat_grp_off[k], g1 = cat_grp_off[k + 1];
   I3 np{0, 0, 0}, tot;
   for (int g = g0 + tid; g < g1; g += kThreads) np.k += npig[(int64_t)a * NG + g];
-  block_scan3(np, lds_i, tot);                                               // also the barrier behind rec / pos
+  nnl_block_scan<kWaves>(np, i3_add, kZero3, lds_i, tot);                                               // also the barrier behind rec / pos
   const int n_pig = tot.k;
   if (g0 == g1 || n_pig == 0) {                                              // no group, or no ground truth that counts: stays -1 (:368, :381)
     for (int r = tid; r < R; r += kThreads) { precision[out0 + r * rstride] = -1.0; scores[out0 + r * rstride] = -1.0; }
@@ -299,7 +227,7 @@ __global__ __launch_bounds__(kThreads) void coco_accumulate_kernel(const int32_t
   I3 carry{0, 0, 0};
   for (int base = 0; base < n; base += kThreads) {
     const I3 f = flags(base + tid);
-    I3 s = block_scan3(f, lds_i, tot);
+    I3 s = nnl_block_scan<kWaves>(f, i3_add, kZero3, lds_i, tot);
     s.k += carry.k; s.t += carry.t; s.f += carry.f;
     if (f.k && (f.t || s.k == 1)) {
       const double rc = (double)s.t / dn;
@@ -314,15 +242,15 @@ __global__ __launch_bounds__(kThreads) void coco_accumulate_kernel(const int32_t
 
   // backward: the same sums from the totals, precision, its running maximum from the right (:406-408), and the picks (:412-414)
   I3 end = carry;
-  double right = -1.0;
+  double right = -1.0, tile_max;
   const double eps = 2.220446049250313e-16;                                  // np.spacing(1)
   for (int base = ((n - 1) / kThreads) * kThreads; n > 0 && base >= 0; base -= kThreads) {
     const I3 f = flags(base + tid);
-    I3 s = block_scan3(f, lds_i, tot);
+    I3 s = nnl_block_scan<kWaves>(f, i3_add, kZero3, lds_i, tot);
     const I3 start{end.k - tot.k, end.t - tot.t, end.f - tot.f};
     s.t += start.t; s.f += start.f;
     const double pr = f.k ? (double)s.t / ((double)s.f + (double)s.t + eps) : -1.0;
-    const double sm = fmax(block_suffix_max(pr, lds_d), right);
+    const double sm = fmax(nnl_block_scan<kWaves, true>(pr, NnlMax(), (double)-INFINITY, lds_d, tile_max), right);
     tile[tid] = sm;
     __syncthreads();
     for (int r = tid; r < R; r += kThreads) {
@@ -378,7 +306,7 @@ __global__ __launch_bounds__(kThreads) void map_integrate_kernel(const int32_t* 
                                                                  const double* __restrict__ score, const uint8_t* __restrict__ correct,
                                                                  const int64_t* __restrict__ ntrue, int64_t C, int64_t Np,
                                                                  double* __restrict__ scratch, double* __restrict__ out) {
-  __shared__ int lds_i[3 * kWaves];
+  __shared__ I3 lds_i[kWaves];
   __shared__ unsigned long long lds_u[kWaves];
   __shared__ double lds_d[kWaves];
   const int tid = threadIdx.x;
@@ -396,11 +324,11 @@ __global__ __launch_bounds__(kThreads) void map_integrate_kernel(const int32_t* 
     if (i < n) {
       f.k = ok[order[i0 + i]] ? 1 : 0;
     }
-    I3 s = block_scan3(f, lds_i, tot);
+    I3 s = nnl_block_scan<kWaves>(f, i3_add, kZero3, lds_i, tot);
     s.k += seen;
     if (i < n && (i == 0 || score[order[i0 + i]] != score[order[i0 + i - 1]]))
       key = ((unsigned long long)(unsigned)i << 32) | (unsigned)(s.k - f.k);
-    key = block_scan_max(key, lds_u, ktot);
+    key = nnl_block_scan<kWaves>(key, NnlMax(), 0ULL, lds_u, ktot);      // 0: "nothing seen", below every key
     if (head > key) key = head;
     if (i < n) {
       const int h = (int)(key >> 32), q = (int)(key & 0xffffffffULL);
@@ -410,18 +338,15 @@ __global__ __launch_bounds__(kThreads) void map_integrate_kernel(const int32_t* 
     if (ktot > head) head = ktot;
   }
   // backward: running maximum from the right over the correct positions, summed at the correct positions (:1744-1747)
-  double right = 0.0, acc = 0.0;
+  double right = 0.0, acc = 0.0, tile_max;
   for (int base = ((n - 1) / kThreads) * kThreads; n > 0 && base >= 0; base -= kThreads) {
     const int i = base + tid;
     const double x = i < n ? v[i] : 0.0;
-    const double sm = fmax(block_suffix_max(x, lds_d), right);
+    const double sm = fmax(nnl_block_scan<kWaves, true>(x, NnlMax(), (double)-INFINITY, lds_d, tile_max), right);
     if (x > 0.0) acc += sm;
-    if (tid == 0) lds_d[0] = sm;
-    __syncthreads();
-    right = lds_d[0];
-    __syncthreads();
+    right = fmax(tile_max, right);               // what thread 0 holds: the maximum from this tile's first position on
   }
-  const double total = block_sum(acc, lds_d);
+  const double total = nnl_block_reduce<kWaves>(acc, NnlSum(), lds_d);
   if (tid == 0) out[(int64_t)t * C + c] = total / (double)ntrue[c];          // 0 / 0 = nan without ground truth, as the host gives
 }
 

@@ -230,12 +230,7 @@ __global__ __launch_bounds__(kMergeBlock) void tta_bbox_merge_kernel(const float
       }
       s_undo[t] = undo[img * P + t];
     }
-    int incl = c;
-#pragma unroll
-    for (int o = 1; o < NNL_WAVE; o <<= 1) {
-      const int v = __shfl_up(incl, o, NNL_WAVE);
-      if (t >= o) incl += v;
-    }
+    const int incl = nnl_wave_scan(c, NnlSum());
     s_cnt[t] = c;
     s_off[t] = incl - c;
     if (t == NNL_WAVE - 1) s_off[NNL_WAVE] = incl;

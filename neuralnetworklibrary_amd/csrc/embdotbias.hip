@@ -44,7 +44,7 @@ __global__ __launch_bounds__(kBlock) void embdotbias_fwd_kernel(
       } else {
         const float zz = acc + bu[u] + bi[it];
         if (z) z[b] = zz;
-        y[b] = has_range ? lo + (hi - lo) * (1.f / (1.f + expf(-zz))) : zz;
+        y[b] = has_range ? lo + (hi - lo) * nnl_sigmoid(zz) : zz;
       }
     }
   }
@@ -63,7 +63,7 @@ __global__ __launch_bounds__(kBlock) void embdotbias_bwd_kernel(
     if ((u < 0) | (u >= n_user) | (it < 0) | (it >= n_item)) continue;
     float g = dy[b];
     if (has_range) {
-      const float s = 1.f / (1.f + expf(-z[b]));
+      const float s = nnl_sigmoid(z[b]);
       g *= (hi - lo) * s * (1.f - s);
     }
     const float* __restrict__ ur = U + u * D;
@@ -90,7 +90,7 @@ __global__ void embdot_g_kernel(const int64_t* __restrict__ x, const float* __re
     if (!((u < 0) | (u >= n_user) | (it < 0) | (it >= n_item))) {
       v = dy[b];
       if (has_range) {
-        const float s = 1.f / (1.f + expf(-z[b]));
+        const float s = nnl_sigmoid(z[b]);
         v *= (hi - lo) * s * (1.f - s);
       }
     }
@@ -119,7 +119,7 @@ __global__ __launch_bounds__(256) void embdot_scan_bwd_kernel(const int64_t* __r
     if (ok) {
       g = dy[t];
       if (has_range) {
-        const float sgm = 1.f / (1.f + expf(-z[t]));
+        const float sgm = nnl_sigmoid(z[t]);
         g *= (hi - lo) * sgm * (1.f - sgm);
       }
     }

@@ -26,17 +26,6 @@ struct AugArgs {
   int has_stats;
 };
 
-// block-wide sum in a fixed tree (the wave's shuffle tree, then the waves in order)
-__device__ __forceinline__ float block_sum(float v, float* red) {
-  v = nnl_wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & (NNL_WAVE - 1)) == 0) red[threadIdx.x / NNL_WAVE] = v;
-  __syncthreads();
-  float r = red[0];
-  for (int w = 1; w < kWaves; ++w) r += red[w];
-  return r;
-}
-
 template <bool LIGHT>
 __global__ __launch_bounds__(kBlock) void image_aug_geometric_kernel(AugArgs a) {
   __shared__ float s_red[kWaves];
@@ -52,7 +41,7 @@ __global__ __launch_bounds__(kBlock) void image_aug_geometric_kernel(AugArgs a) 
   if (LIGHT) {
     float* part = a.partial + ((int64_t)b * a.nblk + blockIdx.x) * 3;
     for (int c = 0; c < 3; ++c) {
-      const float s = block_sum(v[c], s_red);
+      const float s = nnl_block_reduce<kWaves>(v[c], NnlSum(), s_red);
       if (threadIdx.x == 0) part[c] = s;
     }
   }
@@ -70,7 +59,7 @@ __global__ __launch_bounds__(kBlock) void image_aug_lighting_kernel(AugArgs a) {
     for (int c = 0; c < 3; ++c) {
       float acc = 0.f;
       for (int k = threadIdx.x; k < a.nblk; k += kBlock) acc += part[k * 3 + c];
-      mu[c] = block_sum(acc, s_red) / (float)a.npix;
+      mu[c] = nnl_block_reduce<kWaves>(acc, NnlSum(), s_red) / (float)a.npix;
     }
   }
   if (pix >= a.npix) return;

@@ -89,7 +89,6 @@ __device__ __forceinline__ void gate_rows_dot(const float* __restrict__ w, long 
   }
 }
 
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
 
 // x == nullptr: the input is row tokens[pos] of emb [V, ld_emb] (I valid entries), read on the device; an id outside [0, V) reads as a zero row
 __global__ __launch_bounds__(kCellWaves * 64) void lstm_cell_b1_kernel(
@@ -113,10 +112,10 @@ __global__ __launch_bounds__(kCellWaves * 64) void lstm_cell_b1_kernel(
 #pragma unroll
   for (int g = 0; g < 4; ++g) acc[g] = nnl_wave_sum(acc[g]);
   if (lane == 0) {                               // torch's gate order: i, f, g, o
-    const float gi = sigmoidf_(acc[0] + bias[j]);
-    const float gf = sigmoidf_(acc[1] + bias[H + j]);
+    const float gi = nnl_sigmoid(acc[0] + bias[j]);
+    const float gf = nnl_sigmoid(acc[1] + bias[H + j]);
     const float gg = tanhf(acc[2] + bias[2 * H + j]);
-    const float go = sigmoidf_(acc[3] + bias[3 * H + j]);
+    const float go = nnl_sigmoid(acc[3] + bias[3 * H + j]);
     const float cn = gf * c[j] + gi * gg;
     c_out[j] = cn;
     h_out[j] = go * tanhf(cn);
@@ -191,15 +190,6 @@ __device__ __forceinline__ Cand cand_best(Cand a, Cand b) { return better(b.v, b
 
 constexpr Cand kNoCand = {-INFINITY, INT_MAX, -1};
 
-__device__ __forceinline__ Cand wave_best(Cand b) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const Cand other = {__shfl_xor(b.v, o, 64), __shfl_xor(b.i, o, 64), __shfl_xor(b.s, o, 64)};
-    b = cand_best(b, other);
-  }
-  return b;
-}
-
 // the best remaining head among the slices this thread owns (s = tid, tid + kBlock, ...); a taken or empty slice holds index INT_MAX
 __device__ __forceinline__ Cand own_best(const float* hv, const int* hi, int n_slices, int tid) {
   Cand best = kNoCand;
@@ -215,12 +205,13 @@ __global__ __launch_bounds__(kBlock) void lm_pick_kernel(const float* __restrict
                                                          long step, int64_t* __restrict__ tokens, long pos,
                                                          float* __restrict__ top_probs, int64_t* __restrict__ top_indices) {
   extern __shared__ __align__(16) float dyn[];   // (2): hv[n_slices], hi[n_slices]; (3): lv[k * k], li[k * k]
-  __shared__ float wv[4];
-  __shared__ int wi[4], wsl[4];
+  constexpr int kWaves = kBlock / NNL_WAVE;
+  __shared__ float wv[kWaves];
+  __shared__ Cand wc[kWaves];
   __shared__ int sel[kMaxK];
   __shared__ float top_v[kMaxK], csum[kMaxK];
   __shared__ int top_i[kMaxK];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63;
   const int stride = 2 + 2 * k;
   float* hv = dyn;
   int* hi = reinterpret_cast<int*>(dyn + n_slices);
@@ -232,34 +223,21 @@ __global__ __launch_bounds__(kBlock) void lm_pick_kernel(const float* __restrict
     hv[s] = p[2];
     hi[s] = reinterpret_cast<const int*>(p + 2 + k)[0];
   }
-  m = nnl_wave_max(m);
-  if (lane == 0) wv[wave] = m;
-  __syncthreads();
-  const float M = fmaxf(fmaxf(wv[0], wv[1]), fmaxf(wv[2], wv[3]));
-  __syncthreads();
+  const float M = nnl_block_reduce<kWaves>(m, NnlMax(), wv);
   float sum = 0.f;
   for (int s = tid; s < n_slices; s += kBlock) sum += part[(long)s * stride + 1] * expf(part[(long)s * stride] - M);
-  sum = nnl_wave_sum(sum);
-  if (lane == 0) wv[wave] = sum;
-  __syncthreads();
-  const float S = ((wv[0] + wv[1]) + wv[2]) + wv[3];
-  __syncthreads();
+  const float S = nnl_block_reduce<kWaves>(sum, NnlSum(), wv);
   Cand mine = own_best(hv, hi, n_slices, tid);
   for (int r = 0; r < k; ++r) {
-    const Cand b = wave_best(mine);
-    if (lane == 0) { wv[wave] = b.v; wi[wave] = b.i; wsl[wave] = b.s; }
-    __syncthreads();
-    Cand w = {wv[0], wi[0], wsl[0]};
-#pragma unroll
-    for (int x = 1; x < 4; ++x) w = cand_best(w, Cand{wv[x], wi[x], wsl[x]});
+    const Cand w = nnl_block_reduce<kWaves>(mine, cand_best, wc);
     if (tid == 0) sel[r] = w.s;                  // -1: fewer than k slices hold an eligible entry
-    if (w.s >= 0 && (w.s % kBlock) == tid) {     // its owner takes the winning slice out
+    if (w.s >= 0 && (w.s % kBlock) == tid) {     // its owner takes the winning slice out (a thread reads only its own slices' heads)
       hi[w.s] = INT_MAX;
       mine = own_best(hv, hi, n_slices, tid);
     }
-    __syncthreads();
   }
-  float* lv = dyn;                               // hv / hi are dead from here on
+  __syncthreads();                               // sel[] is complete, hv / hi are dead
+  float* lv = dyn;
   int* li = reinterpret_cast<int*>(dyn + k * k);
   for (int t = tid; t < k * k; t += kBlock) {
     const int sl = sel[t / k], q = t % k;
@@ -268,12 +246,12 @@ __global__ __launch_bounds__(kBlock) void lm_pick_kernel(const float* __restrict
     li[t] = sl < 0 ? INT_MAX : reinterpret_cast<const int*>(p + 2 + k)[q];
   }
   __syncthreads();
-  if (wave != 0) return;
+  if (tid >= NNL_WAVE) return;
   int hd = 0;                                    // lane t < k owns list t
   auto head_of = [&](int h) { return (lane < k && h < k && li[lane * k + h] != INT_MAX) ? Cand{lv[lane * k + h], li[lane * k + h], lane} : kNoCand; };
   Cand cur = head_of(0);
   for (int r = 0; r < k; ++r) {
-    const Cand w = wave_best(cur);
+    const Cand w = nnl_wave_reduce(cur, cand_best);
     if (lane == 0) { top_v[r] = w.v; top_i[r] = w.i; }
     if (w.s == lane) cur = head_of(++hd);
   }

@@ -12,16 +12,6 @@ constexpr int kLossBlock = 1024;
 constexpr long kLossOneBlock = 65536;
 constexpr int kLossMaxBlocks = 256;
 
-__device__ __forceinline__ float block_sum(float v, float* red) {
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int w = kLossBlock / 2; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-    __syncthreads();
-  }
-  return red[0];
-}
-
 struct SqErr {   // (a - b)^2
   __device__ __forceinline__ float operator()(float a, float b) const {
     const float d = a - b;
@@ -40,13 +30,13 @@ __global__ __launch_bounds__(kLossBlock) void loss_fwd_kernel(const float* __res
   const Term term;
   float acc = 0.f;
   for (long i = (long)blockIdx.x * kLossBlock + threadIdx.x; i < n; i += (long)gridDim.x * kLossBlock) acc += term(a[i], b[i]);
-  const float s = block_sum(acc, red);
+  const float s = nnl_block_tree_reduce<kLossBlock>(acc, NnlSum(), red);
   if (threadIdx.x == 0) out[blockIdx.x] = gridDim.x == 1 ? s * scale : s;
 }
 
 __global__ __launch_bounds__(kLossBlock) void loss_final_kernel(const float* __restrict__ part, int nparts, float* __restrict__ out, float scale) {
   __shared__ float red[kLossBlock];
-  const float s = block_sum((int)threadIdx.x < nparts ? part[threadIdx.x] : 0.f, red);
+  const float s = nnl_block_tree_reduce<kLossBlock>((int)threadIdx.x < nparts ? part[threadIdx.x] : 0.f, NnlSum(), red);
   if (threadIdx.x == 0) out[0] = s * scale;
 }
 
@@ -65,13 +55,13 @@ __global__ __launch_bounds__(256) void bce_logits_bwd_kernel(const float* __rest
   for (long i = tid; i < n4; i += nthreads) {
     const float4 xv = reinterpret_cast<const float4*>(x)[i], tv = reinterpret_cast<const float4*>(t)[i];
     float4 d;
-    d.x = g * (1.f / (1.f + expf(-xv.x)) - tv.x);
-    d.y = g * (1.f / (1.f + expf(-xv.y)) - tv.y);
-    d.z = g * (1.f / (1.f + expf(-xv.z)) - tv.z);
-    d.w = g * (1.f / (1.f + expf(-xv.w)) - tv.w);
+    d.x = g * (nnl_sigmoid(xv.x) - tv.x);
+    d.y = g * (nnl_sigmoid(xv.y) - tv.y);
+    d.z = g * (nnl_sigmoid(xv.z) - tv.z);
+    d.w = g * (nnl_sigmoid(xv.w) - tv.w);
     reinterpret_cast<float4*>(dx)[i] = d;
   }
-  for (long i = n4 * 4 + tid; i < n; i += nthreads) dx[i] = g * (1.f / (1.f + expf(-x[i])) - t[i]);
+  for (long i = n4 * 4 + tid; i < n; i += nthreads) dx[i] = g * (nnl_sigmoid(x[i]) - t[i]);
 }
 
 template <class Term>
@@ -145,7 +135,7 @@ namespace {
 __global__ __launch_bounds__(256) void scaled_sigmoid_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, float* __restrict__ sg, long n,
                                                                   float lo, float hi) {
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-    const float s = 1.f / (1.f + expf(-x[i]));
+    const float s = nnl_sigmoid(x[i]);
     sg[i] = s;
     y[i] = lo + (hi - lo) * s;
   }
@@ -199,7 +189,7 @@ __global__ __launch_bounds__(kLossBlock) void fbeta_kernel(const float* __restri
     float tp = 0.f, sp = 0.f, st = 0.f;
     for (long c = lane; c < C; c += NNL_WAVE) {
       const float x = pred[r * C + c], t = target[r * C + c];
-      const float p = use_thresh ? (1.f / (1.f + expf(-x)) >= threshold ? 1.f : 0.f) : x;
+      const float p = use_thresh ? (nnl_sigmoid(x) >= threshold ? 1.f : 0.f) : x;
       tp += p * t;
       sp += p;
       st += t;

@@ -52,7 +52,6 @@ bool bptt2_enabled() { return (NNL_ENV_INT("NNL_LSTM_PERSIST", 5) & 4) != 0; }
 // (a 2-D partitioned persistent FORWARD — the twin of lstm_bptt2.hip, bit 3 in round 4 — only tied the first persistent forward
 // (18.3 vs 18.8 us per step at H = 1150, 14.4 vs 9.5 at H = 400: two hand-overs per step against one) and was removed in round 5)
 
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
 
 __global__ void pad_copy_kernel(const float* __restrict__ src, float* __restrict__ dst, int B, int H, int Hp) {
   const int total = B * Hp;

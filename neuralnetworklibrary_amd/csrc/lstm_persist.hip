@@ -48,7 +48,6 @@ constexpr int kMaxU = 5;           // units per workgroup: shape_of's LDS bound 
                                    // (tests/test_lstm_cases_cpu.py holds that against the planner)
 constexpr int kSpinLimit = 1 << 22;
 
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
 
 struct PersistFwd {
   const float* gx;      // [T][B][4H]
@@ -283,7 +282,7 @@ __global__ __launch_bounds__(kFwdBlock) void lstm_persist_fwd_kernel(PersistFwd 
           sum += red[((long)w * ncol + col) * kLanes + b] + red[((long)(w + 1) * ncol + col) * kLanes + b];
         pre[g] = gxv[q][g] + sum;
       }
-      gact[q][0] = sigmoidf_(pre[0]); gact[q][1] = sigmoidf_(pre[1]); gact[q][2] = tanhf(pre[2]); gact[q][3] = sigmoidf_(pre[3]);
+      gact[q][0] = nnl_sigmoid(pre[0]); gact[q][1] = nnl_sigmoid(pre[1]); gact[q][2] = tanhf(pre[2]); gact[q][3] = nnl_sigmoid(pre[3]);
       const float c = gact[q][1] * c_state[q] + gact[q][0] * gact[q][2];
       hv[q] = gact[q][3] * tanhf(c);
       c_state[q] = c;

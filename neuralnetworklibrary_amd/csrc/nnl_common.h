@@ -66,13 +66,4 @@ struct NnlProfScope {
   ~NnlProfScope() { nnl_prof_end(kind, s, work); }
 };
 
-__device__ __forceinline__ float nnl_wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-__device__ __forceinline__ float nnl_wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
+#include "block_ops.h"   // nnl_wave_sum / nnl_wave_max, the workgroup reductions and scans, nnl_sigmoid

@@ -26,10 +26,8 @@ __global__ __launch_bounds__(kBlock) void sqnorm_partial_kernel(const nnl_optim_
   float acc = 0.f;
   if (g)
     for (long i = off + threadIdx.x; i < end; i += kBlock) { const float v = g[i]; acc += v * v; }
-  acc = nnl_wave_sum(acc);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+  acc = nnl_block_reduce<4, NNL_FOLD_PAIRWISE>(acc, NnlSum(), red);
+  if (threadIdx.x == 0) partial[blockIdx.x] = acc;
 }
 
 // coef[0] = min(1, max_norm / (sqrt(sum partial) + 1e-6))   (torch.nn.utils.clip_grad_norm_), fixed summation order.  A NaN norm gives a
@@ -39,14 +37,9 @@ __global__ void clip_coef_kernel(const float* __restrict__ partial, int n, const
   __shared__ double red[kBlock];
   double a = 0.0;
   for (int i = threadIdx.x; i < n; i += kBlock) a += (double)partial[i];
-  red[threadIdx.x] = a;
-  __syncthreads();
-  for (int w = kBlock / 2; w > 0; w >>= 1) {
-    if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-    __syncthreads();
-  }
+  a = nnl_block_tree_reduce<kBlock>(a, NnlSum(), red);
   if (threadIdx.x == 0) {
-    const float total = (float)sqrt(red[0]);
+    const float total = (float)sqrt(a);
     const float c = max_norm / (total + 1e-6f);
     coef[0] = c >= 1.f ? 1.f : c;
     coef[1] = total;

@@ -30,16 +30,9 @@ constexpr int kBlock = 256;    // threads per block = anchors per chunk
 constexpr int kMaxObj = 128;   // objects per image held in LDS
 constexpr int kPre = 8;        // 16-B clas pieces per lane fetched ahead of the matching (K <= 32: the whole chunk)
 
-// block-wide sums of three values with one LDS exchange (red: 12 floats); fixed tree => deterministic
-__device__ __forceinline__ void block_sum3(float& a, float& b, float& c, float* red) {
-  a = nnl_wave_sum(a); b = nnl_wave_sum(b); c = nnl_wave_sum(c);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) { red[wave] = a; red[4 + wave] = b; red[8 + wave] = c; }
-  __syncthreads();
-  a = (red[0] + red[1]) + (red[2] + red[3]);
-  b = (red[4] + red[5]) + (red[6] + red[7]);
-  c = (red[8] + red[9]) + (red[10] + red[11]);
-}
+// the three sums of a chunk travel through one block reduce (one LDS exchange, pairwise fold of the 4 waves)
+struct Sum3 { float focal, sl1, np; };
+__device__ __forceinline__ Sum3 sum3_add(Sum3 a, Sum3 b) { return Sum3{a.focal + b.focal, a.sl1 + b.sl1, a.np + b.np}; }
 
 struct Encoded { float t[4]; };
 
@@ -152,7 +145,7 @@ __global__ __launch_bounds__(kBlock) void retina_fwd_kernel(
   __shared__ int s_cat[kMaxObj];
   __shared__ int s_cnt[2];
   __shared__ int s_t[kBlock];           // per anchor of the chunk: target class (>= 0), -1 negative, -2 ignored / out of range
-  __shared__ float red[12];
+  __shared__ Sum3 red[kBlock / NNL_WAVE];
   const int img = blockIdx.y, tid = threadIdx.x;
   const int a0 = blockIdx.x * kBlock, a = a0 + tid;
   // every global load that does not depend on the matching is issued FIRST — the chunk's class probabilities (up to kPre 16-B
@@ -224,10 +217,10 @@ __global__ __launch_bounds__(kBlock) void retina_fwd_kernel(
       if (t != -2) focal += focal_term<G2>(cp[e], e - an_i * K == t, alpha, gamma);
     }
   }
-  block_sum3(focal, sl1, np, red);
+  const Sum3 s = nnl_block_reduce<kBlock / NNL_WAVE, NNL_FOLD_PAIRWISE>(Sum3{focal, sl1, np}, sum3_add, red);
   if (tid == 0) {
     float* o = part + ((long)img * gridDim.x + blockIdx.x) * 3;
-    o[0] = focal; o[1] = sl1; o[2] = np;
+    o[0] = s.focal; o[1] = s.sl1; o[2] = s.np;
   }
 }
 

@@ -13,7 +13,6 @@ namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ float sigmoidf_(float z) { return 1.f / (1.f + expf(-z)); }
 
 // block = 256 threads = 64 channel lanes x 4 pixel lanes; grid = (ceil(C/64), N)
 __global__ __launch_bounds__(256) void se_squeeze_kernel(const float* __restrict__ x, float* __restrict__ m, int HW, int C) {
@@ -40,7 +39,7 @@ __global__ __launch_bounds__(256) void se_excite_fwd_kernel(const float* __restr
     if (res != nullptr) r = reinterpret_cast<const f32x4*>(res)[i];
     f32x4 o;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = fmaxf(xv[e] * sigmoidf_(zv[e]) + r[e], 0.f);
+    for (int e = 0; e < 4; ++e) o[e] = fmaxf(xv[e] * nnl_sigmoid(zv[e]) + r[e], 0.f);
     reinterpret_cast<f32x4*>(out)[i] = o;
   }
 }

@@ -16,7 +16,6 @@ __device__ __forceinline__ f32x4 buf_load4_policy(__amdgpu_buffer_rsrc_t rsrc, u
 }
 #define buf_load4_pol(rsrc, voff, pol) buf_load4_policy<pol>(rsrc, voff)
 
-__device__ __forceinline__ float nnl_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
 
 // ---- 1. tile decode: blockIdx.x -> the tile (`logical`) and the k slice `kslice` of `nslices` this workgroup computes.  Balanced
 // schedule (p.bal; grid.x = n_main_tiles*main_ks + n_tail_tiles*tail_slices): main tiles first, XCD-remapped, then the tail tiles; a sliced

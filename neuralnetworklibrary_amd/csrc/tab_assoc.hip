@@ -68,45 +68,6 @@ inline Span row_spans(int64_t n) {
   return {nnl_cdiv(tiles, per), per};              // every group owns at least one tile
 }
 
-// sums in a fixed order: shuffle tree inside the wave, then the waves in order; every thread returns the total
-__device__ __forceinline__ double block_sum(double v, double* lds) {
-#pragma unroll
-  for (int o = NNL_WAVE / 2; o > 0; o >>= 1) v += __shfl_down(v, o, NNL_WAVE);
-  if ((threadIdx.x & (NNL_WAVE - 1)) == 0) lds[threadIdx.x / NNL_WAVE] = v;
-  __syncthreads();
-  double r = lds[0];
-#pragma unroll
-  for (int k = 1; k < kWaves; ++k) r += lds[k];
-  __syncthreads();
-  return r;
-}
-__device__ __forceinline__ double block_max(double v, double* lds) {
-#pragma unroll
-  for (int o = NNL_WAVE / 2; o > 0; o >>= 1) v = fmax(v, __shfl_down(v, o, NNL_WAVE));
-  if ((threadIdx.x & (NNL_WAVE - 1)) == 0) lds[threadIdx.x / NNL_WAVE] = v;
-  __syncthreads();
-  double r = lds[0];
-#pragma unroll
-  for (int k = 1; k < kWaves; ++k) r = fmax(r, lds[k]);
-  __syncthreads();
-  return r;
-}
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = NNL_WAVE / 2; o > 0; o >>= 1) v += __shfl_down(v, o, NNL_WAVE);
-  return v;
-}
-__device__ __forceinline__ double wave_min(double v) {
-#pragma unroll
-  for (int o = NNL_WAVE / 2; o > 0; o >>= 1) v = fmin(v, __shfl_down(v, o, NNL_WAVE));
-  return v;
-}
-__device__ __forceinline__ double wave_max(double v) {
-#pragma unroll
-  for (int o = NNL_WAVE / 2; o > 0; o >>= 1) v = fmax(v, __shfl_down(v, o, NNL_WAVE));
-  return v;
-}
-
 // doubles (no NaN) as unsigned keys of the same order; 0 is below every key: "nothing seen"
 __device__ __forceinline__ unsigned long long key_of(double d) {
   const unsigned long long b = (unsigned long long)__double_as_longlong(d);
@@ -170,7 +131,7 @@ __global__ __launch_bounds__(kThreads) void table_stats_kernel(const uint32_t* _
   const int cells = cx * cy;
   double s = 0.0;
   for (int i = threadIdx.x; i < cells; i += kThreads) s += (double)T[i];
-  const double N = block_sum(s, lds);
+  const double N = nnl_block_reduce<kWaves>(s, NnlSum(), lds);
   if (N == 0.0) {
     if (threadIdx.x < 6) o[threadIdx.x] = 0.0;
     return;
@@ -184,8 +145,8 @@ __global__ __launch_bounds__(kThreads) void table_stats_kernel(const uint32_t* _
       nz += 1.0;
     }
   }
-  double hxy = block_sum(h, lds);
-  const double cells_seen = block_sum(nz, lds);
+  double hxy = nnl_block_reduce<kWaves>(h, NnlSum(), lds);
+  const double cells_seen = nnl_block_reduce<kWaves>(nz, NnlSum(), lds);
   double hx = 0.0, rows = 0.0;
   for (int r = threadIdx.x; r < cx; r += kThreads) {
     double m = 0.0;
@@ -196,8 +157,8 @@ __global__ __launch_bounds__(kThreads) void table_stats_kernel(const uint32_t* _
       rows += 1.0;
     }
   }
-  hx = block_sum(hx, lds);
-  rows = block_sum(rows, lds);
+  hx = nnl_block_reduce<kWaves>(hx, NnlSum(), lds);
+  rows = nnl_block_reduce<kWaves>(rows, NnlSum(), lds);
   double hy = 0.0, cols = 0.0;
   for (int j = threadIdx.x; j < cy; j += kThreads) {
     double m = 0.0;
@@ -208,8 +169,8 @@ __global__ __launch_bounds__(kThreads) void table_stats_kernel(const uint32_t* _
       cols += 1.0;
     }
   }
-  hy = block_sum(hy, lds);
-  cols = block_sum(cols, lds);
+  hy = nnl_block_reduce<kWaves>(hy, NnlSum(), lds);
+  cols = nnl_block_reduce<kWaves>(cols, NnlSum(), lds);
   // the reference clamps every cell of the observed x observed table at 1e-20: each empty one adds -1e-20 log(1e-20)
   hxy += (rows * cols - cells_seen) * (-(1e-20 * log(1e-20)));
   if (threadIdx.x == 0) {
@@ -272,8 +233,8 @@ __global__ __launch_bounds__(kThreads) void cat_cont_kernel(const int32_t* __res
           mx = fmax(mx, d);
         }
       }
-      mn = wave_min(mn);
-      mx = wave_max(mx);
+      mn = nnl_wave_min(mn);
+      mx = nnl_wave_max(mx);
       if (lane == 0) {                     // this wave's own slot: no other wave touches it
         mm[p][w][0] = fmin(mm[p][w][0], mn);
         mm[p][w][1] = fmax(mm[p][w][1], mx);
@@ -317,8 +278,8 @@ __global__ __launch_bounds__(kThreads) void cat_cont_final_kernel(const double* 
     q += g[k * 3 + 2];
     ne += g[k * 3] > 0.0 ? 1.0 : 0.0;
   }
-  const double N = block_sum(a, lds), S1 = block_sum(b, lds), S2 = block_sum(q, lds);
-  ne = block_sum(ne, lds);
+  const double N = nnl_block_reduce<kWaves>(a, NnlSum(), lds), S1 = nnl_block_reduce<kWaves>(b, NnlSum(), lds), S2 = nnl_block_reduce<kWaves>(q, NnlSum(), lds);
+  ne = nnl_block_reduce<kWaves>(ne, NnlSum(), lds);
   if (N == 0.0) {
     if (threadIdx.x < 6) o[threadIdx.x] = 0.0;
     return;
@@ -333,8 +294,8 @@ __global__ __launch_bounds__(kThreads) void cat_cont_final_kernel(const double* 
       dev = fmax(dev, fabs(d));
     }
   }
-  between = block_sum(between, lds);
-  dev = block_max(dev, lds);
+  between = nnl_block_reduce<kWaves>(between, NnlSum(), lds);
+  dev = nnl_block_reduce<kWaves>(dev, NnlMax(), lds);
   if (threadIdx.x == 0) {
     const unsigned long long* keys = reinterpret_cast<const unsigned long long*>(g + (int64_t)card * 3);
     o[0] = N;
@@ -410,9 +371,9 @@ __global__ __launch_bounds__(kThreads) void cont_cont_kernel(const double* __res
       }
 #pragma unroll
       for (int k = 0; k < kCorK; ++k) {
-        if (PASS == 1 && (k == 6 || k == 8)) v[k] = wave_min(v[k]);
-        else if (PASS == 1 && (k == 7 || k == 9)) v[k] = wave_max(v[k]);
-        else if (k <= (PASS == 1 ? 5 : 12)) v[k] = wave_sum(v[k]);
+        if (PASS == 1 && (k == 6 || k == 8)) v[k] = nnl_wave_min(v[k]);
+        else if (PASS == 1 && (k == 7 || k == 9)) v[k] = nnl_wave_max(v[k]);
+        else if (k <= (PASS == 1 ? 5 : 12)) v[k] = nnl_wave_sum(v[k]);
       }
       if (lane == 0) {                     // this wave's own slots, tile after tile: a fixed order
 #pragma unroll
@@ -449,9 +410,9 @@ __global__ __launch_bounds__(kThreads) void cont_cont_final_kernel(const double*
   double S[kCorK];
 #pragma unroll
   for (int k = 0; k < kCorK; ++k) {
-    if (PASS == 1 && (k == 6 || k == 8)) S[k] = -block_max(mine ? -src[k] : -inf, lds);
-    else if (PASS == 1 && (k == 7 || k == 9)) S[k] = block_max(mine ? src[k] : -inf, lds);
-    else S[k] = block_sum(mine ? src[k] : 0.0, lds);
+    if (PASS == 1 && (k == 6 || k == 8)) S[k] = -nnl_block_reduce<kWaves>(mine ? -src[k] : -inf, NnlMax(), lds);
+    else if (PASS == 1 && (k == 7 || k == 9)) S[k] = nnl_block_reduce<kWaves>(mine ? src[k] : -inf, NnlMax(), lds);
+    else S[k] = nnl_block_reduce<kWaves>(mine ? src[k] : 0.0, NnlSum(), lds);
   }
   if (threadIdx.x != 0) return;
   double* __restrict__ o = out + gp * 4;

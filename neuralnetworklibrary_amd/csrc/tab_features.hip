@@ -21,40 +21,15 @@ constexpr int kTile = NNL_SEG_SCAN_TILE;
 constexpr int kWaves = kThreads / NNL_WAVE;
 static_assert(kThreads * kItems == kTile, "tile = threads x rows per thread");
 
-__device__ __forceinline__ int wave_incl_max(int v) {
-  const int lane = threadIdx.x & (NNL_WAVE - 1);
-#pragma unroll
-  for (int o = 1; o < NNL_WAVE; o <<= 1) {
-    const int u = __shfl_up(v, o, NNL_WAVE);
-    if (lane >= o) v = max(v, u);
-  }
-  return v;
-}
+struct I2 { int a, b; };      // two maxima travel through one scan
+__device__ __forceinline__ I2 i2_max(I2 x, I2 y) { return I2{max(x.a, y.a), max(x.b, y.b)}; }
 
 // a, b: this thread's maxima.  On return a, b = the maxima over all threads BEFORE this one (-1 for thread 0), ta, tb = over the block.
-__device__ __forceinline__ void block_excl_max2(int& a, int& b, int& ta, int& tb, int* lds) {
-  const int lane = threadIdx.x & (NNL_WAVE - 1), w = threadIdx.x / NNL_WAVE;
-  const int ia = wave_incl_max(a), ib = wave_incl_max(b);
-  if (lane == NNL_WAVE - 1) {
-    lds[w] = ia;
-    lds[kWaves + w] = ib;
-  }
-  __syncthreads();
-  int ea = __shfl_up(ia, 1, NNL_WAVE), eb = __shfl_up(ib, 1, NNL_WAVE);
-  if (lane == 0) ea = eb = -1;
-  ta = tb = -1;
-#pragma unroll
-  for (int k = 0; k < kWaves; ++k) {
-    if (k < w) {
-      ea = max(ea, lds[k]);
-      eb = max(eb, lds[kWaves + k]);
-    }
-    ta = max(ta, lds[k]);
-    tb = max(tb, lds[kWaves + k]);
-  }
-  __syncthreads();      // lds is free again
-  a = ea;
-  b = eb;
+__device__ __forceinline__ void block_excl_max2(int& a, int& b, int& ta, int& tb, I2* lds) {
+  I2 total;
+  const I2 e = nnl_block_scan_exclusive<kWaves>(I2{a, b}, i2_max, I2{-1, -1}, lds, total);
+  a = e.a; b = e.b;
+  ta = total.a; tb = total.b;
 }
 
 struct GapArgs {
@@ -91,7 +66,7 @@ __device__ __forceinline__ void load_items(const GapArgs& a, int64_t p0, int rev
 }
 
 __global__ __launch_bounds__(kThreads) void gaps_tile_max_kernel(GapArgs a) {
-  __shared__ int lds[2 * kWaves];
+  __shared__ I2 lds[kWaves];
   const int rev = blockIdx.y;
   const int64_t tile = blockIdx.x;
   int hv[kItems], ev[kItems];
@@ -111,7 +86,7 @@ __global__ __launch_bounds__(kThreads) void gaps_tile_max_kernel(GapArgs a) {
 
 // one workgroup per direction: tile maxima -> maxima over all EARLIER tiles, in place
 __global__ __launch_bounds__(kThreads) void gaps_carry_scan_kernel(GapArgs a, int64_t ntiles) {
-  __shared__ int lds[2 * kWaves];
+  __shared__ I2 lds[kWaves];
   const int rev = blockIdx.x;
   int run_h = -1, run_e = -1;
   for (int64_t c = 0; c < ntiles; c += kThreads) {
@@ -132,7 +107,7 @@ __global__ __launch_bounds__(kThreads) void gaps_carry_scan_kernel(GapArgs a, in
 }
 
 __global__ __launch_bounds__(kThreads) void gaps_apply_kernel(GapArgs a) {
-  __shared__ int lds[2 * kWaves];
+  __shared__ I2 lds[kWaves];
   __shared__ int carry[2];
   const int rev = blockIdx.y;
   const int64_t tile = blockIdx.x;

@@ -68,7 +68,7 @@ __global__ __launch_bounds__(kBlock) void softmax_ce_fwd_kernel(const float* __r
                                                                  const int64_t* __restrict__ target,
                                                                  float2* __restrict__ stats, float* __restrict__ loss, int V,
                                                                  int32_t* __restrict__ err_flag) {
-  __shared__ float sm[4], ss[4];
+  __shared__ MS red[kBlock / NNL_WAVE];
   const long r = blockIdx.x;
   const float* __restrict__ row = logits + r * V;
   MS acc = {-INFINITY, 0.f};
@@ -87,17 +87,8 @@ __global__ __launch_bounds__(kBlock) void softmax_ce_fwd_kernel(const float* __r
     acc.s = acc.s * expf(acc.m - z) + expf(a - z);
     acc.m = m;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    MS other = {__shfl_xor(acc.m, o, 64), __shfl_xor(acc.s, o, 64)};
-    acc = ms_merge(acc, other);
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) { sm[wave] = acc.m; ss[wave] = acc.s; }
-  __syncthreads();
+  const MS t = nnl_block_reduce<kBlock / NNL_WAVE>(acc, ms_merge, red);
   if (threadIdx.x == 0) {
-    MS t = {sm[0], ss[0]};
-    for (int w = 1; w < 4; ++w) t = ms_merge(t, MS{sm[w], ss[w]});
     const float ls = logf(t.s);
     stats[r] = make_float2(t.m, ls);
     const int64_t tg = target[r];
@@ -111,13 +102,8 @@ __global__ void mean_kernel(const float* __restrict__ v, float* __restrict__ out
   __shared__ float red[kBlock];
   float a = 0.f;
   for (long i = threadIdx.x; i < n; i += kBlock) a += v[i];
-  red[threadIdx.x] = a;
-  __syncthreads();
-  for (int w = kBlock / 2; w > 0; w >>= 1) {
-    if (threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) out[0] = red[0] / (float)n;
+  a = nnl_block_tree_reduce<kBlock>(a, NnlSum(), red);
+  if (threadIdx.x == 0) out[0] = a / (float)n;
 }
 
 // dlogits[r,v] = (p - [v == target[r]]) * gup / rows, p = exp((logits[r,v] - m[r]) - log s[r]), or exp(logits[r,v] - (m[r] + log s[r])) for
@@ -227,8 +213,11 @@ namespace {
 constexpr int kRegBlock = 256;
 constexpr int kRegMaxBlocks = 1024;
 
+struct ArTar { float ar, tar; };        // the two sums travel through one tree
+__device__ __forceinline__ ArTar artar_add(ArTar a, ArTar b) { return ArTar{a.ar + b.ar, a.tar + b.tar}; }
+
 __global__ __launch_bounds__(kRegBlock) void seq_reg_partial_kernel(const float* __restrict__ h, float* __restrict__ part, int T, long R) {
-  __shared__ float red[2][kRegBlock];
+  __shared__ ArTar red[kRegBlock];
   float ar = 0.f, tar = 0.f;
   for (long c = (long)blockIdx.x * kRegBlock + threadIdx.x; c < R; c += (long)gridDim.x * kRegBlock) {
     float prev = h[c];
@@ -254,29 +243,19 @@ __global__ __launch_bounds__(kRegBlock) void seq_reg_partial_kernel(const float*
       prev = v;
     }
   }
-  red[0][threadIdx.x] = ar; red[1][threadIdx.x] = tar;
-  __syncthreads();
-  for (int w = kRegBlock / 2; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) { red[0][threadIdx.x] += red[0][threadIdx.x + w]; red[1][threadIdx.x] += red[1][threadIdx.x + w]; }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) { part[2 * blockIdx.x] = red[0][0]; part[2 * blockIdx.x + 1] = red[1][0]; }
+  const ArTar s = nnl_block_tree_reduce<kRegBlock>(ArTar{ar, tar}, artar_add, red);
+  if (threadIdx.x == 0) { part[2 * blockIdx.x] = s.ar; part[2 * blockIdx.x + 1] = s.tar; }
 }
 
 // out[0] = alpha*ar + beta*tar, out[1] = ar = mean(h^2), out[2] = tar
 __global__ __launch_bounds__(kRegBlock) void seq_reg_final_kernel(const float* __restrict__ part, int nparts, float* __restrict__ out,
                                                                     float alpha, float beta, float inv_n_ar, float inv_n_tar) {
-  __shared__ float red[2][kRegBlock];
+  __shared__ ArTar red[kRegBlock];
   float ar = 0.f, tar = 0.f;
   for (int i = threadIdx.x; i < nparts; i += kRegBlock) { ar += part[2 * i]; tar += part[2 * i + 1]; }
-  red[0][threadIdx.x] = ar; red[1][threadIdx.x] = tar;
-  __syncthreads();
-  for (int w = kRegBlock / 2; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) { red[0][threadIdx.x] += red[0][threadIdx.x + w]; red[1][threadIdx.x] += red[1][threadIdx.x + w]; }
-    __syncthreads();
-  }
+  const ArTar s = nnl_block_tree_reduce<kRegBlock>(ArTar{ar, tar}, artar_add, red);
   if (threadIdx.x == 0) {
-    const float a = red[0][0] * inv_n_ar, t = red[1][0] * inv_n_tar;
+    const float a = s.ar * inv_n_ar, t = s.tar * inv_n_tar;
     out[1] = a; out[2] = t;
     out[0] = alpha * a + beta * t;
   }
