@@ -731,6 +731,41 @@ int nnl_detect_aug(const uint8_t* arena, int64_t arena_bytes, const nnl_image_de
                    int64_t bs, int64_t Hp, int64_t Wp, int64_t N, int64_t row_jit, int64_t col_jit, double rand_scale,
                    const float* mean_std, float* out, float* boxes, int64_t* cats, void* stream);
 
+/* ---- K16: the resident image set — channel statistics and resample of uint8 arenas (device_data.ImageStore) ------------------
+ * Arena and descriptor convention of K9: uint8 HWC RGB images back to back, desc[i] = {byte offset, H, W}; offsets are arbitrary
+ * (no alignment is assumed).  Both entries validate every descriptor row they use IN THE KERNEL against the arena size (offset >= 0,
+ * 1 <= H, W <= 2^24, offset + 3 H W <= bytes) and read or write nothing for a row that fails; no byte outside [arena, arena +
+ * arena_bytes) is read, also not by the 16-byte loads at an image's unaligned ends.  Both are stream-ordered and do not synchronise.
+ *
+ * nnl_image_stats (get_stats, Applications/Vision.py:93-118; the per-image means of TransformBBox's lighting, :576): out uint64
+ * [count, 6], row k for image first + k: out[k][c] = sum of the raw byte values of channel c, out[k][3 + c] = sum of their squares.
+ * Integer arithmetic only (uint32 per load, uint64 above, one 64-bit integer atomic per workgroup and sum): the result is exact and
+ * does not depend on the order of addition or on how an image is split.  An image is cut into NNL_IMAGE_STATS_TILE_BYTES-byte tiles
+ * that `split` workgroups take in turn (split = twice the tiles of the arena's mean image, at most 256), so one large image does not
+ * run on one CU.  The entry zeroes `out`.  Status: the return value covers the host-visible arguments (null pointers, an empty arena,
+ * a window outside [0, n_images)) and the launch; a descriptor row that fails the validation above is reported in its row of `out`,
+ * all six entries = NNL_IMAGE_STATS_INVALID (no image reaches that value: 255^2 2^48 < 2^64 - 1), and the caller must raise
+ * (ops.image_stats does).
+ *
+ * nnl_image_resize_u8 (save_resized, Vision.py:64-91; ImageStore's presize): image i of src is resampled to the H, W of dst_desc[i]
+ * and written at dst_desc[i].offset.  THE DEFINITION, per destination pixel (oy, ox) and channel, Hs x Ws -> Hd x Wd, every operation
+ * rounded to fp32 on its own (compiled without floating-point contraction):
+ *   sy = (float)((double)Hs / (double)Hd);  fy = ((float)oy + 0.5f) * sy - 0.5f;  y0 = floor(fy);  wy = fy - y0;
+ *   ya = clamp(y0, 0, Hs - 1);  yb = clamp(y0 + 1, 0, Hs - 1);            and sx, fx, x0, wx, xa, xb likewise from Ws, Wd, ox
+ *   top = v[ya][xa] * (1 - wx) + v[ya][xb] * wx;   bot = v[yb][xa] * (1 - wx) + v[yb][xb] * wx;      v = (float)byte
+ *   dst = (uint8) min(max(rintf(top * (1 - wy) + bot * wy), 0), 255)                                  rintf: ties to even
+ * i.e. the half-pixel taps of K9's resize (iaug_resize_scale, iaug_resize_taps) and its interpolation order (iaug_resized_pixel)
+ * without the division by 255; no antialiasing.  Hd = Hs and Wd = Ws reproduces the source bytes.  It is NOT cv2.resize on uint8
+ * images: OpenCV interpolates those with 11-bit fixed-point weights, and its bytes differ from these by +-1 in places; OpenCV is
+ * not available where this library is tested, so no claim is made against it.  A pair of rows of which either fails the validation
+ * is skipped (nothing written). */
+#define NNL_IMAGE_STATS_TILE_BYTES 16384
+#define NNL_IMAGE_STATS_INVALID 0xffffffffffffffffull
+int nnl_image_stats(const uint8_t* arena, int64_t arena_bytes, const nnl_image_desc_t* desc, int64_t n_images, int64_t first,
+                    int64_t count, uint64_t* out, void* stream);
+int nnl_image_resize_u8(const uint8_t* src_arena, int64_t src_bytes, const nnl_image_desc_t* src_desc, uint8_t* dst_arena,
+                        int64_t dst_bytes, const nnl_image_desc_t* dst_desc, int64_t n_images, void* stream);
+
 /* ---- K8: fused multi-tensor Optimizer.step ------------------------------------------------------------------------
  * Replaces Optimizer.step (General/Optimizer.py:58-70): decoupled weight decay X *= 1 - wd_g*lr_g (:60-67), global-norm
  * clip (:54-56, torch.nn.utils.clip_grad_norm_) and the torch.optim SGD(momentum) / Adam update (General/Learner.py:17-19)

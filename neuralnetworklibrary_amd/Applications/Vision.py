@@ -11,11 +11,17 @@ K9), replacing the per-image cv2 / numpy `Transform.__call__` (:449-507) in Data
 (TransformBBox :519-612, AspectRatioSampler / AspectRatioCollater :700-812, 'bbox' datasets) works the same way:
 `device_data.DetectionBatches` groups the images by aspect ratio and one kernel per minibatch (ops.detect_aug, K10) lights,
 normalises, flips, resizes, jitters and pads the images and flips, scales and shifts their boxes in float64.
-Out of scope here: file decode and the csv / folder / json constructors (the data classes take decoded H x W x 3 uint8 arrays),
-`pad` and `max_noise` (cv2.GaussianBlur), TransformBBoxShowPreds, TTA_bbox and TransformBBox.get_values, and ImageLearner's
-display helpers (show_images, show_bbox_preds).  Scoring a detector runs on the device too: coco_pascal_eval
+Image FILES (§1.1 open_image / save_resized / get_stats / get_cat_counts / plot_imgsize_histograms :54-189, §4 ImageDataObj.from_csv /
+from_folders / from_json_bbox :901-1200): a folder is decoded once with Pillow into a device_data.ImageStore (threaded, chunked,
+optionally downscaled on upload by ops.image_resize_u8, K16), the datasets hold handles of it, and get_stats takes exact integer
+channel sums on the device (ops.image_stats, K16).  The data classes also still take decoded H x W x 3 uint8 arrays.
+Out of scope here: `pad` and `max_noise` (cv2.GaussianBlur), TransformBBoxShowPreds and TransformBBox.get_values, the display
+helpers ShowImages, ShowImages_from_folder and show_image, and ImageLearner's display helpers (show_images, show_bbox_preds)
+(SURVEY.md §2.1 rows 9, 12).  Scoring a detector runs on the device too: coco_pascal_eval
 (the COCO / Pascal protocol of pycocotools' COCOeval for boxes) and mAP_device (ops.det_eval_coco / ops.det_map, K14).
 """
+import os
+
 import numpy as np
 import torch
 import torch.nn as nn
@@ -44,6 +50,96 @@ imagenet_stats = [np.array([0.485, 0.456, 0.406]), np.array([0.229, 0.224, 0.225
 alternate_stats = [np.array([0.5, 0.5, 0.5]), np.array([0.5, 0.5, 0.5])]
 Pascal_thresholds = [0.5]
 COCO_thresholds = [0.5, 0.55, 0.6, 0.65, 0.7, 0.75, 0.8, 0.85, 0.9, 0.95]
+
+
+# ---- §1.1 general utilities: image files (Vision.py:54-189) --------------------------------------------------------
+# ShowImages, ShowImages_from_folder, show_image and TransformBBoxShowPreds (:274-397, :614-640) are display helpers: out of scope.
+
+def _list_images(folder):
+    "the entries of `folder`, sorted, without macOS `._*` resource forks (the reference takes os.listdir's arbitrary order)"
+    return sorted(f for f in os.listdir(folder) if f[:2] != '._')
+
+
+def open_image_u8(path):
+    """An image file as a uint8 H x W x 3 RGB array (device_data.decode_image_u8): Pillow, no EXIF transpose; L, P, RGBA, LA and CMYK
+    files are converted to RGB; 16-bit and float files, and files that cannot be decoded, raise ValueError naming the file."""
+    from ..device_data import decode_image_u8
+    return decode_image_u8(path)
+
+
+def open_image(img_name):
+    "An image file as float32 RGB in [0, 1], H x W x 3 (Vision.py:54-62), through open_image_u8."
+    return open_image_u8(img_name).astype(np.float32) / 255
+
+
+def _folder_files(img_folder, img_names=None):
+    img_folder = correct_foldername(img_folder)
+    names = _list_images(img_folder) if img_names is None else list(img_names)
+    return img_folder, names
+
+
+def get_stats(img_folder, img_names=None):
+    """[means, stds] (float64 arrays of 3: red, green, blue) over the images `img_names` of `img_folder`, default all of them
+    (Vision.py:93-118): the folder is decoded once into a device_data.ImageStore and the moments come from exact integer channel
+    sums taken on the GPU (ImageStore.channel_stats; the reference averages float32 per-image means on the host).  mean_c is the
+    average over images of the image's channel mean, not pixel-weighted, as in the reference."""
+    from ..device_data import ImageStore
+    img_folder, names = _folder_files(img_folder, img_names)
+    return ImageStore.from_files([img_folder + n for n in names]).channel_stats()
+
+
+def get_cat_counts(csv_file, skip_first=True, plot_hist=True):
+    """Images per category of a single-label csv (`img_name, category` rows; skip_first=False if there is no header row), as a
+    DataFrame with columns 'category' and 'count' in descending count; plot_hist also draws the histogram of the counts
+    (Vision.py:120-150)."""
+    import pandas as pd
+    df = pd.read_csv(csv_file, names=['img_name', 'category'], skiprows=1 if skip_first else 0)
+    cat_counts = df['category'].value_counts()
+    cat_counts = pd.DataFrame({'category': list(cat_counts.index), 'count': list(cat_counts)})
+    if plot_hist:
+        import matplotlib.pyplot as plt
+        plt.hist(cat_counts['count'])
+        plt.xlabel('number images in category')
+        plt.ylabel('frequency')
+    return cat_counts
+
+
+def plot_imgsize_histograms(foldername, ranges=None, num_bins=10):
+    """Histograms of the row sizes, column sizes and aspect ratios (W / H) of the images in `foldername` (Vision.py:152-189).
+    ranges = (row_range, col_range, aspect_ratio_range), each [min, max] or None; num_bins: one int or three.  The sizes are read
+    from the file headers: nothing is decoded.  Returns (rowsizes, colsizes, aspect_ratios)."""
+    import matplotlib.pyplot as plt
+    from ..device_data import _header_size
+    foldername, names = _folder_files(foldername)
+    if ranges is None: ranges = (None, None, None)
+    if type(num_bins) == int: num_bins = (num_bins, num_bins, num_bins)
+    sizes = [_header_size(foldername + n) for n in names]
+    rowsizes, colsizes = [h for h, _ in sizes], [w for _, w in sizes]
+    aspect_ratios = [w / h for h, w in sizes]
+    plt.figure(figsize=(14, 10))
+    for k, (values, title) in enumerate([(rowsizes, 'row sizes'), (colsizes, 'col sizes'), (aspect_ratios, 'aspect ratios')]):
+        plt.subplot(2, 2, k + 1)
+        plt.hist(values, range=ranges[k], bins=num_bins[k])
+        plt.title(title)
+    return rowsizes, colsizes, aspect_ratios
+
+
+def save_resized(img_folder, new_folder, sz):
+    """Resized copies of the images of `img_folder` in `new_folder` (Vision.py:64-91).  sz int: the shorter side becomes sz (the longer
+    int(longer * sz / shorter)), smaller images are ENLARGED, as in the reference; sz = (h, w): every image becomes h x w.  The folder
+    is decoded and resampled on the GPU (ops.image_resize_u8: half-pixel bilinear on float(v), round to nearest even — not the
+    fixed-point arithmetic of cv2.resize on uint8, so single bytes may differ by 1 from the reference's files) and Pillow writes the
+    files under their own names."""
+    from PIL import Image
+    from ..device_data import ImageStore
+    img_folder, names = _folder_files(img_folder)
+    new_folder = correct_foldername(new_folder)
+    os.makedirs(new_folder, exist_ok=True)
+    for lo in range(0, len(names), 256):                          # a bounded number of images is resident at a time
+        part = names[lo:lo + 256]
+        store = ImageStore.from_files([img_folder + n for n in part], presize=sz, _enlarge=True)
+        for i, n in enumerate(part):
+            Image.fromarray(store[i].numpy()).save(new_folder + n)
 
 
 def jaccard(Boxes1, Boxes2):
@@ -297,7 +393,9 @@ class ImageDataset(object):
     'test'.  images: list of {'img': H x W x 3 uint8 array (decoded RGB), 'target': int label | 0-1 array | 0 for test}; for 'bbox'
     'target' is a standard bbox list [(box [xmin, ymin, xmax, ymax], category), ...] (or [] or 0) and every image also carries
     'scale' and 'aspect_ratio' (get_AspectRatioScale), as the reference's from_json_bbox stores them.  The reference keeps file
-    names under 'img' and decodes per item; decoding is left to the caller here, and a file name raises.
+    names under 'img' and decodes per item; here 'img' is a decoded array or a device_data.ResidentImage (a handle of an image that
+    an ImageStore already decoded and uploaded: what from_csv / from_folders / from_json_bbox put there, next to 'file', the name
+    relative to IMG_PATH), and a file name raises.
     Attributes as the reference: IMG_PATH, images, transform, target_type, ds_type, y."""
 
     def __init__(self, IMG_PATH, images, transform, target_type, ds_type):
@@ -313,12 +411,17 @@ class ImageDataset(object):
                 if 'scale' not in im or 'aspect_ratio' not in im:
                     raise ValueError("a 'bbox' dataset needs images[i]['scale'] and images[i]['aspect_ratio']: "
                                      "aspect_ratio, scale = get_AspectRatioScale(img, min_side, max_side)")
+        from ..device_data import ResidentImage
         for im in images:
             a = im['img']
             if isinstance(a, str):
-                raise NotImplementedError("images[i]['img'] is a file name: image decode is not built; pass the decoded H x W x 3 uint8 array")
+                raise NotImplementedError("images[i]['img'] is a file name: an ImageDataset does not decode per item; build the data with "
+                                          "ImageDataObj.from_csv / from_folders / from_json_bbox (or device_data.ImageStore.from_files), or "
+                                          "pass the decoded H x W x 3 uint8 array")
+            if isinstance(a, ResidentImage):
+                continue
             if not (isinstance(a, np.ndarray) and a.dtype == np.uint8 and a.ndim == 3 and a.shape[2] == 3 and a.size > 0):
-                raise ValueError("images[i]['img'] must be a non-empty H x W x 3 uint8 array")
+                raise ValueError("images[i]['img'] must be a non-empty H x W x 3 uint8 array or a device_data.ResidentImage")
         self.IMG_PATH = IMG_PATH
         self.images = images
         self.transform = transform
@@ -342,7 +445,8 @@ class ImageDataObj(object):
     target_type 'bbox' (transforms = get_transforms_bbox(...)): the loaders are device_data.DetectionBatches; train_dl groups the
     images by aspect ratio into minibatches of bs (AspectRatioSampler, :700-728), val_dl and test_dl have batch size 1 in dataset
     order (:865-870; Learner.predict relies on it), and sz is None: every minibatch has its own padded size.
-    The file-based constructors (from_csv, from_folders, from_json_bbox) need image decode and are not built."""
+    The file-based constructors from_csv, from_folders and from_json_bbox (Vision.py:901-1200) decode every image folder once into
+    a device_data.ImageStore and hand the datasets handles of it: train and validation sets split from one folder share one arena."""
 
     def __init__(self, PATH, target_type, categories, bs, transforms, train_images, val_images,
                  test_images=None, train_name='train', val_name='val', test_name=None, num_workers=8, seed=0):
@@ -367,6 +471,230 @@ class ImageDataObj(object):
         self.val_dl = ImageBatches(self.val_ds, bs, shuffle=False, seed=seed)
         if test_name: self.test_dl = ImageBatches(self.test_ds, bs, shuffle=False, seed=seed)
         else: self.test_dl = None
+
+    def get_stats(self, ds_type='train'):
+        """[means, stds] of the 'train', 'val' or 'test' set as the module-level get_stats defines them, from the images that are
+        already resident: nothing is decoded again (a set of decoded arrays is uploaded to a store of its own for the call)."""
+        from ..device_data import ImageStore, ResidentImage
+        ds = getattr(self, ds_type + '_ds')
+        if ds is None:
+            raise ValueError('this ImageDataObj has no %r set' % (ds_type,))
+        imgs = [im['img'] for im in ds.images]
+        if isinstance(imgs[0], ResidentImage):
+            return imgs[0].store.channel_stats([h.index for h in imgs])
+        return ImageStore.from_arrays(imgs).channel_stats()
+
+    @staticmethod
+    def convert_labels_multi(targets, categories_rev):
+        """[category names] per image -> float32 presence / absence vectors over `categories_rev` (name -> index), Vision.py:876-898
+        (which rewrites a DataFrame column in place; this takes and returns lists).  An unknown category raises ValueError naming it."""
+        out = []
+        for names in targets:
+            v = np.zeros(len(categories_rev))
+            for name in names:
+                if name not in categories_rev:
+                    raise ValueError('category %r is not among the categories of the training csv' % (name,))
+                v[categories_rev[name]] = 1
+            out.append(v.astype('float32'))
+        return out
+
+    @staticmethod
+    def _stores(PATH, folder_files, presize, decode_threads):
+        "{folder: {file name: ResidentImage}}: ONE ImageStore per image folder, over the files that are asked of it in first-seen order"
+        from ..device_data import ImageStore
+        handles = {}
+        for folder, files in folder_files.items():
+            names = list(dict.fromkeys(files))
+            store = ImageStore.from_files([PATH + folder + '/' + f for f in names], presize=presize, threads=decode_threads)
+            handles[folder] = {f: store[i] for i, f in enumerate(names)}
+        return handles
+
+    @classmethod
+    def from_csv(cls, PATH, transforms, bs, train_csv='train.csv', val_csv=None, test_csv=None, train_name='train',
+                 val_name=None, test_name=None, target_type='single_label', val_frac=0.2, skip_first=True, suffix='',
+                 *, presize=None, seed=0, decode_threads=None):
+        """An ImageDataObj from csv files, 'single_label' or 'multi_label' (Vision.py:901-1014; same arguments, order and defaults).
+        PATH holds the image folders train_name / val_name / test_name and the csv files train_csv / val_csv / test_csv, rows
+        `img, category` (single) or `img, cat1 cat2 ...` (multi), with a header row iff skip_first.  suffix is appended to every
+        csv file name.  Without val_name a random val_frac of the training rows becomes the validation set (SplitTrainVal, which
+        draws from numpy's GLOBAL generator as the reference does: np.random.seed(k) fixes the split) and both sets read ONE
+        resident copy of the training folder.  A test folder needs no csv: its files are listed.  categories: the sorted category
+        names of the TRAINING csv; targets: int64 labels, or float32 presence vectors.
+        Keyword-only additions: presize (device_data.ImageStore.from_files: store large images downscaled, never enlarged), seed (of
+        the loaders' permutations and transform draws), decode_threads.
+        Deliberate differences from the reference: a listed test folder is sorted and its `._*` files are skipped (os.listdir order
+        is arbitrary); a category of a val / test csv that the training csv lacks raises ValueError naming it (the reference fails
+        later, in a cast); nothing is printed; every image is decoded HERE, once, so an unreadable file raises at construction."""
+        import pandas as pd
+        if target_type not in ('single_label', 'multi_label'):
+            raise ValueError("from_csv builds 'single_label' or 'multi_label' data (got %r)" % (target_type,))
+        PATH = correct_foldername(PATH)
+
+        def read(csv_name):
+            df = pd.read_csv(PATH + csv_name, names=['img_name', 'target'], skiprows=1 if skip_first else 0)
+            target = df['target'].str.split() if target_type == 'multi_label' else df['target']
+            return [{'img_name': n, 'target': t} for n, t in zip(df['img_name'], target)]
+
+        TRAIN = read(train_csv)
+        if target_type == 'single_label':
+            category_names = sorted(set(r['target'] for r in TRAIN))
+        else:
+            category_names = sorted(set(cat for r in TRAIN for cat in r['target']))
+        categories = {i: category_names[i] for i in range(len(category_names))}
+        categories_rev = {category_names[i]: i for i in range(len(category_names))}
+
+        if val_csv:
+            VAL = read(val_csv)
+        else:
+            TRAIN, VAL = SplitTrainVal(TRAIN, val_frac=val_frac)
+            val_name = train_name
+        if test_name and test_csv:
+            TEST = read(test_csv)
+        elif test_name:
+            TEST = [{'img_name': f, 'target': 0} for f in _list_images(PATH + test_name)]
+        else:
+            TEST = None
+
+        def convert(rows, labelled, add_suffix):
+            names = [str(r['img_name']) + (suffix if add_suffix else '') for r in rows]
+            if not labelled:
+                return names, [r['target'] for r in rows]
+            if target_type == 'multi_label':
+                return names, cls.convert_labels_multi([r['target'] for r in rows], categories_rev)
+            for r in rows:
+                if r['target'] not in categories_rev:
+                    raise ValueError('category %r is not among the categories of the training csv' % (r['target'],))
+            return names, [int(categories_rev[r['target']]) for r in rows]
+
+        sets = {'train': (train_name,) + convert(TRAIN, True, True), 'val': (val_name,) + convert(VAL, True, True)}
+        if TEST is not None:
+            sets['test'] = (test_name,) + convert(TEST, bool(test_csv), bool(test_csv))
+        return cls._from_lists(PATH, target_type, categories, bs, transforms, sets, train_name, val_name, test_name, presize, seed,
+                               decode_threads)
+
+    @classmethod
+    def _from_lists(cls, PATH, target_type, categories, bs, transforms, sets, train_name, val_name, test_name, presize, seed,
+                    decode_threads, extra=None):
+        """sets: {'train' | 'val' | 'test': (folder, [file names], [targets])} -> the stores (one per folder), the image lists with
+        handles, then cls(...).  extra: {'train' | ...: [dict of further keys per image]} ('bbox': id, aspect_ratio, scale)."""
+        folder_files = {}
+        for folder, names, _ in sets.values():
+            folder_files.setdefault(folder, []).extend(names)
+        handles = cls._stores(PATH, folder_files, presize, decode_threads)
+        lists = {}
+        for k, (folder, names, targets) in sets.items():
+            lists[k] = [dict({'img': handles[folder][f], 'file': f, 'target': t}, **(extra[k][i] if extra else {}))
+                        for i, (f, t) in enumerate(zip(names, targets))]
+        return cls(PATH, target_type, categories, bs, transforms, lists['train'], lists['val'], lists.get('test'),
+                   train_name, val_name, test_name, seed=seed)
+
+    @classmethod
+    def from_folders(cls, PATH, transforms, bs, train_name='train', val_name=None, test_name=None, val_frac=0.2,
+                     *, presize=None, seed=0, decode_threads=None):
+        """A 'single_label' ImageDataObj from labelled folders (Vision.py:1016-1060; same arguments, order and defaults):
+        PATH/train_name (and PATH/val_name) hold one sub-folder per category with that category's images; PATH/test_name holds the
+        test images themselves.  Without val_name a random val_frac of the training images becomes the validation set (SplitTrainVal:
+        numpy's global generator) and both sets read one resident copy.  Image names are 'category/file'.
+        Keyword-only additions: presize, seed, decode_threads (see from_csv).  Deliberate differences: every os.listdir result is
+        sorted and `._*` entries are skipped (categories and files); nothing is printed."""
+        PATH = correct_foldername(PATH)
+        category_names = _list_images(PATH + train_name)
+        categories = {i: category_names[i] for i in range(len(category_names))}
+        categories_rev = {category_names[i]: i for i in range(len(category_names))}
+
+        def labelled(folder):
+            return [{'img': cat + '/' + f, 'target': categories_rev[cat]} for cat in category_names for f in _list_images(PATH + folder + '/' + cat)]
+
+        train_images = labelled(train_name)
+        if val_name:
+            val_images = labelled(val_name)
+        else:
+            val_name = train_name
+            train_images, val_images = SplitTrainVal(train_images, val_frac=val_frac)
+        rows = lambda folder, L: (folder, [r['img'] for r in L], [r['target'] for r in L])
+        sets = {'train': rows(train_name, train_images), 'val': rows(val_name, val_images)}
+        if test_name:
+            test_files = _list_images(PATH + test_name)
+            sets['test'] = (test_name, test_files, [0] * len(test_files))
+        return cls._from_lists(PATH, 'single_label', categories, bs, transforms, sets, train_name, val_name, test_name, presize, seed,
+                               decode_threads)
+
+    @classmethod
+    def from_json_bbox(cls, PATH, transforms, bs, train_json='train.json', val_json=None, test_json=None,
+                       train_name='train', val_name=None, test_name=None, val_frac=0.2, suffix='', get_ARS=[608, 1216],
+                       *, presize=None, seed=0, decode_threads=None):
+        """A 'bbox' ImageDataObj from COCO / Pascal style json annotation files (Vision.py:1062-1200; same arguments, order and
+        defaults).  A json holds 'categories' [{id, name}], 'images' [{id, file_name}] and 'annotations' [{image_id, bbox = [xmin,
+        ymin, width, height], category_id}].  categories: index -> name in the TRAINING json's order; data.cat2dscat: index -> dataset
+        category id.  Annotations with ignore == 1 or iscrowd == 1 are skipped; boxes become min-max boxes (hw_to_mm); every image
+        carries 'id', 'aspect_ratio' and 'scale' = get_AspectRatioScale(size, *get_ARS), the size read from the file's HEADER (the
+        reference decodes every image for it).  Without val_name a random val_frac of the training images is the validation set
+        (SplitTrainVal: numpy's global generator), sharing the resident copy.  val_dl and test_dl have batch size 1.
+        Keyword-only additions: seed, decode_threads (see from_csv); presize is refused with ValueError: boxes and 'scale' are in
+        original pixels.  Deliberate differences: a listed test folder is sorted (its `._*` files are skipped, as in the reference);
+        nothing is printed."""
+        import json
+        if presize is not None:
+            raise ValueError("from_json_bbox stores the images at their original size: boxes and 'scale' are in original pixels (presize=%r)" % (presize,))
+        from ..device_data import _header_size
+        PATH = correct_foldername(PATH)
+
+        def load(name):
+            with open(PATH + name) as f:
+                return json.load(f)
+
+        trn_json = load(train_json)
+        val_json = load(val_json) if val_json else None
+        test_json = load(test_json) if test_json else None
+        cats = trn_json['categories']
+        categories = {i: cats[i]['name'] for i in range(len(cats))}
+        cat2dscat = {i: cats[i]['id'] for i in range(len(cats))}
+        dscat2cat = {v: k for k, v in cat2dscat.items()}
+
+        def ars(folder, img_name):
+            H, W = _header_size(PATH + folder + '/' + img_name)
+            return get_AspectRatioScale(np.broadcast_to(np.uint8(0), (H, W, 3)), get_ARS[0], get_ARS[1])
+
+        def annotated(js, folder):
+            images = {}
+            for image in js['images']:
+                ID, img_name = image['id'], image['file_name'] + suffix
+                images[ID] = {'id': ID, 'img': img_name, 'target': []}
+                if folder is not None:
+                    images[ID]['aspect_ratio'], images[ID]['scale'] = ars(folder, img_name)
+            for ann in js['annotations']:
+                if (('ignore' in ann) and (ann['ignore'] == 1)) or (('iscrowd' in ann) and (ann['iscrowd'] == 1)):
+                    continue
+                images[ann['image_id']]['target'].append((hw_to_mm(ann['bbox']), dscat2cat[ann['category_id']]))
+            return list(images.values())
+
+        train_images = annotated(trn_json, train_name)
+        if val_name:
+            val_images = annotated(val_json, val_name)
+        else:
+            train_images, val_images = SplitTrainVal(train_images, val_frac=val_frac)
+            val_name = train_name
+        if test_name and test_json:
+            test_images = annotated(test_json, None)
+        elif test_name:
+            test_images = [{'img': fn, 'target': 0} for fn in _list_images(PATH + test_name)]
+        else:
+            test_images = None
+        if test_name:
+            for im in test_images:
+                im['aspect_ratio'], im['scale'] = ars(test_name, im['img'])
+
+        def rows(folder, L):
+            return (folder, [r['img'] for r in L], [r['target'] for r in L])
+        keys = lambda L: [{k: v for k, v in r.items() if k not in ('img', 'target')} for r in L]
+        sets = {'train': rows(train_name, train_images), 'val': rows(val_name, val_images)}
+        extra = {'train': keys(train_images), 'val': keys(val_images)}
+        if test_name:
+            sets['test'], extra['test'] = rows(test_name, test_images), keys(test_images)
+        data = cls._from_lists(PATH, 'bbox', categories, bs, transforms, sets, train_name, val_name, test_name, None, seed,
+                               decode_threads, extra)
+        data.cat2dscat = cat2dscat
+        return data
 
 
 # ---- §5 image classification ---------------------------------------------------------------------------------

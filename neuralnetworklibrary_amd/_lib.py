@@ -146,6 +146,8 @@ SIGNATURES = {
     'nnl_image_aug': (C.c_int, [c_p, i64, c_p, i64, c_p, i64, i64, i64, C.POINTER(f32), C.c_int, c_p, c_p, sz, c_p]),
     'nnl_detect_aug': (C.c_int, [c_p, i64, c_p, i64, c_p, c_p, c_p, i64, c_p, i64, i64, i64, i64, i64, i64, f64, C.POINTER(f32),
                                  c_p, c_p, c_p, c_p]),
+    'nnl_image_stats': (C.c_int, [c_p, i64, c_p, i64, i64, i64, c_p, c_p]),
+    'nnl_image_resize_u8': (C.c_int, [c_p, i64, c_p, c_p, i64, c_p, i64, c_p]),
     'nnl_optim_chunk_elems': (i64, []),
     'nnl_optim_patch': (C.c_int, [c_p, c_p, c_p, i64, c_p]),
     'nnl_optim_step': (C.c_int, [c_p, c_p, c_p, i64, C.c_int, c_p, C.c_int, c_p, c_p]),

@@ -20,6 +20,14 @@ by the HIP augmenter (ops.image_aug) — at 5 520 img/s per GPU the reference's 
 categories, in HBM; minibatches grouped by aspect ratio (AspectRatioSampler, Vision.py:700-728); one kernel per minibatch
 (ops.detect_aug) does TransformBBox.__call__ (:559-603) and AspectRatioCollater (:758-812), whose cv2.resize per image in ONE
 DataLoader worker would otherwise set the epoch time of the RetinaNet step.
+
+`ImageStore` is the resident image set itself (K16): built once from decoded arrays or from image FILES (header sizes first, one
+arena allocation, threaded Pillow decode chunk by chunk through a pinned staging buffer, optional downscale on upload by
+ops.image_resize_u8), with exact channel statistics from ops.image_stats.  Datasets whose images are `ResidentImage` handles of one
+store give loaders that read the store's arena: train and validation sets split from one folder share one copy.  A dataset of
+decoded arrays goes through `_upload_images` as before.  For handle-backed detection sets the per-image channel means come from
+the store's integer table by the same expression as on the array path, float32(sum / (255 H W)) with the quotient in fp64, so the
+two agree to the bit (the loaders are tested to within 1 ulp of fp32 of each other, the bound of one rounding).
 """
 import numpy as np
 import torch
@@ -28,7 +36,7 @@ from . import ops
 
 from .dist import shard_bounds
 
-__all__ = ['DeviceBatches', 'ImageBatches', 'DetectionBatches']
+__all__ = ['DeviceBatches', 'ImageBatches', 'DetectionBatches', 'ImageStore', 'ResidentImage', 'decode_image_u8', 'presize_shape']
 
 
 def _map(f, x):
@@ -96,6 +104,244 @@ def _upload_images(images, device):
     return imgs, shapes, arena, torch.from_numpy(desc).to(device)
 
 
+_DEEP_MODES = ('I', 'F', 'I;16', 'I;16B', 'I;16L', 'I;16N')
+_RGB_MODES = ('RGB', 'L', 'P', 'RGBA', 'LA', 'CMYK', '1')
+
+
+def decode_image_u8(path):
+    """One image file as a uint8 H x W x 3 RGB array, through Pillow.  No EXIF transpose (cv2.imread(IMREAD_UNCHANGED), which the
+    reference's open_image uses, applies none either).  Modes L, P, RGBA, LA, CMYK (and 1) go through .convert('RGB'); 16-bit
+    integer and float modes raise ValueError naming the file, as does a file that cannot be decoded.  (Pillow itself reduces a
+    16-bit-per-channel RGB PNG to 8 bits on open; such a file arrives as 'RGB' and cannot be told apart here.)"""
+    from PIL import Image
+    try:
+        with Image.open(path) as im:
+            if im.mode in _DEEP_MODES:
+                raise ValueError('%s: mode %r holds more than 8 bits per channel; convert the file to 8-bit RGB' % (path, im.mode))
+            if im.mode not in _RGB_MODES:
+                raise ValueError('%s: unsupported image mode %r' % (path, im.mode))
+            a = np.asarray(im if im.mode == 'RGB' else im.convert('RGB'), dtype=np.uint8)
+    except ValueError:
+        raise
+    except Exception as e:                                   # Pillow raises OSError / SyntaxError / struct.error on bad files
+        raise ValueError('%s: cannot decode the image (%s: %s)' % (path, type(e).__name__, e))
+    if a.ndim != 3 or a.shape[2] != 3 or a.size == 0:
+        raise ValueError('%s: decoded to shape %r, not H x W x 3' % (path, a.shape))
+    return np.ascontiguousarray(a)
+
+
+def _header_size(path):
+    "(H, W) of an image file from its header: nothing is decoded"
+    from PIL import Image
+    try:
+        with Image.open(path) as im:
+            w, h = im.size
+    except Exception as e:
+        raise ValueError('%s: cannot read the image header (%s: %s)' % (path, type(e).__name__, e))
+    if h < 1 or w < 1:
+        raise ValueError('%s: empty image (%d x %d)' % (path, h, w))
+    return int(h), int(w)
+
+
+def presize_shape(H, W, presize, enlarge=False):
+    """The resident (H, W) of an H x W image under `presize`: None keeps it; (h, w) stores every image at that size; an int s stores
+    an image whose shorter side exceeds s with the shorter side = s and the longer = int(longer * s / shorter) (save_resized's rule,
+    Vision.py:85-88), and a smaller image as it is unless `enlarge`."""
+    if presize is None:
+        return H, W
+    if isinstance(presize, (int, np.integer)):
+        s = int(presize)
+        if s < 1:
+            raise ValueError('presize must be positive (got %r)' % (presize,))
+        if min(H, W) <= s and not (enlarge and min(H, W) < s):
+            return H, W
+        return (s, max(1, int(W * s / H))) if H <= W else (max(1, int(H * s / W)), s)
+    h, w = presize
+    if int(h) < 1 or int(w) < 1:
+        raise ValueError('presize must be positive (got %r)' % (presize,))
+    return int(h), int(w)
+
+
+def _desc_table(shapes):
+    "int64 [n, 3] = (byte offset, H, W) of images stored back to back, and the total byte count"
+    desc = np.zeros((len(shapes), 3), dtype=np.int64)
+    desc[:, 1:] = shapes
+    sizes = 3 * desc[:, 1] * desc[:, 2]
+    desc[1:, 0] = np.cumsum(sizes)[:-1]
+    return desc, int(sizes.sum())
+
+
+class ResidentImage:
+    """Handle of image `index` of an ImageStore: what an ImageDataset carries as images[i]['img'] in place of a decoded array.
+    `.shape` is the resident (H, W, 3); `.numpy()` reads the bytes back (tests and displays: it is a device-to-host copy)."""
+    __slots__ = ('store', 'index')
+
+    def __init__(self, store, index):
+        self.store, self.index = store, int(index)
+
+    @property
+    def shape(self):
+        H, W = self.store.shapes[self.index]
+        return (H, W, 3)
+
+    def numpy(self):
+        off, H, W = (int(v) for v in self.store.desc_host[self.index])
+        return self.store.arena[off:off + 3 * H * W].cpu().numpy().reshape(H, W, 3)
+
+    def __repr__(self):
+        return 'ResidentImage(%d, shape=%r)' % (self.index, self.shape)
+
+
+class ImageStore:
+    """A resident image set, built once and shared by every dataset and loader cut from it: `arena` uint8 [bytes] (HWC RGB images
+    back to back) and `desc` int64 [n, 3] (byte offset, H, W) on `device`, the convention of ops.image_aug / ops.detect_aug.
+    Attributes: arena, desc, desc_host (numpy copy of desc), shapes [(H, W)] as resident, orig_shapes [(H, W)] as decoded, paths
+    (from_files; else None), device.  store[i] is a ResidentImage handle.  Train and validation sets split from one folder hold
+    handles of ONE store, so their loaders read one arena."""
+
+    def __init__(self, arena, desc_host, orig_shapes, paths, device):
+        self.arena, self.device = arena, device
+        self.desc_host = desc_host
+        self.desc = torch.from_numpy(desc_host).to(device)
+        self.shapes = [(int(h), int(w)) for h, w in desc_host[:, 1:]]
+        self.orig_shapes = [(int(h), int(w)) for h, w in orig_shapes]
+        self.paths = paths
+        self._stats = None
+
+    @staticmethod
+    def _device(device):
+        from .General.Core import default_device
+        return torch.device(device if device is not None else default_device())
+
+    @classmethod
+    def from_arrays(cls, arrays, device=None):
+        "a store of decoded uint8 H x W x 3 arrays (one host concatenation, one upload)"
+        device = cls._device(device)
+        imgs = [np.ascontiguousarray(a) for a in arrays]
+        for a in imgs:
+            if not (a.dtype == np.uint8 and a.ndim == 3 and a.shape[2] == 3 and a.size > 0):
+                raise ValueError('ImageStore.from_arrays takes non-empty H x W x 3 uint8 arrays')
+        if not imgs:
+            raise ValueError('ImageStore: no images')
+        shapes = [(a.shape[0], a.shape[1]) for a in imgs]
+        desc, _ = _desc_table(shapes)
+        arena = torch.from_numpy(np.concatenate([a.reshape(-1) for a in imgs])).to(device)
+        return cls(arena, desc, shapes, None, device)
+
+    @classmethod
+    def from_files(cls, paths, device=None, presize=None, threads=None, chunk_bytes=256 << 20, _enlarge=False):
+        """A store of image files.  Every file's size is read from its header first (nothing is decoded), the resident shapes follow
+        from `presize` (presize_shape: an int never enlarges) and the arena is allocated ONCE; the files are then decoded
+        (decode_image_u8) by `threads` workers, chunk by chunk of at most `chunk_bytes` decoded bytes (a chunk holds at least one
+        image), into one pinned staging buffer, and every chunk is copied into its slice of the arena: the host never holds more than
+        one chunk decoded.  With `presize` a chunk goes to a temporary device buffer and ops.image_resize_u8 writes its images into
+        the arena (needs a CUDA device).  threads: default min(16, NNL_DECODE_THREADS or 8), never above 16, never the CPU count.
+        A file whose header cannot be read raises ValueError before anything is allocated; one that fails to decode raises ValueError
+        (naming the file) before its chunk is uploaded, and no store is returned."""
+        from concurrent.futures import ThreadPoolExecutor
+        import os
+        device = cls._device(device)
+        paths = [str(p) for p in paths]
+        if not paths:
+            raise ValueError('ImageStore: no images')
+        if presize is not None and device.type != 'cuda':
+            raise ValueError('ImageStore.from_files: presize resamples on the GPU (ops.image_resize_u8) and needs a CUDA device, got %s' % device)
+        if threads is None:
+            threads = int(os.environ.get('NNL_DECODE_THREADS', 8))
+        threads = max(1, min(16, int(threads)))
+        orig = [_header_size(p) for p in paths]
+        shapes = [presize_shape(H, W, presize, _enlarge) for H, W in orig]
+        desc, total = _desc_table(shapes)
+        src_sizes = [3 * H * W for H, W in orig]
+        chunks, lo, acc = [], 0, 0                          # [lo, hi) runs of images of at most chunk_bytes decoded bytes
+        for i, nb in enumerate(src_sizes):
+            if i > lo and acc + nb > chunk_bytes:
+                chunks.append((lo, i))
+                lo, acc = i, 0
+            acc += nb
+        chunks.append((lo, len(paths)))
+        stage_bytes = max(sum(src_sizes[a:z]) for a, z in chunks)
+        arena = torch.empty(total, dtype=torch.uint8, device=device)
+        stage = torch.empty(stage_bytes, dtype=torch.uint8, pin_memory=device.type == 'cuda')
+        stage_np = stage.numpy()
+
+        def decode(i, off):
+            a = decode_image_u8(paths[i])
+            if (a.shape[0], a.shape[1]) != orig[i]:
+                raise ValueError('%s: decoded to %d x %d, its header says %d x %d' % ((paths[i],) + a.shape[:2] + orig[i]))
+            stage_np[off:off + a.size] = a.reshape(-1)
+
+        with ThreadPoolExecutor(max_workers=threads) as pool:
+            for a, z in chunks:
+                offs = np.concatenate([[0], np.cumsum(src_sizes[a:z])]).astype(np.int64)
+                for f in [pool.submit(decode, i, int(offs[i - a])) for i in range(a, z)]:
+                    f.result()                               # a ValueError of a worker surfaces here, before the upload
+                nb = int(offs[-1])
+                if presize is None:
+                    d0 = int(desc[a, 0])
+                    arena[d0:d0 + nb].copy_(stage[:nb])
+                else:
+                    tmp = stage[:nb].to(device, non_blocking=True)
+                    src = np.stack([offs[:-1], [h for h, _ in orig[a:z]], [w for _, w in orig[a:z]]], axis=1).astype(np.int64)
+                    ops.image_resize_u8(tmp, torch.from_numpy(src).to(device), torch.from_numpy(desc[a:z].copy()).to(device), arena)
+                if device.type == 'cuda':
+                    torch.cuda.current_stream(device).synchronize()     # the staging buffer is written again by the next chunk
+        return cls(arena, desc, orig, paths, device)
+
+    def __len__(self):
+        return len(self.shapes)
+
+    def __getitem__(self, i):
+        i = int(i)
+        if not -len(self) <= i < len(self):
+            raise IndexError('image %d of a store of %d' % (i, len(self)))
+        return ResidentImage(self, i % len(self))
+
+    def stats(self, indices=None):
+        """uint64 numpy [m, 6]: per image the exact channel sums of v and of v^2 over its resident bytes (ops.image_stats; the whole
+        store's table is computed once and kept).  indices: image numbers, default all.  A store that was built on the CPU device
+        (no GPU in reach: the listing logic under test) adds the same integers with numpy over its host arena."""
+        if self._stats is None and self.device.type == 'cuda':
+            self._stats = ops.image_stats(self.arena, self.desc)
+        elif self._stats is None:
+            flat = self.arena.numpy()
+            px = [flat[o:o + 3 * h * w].reshape(-1, 3).astype(np.uint64) for o, h, w in self.desc_host]
+            self._stats = np.stack([np.concatenate([p.sum(axis=0, dtype=np.uint64), (p * p).sum(axis=0, dtype=np.uint64)]) for p in px])
+        return self._stats.copy() if indices is None else self._stats[np.asarray(indices, dtype=np.int64)]
+
+    def channel_stats(self, indices=None):
+        """[means, stds], float64 arrays of 3, with get_stats' definition (Vision.py:93-118): mean_c = the plain average over the
+        images of the image's channel mean of v / 255; var_c = the average over the images of the image's channel mean of
+        (v / 255)^2, minus mean_c^2 (NOT pixel-weighted).  From the exact integer sums, in fp64: per image one quotient
+        sum / (255 H W) resp. sum2 / (255^2 H W), then the average."""
+        t = self.stats(indices)
+        idx = np.arange(len(self)) if indices is None else np.asarray(indices, dtype=np.int64)
+        pixels = np.array([float(self.shapes[i][0] * self.shapes[i][1]) for i in idx], dtype=np.float64)[:, None]
+        n = float(len(idx))
+        means = (t[:, :3].astype(np.float64) / (255.0 * pixels)).sum(axis=0) / n
+        second = (t[:, 3:].astype(np.float64) / (65025.0 * pixels)).sum(axis=0) / n
+        return [means, np.sqrt(second - means ** 2)]
+
+
+def _resident(images, device):
+    """The arena of a dataset's images: (host arrays or None, [(H, W)], arena, desc, store or None, image numbers in the store).
+    Decoded arrays are concatenated and uploaded (`_upload_images`); ResidentImage handles of ONE store on `device` give the store's
+    arena and an index_select of its table: nothing is copied."""
+    handles = [isinstance(im['img'], ResidentImage) for im in images]
+    if not any(handles):
+        return _upload_images(images, device) + (None, None)
+    if not all(handles):
+        raise ValueError("a dataset's images are either all decoded arrays or all handles of one ImageStore")
+    store = images[0]['img'].store
+    if any(im['img'].store is not store for im in images):
+        raise ValueError("a dataset's image handles must belong to one ImageStore")
+    if store.arena.device != torch.empty(0, device=device).device:
+        raise ValueError('the ImageStore lives on %s, the loader on %s' % (store.device, device))
+    idx = np.array([im['img'].index for im in images], dtype=np.int64)
+    desc = store.desc.index_select(0, torch.from_numpy(idx).to(device))
+    return None, [store.shapes[i] for i in idx], store.arena, desc, store, idx
+
+
 class ImageBatches:
     """Iterable of (x, y) minibatches of an Applications.Vision.ImageDataset, transformed on `device` by ops.image_aug.
 
@@ -117,7 +363,7 @@ class ImageBatches:
         self.explicit_params = explicit_params
         self.epoch = 0
         self.dp_info = None          # (rows of the last yielded shard that count, rows of its GLOBAL minibatch): Learner reads it
-        _, self.shapes, self.arena, self.desc = _upload_images(ds.images, self.device)
+        _, self.shapes, self.arena, self.desc, self.store, _ = _resident(ds.images, self.device)
         if ds.ds_type == 'test':
             y = torch.zeros(self.n, dtype=torch.int64)
         elif ds.target_type == 'single_label':
@@ -200,8 +446,11 @@ class DetectionBatches:
         self.epoch = 0
         self.dp_info = None          # (rows of the last yielded shard that count, rows of its GLOBAL minibatch): Learner reads it
         self.last_draws = None       # kept by `with_transform` views only
-        imgs, self.shapes, self.arena, self.desc = _upload_images(ds.images, self.device)
-        sums = np.stack([a.reshape(-1, 3).sum(axis=0, dtype=np.int64) for a in imgs])
+        imgs, self.shapes, self.arena, self.desc, self.store, store_idx = _resident(ds.images, self.device)
+        if self.store is None:
+            sums = np.stack([a.reshape(-1, 3).sum(axis=0, dtype=np.int64) for a in imgs])
+        else:                                                   # the same exact integers, from the store's device-side table
+            sums = self.store.stats(store_idx)[:, :3]
         pixels = np.array([255.0 * H * W for H, W in self.shapes], dtype=np.float64)
         self.image_mean = torch.from_numpy((sums.astype(np.float64) / pixels[:, None]).astype(np.float32)).to(self.device)
         self.scales = [float(im['scale']) for im in ds.images]

@@ -1633,6 +1633,59 @@ __all__ += ['detect_aug']
 
 
 # ---------------------------------------------------------------------------------------------------------
+# K16 the resident image set: exact channel sums and a uint8 resample of arenas (include/nnl.h).
+# ---------------------------------------------------------------------------------------------------------
+IMAGE_STATS_TILE_BYTES = 16384            # NNL_IMAGE_STATS_TILE_BYTES: an image above this many bytes is split over workgroups
+_IMAGE_STATS_INVALID = -1                 # NNL_IMAGE_STATS_INVALID seen through int64
+
+
+def _check_arena(name, arena, desc):
+    require_cuda(arena, desc)
+    if arena.dtype != torch.uint8 or desc.dtype != torch.int64:
+        raise TypeError('%s: an arena must be uint8 and its desc int64' % name)
+    if not (arena.is_contiguous() and desc.is_contiguous()) or arena.dim() != 1:
+        raise ValueError('%s: an arena must be a contiguous 1-d tensor and its desc contiguous' % name)
+    if desc.dim() != 2 or desc.shape[1] != 3:
+        raise ValueError('%s: desc must be [n_images, 3]' % name)
+
+
+def image_stats(arena, desc, first=0, count=None):
+    """Exact per-image channel sums of a uint8 arena (nnl_image_stats): arena uint8 [bytes] and desc int64 [n_images, 3] as for
+    `image_aug`; rows [first, first + count) of desc (default: all).  Returns a numpy uint64 [count, 6] = (sum v per channel, sum v^2
+    per channel) of the raw byte values.  Integer sums: exact and the same bits on every call.  The table is read back to the host
+    (it is 48 bytes per image); a desc row that does not lie inside the arena raises ValueError (the kernel reads nothing for it)."""
+    _check_arena('image_stats', arena, desc)
+    count = desc.shape[0] - int(first) if count is None else int(count)
+    out = torch.empty(max(count, 0), 6, dtype=torch.int64, device=arena.device)
+    check(lib.nnl_image_stats(ptr(arena), arena.numel(), ptr(desc), desc.shape[0], int(first), count, ptr(out), stream()))
+    table = out.cpu().numpy()
+    bad = np.nonzero((table == _IMAGE_STATS_INVALID).all(axis=1))[0]
+    if len(bad):
+        raise ValueError('image_stats: desc row %d does not describe an image inside the arena of %d bytes' % (int(first) + int(bad[0]), arena.numel()))
+    return table.view(np.uint64)
+
+
+def image_resize_u8(src_arena, src_desc, dst_desc, dst_arena=None):
+    """Image i of the uint8 arena `src_arena` (src_desc int64 [n, 3] = byte offset, H, W) resampled to the H, W of dst_desc[i] and
+    written at dst_desc[i]'s offset of `dst_arena` (nnl_image_resize_u8; include/nnl.h holds the formula: half-pixel bilinear on
+    float(v), rintf, clamp; equal sizes copy).  dst_arena=None allocates one that ends with the last image of dst_desc (one small
+    read-back).  Returns dst_arena."""
+    _check_arena('image_resize_u8', src_arena, src_desc)
+    if tuple(dst_desc.shape) != tuple(src_desc.shape):
+        raise ValueError('image_resize_u8: dst_desc must have one row per row of src_desc')
+    if dst_arena is None:
+        d = dst_desc.cpu().numpy()
+        dst_arena = torch.empty(int((d[:, 0] + 3 * d[:, 1] * d[:, 2]).max()), dtype=torch.uint8, device=src_arena.device)
+    _check_arena('image_resize_u8', dst_arena, dst_desc)
+    check(lib.nnl_image_resize_u8(ptr(src_arena), src_arena.numel(), ptr(src_desc), ptr(dst_arena), dst_arena.numel(), ptr(dst_desc),
+                                  src_desc.shape[0], stream()))
+    return dst_arena
+
+
+__all__ += ['image_stats', 'image_resize_u8', 'IMAGE_STATS_TILE_BYTES']
+
+
+# ---------------------------------------------------------------------------------------------------------
 # K11 detection test-time augmentation: the undo and concatenation of TTA_bbox (include/nnl.h).
 # ---------------------------------------------------------------------------------------------------------
 # nnl_tta_undo_t: one 20-byte row per (image, pass)
