@@ -59,37 +59,29 @@ int dispatch_rowk(const IgemmRowkParams& p, hipStream_t s) {
 }
 
 
-// LDS-DMA staging of the 64x64 tile (igemm_taps.h): an experiment kept behind NNL_IGEMM_DMA (0 off = default, 1 BK=16 launches,
-// 2 BK=32 launches, 3 both).  Measured per ResNet-34 layer (bench_conv.py --ab NNL_IGEMM_DMA=0,3): +3.5 % on the 56x56 / C=64
-// stage, -1 % on 28x28 / C=128, -7 % with BK=32 (two buffers); inside the full training step the gain on the C=64 stage
-// does not show (15.44 ms/step either way), so register staging stays the shipped path.
-static bool taps_dma(int bk) {
-  const int m = NNL_ENV_INT("NNL_IGEMM_DMA", 0);
-  return bk == 16 ? (m & 1) != 0 : (m & 2) != 0;
+// The instantiation of the 64x64 tile that a (BK, KTAIL) pair runs; every launcher below asks here.  Its k loop: BK 16 keeps two
+// tiles in flight (PF = 2, igemm_taps.h), BK 32 one tile.  Measured per ResNet-34 layer at 64 images (profiles/r3_pf2_bs64.log):
+// PF = 2 on BK 16 (the 28x28 / C = 128 stage) fwd 107.0 -> 111.7 TF/s, dgrad 112.7 -> 116.7; on BK 32 it needs 148 VGPRs (three
+// workgroups per CU instead of four) and LOSES 3-8 % on every stride-1 layer (l1 107 -> 104, l4 117 -> 109).  KTAIL masks the k tail
+// in the loads of the one-tile loop, at either BK.
+using TapsKernel = void (*)(IgemmTapsParams);
+static TapsKernel taps64_kernel(int bk, bool ktail) {
+  if (ktail) return bk == 32 ? igemm_taps_kernel<64, 64, 32, 2, 2, 0, 1, true> : igemm_taps_kernel<64, 64, 16, 2, 2, 0, 1, true>;
+  return bk == 32 ? igemm_taps_kernel<64, 64, 32, 2, 2> : igemm_taps_kernel<64, 64, 16, 2, 2, 0, 2>;
 }
 
-// The 64x64 tile's k loop: BK 16 keeps two tiles in flight (PF = 2, igemm_taps.h), BK 32 one tile with pipelined LDS fragment
-// reads (+2-3 %).  Measured per ResNet-34 layer at 64 images (profiles/r3_pf2_bs64.log): PF = 2 on BK 16 (the 28x28 / C = 128
-// stage) fwd 107.0 -> 111.7 TF/s, dgrad 112.7 -> 116.7; on BK 32 it needs 148 VGPRs (three workgroups per CU instead of four)
-// and LOSES 3-8 % on every stride-1 layer (l1 107 -> 104, l4 117 -> 109).  The larger tiles use the plain k loop.
+// (the larger tiles use the one-tile k loop)
 template <int BM, int BN, int BK = 16>
 int launch_taps(IgemmTapsParams p, hipStream_t s) {
   p.grid_m = (int)nnl_cdiv(p.M, BM);
   p.grid_n = (int)nnl_cdiv(p.Nc, BN);
   p.cls_tiles = p.grid_m * p.grid_n;
   const dim3 grid((unsigned)(p.grid_m * p.grid_n * (p.ncls > 1 ? p.ncls : 1)), p.ksplit > 1 ? p.ksplit : 1);
-  NNL_ROUTE("taps<%d,%d,%d>%s%s%s", BM, BN, BK, (BM == 64 && BN == 64 && taps_dma(BK)) ? ":dma" : "", p.ncls > 1 ? ":ncls" : "",
-            p.ksplit > 1 ? ":ksplit" : "");
-  if constexpr (BM == 64 && BN == 64) {
-    if (taps_dma(BK))
-      hipLaunchKernelGGL((igemm_taps_kernel<64, 64, BK, 2, 2, false, 0, true>), grid, dim3(256), 0, s, p);
-    else if constexpr (BK == 16)
-      hipLaunchKernelGGL((igemm_taps_kernel<64, 64, 16, 2, 2, true, 0, false, 2>), grid, dim3(256), 0, s, p);
-    else
-      hipLaunchKernelGGL((igemm_taps_kernel<64, 64, BK, 2, 2, true>), grid, dim3(256), 0, s, p);
-  } else {
+  NNL_ROUTE("taps<%d,%d,%d>%s%s", BM, BN, BK, p.ncls > 1 ? ":ncls" : "", p.ksplit > 1 ? ":ksplit" : "");
+  if constexpr (BM == 64 && BN == 64)
+    hipLaunchKernelGGL(taps64_kernel(BK, false), grid, dim3(256), 0, s, p);
+  else
     hipLaunchKernelGGL((igemm_taps_kernel<BM, BN, BK, 2, 2>), grid, dim3(256), 0, s, p);
-  }
   NNL_CHECK_LAUNCH();
   return NNL_OK;
 }
@@ -101,7 +93,7 @@ int launch_taps_ktail(IgemmTapsParams p, hipStream_t s) {
   p.grid_n = (int)nnl_cdiv(p.Nc, 64);
   p.cls_tiles = p.grid_m * p.grid_n;
   NNL_ROUTE("taps_ktail<%d>", BK);
-  hipLaunchKernelGGL((igemm_taps_kernel<64, 64, BK, 2, 2, true, 0, false, 1, true>), dim3((unsigned)(p.grid_m * p.grid_n), 1), dim3(256), 0, s, p);
+  hipLaunchKernelGGL(taps64_kernel(BK, true), dim3((unsigned)(p.grid_m * p.grid_n), 1), dim3(256), 0, s, p);
   NNL_CHECK_LAUNCH();
   return NNL_OK;
 }
@@ -145,21 +137,10 @@ int launch_balanced(IgemmTapsParams p, const SplitPlan& pl, float* ws, int* coun
   p.grid_m = (int)nnl_cdiv(p.M, 64);
   p.grid_n = (int)nnl_cdiv(p.Nc, 64);
   const unsigned grid = split_bind(p, pl, ws, p.M, 1, counters);
-  NNL_ROUTE("balanced<%d>%s%s%s%s:%s@main_ks=%d,tail_slices=%d", pl.bk == 32 ? 32 : 16, p.ktail ? ":ktail" : "",
-            (!p.ktail && taps_dma(pl.bk == 32 ? 32 : 16)) ? ":dma" : "", pl.main_ks > 1 ? ":main_ks" : "", pl.tail_slices > 1 ? ":tail_slices" : "",
+  NNL_ROUTE("balanced<%d>%s%s%s:%s@main_ks=%d,tail_slices=%d", pl.bk == 32 ? 32 : 16, p.ktail ? ":ktail" : "",
+            pl.main_ks > 1 ? ":main_ks" : "", pl.tail_slices > 1 ? ":tail_slices" : "",
             p.tile_counters != nullptr ? "counters" : "reduce", pl.main_ks, pl.tail_slices);
-  if (p.ktail && pl.bk == 32)
-    hipLaunchKernelGGL((igemm_taps_kernel<64, 64, 32, 2, 2, true, 0, false, 1, true>), dim3(grid), dim3(256), 0, s, p);
-  else if (p.ktail)
-    hipLaunchKernelGGL((igemm_taps_kernel<64, 64, 16, 2, 2, true, 0, false, 1, true>), dim3(grid), dim3(256), 0, s, p);
-  else if (pl.bk == 32 && taps_dma(32))
-    hipLaunchKernelGGL((igemm_taps_kernel<64, 64, 32, 2, 2, false, 0, true>), dim3(grid), dim3(256), 0, s, p);
-  else if (pl.bk != 32 && taps_dma(16))
-    hipLaunchKernelGGL((igemm_taps_kernel<64, 64, 16, 2, 2, false, 0, true>), dim3(grid), dim3(256), 0, s, p);
-  else if (pl.bk == 32)
-    hipLaunchKernelGGL((igemm_taps_kernel<64, 64, 32, 2, 2, true>), dim3(grid), dim3(256), 0, s, p);
-  else
-    hipLaunchKernelGGL((igemm_taps_kernel<64, 64, 16, 2, 2, true, 0, false, 2>), dim3(grid), dim3(256), 0, s, p);
+  hipLaunchKernelGGL(taps64_kernel(pl.bk, p.ktail != 0), dim3(grid), dim3(256), 0, s, p);
   NNL_CHECK_LAUNCH();
   if (p.tile_counters != nullptr) return NNL_OK;             // the kernel reduced its own slabs
   const int Nc4 = p.Nc / 4;
@@ -243,12 +224,11 @@ bool taps_ok(long a_elems, long b_elems, int C, int ntaps) {
   return C % 16 == 0 && ntaps <= IGEMM_MAX_TAPS && a_elems * 4 < (1L << 31) && b_elems * 4 < (1L << 32) - 64;
 }
 
-// 1: the tap-table kernel as is; 2: its KTAIL instantiation (one tap, C a multiple of 4 only: NNL_IGEMM_KTAIL=0 sends those shapes
-// back to the first-generation kernel); 0: neither
+// 1: the tap-table kernel as is; 2: its KTAIL instantiation (one tap, C a multiple of 4 only, at least 32); 0: neither (the
+// first-generation kernel serves the shape)
 int taps_kind(long a_elems, long b_elems, int C, int ntaps) {
   if (taps_ok(a_elems, b_elems, C, ntaps)) return 1;
-  if (ntaps == 1 && C % 4 == 0 && C >= 32 && a_elems * 4 < (1L << 31) && b_elems * 4 < (1L << 32) - 64 && NNL_ENV_INT("NNL_IGEMM_KTAIL", 1) != 0)
-    return 2;
+  if (ntaps == 1 && C % 4 == 0 && C >= 32 && a_elems * 4 < (1L << 31) && b_elems * 4 < (1L << 32) - 64) return 2;
   return 0;
 }
 
@@ -823,9 +803,9 @@ int nnl_internal_lstm_step(IgemmTapsParams q, int epi, hipStream_t s) {
   q.bal = 0;
   const dim3 grid(q.grid_m * q.grid_n, q.ksplit > 1 ? q.ksplit : 1), block(256);
   if (epi == 1)
-    hipLaunchKernelGGL((igemm_taps_kernel<64, 64, 32, 2, 2, true, 1>), grid, block, 0, s, q);
+    hipLaunchKernelGGL((igemm_taps_kernel<64, 64, 32, 2, 2, 1>), grid, block, 0, s, q);
   else
-    hipLaunchKernelGGL((igemm_taps_kernel<64, 64, 32, 2, 2, true, 2>), grid, block, 0, s, q);
+    hipLaunchKernelGGL((igemm_taps_kernel<64, 64, 32, 2, 2, 2>), grid, block, 0, s, q);
   NNL_CHECK_LAUNCH();
   return NNL_OK;
 }

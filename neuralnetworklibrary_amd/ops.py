@@ -668,7 +668,7 @@ def _conv_act_gate(y, dyn, g, relu, want_db):
 def _conv_dgrad_operands(dy4, w4, g4, K):
     """(dy, W^T [C,R,S,K'], geometry) of the dgrad: the K-padded-to-4 set as is, or with K padded on to a multiple of 16; the filter
     transpose comes from the caches of prepare_backward's window where it can"""
-    ktail = g4.R == 1 and g4.S == 1 and g4.K % 4 == 0 and os.environ.get('NNL_IGEMM_KTAIL', '1') != '0'     # the tap kernel masks the k tail itself
+    ktail = g4.R == 1 and g4.S == 1 and g4.K % 4 == 0            # the tap kernel masks the k tail itself
     dyd, gd, padk, wkey = dy4, g4, 0, None
     f = _OPEN or _CLOSED                     # (f.wt is non-empty only inside the backward window, after the batched transposes)
     if g4.K % 16 != 0 and g4.K >= 32 and not ktail:

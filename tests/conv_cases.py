@@ -96,15 +96,12 @@ HAND = [
     # channel switches: tap table (C % 16), KTAIL (one tap, C % 4, >= 32), row-k (the rest)
     _c('ktail16', 2, 36, 8, 8, 64, 1, 1, 1, 0, 'one tap, C = 36: KTAIL with the 16-wide k block; dgrad (K = 64) on the tap table'),
     _c('ktail32', 2, 100, 8, 8, 44, 1, 1, 1, 0, 'one tap, C = 100: KTAIL with the 32-wide k block; dgrad KTAIL 16 (K = 44)'),
-    _c('ktail-off', 2, 36, 8, 8, 44, 1, 1, 1, 0, 'NNL_IGEMM_KTAIL=0 sends one-tap C % 4 shapes back to the row-k kernel', {'NNL_IGEMM_KTAIL': '0'}),
     _c('ktail-bal', 1, 500, 32, 32, 1000, 1, 1, 1, 0, '1024 x 500 x 1000: few long tiles, KTAIL under the balanced schedule'),
     _c('rowk-1x1-c20', 2, 20, 8, 8, 20, 1, 1, 1, 0, 'one tap, C = 20 < 32: neither tap table nor KTAIL'),
     _c('rowk-c4', 5, 4, 13, 13, 4, 3, 3, 1, 1, 'C = K = 4'),
     _c('rowk-c180', 2, 180, 7, 7, 36, 3, 3, 1, 1, 'C = 180, K = 36: row-k in both directions'),
     # tile shapes of the tap-table kernel (the cost formula of dispatch_taps) and of the row-k kernel (block counts)
     _c('taps128x128-onetap', 1, 16, 32, 32, 8192, 1, 1, 1, 0, 'one tap, Nc >= 8192, M >= 1024: the 128 x 128 rule'),
-    _c('dma', 2, 64, 16, 16, 64, 3, 3, 2, 1, 'NNL_IGEMM_DMA=3: LDS-DMA staging of the 64 x 64 tile', {'NNL_IGEMM_DMA': '3', 'NNL_CONV_WINO': '0'}),
-    _c('dma-bal', 8, 128, 14, 14, 256, 3, 3, 1, 1, 'NNL_IGEMM_DMA=3 under the balanced schedule', {'NNL_IGEMM_DMA': '3', 'NNL_CONV_WINO': '0'}),
     _c('bal-off', 8, 128, 14, 14, 256, 3, 3, 1, 1, 'NNL_IGEMM_BALANCE=0: the plain grid on a shape the balanced schedule takes',
        {'NNL_IGEMM_BALANCE': '0', 'NNL_CONV_WINO': '0'}),
     _c('bal-force', 8, 256, 14, 14, 256, 3, 3, 2, 1, 'NNL_IGEMM_BALANCE=2 forces a sliced plan', {'NNL_IGEMM_BALANCE': '2', 'NNL_CONV_WINO': '0'}),

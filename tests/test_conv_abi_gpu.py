@@ -253,8 +253,8 @@ def _bal(bk, extra=('',)):
 KNOWN = set(
     ['rowk<%d,%d>:%s' % (bm, bn, m) for bm, bn in ((64, 64), (128, 64), (64, 128), (128, 128)) for m in ('fwd', 'dgrad')] +
     ['taps<128,128,16>', 'taps<128,128,16>:ncls'] +
-    ['taps<64,64,%d>%s%s%s' % (bk, d, n, k) for bk in (16, 32) for d in ('', ':dma') for n in ('', ':ncls') for k in ('', ':ksplit')] +
-    ['taps_ktail<16>', 'taps_ktail<32>'] + _bal(16, ('', ':ktail', ':dma')) + _bal(32, ('', ':ktail', ':dma')) +
+    ['taps<64,64,%d>%s%s' % (bk, n, k) for bk in (16, 32) for n in ('', ':ncls') for k in ('', ':ksplit')] +
+    ['taps_ktail<16>', 'taps_ktail<32>'] + _bal(16, ('', ':ktail')) + _bal(32, ('', ':ktail')) +
     ['slab_reduce:main', 'slab_reduce:tail', 'dgrad:merged', 'dgrad:per_class', 'dgrad:need_zero'] +
     ['wino1d_filter', 'wino1d_filter:flip', 'wino2d_filter', 'wino2d_filter:flip'] +
     ['wino1d<%d>:%s:%s' % (bk, pl, u) for bk in (16, 32) for pl in ('plain', 'ksliced') for u in ('own_u', 'u_pre')] +
@@ -272,7 +272,6 @@ ROUTES = {
         'rowk<64,64>:fwd', 'rowk<128,64>:fwd', 'rowk<64,128>:fwd', 'rowk<128,128>:fwd',      # bigM-rowk-k36, rowk64x128, bigM-rowk
         'taps<64,64,16>', 'taps<64,64,32>',
         'taps<128,128,16>',                                   # the one-tap Nc >= 8192 rule only (taps128x128-onetap)
-        'taps<64,64,32>:dma',                                 # NNL_IGEMM_DMA=3: dma / dma-bal without a workspace
         'taps_ktail<16>', 'taps_ktail<32>',
         'balanced<16>:tail_slices:counters', 'balanced<16>:tail_slices:reduce',
         'balanced<32>:tail_slices:counters', 'balanced<32>:tail_slices:reduce',
@@ -283,8 +282,6 @@ ROUTES = {
         'balanced<32>:ktail:main_ks:counters', 'balanced<32>:ktail:main_ks:reduce',          # ktail-bal-fwd
         'balanced<16>:ktail:tail_slices:counters', 'balanced<16>:ktail:tail_slices:reduce',  # ktail-bal16
         'balanced<32>:main_ks:tail_slices:counters', 'balanced<32>:main_ks:tail_slices:reduce',
-        'balanced<32>:dma:tail_slices:counters', 'balanced<32>:dma:tail_slices:reduce',      # NNL_IGEMM_DMA=3: dma
-        'balanced<32>:dma:main_ks:tail_slices:counters', 'balanced<32>:dma:main_ks:tail_slices:reduce',       # ... dma-bal
         'slab_reduce:main', 'slab_reduce:tail',
         'wino1d_filter', 'wino1d<16>:plain:own_u', 'wino1d<32>:plain:own_u', 'wino1d<16>:ksliced:own_u', 'wino1d<32>:ksliced:own_u',
         'wino2d_filter', 'wino2d<32,3>:plain:own_u', 'wino2d<16,4>:plain:own_u', 'wino2d<32,3>:ksliced:own_u', 'wino2d<16,4>:ksliced:own_u',
@@ -293,7 +290,6 @@ ROUTES = {
     'dgrad': [
         'rowk<64,64>:dgrad', 'rowk<128,64>:dgrad', 'rowk<64,128>:dgrad', 'rowk<128,128>:dgrad',
         'taps<64,64,16>', 'taps<64,64,32>', 'taps<64,64,16>:ncls', 'taps<64,64,32>:ncls',
-        'taps<64,64,32>:dma', 'taps<64,64,32>:dma:ncls',      # NNL_IGEMM_DMA=3: dma-bal without a workspace, dma
         'taps_ktail<16>', 'taps_ktail<32>',
         'dgrad:merged', 'dgrad:per_class', 'dgrad:need_zero',
         'balanced<16>:tail_slices:counters', 'balanced<16>:tail_slices:reduce',
@@ -304,7 +300,6 @@ ROUTES = {
         'balanced<16>:main_ks:tail_slices:counters', 'balanced<16>:main_ks:tail_slices:reduce',              # bal16-mainks-tail
         'balanced<32>:ktail:tail_slices:counters', 'balanced<32>:ktail:tail_slices:reduce',                  # ktail-bal-tail
         'balanced<32>:ktail:main_ks:tail_slices:counters', 'balanced<32>:ktail:main_ks:tail_slices:reduce',  # ktail-bal-both
-        'balanced<32>:dma:tail_slices:counters', 'balanced<32>:dma:tail_slices:reduce',                      # NNL_IGEMM_DMA=3: dma-bal
         'balanced<32>:ktail:main_ks:counters', 'balanced<32>:ktail:main_ks:reduce',                          # ktail-bal (K = 1000)
         'slab_reduce:main', 'slab_reduce:tail',
         # the cases with C == K pose the forward's problem again: wino1d-ksliced, wino1d-forced / wino2d-pos without tile counters,
@@ -335,8 +330,8 @@ NOT_REACHED = {
     'balanced<16>:ktail:main_ks*':
         'KTAIL under the 16-wide k block means a (rounded) C below 256, at most 14 k steps per tile; plan_balance needs 8 per slice for '
         'main_ks = 2.  No input selects it.',
-    'balanced<*>:dma:* beyond the three dma cases, balanced<32>:ktail:main_ks:tail_slices in the forward':
-        'the LDS-DMA experiment (NNL_IGEMM_DMA) is run on three shapes, not on every plan; the KTAIL plan with both slicings runs in the dgrad.',
+    'balanced<32>:ktail:main_ks:tail_slices in the forward':
+        'the KTAIL plan with both slicings runs in the dgrad.',
     'the > kTileCounters fallback (more than 65 536 tiles of a sliced plan: second-launch reduce although counters were passed)':
         'needs more than 2^28 output elements, past the size limit of the list.',
     'wino1d / wino2d :u_pre':

@@ -120,8 +120,7 @@ def test_planner_queries_agree_with_what_the_list_marks(monkeypatch):
     from neuralnetworklibrary_amd._lib import lib
     seen = set()
     for c in cc.CASES:
-        for k in ('NNL_CONV_WINO', 'NNL_WINO2_POS', 'NNL_WINO_PLAN_KS', 'NNL_WINO_PLAN_S', 'NNL_IGEMM_BALANCE', 'NNL_IGEMM_KTAIL', 'NNL_IGEMM_DMA',
-                  'NNL_WGRAD_WINO', 'NNL_WGRAD_WINO2D'):
+        for k in ('NNL_CONV_WINO', 'NNL_WINO2_POS', 'NNL_WINO_PLAN_KS', 'NNL_WINO_PLAN_S', 'NNL_IGEMM_BALANCE', 'NNL_WGRAD_WINO', 'NNL_WGRAD_WINO2D'):
             monkeypatch.delenv(k, raising=False)
         for k, v in c.env.items():
             monkeypatch.setenv(k, v)
@@ -137,7 +136,7 @@ def test_planner_queries_agree_with_what_the_list_marks(monkeypatch):
             assert pf == 2 and wf >= c.K * 16 * c.C * 4, cc.case_id(c)
         if c.name == 'wino-none':
             assert pf == 0 and pd == 0
-        if c.name.startswith('bal-') and c.name != 'bal-off' or c.name == 'dma-bal':
+        if c.name.startswith('bal-') and c.name != 'bal-off':
             assert wf > 0, cc.case_id(c)
         if c.name == 'bal-off':
             assert wf == 0 and wd == 0

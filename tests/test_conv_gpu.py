@@ -51,6 +51,8 @@ CASES = [
     (70, 36, 1, 1, 44, 1, 1, 0, False, False),      # ragged tiles, k tail of 4 in a 32-wide block
     (2, 40, 9, 7, 100, 1, 1, 0, True, True),        # a 1x1 convolution over pixels
     (3, 52, 8, 8, 60, 1, 2, 0, True, False),        # 1x1 / stride 2
+    (16, 64, 56, 56, 64, 3, 1, 1, False, False),    # layer1 / layer3 3x3 at 16 images: the grids of the training batch
+    (16, 256, 14, 14, 256, 3, 1, 1, True, True),
 ]
 
 
@@ -290,21 +292,6 @@ def _grad_slot_hand_over(stride, give_first, K, R, pad):
     (y1 + yd).backward(dy.to(DEV))
     assert slot.tensor is None and slot.closed
     assert_close(xg.grad, xr.grad.float(), 1e-4, 1e-5 * xr.grad.abs().max().item(), 'dx = dgrad(conv1) + dgrad(shortcut)')
-
-
-DMA_CASES = [c for c in CASES if c[1] % 32 == 0 and c[4] % 4 == 0][:6] + [(16, 64, 56, 56, 64, 3, 1, 1, False, False),
-                                                                            (16, 256, 14, 14, 256, 3, 1, 1, True, True)]
-
-
-@pytest.mark.parametrize('case', DMA_CASES, ids=[str(c) for c in DMA_CASES])
-def test_conv2d_lds_dma_staging_variant(case, monkeypatch):
-    """The LDS-DMA staging variant of the 64x64 kernels (NNL_IGEMM_DMA, off by default: DESIGN.md switches table) computes the
-    same convolution: forward / dgrad through `buffer_load ... lds` into the swizzled unpadded image, three (BK 16) or two
-    (BK 32) buffers, on plain and balanced grids."""
-    monkeypatch.setenv('NNL_IGEMM_DMA', '3')
-    from neuralnetworklibrary_amd._lib import lib
-    lib.nnl_reload_env()
-    test_conv2d_fwd_bwd(case)
 
 
 def test_shared_conv_weight_under_gradsync_is_not_aliased():

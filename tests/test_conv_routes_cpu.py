@@ -24,8 +24,8 @@ import conv_cases as cc
 pytestmark = pytest.mark.skipif(torch.cuda.is_available(), reason='fake pointers: only where no launch can happen')
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'conv_routes.txt')
-SWITCHES = ('NNL_CONV_WINO', 'NNL_CONV_WINO2', 'NNL_WINO2_POS', 'NNL_WINO_PLAN_KS', 'NNL_WINO_PLAN_S', 'NNL_IGEMM_BALANCE', 'NNL_IGEMM_KTAIL',
-            'NNL_IGEMM_DMA', 'NNL_WGRAD_WINO', 'NNL_WGRAD_WINO2D', 'NNL_WINO_BALANCE', 'NNL_WINO2_CHUNK')
+SWITCHES = ('NNL_CONV_WINO', 'NNL_CONV_WINO2', 'NNL_WINO2_POS', 'NNL_WINO_PLAN_KS', 'NNL_WINO_PLAN_S', 'NNL_IGEMM_BALANCE', 'NNL_WGRAD_WINO',
+            'NNL_WGRAD_WINO2D', 'NNL_WINO_BALANCE', 'NNL_WINO2_CHUNK')
 CALL_MODES = ('ws+cnt', 'ws', 'none')
 
 

@@ -42,8 +42,8 @@ CASES = [
     ('igemm_wgrad2d_kernelILi128ELi16ELi1E', 32, 106, None),         # ... 128 x 128 tile (was 125)
     ('igemm_wgrad_kernelILi64ELi64ELi32ELi2ELi2ELb1ELi1ELb0ELb1E', 16, 40, None),     # direct weight gradient, PAIR staging (one-chunk staging: 56)
     ('igemm_wgrad_kernelILi128ELi128ELi16ELi2ELi2ELb1ELi1ELb0ELb1E', 32, 56, None),   # (one-chunk staging: 70)
-    ('igemm_taps_kernelILi64ELi64ELi32ELi2ELi2ELb1ELi0ELb0ELi1ELb0E', 16, 20, 0),     # forward / dgrad tap kernel: address state is scalar
-    ('igemm_taps_kernelILi64ELi64ELi16ELi2ELi2ELb1ELi0ELb0ELi2ELb0E', 16, 12, 0),     # two tiles in flight: NO accumulator copies in the loop (was 16 x v_mov_b64)
+    ('igemm_taps_kernelILi64ELi64ELi32ELi2ELi2ELi0ELi1ELb0E', 16, 20, 0),     # forward / dgrad tap kernel: address state is scalar
+    ('igemm_taps_kernelILi64ELi64ELi16ELi2ELi2ELi0ELi2ELb0E', 16, 12, 0),     # two tiles in flight: NO accumulator copies in the loop (was 16 x v_mov_b64)
 ]
 
 

@@ -97,7 +97,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--bs', type=int, default=64)
     ap.add_argument('--net', default='r34', help="'r34' (ResNet-34 at 224, default) or 'r50' (RetinaNet R50-FPN at 512)")
-    ap.add_argument('--ab', default=None, help='A/B in ONE process, interleaved: ENVVAR=v0,v1[,v2] (e.g. NNL_IGEMM_DMA=0,3); several variables per setting: A+B=0+1,3+2')
+    ap.add_argument('--ab', default=None, help='A/B in ONE process, interleaved: ENVVAR=v0,v1[,v2] (e.g. NNL_CONV_WINO=0,1); several variables per setting: A+B=0+1,3+2')
     ap.add_argument('--only', default=None, help='comma-separated layer-name substrings to keep (e.g. 3x3)')
     args = ap.parse_args()
     global LAYERS
