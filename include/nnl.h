@@ -917,6 +917,67 @@ size_t nnl_det_map_integrate_workspace_bytes(int64_t Np, int64_t T);
 int nnl_det_map_integrate(const int32_t* cat_pr_off, const int32_t* order, const double* score, const uint8_t* correct, const int64_t* ntrue,
                           int64_t C, int64_t Np, int64_t T, void* workspace, size_t workspace_bytes, double* out, void* stream);
 
+/* ---- K17: tokeniser and vocabulary of the text workflow (Applications/Text.py:28-122) ----------------------------------------
+ * A corpus is ONE resident byte buffer: bytes uint8 [B], 0 <= B < 2^31, and text_off int64 [n+1] (n >= 1, text_off[0] = 0,
+ * non-decreasing, text_off[n] = B; the CALLER checks that before the upload), text j being bytes [text_off[j], text_off[j+1]).  No
+ * token crosses a text boundary and no rule looks across one.  mode NNL_TEXT_MODE_GRAMMAR cuts by the byte grammar of DESIGN.md
+ * section 8 (what Tokenizer.proc_text / spacy_tok and do_caps do, Text.py:40-41, 58-67, 69-75) and compares, hashes and returns tokens
+ * with A-Z lowered; NNL_TEXT_MODE_SPLIT cuts maximal runs of non-whitespace bytes and lowers nothing (what numericalize reads,
+ * Text.py:95-122).  A token is a record (tok_start int32, tok_len int32); the pseudo-token t_up has tok_len = NNL_TEXT_TUP_LEN and the
+ * start of the token it precedes, and stands for the four bytes "t_up" wherever a token's bytes are read.  Every pointer is a
+ * DEVICE pointer; the caller owns every buffer; arguments are validated before any HIP call.  Integer atomics only, every phase its
+ * own launch, no workgroup waits for another, every loop is bounded by B, T, n or the table's capacity.
+ *
+ * nnl_text_token_count (replaces the token lists of Text.py:77-93 as a count): per-tile token counts (tiles of NNL_TEXT_TILE bytes,
+ * t_up included), then their exclusive scan by one workgroup: tile_base int64 [cdiv(B, NNL_TEXT_TILE) + 1], the last entry the total
+ * T, which the host reads once to size the outputs of nnl_text_token_fill.
+ * nnl_text_token_fill (Text.py:40-41, 69-75): tok_start, tok_len int32 [T] in byte order, and text_tok_off int64 [n+1]: text j owns
+ * tokens [text_tok_off[j], text_tok_off[j+1]).  T must be the total nnl_text_token_count gave for the same bytes, offsets and mode.
+ * nnl_text_token_hash (the hashing inside collections.Counter, Text.py:113): keys uint64 [T] = (h(seed, the token's lowered bytes)
+ * AND hash_mask), a zero result replaced by hash_mask's lowest set bit: key 0 means "empty slot".  hash_mask != 0.
+ * nnl_text_vocab_insert (Counter, Text.py:112-113): open addressing, linear probing from a slot derived from the key, in table_key
+ * uint64 [cap], table_count int32 [cap], table_first int32 [cap]; cap a power of two in [16, 2^30].  reset != 0 clears the table and
+ * status first (a launch of its own).  One 64-bit compare-and-swap per probe step; on a hit or a win the slot's count is incremented,
+ * its first token index atomicMin-ed with t, and tok_slot[t] = slot.  A token that finds no slot in cap steps sets bit
+ * NNL_TEXT_STATUS_OVERFLOW of status int32 [1] and gets tok_slot[t] = -1.  Which of two keys sharing a home slot gets it depends on
+ * arrival order, so slot NUMBERS differ between calls; counts and first indices do not.
+ * nnl_text_vocab_verify: every token with a slot compares its length and lowered bytes with token table_first[slot], in the token
+ * stream ftok_start / ftok_len / fbytes that slot's first index refers to (the same stream for a corpus's own vocabulary);
+ * mismatches int32 [1] is incremented per differing token (the caller zeroes it).  Zero mismatches = every slot holds ONE string.
+ * nnl_text_vocab_compact: the occupied slots as rows (slot, count, first, tok_start[first], tok_len[first]) of list int32 [max_rows, 5]
+ * in no particular order, n_rows int32 [1] (zeroed by the caller) their number; rows beyond max_rows are counted, not written.
+ * nnl_text_vocab_assign (the stoi dict of Text.py:114-117): slot_id int32 [cap] = 0 everywhere, then slot_id[slots[k]] = ids[k]
+ * for k < K (slots, ids int32 [K]; two launches).
+ * nnl_text_vocab_lookup (the defaultdict lookups of Text.py:119-120 for a GIVEN stoi): the vocabulary's strings are a token stream of
+ * their own (vbytes, vtok_start, vtok_len), inserted and verified by the entries above.  Data token t probes with keys[t]: an empty
+ * slot or cap steps give tok_slot[t] = -1; a slot with the same key gives that slot if the token's lowered bytes equal the
+ * vocabulary string table_first[slot], else -1 (the vocabulary's keys are distinct once verified, so no other slot can hold it).
+ * nnl_text_ids_write (Text.py:120, :144): ids int64 [T], ids[p] = tok_slot[t] < 0 ? 0 : slot_id[tok_slot[t]], p = t, or with
+ * reverse != 0 the mirror position of t inside its text. */
+#define NNL_TEXT_TILE 1024
+#define NNL_TEXT_TUP_LEN (-1)
+enum { NNL_TEXT_MODE_GRAMMAR = 0, NNL_TEXT_MODE_SPLIT = 1 };
+enum { NNL_TEXT_STATUS_OVERFLOW = 1 };
+int nnl_text_token_count(const uint8_t* bytes, int64_t B, const int64_t* text_off, int64_t n, int mode, int64_t* tile_base, void* stream);
+int nnl_text_token_fill(const uint8_t* bytes, int64_t B, const int64_t* text_off, int64_t n, int mode, const int64_t* tile_base, int64_t T,
+                        int32_t* tok_start, int32_t* tok_len, int64_t* text_tok_off, void* stream);
+int nnl_text_token_hash(const uint8_t* bytes, int64_t B, const int32_t* tok_start, const int32_t* tok_len, int64_t T, int mode,
+                        uint64_t seed, uint64_t hash_mask, uint64_t* keys, void* stream);
+int nnl_text_vocab_insert(const uint64_t* keys, int64_t T, uint64_t* table_key, int32_t* table_count, int32_t* table_first, int64_t cap,
+                          int reset, int32_t* tok_slot, int32_t* status, void* stream);
+int nnl_text_vocab_verify(const uint8_t* bytes, int64_t B, const int32_t* tok_start, const int32_t* tok_len, const int32_t* tok_slot,
+                          int64_t T, int mode, const uint8_t* fbytes, int64_t FB, const int32_t* ftok_start, const int32_t* ftok_len,
+                          int64_t FT, int fmode, const int32_t* table_first, int64_t cap, int32_t* mismatches, void* stream);
+int nnl_text_vocab_compact(const uint64_t* table_key, const int32_t* table_count, const int32_t* table_first, int64_t cap,
+                           const int32_t* tok_start, const int32_t* tok_len, int64_t T, int32_t* list, int64_t max_rows, int32_t* n_rows,
+                           void* stream);
+int nnl_text_vocab_assign(const int32_t* slots, const int32_t* ids, int64_t K, int32_t* slot_id, int64_t cap, void* stream);
+int nnl_text_vocab_lookup(const uint8_t* bytes, int64_t B, const int32_t* tok_start, const int32_t* tok_len, const uint64_t* keys,
+                          int64_t T, int mode, const uint8_t* vbytes, int64_t VB, const int32_t* vtok_start, const int32_t* vtok_len,
+                          int64_t VT, const uint64_t* table_key, const int32_t* table_first, int64_t cap, int32_t* tok_slot, void* stream);
+int nnl_text_ids_write(const int32_t* tok_slot, const int32_t* slot_id, int64_t cap, const int64_t* text_tok_off, int64_t n, int64_t T,
+                       int reverse, int64_t* ids, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -9,10 +9,15 @@ bias_ih_l0,bias_hh_l0,weight_hh_l0_raw}, dec.lin.weight tied) and quirks as the 
 after EVERY LSTM layer including the last (Text.py:546), hidden state is carried (detached) across batches and never
 reset by the Learner (Text.py:547-550).  Text generation (K5d, Text.py:655-676): LanguageModelNet.predict_from_tokens /
 predict_from_string on ops_text.LstmCellB1 and ops_text.LmNextToken (batch 1, one timestep, nothing read back inside the loop).
-spaCy tokenisation / numericalisation (:19-229) is CPU text preparation and
-out of scope.
+Tokenisation / numericalisation (:19-229) is partly built (K17): `Tokenizer`, `tokenize`, `tokenize_mp`,
+`numericalize` and the string / file routes of the datasets run on the HIP tokeniser and vocabulary kernels of
+csrc/text_tokens.hip with the package's OWN byte grammar (see `Tokenizer`), opted into with the keyword-only `tokenizer=`
+argument; spaCy itself, corpora of 2^31 bytes or more, a parallel host pre-rule pass, ids kept resident for the LM loader and the
+wt103 vocabulary are not built.
 """
 import math
+import os
+import re
 
 import numpy as np
 import torch
@@ -30,6 +35,115 @@ from .. import ops, ops_text
 from ..dist import keyed_mask
 
 
+# ---- tokenisation and numericalisation (Text.py:19-122) on the HIP tokeniser (K17) ------------------------------------------------
+
+class Tokenizer(object):
+    """The reference's Tokenizer (Text.py:28-75) without spaCy: host pre-rules on the Python string, then the package's OWN byte
+    grammar on the device (csrc/text_tokens.hip, csrc/text_grammar.h).  `lang` is accepted and ignored.  Nothing is printed.
+
+    Host pre-rules, in this order (they change a text's length, so they run as re.sub before the upload): (1) re_rep: a
+    non-space character repeated 4 times or more -> ' tk_rep <n> <c> '; (2) re_word_rep: a word (with what separates it from the next)
+    repeated 4 times or more -> ' tk_wrep <n> <word> '; (3) <br /> -> newline; (4) '/' and '#' get a space on either side.  The
+    reference applies do_caps between (2) and (4) and (3) last; (3) and (4) commute with the case rule below: `br` has 2 letters and
+    never gets t_up, and '/' and '#' are not word bytes.
+
+    The grammar, over the UTF-8 bytes of ONE text (no token crosses a text boundary, no rule looks across one).  Byte classes:
+    S = 0x09-0x0D and 0x20; W = 0-9 A-Z a-z _ and every byte >= 0x80 (multibyte characters are word characters and are never
+    cased); P = everything else; a '.' or ',' whose two neighbours are both ASCII digits counts as W (3.5 and 1,000 stay whole).
+      * A maximal run of W bytes is a token.
+      * A maximal run of one repeated P byte is a token: ... -- !!
+      * S separates tokens and is never a token (spaCy emits whitespace tokens; this grammar does not).
+      * An apostrophe with a letter, digit or _ (a W byte proper) on both sides starts a token that runs through the following W
+        run: 's 're 'll.  If the byte before it is n / N and the run after it is exactly t / T, the token is n't and the word
+        before ends one byte earlier: don't -> do, n't; n't alone -> n't.
+      * <eos>, <bos>, <unk> (lower case) are single tokens and take precedence over every other rule.
+    Whether a token starts at a byte depends on at most 5 bytes before it and 4 after it; nothing is sequential.
+    Case rule (do_caps, Text.py:58-67, restricted to ASCII): if a token begins a maximal run of letters, digits, _ and bytes >= 0x80
+    (the digit rule does not extend this run, and it may reach past the token: DON'T) that is longer than 2 bytes and has at least
+    one A-Z and no a-z, the pseudo-token t_up precedes the token.  Every token is compared, hashed and returned with A-Z lowered.
+    Mode `split` (numericalize on already tokenised input): tokens are maximal runs of non-S bytes; no case rule, no lowering.
+
+    Deliberate differences from the reference: no whitespace tokens; only ASCII letters are cased; no spaCy exceptions list (only
+    the contraction rules above); an all-capitals run that begins INSIDE a token ('CLOCK in O'CLOCK, 5AB in 3.5AB) gets no t_up and
+    does not split the token, where do_caps' inserted spaces would; nothing is printed; tokenize_mp's `ncpus` is ignored."""
+
+    re_br = re.compile(r'<\s*br\s*/?>', re.IGNORECASE)
+    re_rep = re.compile(r'(\S)(\1{3,})')
+    re_word_rep = re.compile(r'(\b\w+\W+)(\1{3,})')
+    re_slash_hash = re.compile(r'([/#])')
+
+    def __init__(self, lang='en'):
+        self.lang = lang
+
+    def sub_br(self, x):
+        return self.re_br.sub('\n', x)
+
+    @staticmethod
+    def replace_rep(m):
+        c, rest = m.groups()
+        return ' tk_rep %d %s ' % (len(rest) + 1, c)
+
+    @staticmethod
+    def replace_wrep(m):
+        w, rest = m.groups()
+        return ' tk_wrep %d %s ' % (len(rest.split()) + 1, w)
+
+    def pre_rules(self, s):
+        "the four host rules on one text, in the order of the class docstring"
+        s = self.re_rep.sub(Tokenizer.replace_rep, s)
+        s = self.re_word_rep.sub(Tokenizer.replace_wrep, s)
+        return self.re_slash_hash.sub(r' \1 ', self.sub_br(s))
+
+    def corpus(self, ss):
+        "pre-rules on every text, then ONE upload: the ops_text.TextCorpus the kernels read (ValueError from 2^31 bytes on)"
+        return ops_text.TextCorpus.from_texts([self.pre_rules(s).encode('utf-8', 'surrogateescape') for s in ss])
+
+    def proc_text(self, s):
+        "one text -> its token strings"
+        return self.proc_texts([s])[0]
+
+    def proc_texts(self, ss):
+        "texts -> token-string lists: one upload, one pass of the token kernels, one copy back of the token records"
+        ss = list(ss)
+        if not ss:
+            return []
+        corpus = self.corpus(ss)
+        return ops_text.token_strings(corpus, ops_text.token_bounds(corpus, ops_text.TEXT_MODE_GRAMMAR))
+
+
+def tokenize(ss):
+    "token-string lists of the texts ss (Text.py:77-83), through Tokenizer().proc_texts"
+    return Tokenizer().proc_texts(ss)
+
+
+def tokenize_mp(ss, ncpus=None):
+    "as tokenize (Text.py:85-93); `ncpus` is accepted and ignored: there is no process pool, the texts go through the device in one pass"
+    return Tokenizer().proc_texts(ss)
+
+
+def _split_corpus(ss):
+    "already tokenised texts as a corpus for the `split` mode: tokens joined by one space; a token the mode would cut or lose raises"
+    texts = []
+    for toks in ss:
+        enc = [t.encode('utf-8', 'surrogateescape') for t in toks]
+        for t, b in zip(toks, enc):
+            if not b or len(b.split()) != 1 or len(b.split()[0]) != len(b):
+                raise ValueError('numericalize: token %r is empty or contains whitespace (0x09-0x0D, 0x20)' % (t,))
+        texts.append(b' '.join(enc))
+    return ops_text.TextCorpus.from_texts(texts)
+
+
+def numericalize(ss, max_vocab=60000, min_freq=6, stoi=None):
+    """(ss_numeric, stoi) for lists of token strings (Text.py:95-122), on the device through the `split` mode: without `stoi` the
+    vocabulary is the max_vocab most common tokens (ties in order of first occurrence) that then occur at least min_freq times,
+    after _unk_ _pad_ _bos_ _eos_; with `stoi`, tokens it lacks give 0.  Nothing is printed."""
+    ss = [list(toks) for toks in ss]
+    if not ss:
+        return [], (stoi if stoi is not None else {s: i for i, s in enumerate(ops_text.TEXT_SPECIALS)})
+    out = ops_text.text_numericalize(_split_corpus(ss), ops_text.TEXT_MODE_SPLIT, max_vocab, min_freq, stoi)
+    return out.lists(), out.stoi
+
+
 # ---- data: datasets (Text.py:127-229) -------------------------------------------------------------------------------
 
 _NO_TOKENIZER = ('tokenisation (spaCy) is not part of this package (SURVEY.md §2.1 row 14): pass token-id lists, e.g. what the '
@@ -37,19 +151,36 @@ _NO_TOKENIZER = ('tokenisation (spaCy) is not part of this package (SURVEY.md §
 
 
 class TextDataset(object):
-    """Texts + labels for language modelling and text classification (Text.py:127-187).  `texts` are token-id lists (what the
-    reference computes from strings with tokenize_mp + numericalize); strings raise NotImplementedError.  `stoi` is kept as
-    given.  Same attributes as the reference: texts / labels as pandas Series, the sorted label_dict, num_tokens."""
+    """Texts + labels for language modelling and text classification (Text.py:127-187).  Same attributes as the reference: texts /
+    labels as pandas Series, the sorted label_dict, num_tokens.
 
-    def __init__(self, texts, labels, stoi=None, reverse=False):
+    tokenizer=None (default): `texts` are token-id lists (what the reference computes from strings with tokenize_mp + numericalize);
+    strings raise NotImplementedError; `stoi` is kept as given.
+    tokenizer=Tokenizer(): `texts` are strings and the fused route runs: the tokenizer's host pre-rules, one upload, the kernels of
+    csrc/text_tokens.hip (token bounds, then the vocabulary built from these texts with max_vocab / min_freq — or the lookup in a given
+    `stoi` — and the ids, reversed per text on the device if `reverse`), one copy back of ids and offsets.  Token strings are never
+    materialised on the host, apart from the vocabulary; the result equals numericalize(tokenize(texts), max_vocab, min_freq, stoi)."""
+
+    def __init__(self, texts, labels, stoi=None, reverse=False, *, tokenizer=None, max_vocab=60000, min_freq=6):
         import pandas as pd
         texts = list(texts)
-        if any(isinstance(t, str) for t in texts):
-            raise NotImplementedError(_NO_TOKENIZER)
-        self.stoi, self.reverse = stoi, reverse
-        self.texts = pd.Series([[int(v) for v in t] for t in texts], dtype=object)
-        if reverse:
-            self.texts = pd.Series([list(reversed(t)) for t in self.texts], dtype=object)
+        self.reverse = reverse
+        if tokenizer is not None:
+            if not all(isinstance(t, str) for t in texts):
+                raise TypeError('TextDataset: with a tokenizer every text must be a string')
+            if texts:
+                out = ops_text.text_numericalize(tokenizer.corpus(texts), ops_text.TEXT_MODE_GRAMMAR, max_vocab, min_freq, stoi, reverse)
+                self.stoi, ids = out.stoi, out.lists()
+            else:
+                self.stoi, ids = (stoi if stoi is not None else {s: i for i, s in enumerate(ops_text.TEXT_SPECIALS)}), []
+            self.texts = pd.Series(ids, dtype=object)
+        else:
+            if any(isinstance(t, str) for t in texts):
+                raise NotImplementedError(_NO_TOKENIZER)
+            self.stoi = stoi
+            self.texts = pd.Series([[int(v) for v in t] for t in texts], dtype=object)
+            if reverse:
+                self.texts = pd.Series([list(reversed(t)) for t in self.texts], dtype=object)
         self.num_tokens = sum(len(t) for t in self.texts)
         unique_labels = sorted(list(set(labels)))
         self.label_dict = {lab: i for i, lab in enumerate(unique_labels)}
@@ -76,12 +207,46 @@ class TextDataset(object):
         return train_ds, val_ds
 
     @classmethod
-    def from_csv(cls, csv_file, text_col, label_col=None, stoi=None, reverse=False):
-        raise NotImplementedError(_NO_TOKENIZER)
+    def from_csv(cls, csv_file, text_col, label_col=None, stoi=None, reverse=False, *, tokenizer=None, max_vocab=60000, min_freq=6):
+        "one text per csv row, labels from `label_col` or all 0 (Text.py:180-187); needs a tokenizer"
+        if tokenizer is None:
+            raise NotImplementedError(_NO_TOKENIZER)
+        import pandas as pd
+        df = pd.read_csv(csv_file)
+        labels = list(df[label_col]) if label_col else [0] * len(df)
+        return cls([str(t) for t in df[text_col]], labels, stoi, reverse, tokenizer=tokenizer, max_vocab=max_vocab, min_freq=min_freq)
 
     @classmethod
-    def from_text_files(cls, folder, labels, stoi=None, reverse=False):
-        raise NotImplementedError(_NO_TOKENIZER)
+    def from_text_files(cls, folder, labels, stoi=None, reverse=False, *, tokenizer=None, max_vocab=60000, min_freq=6):
+        """.txt files of `folder` (labels=None: all labelled 0), of each of its sub-folders (labels='All') or of the sub-folders named
+        in the list `labels`, the sub-folder's name being the label (Text.py:189-229); needs a tokenizer.  Deliberate differences from
+        the reference, as on the image side (Vision.py's from_folders): every listing is SORTED (os.listdir's order is the file
+        system's), files whose name starts with '._' are skipped, files are read as bytes, decoded as UTF-8 with errors='replace',
+        and closed, and the caller's `labels` list is not sorted in place."""
+        if tokenizer is None:
+            raise NotImplementedError(_NO_TOKENIZER)
+        folder = correct_foldername(folder)
+
+        def read_all(sub):
+            names = sorted(fn for fn in os.listdir(folder + sub) if fn.endswith('.txt') and not fn.startswith('._'))
+            out = []
+            for fn in names:
+                with open(os.path.join(folder + sub, fn), 'rb') as f:
+                    out.append(f.read().decode('utf-8', errors='replace'))
+            return out
+
+        if labels is None:
+            texts = read_all('')
+            text_labels = [0] * len(texts)
+        else:
+            if isinstance(labels, str):
+                labels = [d for d in os.listdir(folder) if os.path.isdir(folder + d)]
+            texts, text_labels = [], []
+            for lab in sorted(labels):
+                got = read_all(lab)
+                texts += got
+                text_labels += [lab] * len(got)
+        return cls(texts, text_labels, stoi, reverse, tokenizer=tokenizer, max_vocab=max_vocab, min_freq=min_freq)
 
 
 # ---- data: text-classification batches (Text.py:334-440) -----------------------------------------------------------
@@ -151,12 +316,33 @@ class TextClassificationDataObj(object):
             self.test_dl = DataLoader(test_ds, collate_fn=collater, batch_sampler=sampler_test, num_workers=num_workers)
 
     @classmethod
-    def from_csv(cls, bs, csv_train, csv_val=None, csv_test=None, text_col='text', label_col='label', reverse=False, stoi=None):
-        raise NotImplementedError(_NO_TOKENIZER)
+    def from_csv(cls, bs, csv_train, csv_val=None, csv_test=None, text_col='text', label_col='label', reverse=False, stoi=None, *,
+                 tokenizer=None, max_vocab=60000, min_freq=6, bpg=10, num_workers=6):
+        "csv files -> data object (Text.py:411-424): the vocabulary comes from the train file; without csv_val the train set is split"
+        if tokenizer is None:
+            raise NotImplementedError(_NO_TOKENIZER)
+        train_ds = TextDataset.from_csv(csv_train, text_col, label_col, stoi, reverse, tokenizer=tokenizer, max_vocab=max_vocab, min_freq=min_freq)
+        stoi = train_ds.stoi
+        if csv_val:
+            val_ds = TextDataset.from_csv(csv_val, text_col, label_col, stoi, reverse, tokenizer=tokenizer)
+        else:
+            train_ds, val_ds = train_ds.split_train_val()
+        test_ds = TextDataset.from_csv(csv_test, text_col, label_col, stoi, reverse, tokenizer=tokenizer) if csv_test else None
+        return cls(train_ds, val_ds, test_ds, bs, bpg, num_workers)
 
     @classmethod
-    def from_folders(cls, bs, labels, train, val=None, test=None, reverse=False, stoi=None):
-        raise NotImplementedError(_NO_TOKENIZER)
+    def from_folders(cls, bs, labels, train, val=None, test=None, reverse=False, stoi=None, *, tokenizer=None, max_vocab=60000, min_freq=6, bpg=10, num_workers=6):
+        "folders of .txt files in label sub-folders -> data object (Text.py:426-438); `labels` as in TextDataset.from_text_files"
+        if tokenizer is None:
+            raise NotImplementedError(_NO_TOKENIZER)
+        train_ds = TextDataset.from_text_files(train, labels, stoi, reverse, tokenizer=tokenizer, max_vocab=max_vocab, min_freq=min_freq)
+        stoi = train_ds.stoi
+        if val:
+            val_ds = TextDataset.from_text_files(val, labels, stoi, reverse, tokenizer=tokenizer)
+        else:
+            train_ds, val_ds = train_ds.split_train_val()
+        test_ds = TextDataset.from_text_files(test, labels, stoi, reverse, tokenizer=tokenizer) if test else None
+        return cls(train_ds, val_ds, test_ds, bs, bpg, num_workers)
 
 
 # ---- data: language-model batches (Text.py:231-332) ----------------------------------------------------------------
@@ -226,6 +412,36 @@ class LanguageModelDataObj(object):
         self.val_dl = LanguageModelDataLoader(val_ds, bs, bptt, False, device_resident)
         if test_ds:
             self.test_dl = LanguageModelDataLoader(test_ds, bs, bptt, False, device_resident)
+
+    @classmethod
+    def from_csv(cls, bs, bptt, csv_train, csv_val=None, csv_test=None, text_col='text', reverse=False, *, tokenizer=None,
+                 max_vocab=60000, min_freq=6, device_resident=False):
+        "csv files with one text per row -> data object (Text.py:306-318); the vocabulary comes from the train file"
+        if tokenizer is None:
+            raise NotImplementedError(_NO_TOKENIZER)
+        train_ds = TextDataset.from_csv(csv_train, text_col, None, None, reverse, tokenizer=tokenizer, max_vocab=max_vocab, min_freq=min_freq)
+        stoi = train_ds.stoi
+        if csv_val:
+            val_ds = TextDataset.from_csv(csv_val, text_col, None, stoi, reverse, tokenizer=tokenizer)
+        else:
+            train_ds, val_ds = train_ds.split_train_val()
+        test_ds = TextDataset.from_csv(csv_test, text_col, None, stoi, reverse, tokenizer=tokenizer) if csv_test else None
+        return cls(train_ds, val_ds, test_ds, bs, bptt, device_resident)
+
+    @classmethod
+    def from_folders(cls, bs, bptt, labels, train, val=None, test=None, reverse=False, *, tokenizer=None, max_vocab=60000, min_freq=6,
+                     device_resident=False):
+        "folders of .txt files -> data object (Text.py:320-332); `labels` as in TextDataset.from_text_files"
+        if tokenizer is None:
+            raise NotImplementedError(_NO_TOKENIZER)
+        train_ds = TextDataset.from_text_files(train, labels, None, reverse, tokenizer=tokenizer, max_vocab=max_vocab, min_freq=min_freq)
+        stoi = train_ds.stoi
+        if val:
+            val_ds = TextDataset.from_text_files(val, labels, stoi, reverse, tokenizer=tokenizer)
+        else:
+            train_ds, val_ds = train_ds.split_train_val()
+        test_ds = TextDataset.from_text_files(test, labels, stoi, reverse, tokenizer=tokenizer) if test else None
+        return cls(train_ds, val_ds, test_ds, bs, bptt, device_resident)
 
 
 # ---- models --------------------------------------------------------------------------------------------------------

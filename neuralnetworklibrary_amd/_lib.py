@@ -175,6 +175,15 @@ SIGNATURES = {
     'nnl_det_map_match': (C.c_int, [c_p, c_p, c_p, c_p, i64, i64, i64, c_p, i64, c_p, c_p]),
     'nnl_det_map_integrate_workspace_bytes': (sz, [i64, i64]),
     'nnl_det_map_integrate': (C.c_int, [c_p, c_p, c_p, c_p, c_p, i64, i64, i64, c_p, sz, c_p, c_p]),
+    'nnl_text_token_count': (C.c_int, [c_p, i64, c_p, i64, C.c_int, c_p, c_p]),
+    'nnl_text_token_fill': (C.c_int, [c_p, i64, c_p, i64, C.c_int, c_p, i64, c_p, c_p, c_p, c_p]),
+    'nnl_text_token_hash': (C.c_int, [c_p, i64, c_p, c_p, i64, C.c_int, C.c_uint64, C.c_uint64, c_p, c_p]),
+    'nnl_text_vocab_insert': (C.c_int, [c_p, i64, c_p, c_p, c_p, i64, C.c_int, c_p, c_p, c_p]),
+    'nnl_text_vocab_verify': (C.c_int, [c_p, i64, c_p, c_p, c_p, i64, C.c_int, c_p, i64, c_p, c_p, i64, C.c_int, c_p, i64, c_p, c_p]),
+    'nnl_text_vocab_compact': (C.c_int, [c_p, c_p, c_p, i64, c_p, c_p, i64, c_p, i64, c_p, c_p]),
+    'nnl_text_vocab_assign': (C.c_int, [c_p, c_p, i64, c_p, i64, c_p]),
+    'nnl_text_vocab_lookup': (C.c_int, [c_p, i64, c_p, c_p, c_p, i64, C.c_int, c_p, i64, c_p, c_p, i64, c_p, c_p, i64, c_p, c_p]),
+    'nnl_text_ids_write': (C.c_int, [c_p, c_p, i64, c_p, i64, i64, C.c_int, c_p, c_p]),
 }
 
 for _name, (_res, _args) in SIGNATURES.items():

@@ -1,6 +1,7 @@
 """Language-model ops on the C ABI (K5 / K5b): LSTM layer, embedding with vocabulary-row dropout, fused softmax-CE.
 Imported into `ops` (use `ops.lstm_layer`, `ops.embedding_rowmask`, `ops.softmax_cross_entropy`).  Text generation (K5d):
-`LstmCellB1` / `lstm_cell_b1` and `LmNextToken` / `lm_next_token`, the batch-1 decode kernels of csrc/lm_generate.hip."""
+`LstmCellB1` / `lstm_cell_b1` and `LmNextToken` / `lm_next_token`, the batch-1 decode kernels of csrc/lm_generate.hip.  Tokeniser and
+vocabulary (K17): `TextCorpus`, `token_bounds`, `vocab_build_exact`, `text_numericalize`, the kernels of csrc/text_tokens.hip."""
 import torch
 import torch.nn.functional as F
 
@@ -368,3 +369,286 @@ def lm_next_token(emb, h, k, u, step, tokens, pos, top_probs=None, top_indices=N
     "one call of LmNextToken (see there); returns tokens"
     LmNextToken(emb, k, u, tokens, top_probs, top_indices, n_special, E, logits_out, workspace)(h, step, pos)
     return tokens
+
+
+# ---- tokeniser and vocabulary (K17, csrc/text_tokens.hip): a corpus is one resident byte buffer ---------------------------------------
+
+TEXT_TILE = 1024                         # NNL_TEXT_TILE: bytes per scan tile (tests place tokens on its edges)
+TEXT_TUP_LEN = -1                        # NNL_TEXT_TUP_LEN: tok_len of the pseudo-token t_up
+TEXT_MODE_GRAMMAR, TEXT_MODE_SPLIT = 0, 1
+TEXT_STATUS_OVERFLOW = 1
+TEXT_MAX_BYTES = 2 ** 31 - 1
+TEXT_HASH_MASK = 2 ** 64 - 1             # the product path keeps all 64 key bits; tests narrow it to force collisions
+TEXT_SEEDS = (0x243F6A8885A308D3, 0x13198A2E03707344, 0xA4093822299F31D0)      # a mismatch retries with the next; then RuntimeError
+TEXT_SPECIALS = ('_unk_', '_pad_', '_bos_', '_eos_')
+
+
+def _text_device(device=None):
+    return torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+
+
+class TextCorpus:
+    """Texts as ONE byte buffer on the device plus their offsets: `data` bytes [B] (B < 2^31, else ValueError: chunking is not built),
+    `offsets` n + 1 non-decreasing ints from 0 to B, text j = data[offsets[j]:offsets[j + 1]].  Offsets and bytes travel in one upload.
+    `host` keeps the bytes for decoding the few strings the host needs (the vocabulary)."""
+
+    def __init__(self, data, offsets, device=None):
+        import numpy as np
+        data = bytes(data)
+        off = np.ascontiguousarray(np.asarray(offsets, dtype=np.int64).reshape(-1))
+        if len(data) > TEXT_MAX_BYTES:
+            raise ValueError('TextCorpus: %d bytes; one resident buffer holds fewer than 2^31 (chunking is not built)' % len(data))
+        if off.size < 2 or off[0] != 0 or off[-1] != len(data) or (np.diff(off) < 0).any():
+            raise ValueError('TextCorpus: offsets must be n + 1 >= 2 non-decreasing values from 0 to len(data)')
+        self.host, self.host_offsets, self.n, self.B = data, off, off.size - 1, len(data)
+        head = off.size * 8
+        buf = np.empty(head + max(self.B, 1), dtype=np.uint8)
+        buf[:head] = off.view(np.uint8)
+        buf[head:head + self.B] = np.frombuffer(data, dtype=np.uint8)
+        dev = torch.from_numpy(buf).to(_text_device(device))
+        self.offsets, self.bytes = dev[:head].view(torch.int64), dev[head:]
+
+    @classmethod
+    def from_texts(cls, texts, device=None):
+        "texts: byte strings, laid end to end (the grammar never looks across a text boundary, so no separator is needed)"
+        import numpy as np
+        texts = [bytes(t) for t in texts]
+        if not texts:
+            raise ValueError('TextCorpus: no texts')
+        off = np.zeros(len(texts) + 1, dtype=np.int64)
+        np.cumsum([len(t) for t in texts], out=off[1:])
+        if off[-1] > TEXT_MAX_BYTES:
+            raise ValueError('TextCorpus: %d bytes; one resident buffer holds fewer than 2^31 (chunking is not built)' % off[-1])
+        return cls(b''.join(texts), off, device)
+
+
+class TextTokens:
+    "token records of a corpus on the device: start / len int32 [T] (len TEXT_TUP_LEN = the pseudo-token t_up), text_off int64 [n + 1]"
+
+    def __init__(self, start, length, text_off, T, mode):
+        self.start, self.len, self.text_off, self.T, self.mode = start, length, text_off, T, mode
+
+
+def token_bounds(corpus, mode=TEXT_MODE_GRAMMAR):
+    """Cuts `corpus` into tokens (nnl_text_token_count, one read of the total, nnl_text_token_fill).  The records and the per-text
+    token offsets share one int64 buffer [T + n + 1] so that ids and offsets later come back in one copy (see text_numericalize)."""
+    require_cuda(corpus.bytes)
+    dev = corpus.bytes.device
+    ntiles = (corpus.B + TEXT_TILE - 1) // TEXT_TILE
+    tile_base = torch.empty(ntiles + 1, dtype=torch.int64, device=dev)
+    check(lib.nnl_text_token_count(ptr(corpus.bytes), corpus.B, ptr(corpus.offsets), corpus.n, int(mode), ptr(tile_base), stream()))
+    T = int(tile_base[-1].item())
+    rec = torch.empty(2, max(T, 1), dtype=torch.int32, device=dev)
+    text_off = torch.empty(corpus.n + 1, dtype=torch.int64, device=dev)
+    check(lib.nnl_text_token_fill(ptr(corpus.bytes), corpus.B, ptr(corpus.offsets), corpus.n, int(mode), ptr(tile_base), T, ptr(rec[0]),
+                                  ptr(rec[1]), ptr(text_off), stream()))
+    return TextTokens(rec[0], rec[1], text_off, T, int(mode))
+
+
+def token_hash(corpus, toks, seed, hash_mask=None):
+    "uint64 keys [T] (as an int64 tensor) of the tokens' lowered bytes (nnl_text_token_hash); key 0 never occurs"
+    mask = TEXT_HASH_MASK if hash_mask is None else int(hash_mask)
+    keys = torch.empty(max(toks.T, 1), dtype=torch.int64, device=corpus.bytes.device)
+    check(lib.nnl_text_token_hash(ptr(corpus.bytes), corpus.B, ptr(toks.start), ptr(toks.len), toks.T, toks.mode, int(seed) & (2 ** 64 - 1),
+                                  mask, ptr(keys), stream()))
+    return keys
+
+
+def vocab_capacity(T):
+    "the table size for T tokens: a power of two >= 2 T and >= 1024"
+    cap = 1024
+    while cap < 2 * T:
+        cap *= 2
+    return cap
+
+
+class VocabTable:
+    "caller-allocated open-addressing table: key uint64 [cap] (0 = empty), count int32 [cap], first int32 [cap], status int32 [1]"
+
+    def __init__(self, cap, device=None):
+        dev = _text_device(device)
+        self.cap = int(cap)
+        self.key = torch.empty(self.cap, dtype=torch.int64, device=dev)
+        self.count = torch.empty(self.cap, dtype=torch.int32, device=dev)
+        self.first = torch.empty(self.cap, dtype=torch.int32, device=dev)
+        self.status = torch.zeros(1, dtype=torch.int32, device=dev)
+
+
+def vocab_insert(keys, T, table, reset=True):
+    """The raw insert (nnl_text_vocab_insert): returns tok_slot int32 [T] (-1 = no slot found).  table.status gets the overflow bit;
+    the call itself always returns: the probe loop ends after table.cap steps."""
+    tok_slot = torch.empty(max(T, 1), dtype=torch.int32, device=keys.device)
+    check(lib.nnl_text_vocab_insert(ptr(keys), T, ptr(table.key), ptr(table.count), ptr(table.first), table.cap, 1 if reset else 0,
+                                    ptr(tok_slot), ptr(table.status), stream()))
+    return tok_slot
+
+
+def vocab_verify(corpus, toks, tok_slot, table, first_corpus=None, first_toks=None):
+    "the number of tokens whose bytes differ from the first token of their slot (nnl_text_vocab_verify); 0 = the table is exact"
+    fc, ft = first_corpus or corpus, first_toks or toks
+    mism = torch.zeros(1, dtype=torch.int32, device=corpus.bytes.device)
+    check(lib.nnl_text_vocab_verify(ptr(corpus.bytes), corpus.B, ptr(toks.start), ptr(toks.len), ptr(tok_slot), toks.T, toks.mode,
+                                    ptr(fc.bytes), fc.B, ptr(ft.start), ptr(ft.len), ft.T, ft.mode, ptr(table.first), table.cap, ptr(mism),
+                                    stream()))
+    return mism
+
+
+def vocab_build(corpus, toks, seed, hash_mask=None, cap=None):
+    """hash, insert and verify with ONE seed: (table, tok_slot, mismatches).  RuntimeError if the table overflowed; a non-zero
+    mismatch count means two different strings share a slot and the table must not be used (vocab_build_exact retries)."""
+    keys = token_hash(corpus, toks, seed, hash_mask)
+    table = VocabTable(vocab_capacity(toks.T) if cap is None else cap, corpus.bytes.device)
+    tok_slot = vocab_insert(keys, toks.T, table)
+    mism = vocab_verify(corpus, toks, tok_slot, table)
+    status, mism = (int(v) for v in torch.cat([table.status, mism]).tolist())          # one small read for both
+    if status & TEXT_STATUS_OVERFLOW:
+        raise RuntimeError('text vocabulary: the table of %d slots overflowed (%d tokens)' % (table.cap, toks.T))
+    return table, tok_slot, mism
+
+
+def vocab_build_exact(corpus, toks, hash_mask=None, cap=None):
+    "vocab_build over TEXT_SEEDS until no token mismatches its slot: (table, tok_slot, seed); RuntimeError after the last seed"
+    for seed in TEXT_SEEDS:
+        table, tok_slot, mism = vocab_build(corpus, toks, seed, hash_mask, cap)
+        if mism == 0:
+            return table, tok_slot, seed
+    raise RuntimeError('text vocabulary: hash collisions under %d seeds in a row (%d tokens still differ from their slot)' % (len(TEXT_SEEDS), mism))
+
+
+def vocab_compact(table, toks):
+    """The occupied slots as a numpy int32 array [K, 5] = (slot, count, first, tok_start[first], tok_len[first]), sorted by `first`
+    (nnl_text_vocab_compact writes them in no particular order).  Counts and first indices are the same on every call; the slot
+    numbers depend on which of two colliding keys arrived first."""
+    dev = table.key.device
+    max_rows = max(min(table.cap, toks.T), 1)
+    out = torch.zeros(max_rows * 5 + 1, dtype=torch.int32, device=dev)           # rows, then the row counter: one copy back
+    check(lib.nnl_text_vocab_compact(ptr(table.key), ptr(table.count), ptr(table.first), table.cap, ptr(toks.start), ptr(toks.len), toks.T,
+                                     ptr(out), max_rows, ptr(out[max_rows * 5:]), stream()))
+    host = out.cpu().numpy()
+    K = int(host[-1])
+    if K > max_rows:
+        raise RuntimeError('text vocabulary: %d occupied slots for %d tokens' % (K, toks.T))
+    rows = host[:K * 5].reshape(K, 5)
+    return rows[rows[:, 2].argsort(kind='stable')]
+
+
+def vocab_assign(table, slots, ids):
+    "slot_id int32 [cap]: 0 everywhere but slot_id[slots[k]] = ids[k] (nnl_text_vocab_assign); slots, ids: host integer sequences"
+    import numpy as np
+    dev = table.key.device
+    K = len(slots)
+    both = np.zeros((2, max(K, 1)), dtype=np.int32)
+    both[0, :K], both[1, :K] = slots, ids
+    both = torch.from_numpy(both).to(dev)
+    slot_id = torch.empty(table.cap, dtype=torch.int32, device=dev)
+    check(lib.nnl_text_vocab_assign(ptr(both[0]), ptr(both[1]), K, ptr(slot_id), table.cap, stream()))
+    return slot_id
+
+
+def vocab_lookup(corpus, toks, keys, vcorpus, vtoks, table):
+    "tok_slot int32 [T]: the slot of the vocabulary string equal to each token, -1 if there is none (nnl_text_vocab_lookup)"
+    tok_slot = torch.empty(max(toks.T, 1), dtype=torch.int32, device=corpus.bytes.device)
+    check(lib.nnl_text_vocab_lookup(ptr(corpus.bytes), corpus.B, ptr(toks.start), ptr(toks.len), ptr(keys), toks.T, toks.mode,
+                                    ptr(vcorpus.bytes), vcorpus.B, ptr(vtoks.start), ptr(vtoks.len), vtoks.T, ptr(table.key), ptr(table.first),
+                                    table.cap, ptr(tok_slot), stream()))
+    return tok_slot
+
+
+def ids_write(tok_slot, slot_id, cap, toks, n, reverse=False, out=None):
+    "ids int64 [T] = slot_id[tok_slot] (0 where tok_slot < 0), every text's tokens mirrored if `reverse` (nnl_text_ids_write)"
+    ids = torch.empty(max(toks.T, 1), dtype=torch.int64, device=tok_slot.device) if out is None else out
+    check(lib.nnl_text_ids_write(ptr(tok_slot), ptr(slot_id), int(cap), ptr(toks.text_off), int(n), toks.T, 1 if reverse else 0, ptr(ids), stream()))
+    return ids
+
+
+def _token_string(corpus, start, length, lower):
+    if length == TEXT_TUP_LEN:
+        return 't_up'
+    b = corpus.host[start:start + length]
+    return (b.lower() if lower else b).decode('utf-8', 'surrogateescape')        # bytes.lower() lowers A-Z only
+
+
+def token_strings(corpus, toks):
+    "the tokens of every text as Python strings: list (per text) of lists — one copy back of the records, then host slicing"
+    import numpy as np
+    rec = torch.stack([toks.start, toks.len]).cpu().numpy()
+    off = toks.text_off.cpu().numpy()
+    data = corpus.host.lower() if toks.mode == TEXT_MODE_GRAMMAR else corpus.host
+    out = []
+    for j in range(corpus.n):
+        row = []
+        for t in range(int(off[j]), int(off[j + 1])):
+            s, l = int(rec[0, t]), int(rec[1, t])
+            row.append('t_up' if l == TEXT_TUP_LEN else data[s:s + l].decode('utf-8', 'surrogateescape'))
+        out.append(row)
+    return out
+
+
+class TextIds:
+    """What text_numericalize returns: ids int64 [T] and offsets int64 [n + 1] (numpy; text j = ids[offsets[j]:offsets[j + 1]]), the
+    stoi dict, and, for a vocabulary built here, counts = {token: occurrences} of the kept tokens (None for a given stoi)."""
+
+    def __init__(self, ids, offsets, stoi, counts):
+        self.ids, self.offsets, self.stoi, self.counts = ids, offsets, stoi, counts
+
+    def lists(self):
+        flat = self.ids.tolist()
+        off = self.offsets.tolist()
+        return [flat[off[j]:off[j + 1]] for j in range(len(off) - 1)]
+
+
+def text_numericalize(corpus, mode, max_vocab=60000, min_freq=6, stoi=None, reverse=False, hash_mask=None, cap=None):
+    """Token ids of every text of `corpus`, on the device end to end: token bounds, then either a vocabulary built from the corpus
+    (stoi=None: hash, insert, verify, compact; the host sorts the distinct tokens by (-count, first occurrence), cuts at max_vocab, THEN
+    drops count < min_freq — numericalize's order, Text.py:113-114 — and prefixes TEXT_SPECIALS) or a lookup in the given `stoi`
+    (absent tokens give 0).  A hash collision is detected, never merged: the build retries with the next seed and raises RuntimeError
+    after the last, as it does when the table overflows.  Only the kept vocabulary strings (and the distinct tokens as long as a special,
+    to find one spelled like it) are decoded on the host."""
+    import numpy as np
+    toks = token_bounds(corpus, mode)
+    dev = corpus.bytes.device
+    lower = mode == TEXT_MODE_GRAMMAR
+    counts = None
+    if stoi is None:
+        names, counts = list(TEXT_SPECIALS), {}
+        if toks.T:
+            table, tok_slot, _ = vocab_build_exact(corpus, toks, hash_mask, cap)
+            rows = vocab_compact(table, toks)
+            order = np.lexsort((rows[:, 2], -rows[:, 1].astype(np.int64)))[:max_vocab]
+            kept = rows[order]
+            kept = kept[kept[:, 1] >= min_freq]
+            for slot, count, first, start, length in kept.tolist():
+                names.append(_token_string(corpus, start, length, lower))
+                counts[names[-1]] = count
+            slots, ids = kept[:, 0].tolist(), list(range(len(TEXT_SPECIALS), len(names)))        # the id is the position in `names`
+            # a corpus token spelled like a special that was NOT kept still finds the special's entry in stoi (Text.py:119-120)
+            for slot, count, first, start, length in rows[np.isin(rows[:, 4], [len(s) for s in TEXT_SPECIALS])].tolist():
+                s = _token_string(corpus, start, length, lower)
+                if s in TEXT_SPECIALS and s not in counts:
+                    slots.append(slot)
+                    ids.append(TEXT_SPECIALS.index(s))
+            slot_id = vocab_assign(table, slots, ids)
+        stoi = {s: i for i, s in enumerate(names)}     # as Text.py:117: a corpus token spelled like a special takes the later position
+    else:
+        vocab = list(stoi.items())
+        if any(not (0 <= int(i) < 2 ** 31) for _, i in vocab):
+            raise ValueError('text_numericalize: stoi values must lie in [0, 2^31)')
+        if toks.T and vocab:
+            vcorpus = TextCorpus.from_texts([s.encode('utf-8', 'surrogateescape') for s, _ in vocab], dev)
+            vrec = np.stack([vcorpus.host_offsets[:-1], np.diff(vcorpus.host_offsets)]).astype(np.int32)
+            vrec = torch.from_numpy(vrec).to(dev)
+            vtoks = TextTokens(vrec[0], vrec[1], vcorpus.offsets, len(vocab), TEXT_MODE_SPLIT)     # each string is one token, as it is
+            table, _, seed = vocab_build_exact(vcorpus, vtoks, hash_mask, cap)
+            rows = vocab_compact(table, vtoks)
+            slot_id = vocab_assign(table, rows[:, 0], [int(vocab[f][1]) for f in rows[:, 2].tolist()])
+            tok_slot = vocab_lookup(corpus, toks, token_hash(corpus, toks, seed, hash_mask), vcorpus, vtoks, table)
+        elif toks.T:
+            table = VocabTable(16, dev)
+            tok_slot = torch.full((toks.T,), -1, dtype=torch.int32, device=dev)
+            slot_id = torch.zeros(16, dtype=torch.int32, device=dev)
+    both = torch.empty(toks.T + corpus.n + 1, dtype=torch.int64, device=dev)      # ids | offsets: one copy back
+    both[toks.T:] = toks.text_off
+    if toks.T:
+        ids_write(tok_slot, slot_id, table.cap, toks, corpus.n, reverse, out=both)
+    host = both.cpu().numpy()
+    return TextIds(host[:toks.T], host[toks.T:], stoi, counts)
