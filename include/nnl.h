@@ -320,7 +320,7 @@ int nnl_bn_sync_bwd(const float* dy, const float* y, const uint32_t* relu_mask, 
                     int world, float* dx, float* dres, float* dgamma, float* dbeta, int64_t rows, int64_t C, int relu,
                     void* workspace, size_t workspace_bytes, void* stream);
 
-/* ---- pooling of the vision path (NHWC, C % 4 == 0 for maxpool) ---------------------------------------------------------
+/* ---- pooling of the vision path (NHWC; maxpool takes any C: 4-channel vectors when C % 4 == 0, a scalar-channel route otherwise) ----
  * nn.MaxPool2d(ksize, stride, pad) of the ResNet stem (Applications/VisionModels/retinanet.py:307,374; torchvision
  * resnet.maxpool) with torch's tie rule — `if ((val > max) || isnan(val))` in (kh, kw) scan order.  idx [N,P,Q,C] uint8 =
  * kh*ksize + kw of the winning tap, kept for the backward, which GATHERS (each input pixel sums dy over the windows whose
@@ -356,6 +356,43 @@ int nnl_gconv2d_dgrad(const float* dy, const float* w, float* dx, int64_t N, int
 size_t nnl_gconv2d_workspace_bytes(int64_t N, int64_t H, int64_t W, int64_t C, int64_t K, int64_t G, int R, int stride, int pad);
 int nnl_gconv2d_wgrad(const float* x, const float* dy, float* dw, void* ws, size_t ws_bytes, int64_t N, int64_t H, int64_t W, int64_t C,
                       int64_t K, int64_t G, int R, int stride, int pad, void* stream);
+
+/* ---- K18: depthwise convolution, nn.Conv2d(C, C, R, groups = C) (Applications/VisionModels/nasnet.py SeparableConv2d) ------------------
+ * Activations NHWC fp32; w is the parameter as it is stored, [C, 1, R, R]; dw comes back in that layout.  R in {3, 5, 7}, stride in {1, 2},
+ * any C (a 4-channel vector route when C % 4 == 0, a scalar-channel route otherwise).  The padding is stated from the top/left only: tap
+ * (r, s) of output (p, q) reads x[p stride - pad_lo + r, q stride - pad_lo + s], everything outside the image reads as zero, and the
+ * caller states P and Q: 0 <= pad_lo <= R - 1, P >= 1, (P - 1) stride - pad_lo <= H - 1 (every window touches the image), Q likewise.
+ * N < 65536, every tensor below 2^31 elements.  Anything else is NNL_ERR_INVALID_ARG and nothing is launched.
+ * relu_in != 0 convolves max(x, 0) (the ReLU in front of every BranchSeparables, whose input other branches read un-rectified).
+ * Every sum runs in a fixed order and there are no atomics: two calls on the same inputs give the same bits.
+ * nnl_dwconv2d_fwd: y [N,P,Q,C] = conv(act(x), w) + bias (bias may be NULL). */
+int nnl_dwconv2d_fwd(const float* x, const float* w, const float* bias, float* y, int64_t N, int64_t H, int64_t W, int64_t C, int64_t P,
+                     int64_t Q, int R, int stride, int pad_lo, int relu_in, void* stream);
+/* nnl_dwconv2d_dgrad: dx [N,H,W,C] from dy [N,P,Q,C], gathered per input pixel over the taps whose output position exists; every element
+ * of dx is written.  With relu_in the result is gated by x > 0 (x is required then, and may be NULL otherwise). */
+int nnl_dwconv2d_dgrad(const float* dy, const float* w, const float* x, float* dx, int64_t N, int64_t H, int64_t W, int64_t C, int64_t P,
+                       int64_t Q, int R, int stride, int pad_lo, int relu_in, void* stream);
+/* nnl_dwconv2d_wgrad: dw[c, r, s] = sum over n, p, q of dy * act(x).  The N*P*Q pixels are cut into slabs whose partial sums go to the
+ * workspace (nnl_dwconv2d_wgrad_workspace_bytes; 0 = one slab, ws may be NULL) and are added in slab order by a second launch; a
+ * workspace that is too small is NNL_ERR_WORKSPACE. */
+size_t nnl_dwconv2d_wgrad_workspace_bytes(int64_t N, int64_t H, int64_t W, int64_t C, int64_t P, int64_t Q, int R, int stride, int pad_lo);
+int nnl_dwconv2d_wgrad(const float* x, const float* dy, float* dw, void* ws, size_t ws_bytes, int64_t N, int64_t H, int64_t W, int64_t C,
+                       int64_t P, int64_t Q, int R, int stride, int pad_lo, int relu_in, void* stream);
+
+/* ---- K18: average pooling and strided subsampling of the NASNet cells (nasnet.py AvgPoolPad, the cells' AvgPool2d, path_1 / path_2) ----
+ * nnl_avgpool2d_*: nn.AvgPool2d(ksize, stride, pad, count_include_pad), NHWC, any C, with the same stated-P/Q, pad_lo convention and
+ * checks as the depthwise convolution (1 <= ksize <= 15, 0 <= pad_lo <= ksize - 1).  The divisor of a window is the number of its taps
+ * inside the image (count_include_pad == 0) or ksize^2.  The backward gathers: no atomics. */
+int nnl_avgpool2d_fwd(const float* x, float* y, int64_t N, int64_t H, int64_t W, int64_t C, int64_t P, int64_t Q, int ksize, int stride,
+                      int pad_lo, int count_include_pad, void* stream);
+int nnl_avgpool2d_bwd(const float* dy, float* dx, int64_t N, int64_t H, int64_t W, int64_t C, int64_t P, int64_t Q, int ksize, int stride,
+                      int pad_lo, int count_include_pad, void* stream);
+/* nnl_subsample2d_*: y[p, q] = x[p stride + off, q stride + off], or 0 outside the image: AvgPool2d(1, stride) (off = 0) and the
+ * ZeroPad2d((0, 1, 0, 1)) -> [1:, 1:] -> AvgPool2d(1, 2) chain (off = 1).  The backward writes every element of dx. */
+int nnl_subsample2d_fwd(const float* x, float* y, int64_t N, int64_t H, int64_t W, int64_t C, int64_t P, int64_t Q, int stride, int off,
+                        void* stream);
+int nnl_subsample2d_bwd(const float* dy, float* dx, int64_t N, int64_t H, int64_t W, int64_t C, int64_t P, int64_t Q, int stride, int off,
+                        void* stream);
 
 /* ---- K15: squeeze-and-excitation tail of a SENet block (Applications/VisionModels/senet.py:118-137 SEModule, :161-162) -------------
  *   out = relu( x * sigmoid(z[n, c]) + residual ),  z = fc2(relu(fc1(m))),  m[n, c] = mean over the HW pixels of x   (x NHWC = [N, HW, C])

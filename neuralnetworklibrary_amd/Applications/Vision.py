@@ -726,11 +726,15 @@ def _num_features(body, data):
     """Channel count of the body's output.  The reference pushes a zero image through the training-mode body
     (Vision.py:1312-1313), which as a side effect moves every BN running stat one momentum step towards (0, 0); with a
     GPU present the same probe runs here (on the device: the HIP body has no CPU path) so the buffers match.  Without
-    a GPU (host-logic tests) the count is read off the last conv / batch-norm."""
+    a GPU (host-logic tests) the count is the body's own `num_features` (a body whose output is a concatenation, NASNetALarge), or
+    is read off the last conv / batch-norm."""
     if torch.cuda.is_available():
         dev = default_device()
         with torch.no_grad():
             return body.to(dev)(torch.zeros(1, 3, data.sz[0], data.sz[1], device=dev)).shape[1]
+    last = getattr(body, 'num_features', None)
+    if isinstance(last, int):
+        return last
     last = None
     for m in body.modules():
         if isinstance(m, nn.BatchNorm2d):

@@ -18,7 +18,7 @@ import torch.nn as nn
 from ... import ops
 from ...General.Core import default_device
 
-__all__ = ['HipConv2d', 'HipGroupedConv2d', 'conv3x3', 'BasicBlock', 'Bottleneck', 'PyramidFeatures', 'RegressionModel',
+__all__ = ['HipConv2d', 'HipGroupedConv2d', 'HipDepthwiseConv2d', 'HipAvgPool2d', 'conv3x3', 'BasicBlock', 'Bottleneck', 'PyramidFeatures', 'RegressionModel',
            'ClassificationModel', 'RetinaNet', 'retinanet18', 'retinanet34', 'retinanet50', 'retinanet101',
            'retinanet152', 'get_anchor_set', 'get_anchor_shifts', 'AnchorGenerator', 'intersections', 'jaccard', 'nms',
            'BBoxPredictor']
@@ -75,6 +75,49 @@ class HipMaxPool2d(nn.MaxPool2d):
         if self.dilation != 1 or self.return_indices or not all(isinstance(v, int) for v in (k, s, p)):
             raise NotImplementedError('HipMaxPool2d: only the square pooling the reference uses')
         return ops.maxpool2d(x, k, s, p, ceil_mode=self.ceil_mode)
+
+
+class HipDepthwiseConv2d(nn.Conv2d):
+    """nn.Conv2d(C, C, R, groups=C) (same parameters / state_dict) on the depthwise kernels of csrc/dwconv.hip (ops.depthwise_conv2d): the
+    first half of NASNet's SeparableConv2d (nasnet.py:93-107).  The weight stays in the parameter's own layout, [C, 1, R, R].
+    relu_in=True convolves relu(x); zero_pad=z computes `ZeroPad2d((z, 0, z, 0))` -> this convolution -> `[1:, 1:]` as one asymmetric
+    convolution (ops.fold_zero_pad), without a padded or a sliced tensor."""
+
+    def forward(self, x, relu_in=False, zero_pad=None):
+        if self.dilation != (1, 1):
+            raise NotImplementedError('HipDepthwiseConv2d: dilation %r is not supported' % (self.dilation,))
+        if self.kernel_size[0] != self.kernel_size[1]:
+            raise NotImplementedError('HipDepthwiseConv2d: kernel_size %r must be square' % (self.kernel_size,))
+        if not (self.groups == self.in_channels == self.out_channels):
+            raise NotImplementedError('HipDepthwiseConv2d: groups %r must equal the %d input and %d output channels'
+                                      % (self.groups, self.in_channels, self.out_channels))
+        if self.padding_mode != 'zeros' or isinstance(self.padding, str) or self.padding[0] != self.padding[1]:
+            raise NotImplementedError('HipDepthwiseConv2d: padding_mode %r / padding %r is not supported' % (self.padding_mode, self.padding))
+        if self.stride[0] != self.stride[1]:
+            raise NotImplementedError('HipDepthwiseConv2d: stride %r must be the same in both directions' % (self.stride,))
+        R, s, p = self.kernel_size[0], self.stride[0], self.padding[0]
+        lo = size = None
+        if zero_pad is not None:
+            (lo, P), (_, Q) = ops.fold_zero_pad(x.shape[2], R, s, p, zero_pad), ops.fold_zero_pad(x.shape[3], R, s, p, zero_pad)
+            size = (P, Q)
+        return ops.depthwise_conv2d(x, self.weight, self.bias, s, p, pad_lo=lo, out_size=size, relu_in=relu_in)
+
+
+class HipAvgPool2d(nn.AvgPool2d):
+    """nn.AvgPool2d (square window, floor mode, no divisor override) on the NHWC HIP kernels of csrc/pool.hip; a 1 x 1 window is the
+    strided subsample.  zero_pad=z folds `ZeroPad2d((z, 0, z, 0))` -> pool -> `[1:, 1:]` (NASNet's AvgPoolPad) into one launch."""
+
+    def forward(self, x, zero_pad=None):
+        k, s, p = self.kernel_size, self.stride, self.padding
+        if self.ceil_mode or self.divisor_override is not None or not all(isinstance(v, int) for v in (k, s, p)):
+            raise NotImplementedError('HipAvgPool2d: only the square floor-mode pooling the reference uses')
+        if k == 1 and p == 0 and zero_pad is None:
+            return ops.subsample2d(x, s, 0)
+        lo = size = None
+        if zero_pad is not None:
+            (lo, P), (_, Q) = ops.fold_zero_pad(x.shape[2], k, s, p, zero_pad), ops.fold_zero_pad(x.shape[3], k, s, p, zero_pad)
+            size = (P, Q)
+        return ops.avgpool2d(x, k, s, p, count_include_pad=self.count_include_pad, pad_lo=lo, out_size=size)
 
 
 class _ConvReLU(HipConv2d):

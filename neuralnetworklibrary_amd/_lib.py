@@ -87,6 +87,14 @@ SIGNATURES = {
     'nnl_gconv2d_dgrad': (C.c_int, [c_p, c_p, c_p, i64, i64, i64, i64, i64, i64, C.c_int, C.c_int, C.c_int, c_p]),
     'nnl_gconv2d_workspace_bytes': (sz, [i64, i64, i64, i64, i64, i64, C.c_int, C.c_int, C.c_int]),
     'nnl_gconv2d_wgrad': (C.c_int, [c_p, c_p, c_p, c_p, sz, i64, i64, i64, i64, i64, i64, C.c_int, C.c_int, C.c_int, c_p]),
+    'nnl_dwconv2d_fwd': (C.c_int, [c_p, c_p, c_p, c_p, i64, i64, i64, i64, i64, i64, C.c_int, C.c_int, C.c_int, C.c_int, c_p]),
+    'nnl_dwconv2d_dgrad': (C.c_int, [c_p, c_p, c_p, c_p, i64, i64, i64, i64, i64, i64, C.c_int, C.c_int, C.c_int, C.c_int, c_p]),
+    'nnl_dwconv2d_wgrad_workspace_bytes': (sz, [i64, i64, i64, i64, i64, i64, C.c_int, C.c_int, C.c_int]),
+    'nnl_dwconv2d_wgrad': (C.c_int, [c_p, c_p, c_p, c_p, sz, i64, i64, i64, i64, i64, i64, C.c_int, C.c_int, C.c_int, C.c_int, c_p]),
+    'nnl_avgpool2d_fwd': (C.c_int, [c_p, c_p, i64, i64, i64, i64, i64, i64, C.c_int, C.c_int, C.c_int, C.c_int, c_p]),
+    'nnl_avgpool2d_bwd': (C.c_int, [c_p, c_p, i64, i64, i64, i64, i64, i64, C.c_int, C.c_int, C.c_int, C.c_int, c_p]),
+    'nnl_subsample2d_fwd': (C.c_int, [c_p, c_p, i64, i64, i64, i64, i64, i64, C.c_int, C.c_int, c_p]),
+    'nnl_subsample2d_bwd': (C.c_int, [c_p, c_p, i64, i64, i64, i64, i64, i64, C.c_int, C.c_int, c_p]),
     'nnl_se_squeeze': (C.c_int, [c_p, c_p, i64, i64, i64, c_p]),
     'nnl_se_excite_fwd': (C.c_int, [c_p, c_p, c_p, c_p, i64, i64, i64, c_p]),
     'nnl_se_excite_bwd': (C.c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, i64, i64, i64, c_p]),

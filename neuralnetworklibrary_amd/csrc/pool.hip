@@ -5,7 +5,8 @@
 //     reproducible;
 //   * AdaptiveConcatPool2d (reference General/Layers.py:78-87): cat([AdaptiveMaxPool2d(1), AdaptiveAvgPool2d(1)], 1) as one
 //     pass over the [N, HW, C] activation; the max gradient goes to the first arg-max pixel (torch's adaptive_max_pool2d
-//     backward), the mean gradient to every pixel.
+//     backward), the mean gradient to every pixel;
+//   * AvgPool2d and the strided subsample of the NASNet cells (at the end of this file).
 // Algorithmic bytes: maxpool fwd 4*(in + out) + out (uint8 window index), bwd 4*(in + ~2.25*out) ; concat-pool 4*in each way.
 #include "nnl_common.h"
 
@@ -82,6 +83,65 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const float* __restric
   }
 }
 
+// The scalar-channel route of the two kernels above, for C % 4 != 0 (NASNet's CellStem0 pools 42 channels, nasnet.py:183): one thread =
+// one pixel x ONE channel; the same scan order, tie rule, NaN rule and gather backward.
+__global__ __launch_bounds__(256) void maxpool_fwd_c1_kernel(const float* __restrict__ x, float* __restrict__ y,
+                                                             uint8_t* __restrict__ idx, int N, int H, int W, int C, int P, int Q,
+                                                             int ks, int stride, int pad) {
+  const long total = (long)N * P * Q * C;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int c = (int)(i % C);
+    long r = i / C;
+    const int q = (int)(r % Q); r /= Q;
+    const int p = (int)(r % P);
+    const int n = (int)(r / P);
+    float best = -__builtin_inff();
+    int bi = -1;
+    for (int kh = 0; kh < ks; ++kh) {
+      const int h = p * stride - pad + kh;
+      if ((unsigned)h >= (unsigned)H) continue;
+      for (int kw = 0; kw < ks; ++kw) {
+        const int w = q * stride - pad + kw;
+        if ((unsigned)w >= (unsigned)W) continue;
+        const float v = x[((long)(n * H + h) * W + w) * C + c];
+        if (bi < 0 || v > best || v != v) {
+          best = v;
+          bi = kh * ks + kw;
+        }
+      }
+    }
+    y[i] = best;
+    idx[i] = (uint8_t)bi;
+  }
+}
+
+__global__ __launch_bounds__(256) void maxpool_bwd_c1_kernel(const float* __restrict__ dy, const uint8_t* __restrict__ idx,
+                                                             float* __restrict__ dx, int N, int H, int W, int C, int P, int Q, int ks,
+                                                             int stride, int pad) {
+  const long total = (long)N * H * W * C;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int c = (int)(i % C);
+    long r = i / C;
+    const int w = (int)(r % W); r /= W;
+    const int h = (int)(r % H);
+    const int n = (int)(r / H);
+    float acc = 0.f;
+    int p_lo = h + pad - ks + 1; p_lo = p_lo > 0 ? (p_lo + stride - 1) / stride : 0;
+    int p_hi = (h + pad) / stride; if (p_hi > P - 1) p_hi = P - 1;
+    int q_lo = w + pad - ks + 1; q_lo = q_lo > 0 ? (q_lo + stride - 1) / stride : 0;
+    int q_hi = (w + pad) / stride; if (q_hi > Q - 1) q_hi = Q - 1;
+    for (int p = p_lo; p <= p_hi; ++p) {
+      const int kh = h + pad - p * stride;
+      for (int q = q_lo; q <= q_hi; ++q) {
+        const int t = kh * ks + (w + pad - q * stride);
+        const long o = ((long)(n * P + p) * Q + q) * C + c;
+        if (idx[o] == t) acc += dy[o];
+      }
+    }
+    dx[i] = acc;
+  }
+}
+
 // block = 256 threads = 64 channel lanes x 4 pixel lanes; grid = (ceil(C/64), N)
 __global__ __launch_bounds__(256) void concat_pool_fwd_kernel(const float* __restrict__ x, float* __restrict__ out,
                                                               int32_t* __restrict__ argmax, int HW, int C) {
@@ -149,13 +209,19 @@ bool pool_out_ok(int64_t H, int64_t P, int ksize, int stride, int pad) {
 
 extern "C" int nnl_maxpool2d_fwd(const float* x, float* y, uint8_t* idx, int64_t N, int64_t H, int64_t W, int64_t C, int64_t P,
                                  int64_t Q, int ksize, int stride, int pad, void* stream) {
-  NNL_CHECK_ARG(x && y && idx && N > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0, "maxpool2d_fwd: bad argument (C %% 4 == 0)");
+  NNL_CHECK_ARG(x && y && idx && N > 0 && H > 0 && W > 0 && C > 0, "maxpool2d_fwd: bad argument");
   NNL_CHECK_ARG(ksize >= 1 && ksize <= 15 && stride >= 1 && pad >= 0 && 2 * pad <= ksize, "maxpool2d_fwd: bad window");
   NNL_CHECK_ARG(pool_out_ok(H, P, ksize, stride, pad) && pool_out_ok(W, Q, ksize, stride, pad), "maxpool2d_fwd: bad P/Q");
   NNL_CHECK_ARG(N * H * W * C < (1L << 40), "maxpool2d_fwd: tensor too large");
   hipStream_t s = (hipStream_t)stream;
-  const long total = N * P * Q * (C / 4);
   NnlProfScope prof(NNL_PROF_ELEMENTWISE, s, 4.0 * N * H * W * C + 5.0 * N * P * Q * C);
+  if (C % 4 != 0) {
+    hipLaunchKernelGGL(maxpool_fwd_c1_kernel, dim3(ew_blocks(N * P * Q * C)), dim3(256), 0, s, x, y, idx, (int)N, (int)H, (int)W, (int)C,
+                       (int)P, (int)Q, ksize, stride, pad);
+    NNL_CHECK_LAUNCH();
+    return NNL_OK;
+  }
+  const long total = N * P * Q * (C / 4);
   hipLaunchKernelGGL(maxpool_fwd_kernel, dim3(ew_blocks(total)), dim3(256), 0, s, x, y, idx, (int)N, (int)H, (int)W, (int)(C / 4),
                      (int)P, (int)Q, ksize, stride, pad);
   NNL_CHECK_LAUNCH();
@@ -164,12 +230,18 @@ extern "C" int nnl_maxpool2d_fwd(const float* x, float* y, uint8_t* idx, int64_t
 
 extern "C" int nnl_maxpool2d_bwd(const float* dy, const uint8_t* idx, float* dx, int64_t N, int64_t H, int64_t W, int64_t C,
                                  int64_t P, int64_t Q, int ksize, int stride, int pad, void* stream) {
-  NNL_CHECK_ARG(dy && dx && idx && N > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0, "maxpool2d_bwd: bad argument (C %% 4 == 0)");
+  NNL_CHECK_ARG(dy && dx && idx && N > 0 && H > 0 && W > 0 && C > 0, "maxpool2d_bwd: bad argument");
   NNL_CHECK_ARG(ksize >= 1 && ksize <= 15 && stride >= 1 && pad >= 0 && 2 * pad <= ksize, "maxpool2d_bwd: bad window");
   NNL_CHECK_ARG(pool_out_ok(H, P, ksize, stride, pad) && pool_out_ok(W, Q, ksize, stride, pad), "maxpool2d_bwd: bad P/Q");
   hipStream_t s = (hipStream_t)stream;
-  const long total = N * H * W * (C / 4);
   NnlProfScope prof(NNL_PROF_ELEMENTWISE, s, 4.0 * N * H * W * C + 5.0 * N * P * Q * C);
+  if (C % 4 != 0) {
+    hipLaunchKernelGGL(maxpool_bwd_c1_kernel, dim3(ew_blocks(N * H * W * C)), dim3(256), 0, s, dy, idx, dx, (int)N, (int)H, (int)W, (int)C,
+                       (int)P, (int)Q, ksize, stride, pad);
+    NNL_CHECK_LAUNCH();
+    return NNL_OK;
+  }
+  const long total = N * H * W * (C / 4);
   hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(ew_blocks(total)), dim3(256), 0, s, dy, idx, dx, (int)N, (int)H, (int)W, (int)(C / 4),
                      (int)P, (int)Q, ksize, stride, pad);
   NNL_CHECK_LAUNCH();
@@ -225,6 +297,195 @@ extern "C" int nnl_upsample2_bwd(const float* dy, float* dsmall, int64_t N, int6
   long blocks = nnl_cdiv(total4, 256);
   if (blocks > 16384) blocks = 16384;
   hipLaunchKernelGGL(upsample2_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, s, dy, dsmall, total4, (int)h, (int)w, (int)(C / 4));
+  NNL_CHECK_LAUNCH();
+  return NNL_OK;
+}
+
+
+// ---- average pooling and strided subsampling of the NASNet cells (reference Applications/VisionModels/nasnet.py:79-90, 186-189, 232-238) ----
+// nn.AvgPool2d(ksize, stride, pad, count_include_pad) with the padding stated from the top/left only: tap (kh, kw) of output (p, q) reads
+// x[p stride - pad_lo + kh, q stride - pad_lo + kw], the caller states P and Q, taps outside the image add nothing.  The divisor is the
+// number of taps inside the image (count_include_pad = 0) or ksize^2.  One thread = one pixel x one channel vector (4 channels when
+// C % 4 == 0, else 1); the backward gathers over the windows that contain the input pixel, in (p, q) order: no atomics.
+// HBM-bound: 4 B per input element + 4 B per output element, each way.
+namespace {
+
+template <int V> struct PoolVec;
+template <> struct PoolVec<1> { typedef float T; };
+template <> struct PoolVec<4> { typedef f32x4 T; };
+
+struct WGeom { int N, H, W, Cv, P, Q, ks, stride, pad_lo, incl; };
+
+// in-image taps of the window that starts at `lo` along an axis of `len`
+__device__ __forceinline__ int taps_inside(int lo, int ks, int len) { return min(lo + ks, len) - max(lo, 0); }
+
+template <int V>
+__global__ __launch_bounds__(256) void avgpool_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, WGeom g) {
+  typedef typename PoolVec<V>::T VT;
+  const long total = (long)g.N * g.P * g.Q * g.Cv;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int c = (int)(i % g.Cv);
+    long r = i / g.Cv;
+    const int q = (int)(r % g.Q); r /= g.Q;
+    const int p = (int)(r % g.P);
+    const long n = r / g.P;
+    const int hl = p * g.stride - g.pad_lo, wl = q * g.stride - g.pad_lo;
+    VT acc = VT(0.f);
+    for (int kh = 0; kh < g.ks; ++kh) {
+      const int h = hl + kh;
+      if ((unsigned)h >= (unsigned)g.H) continue;
+      for (int kw = 0; kw < g.ks; ++kw) {
+        const int w = wl + kw;
+        if ((unsigned)w >= (unsigned)g.W) continue;
+        acc += reinterpret_cast<const VT*>(x)[((n * g.H + h) * g.W + w) * g.Cv + c];
+      }
+    }
+    const int div = g.incl ? g.ks * g.ks : taps_inside(hl, g.ks, g.H) * taps_inside(wl, g.ks, g.W);
+    reinterpret_cast<VT*>(y)[i] = acc / (float)div;
+  }
+}
+
+template <int V>
+__global__ __launch_bounds__(256) void avgpool_bwd_kernel(const float* __restrict__ dy, float* __restrict__ dx, WGeom g) {
+  typedef typename PoolVec<V>::T VT;
+  const long total = (long)g.N * g.H * g.W * g.Cv;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int c = (int)(i % g.Cv);
+    long r = i / g.Cv;
+    const int w = (int)(r % g.W); r /= g.W;
+    const int h = (int)(r % g.H);
+    const long n = r / g.H;
+    // windows p with p stride - pad_lo <= h <= p stride - pad_lo + ks - 1
+    int p_lo = h + g.pad_lo - g.ks + 1; p_lo = p_lo > 0 ? (p_lo + g.stride - 1) / g.stride : 0;
+    int p_hi = (h + g.pad_lo) / g.stride; if (p_hi > g.P - 1) p_hi = g.P - 1;
+    int q_lo = w + g.pad_lo - g.ks + 1; q_lo = q_lo > 0 ? (q_lo + g.stride - 1) / g.stride : 0;
+    int q_hi = (w + g.pad_lo) / g.stride; if (q_hi > g.Q - 1) q_hi = g.Q - 1;
+    VT acc = VT(0.f);
+    for (int p = p_lo; p <= p_hi; ++p) {
+      const int th = g.incl ? g.ks : taps_inside(p * g.stride - g.pad_lo, g.ks, g.H);
+      for (int q = q_lo; q <= q_hi; ++q) {
+        const int tw = g.incl ? g.ks : taps_inside(q * g.stride - g.pad_lo, g.ks, g.W);
+        acc += reinterpret_cast<const VT*>(dy)[((n * g.P + p) * g.Q + q) * g.Cv + c] / (float)(th * tw);
+      }
+    }
+    reinterpret_cast<VT*>(dx)[i] = acc;
+  }
+}
+
+// y[p, q] = x[p stride + off, q stride + off], 0 outside the image; BWD scatters nothing: every input pixel looks up its one output
+template <int V, bool BWD>
+__global__ __launch_bounds__(256) void subsample_kernel(const float* __restrict__ src, float* __restrict__ dst, WGeom g, int off) {
+  typedef typename PoolVec<V>::T VT;
+  const int A = BWD ? g.H : g.P, B = BWD ? g.W : g.Q;            // the extent of dst
+  const long total = (long)g.N * A * B * g.Cv;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int c = (int)(i % g.Cv);
+    long r = i / g.Cv;
+    const int b = (int)(r % B); r /= B;
+    const int a = (int)(r % A);
+    const long n = r / A;
+    VT v = VT(0.f);
+    if (BWD) {
+      const int th = a - off, tw = b - off;
+      const int p = th / g.stride, q = tw / g.stride;
+      if (th >= 0 && tw >= 0 && p * g.stride == th && q * g.stride == tw && p < g.P && q < g.Q)
+        v = reinterpret_cast<const VT*>(src)[((n * g.P + p) * g.Q + q) * g.Cv + c];
+    } else {
+      const int h = a * g.stride + off, w = b * g.stride + off;
+      if (h < g.H && w < g.W) v = reinterpret_cast<const VT*>(src)[((n * g.H + h) * g.W + w) * g.Cv + c];
+    }
+    reinterpret_cast<VT*>(dst)[i] = v;
+  }
+}
+
+int window_geom(const char* who, int64_t N, int64_t H, int64_t W, int64_t C, int64_t P, int64_t Q, int ksize, int stride, int pad_lo,
+                int incl, WGeom* g) {
+  NNL_CHECK_ARG(N > 0 && H > 0 && W > 0 && C > 0, "%s: sizes must be positive", who);
+  NNL_CHECK_ARG(ksize >= 1 && ksize <= 15 && stride >= 1, "%s: bad window (1 <= ksize <= 15, stride >= 1)", who);
+  NNL_CHECK_ARG(pad_lo >= 0 && pad_lo <= ksize - 1, "%s: pad_lo = %d (0 .. ksize - 1)", who, pad_lo);
+  NNL_CHECK_ARG(P >= 1 && (P - 1) * stride - pad_lo <= H - 1, "%s: P = %ld: every window must touch the %ld rows", who, (long)P, (long)H);
+  NNL_CHECK_ARG(Q >= 1 && (Q - 1) * stride - pad_lo <= W - 1, "%s: Q = %ld: every window must touch the %ld columns", who, (long)Q, (long)W);
+  NNL_CHECK_ARG(H < (1L << 24) && W < (1L << 24) && P < (1L << 24) && Q < (1L << 24) && N * H * W * C < (1L << 40) && N * P * Q * C < (1L << 40),
+                "%s: tensor too large", who);
+  const int V = C % 4 == 0 ? 4 : 1;
+  *g = WGeom{(int)N, (int)H, (int)W, (int)(C / V), (int)P, (int)Q, ksize, stride, pad_lo, incl != 0};
+  return NNL_OK;
+}
+
+}  // namespace
+
+extern "C" int nnl_avgpool2d_fwd(const float* x, float* y, int64_t N, int64_t H, int64_t W, int64_t C, int64_t P, int64_t Q, int ksize,
+                                 int stride, int pad_lo, int count_include_pad, void* stream) {
+  WGeom g;
+  if (int e = window_geom("avgpool2d_fwd", N, H, W, C, P, Q, ksize, stride, pad_lo, count_include_pad, &g)) return e;
+  NNL_CHECK_ARG(x && y, "avgpool2d_fwd: null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  NnlProfScope prof(NNL_PROF_ELEMENTWISE, s, 4.0 * N * H * W * C + 4.0 * N * P * Q * C);
+  const dim3 grid(ew_blocks(N * P * Q * g.Cv));
+  if (C % 4 == 0)
+    hipLaunchKernelGGL(avgpool_fwd_kernel<4>, grid, dim3(256), 0, s, x, y, g);
+  else
+    hipLaunchKernelGGL(avgpool_fwd_kernel<1>, grid, dim3(256), 0, s, x, y, g);
+  NNL_CHECK_LAUNCH();
+  return NNL_OK;
+}
+
+extern "C" int nnl_avgpool2d_bwd(const float* dy, float* dx, int64_t N, int64_t H, int64_t W, int64_t C, int64_t P, int64_t Q, int ksize,
+                                 int stride, int pad_lo, int count_include_pad, void* stream) {
+  WGeom g;
+  if (int e = window_geom("avgpool2d_bwd", N, H, W, C, P, Q, ksize, stride, pad_lo, count_include_pad, &g)) return e;
+  NNL_CHECK_ARG(dy && dx, "avgpool2d_bwd: null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  NnlProfScope prof(NNL_PROF_ELEMENTWISE, s, 4.0 * N * H * W * C + 4.0 * N * P * Q * C);
+  const dim3 grid(ew_blocks(N * H * W * g.Cv));
+  if (C % 4 == 0)
+    hipLaunchKernelGGL(avgpool_bwd_kernel<4>, grid, dim3(256), 0, s, dy, dx, g);
+  else
+    hipLaunchKernelGGL(avgpool_bwd_kernel<1>, grid, dim3(256), 0, s, dy, dx, g);
+  NNL_CHECK_LAUNCH();
+  return NNL_OK;
+}
+
+namespace {
+int subsample_geom(const char* who, int64_t N, int64_t H, int64_t W, int64_t C, int64_t P, int64_t Q, int stride, int off, WGeom* g) {
+  NNL_CHECK_ARG(N > 0 && H > 0 && W > 0 && C > 0 && P > 0 && Q > 0, "%s: sizes must be positive", who);
+  NNL_CHECK_ARG(stride >= 1 && off >= 0 && off < (1 << 24), "%s: bad stride = %d / off = %d", who, stride, off);
+  NNL_CHECK_ARG(H < (1L << 24) && W < (1L << 24) && P < (1L << 24) && Q < (1L << 24) && N * H * W * C < (1L << 40) && N * P * Q * C < (1L << 40),
+                "%s: tensor too large", who);
+  const int V = C % 4 == 0 ? 4 : 1;
+  *g = WGeom{(int)N, (int)H, (int)W, (int)(C / V), (int)P, (int)Q, 1, stride, 0, 0};
+  return NNL_OK;
+}
+}  // namespace
+
+extern "C" int nnl_subsample2d_fwd(const float* x, float* y, int64_t N, int64_t H, int64_t W, int64_t C, int64_t P, int64_t Q, int stride,
+                                   int off, void* stream) {
+  WGeom g;
+  if (int e = subsample_geom("subsample2d_fwd", N, H, W, C, P, Q, stride, off, &g)) return e;
+  NNL_CHECK_ARG(x && y, "subsample2d_fwd: null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  NnlProfScope prof(NNL_PROF_ELEMENTWISE, s, 8.0 * N * P * Q * C);
+  const dim3 grid(ew_blocks(N * P * Q * g.Cv));
+  if (C % 4 == 0)
+    hipLaunchKernelGGL((subsample_kernel<4, false>), grid, dim3(256), 0, s, x, y, g, off);
+  else
+    hipLaunchKernelGGL((subsample_kernel<1, false>), grid, dim3(256), 0, s, x, y, g, off);
+  NNL_CHECK_LAUNCH();
+  return NNL_OK;
+}
+
+extern "C" int nnl_subsample2d_bwd(const float* dy, float* dx, int64_t N, int64_t H, int64_t W, int64_t C, int64_t P, int64_t Q, int stride,
+                                   int off, void* stream) {
+  WGeom g;
+  if (int e = subsample_geom("subsample2d_bwd", N, H, W, C, P, Q, stride, off, &g)) return e;
+  NNL_CHECK_ARG(dy && dx, "subsample2d_bwd: null pointer");
+  hipStream_t s = (hipStream_t)stream;
+  NnlProfScope prof(NNL_PROF_ELEMENTWISE, s, 4.0 * N * H * W * C + 4.0 * N * P * Q * C);
+  const dim3 grid(ew_blocks(N * H * W * g.Cv));
+  if (C % 4 == 0)
+    hipLaunchKernelGGL((subsample_kernel<4, true>), grid, dim3(256), 0, s, dy, dx, g, off);
+  else
+    hipLaunchKernelGGL((subsample_kernel<1, true>), grid, dim3(256), 0, s, dy, dx, g, off);
   NNL_CHECK_LAUNCH();
   return NNL_OK;
 }

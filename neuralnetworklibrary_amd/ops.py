@@ -1229,7 +1229,8 @@ def conv_bn_relu_maxpool(conv, bn, pool, x):
 
 def maxpool2d(x, ksize=3, stride=2, pad=1, ceil_mode=False):
     """nn.MaxPool2d(ksize, stride, pad, ceil_mode=ceil_mode) (no dilation) — the ResNet stem pool (retinanet.py:307,374), in ceil
-    mode the SENet one (senet.py:314-315) — NHWC, channel count a multiple of 4; torch's first-maximum tie rule, deterministic
+    mode the SENet one (senet.py:314-315) and NASNet's MaxPoolPad (nasnet.py:65-76, as ksize 3 / stride 2 / pad 0) — NHWC, any channel
+    count (4-channel vectors when it is a multiple of 4, a scalar-channel route otherwise); torch's first-maximum tie rule, deterministic
     gather-style backward (pool.hip).  ceil_mode changes the output size only: the kernels skip the taps outside the input."""
     return _MaxPool2d.apply(x, int(ksize), int(stride), int(pad), bool(ceil_mode))
 
@@ -1355,6 +1356,176 @@ def se_excite(x, fc1, fc2, residual=None):
     """relu(x * sigmoid(fc2(relu(fc1(avg_pool(x))))) + residual) for the 1x1 convolutions fc1 [C/r, C, 1, 1] and fc2 [C, C/r, 1, 1]
     (with bias) of an SEModule; residual None = no shortcut term.  x logical [N,C,H,W], C a multiple of 4."""
     return _SEExcite.apply(x, residual, fc1.weight, fc1.bias, fc2.weight, fc2.bias)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# K18 depthwise convolution, average pooling and strided subsampling (NASNet-A-Large, Applications/VisionModels/nasnet.py)
+# ---------------------------------------------------------------------------------------------------------
+def fold_zero_pad(H, R, stride, pad, z):
+    """(pad_lo, P) of the single window op that equals `ZeroPad2d((z, 0, z, 0))` -> a window op (kernel R, `stride`, symmetric padding
+    `pad`) -> `[1:, 1:]` along an axis of H (reference nasnet.py:65-90, 152-167).  Output i of the chain is output i + 1 of the op on the
+    padded axis, whose window starts at (i + 1) stride - pad - z in the un-padded coordinates: pad_lo = pad + z - stride; and the chain
+    keeps (H + z + 2 pad - R) // stride + 1 - 1 outputs.  At R = 3, stride = pad = z = 1 it degenerates to the plain op (1, H)."""
+    return pad + z - stride, (H + z + 2 * pad - R) // stride
+
+
+def _window_args(H, W, R, stride, pad, pad_lo, out_size):
+    "(pad_lo, P, Q) of a window op: symmetric `pad` unless pad_lo / out_size state the folded form"
+    if pad_lo is None:
+        pad_lo = pad
+    if out_size is None:
+        P, Q = (H + 2 * pad - R) // stride + 1, (W + 2 * pad - R) // stride + 1
+    else:
+        P, Q = (out_size, out_size) if isinstance(out_size, int) else out_size
+    return int(pad_lo), int(P), int(Q)
+
+
+def _window_check(who, x_shape, R, rmax_text, r_ok, stride, stride_ok, pad, pad_lo, out_size):
+    "the shared domain of csrc/dwconv.hip and the average pool, checked before any device is needed: names the offending argument"
+    if len(x_shape) != 4:
+        raise NotImplementedError('%s: x %s must be 4-D' % (who, tuple(x_shape)))
+    if not r_ok:
+        raise NotImplementedError('%s: kernel_size %r is not supported (%s)' % (who, R, rmax_text))
+    if not stride_ok:
+        raise NotImplementedError('%s: stride %r is not supported' % (who, stride))
+    if not isinstance(pad, int) or pad < 0 or pad > R // 2:
+        raise NotImplementedError('%s: padding %r is not supported (0 .. kernel_size // 2)' % (who, pad))
+    H, W = x_shape[2], x_shape[3]
+    lo, P, Q = _window_args(H, W, R, stride, pad, pad_lo, out_size)
+    if lo < 0 or lo > R - 1:
+        raise NotImplementedError('%s: pad_lo %r is not supported (0 .. kernel_size - 1)' % (who, lo))
+    if P < 1 or Q < 1 or (P - 1) * stride - lo > H - 1 or (Q - 1) * stride - lo > W - 1:
+        raise NotImplementedError('%s: out_size %r is not supported: every window must touch the %d x %d input' % (who, (P, Q), H, W))
+    return lo, P, Q
+
+
+def _dwconv_check(x_shape, w_shape, stride, pad, pad_lo, out_size):
+    if len(w_shape) != 4:
+        raise NotImplementedError('depthwise_conv2d: weight %s must be 4-D' % (tuple(w_shape),))
+    K, Cg, R, S = w_shape
+    if len(x_shape) == 4 and (K != x_shape[1] or Cg != 1):
+        raise NotImplementedError('depthwise_conv2d: weight %s is not depthwise for %d input channels (groups == in_channels == '
+                                  'out_channels)' % (tuple(w_shape), x_shape[1]))
+    return _window_check('depthwise_conv2d', x_shape, R, '3x3, 5x5 or 7x7', R == S and R in (3, 5, 7), stride, stride in (1, 2), pad,
+                         pad_lo, out_size)
+
+
+def _avgpool_check(x_shape, ksize, stride, pad, pad_lo, out_size):
+    return _window_check('avgpool2d', x_shape, ksize, 'an int in 1 .. 15', isinstance(ksize, int) and 1 <= ksize <= 15, stride,
+                         isinstance(stride, int) and stride >= 1, pad, pad_lo, out_size)
+
+
+class _DepthwiseConv2d(torch.autograd.Function):
+    """nn.Conv2d(C, C, R, groups=C) forward / backward (reference nasnet.py:93-107) on csrc/dwconv.hip, with the input ReLU of a
+    BranchSeparables fused into the load.  Plain autograd: no GradSlot, no prepared filters."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, stride, pad, pad_lo, out_size, relu_in):
+        lo, P, Q = _dwconv_check(x.shape, weight.shape, stride, pad, pad_lo, out_size)
+        require_cuda(x, weight, bias)
+        xn, wn = to_nhwc(x.float()), _f32c(weight)                           # weight [C, 1, R, R] as stored
+        b = None if bias is None else _f32c(bias)
+        N, H, W, C = xn.shape
+        R = wn.shape[2]
+        y = torch.empty((N, P, Q, C), dtype=torch.float32, device=x.device)
+        check(lib.nnl_dwconv2d_fwd(ptr(xn), ptr(wn), ptr(b), ptr(y), N, H, W, C, P, Q, R, stride, lo, int(relu_in), stream()))
+        ctx.cfg = (N, H, W, C, P, Q, R, stride, lo, int(relu_in), bias is not None)
+        ctx.save_for_backward(xn, wn)
+        return from_nhwc(y)
+
+    @staticmethod
+    def backward(ctx, dy):
+        xn, wn = ctx.saved_tensors
+        dims, relu_in, has_bias = ctx.cfg[:9], ctx.cfg[9], ctx.cfg[10]
+        N, H, W, C, P, Q = dims[:6]
+        dyn = to_nhwc(dy.float())
+        dx = dw = db = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty_like(xn)
+            check(lib.nnl_dwconv2d_dgrad(ptr(dyn), ptr(wn), ptr(xn), ptr(dx), *dims, relu_in, stream()))
+            dx = from_nhwc(dx)
+        if ctx.needs_input_grad[1]:
+            dw = torch.empty_like(wn)
+            wsb = int(lib.nnl_dwconv2d_wgrad_workspace_bytes(*dims))
+            ws = _workspace(wsb, dyn.device)
+            check(lib.nnl_dwconv2d_wgrad(ptr(xn), ptr(dyn), ptr(dw), ptr(ws), wsb, *dims, relu_in, stream()))
+        if has_bias and ctx.needs_input_grad[2]:
+            db = torch.empty(C, dtype=torch.float32, device=dyn.device)
+            cb = int(lib.nnl_colsum_workspace_bytes(N * P * Q, C))
+            cws = _workspace(cb, dyn.device, floor=True)
+            check(lib.nnl_colsum(ptr(dyn), ptr(db), N * P * Q, C, ptr(cws), cb, stream()))
+        return dx, dw, db, None, None, None, None, None
+
+
+def depthwise_conv2d(x, weight, bias, stride, pad, pad_lo=None, out_size=None, relu_in=False):
+    """y = conv2d([relu](x), weight, bias, stride, padding=pad, groups=C); x logical [N,C,H,W], weight [C, 1, R, R].  Domain: R in
+    {3, 5, 7}, stride in {1, 2}, any C.  pad_lo / out_size state an asymmetric form instead (tap r of output p reads row p stride -
+    pad_lo + r; out_size = P or (P, Q)): see fold_zero_pad.  Anything else raises NotImplementedError naming the argument."""
+    return _DepthwiseConv2d.apply(x, weight, bias, int(stride), pad, pad_lo, out_size, bool(relu_in))
+
+
+class _AvgPool2d(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, ksize, stride, pad, count_include_pad, pad_lo, out_size):
+        lo, P, Q = _avgpool_check(x.shape, ksize, stride, pad, pad_lo, out_size)
+        require_cuda(x)
+        xn = to_nhwc(x.float())
+        N, H, W, C = xn.shape
+        y = torch.empty((N, P, Q, C), dtype=torch.float32, device=x.device)
+        ctx.cfg = (N, H, W, C, P, Q, ksize, stride, lo, int(count_include_pad))
+        check(lib.nnl_avgpool2d_fwd(ptr(xn), ptr(y), *ctx.cfg, stream()))
+        return from_nhwc(y)
+
+    @staticmethod
+    def backward(ctx, dy):
+        N, H, W, C = ctx.cfg[:4]
+        dyn = to_nhwc(dy.float())
+        dx = torch.empty((N, H, W, C), dtype=torch.float32, device=dy.device)
+        check(lib.nnl_avgpool2d_bwd(ptr(dyn), ptr(dx), *ctx.cfg, stream()))
+        return from_nhwc(dx), None, None, None, None, None, None
+
+
+def avgpool2d(x, ksize, stride, pad, count_include_pad=True, pad_lo=None, out_size=None):
+    """nn.AvgPool2d(ksize, stride, pad, count_include_pad=...) (floor mode), NHWC, any channel count (pool.hip); pad_lo / out_size as
+    for depthwise_conv2d.  ksize 1 .. 15; anything else raises NotImplementedError naming the argument."""
+    return _AvgPool2d.apply(x, ksize, stride, pad, bool(count_include_pad), pad_lo, out_size)
+
+
+def _subsample_check(x_shape, stride, off):
+    if len(x_shape) != 4:
+        raise NotImplementedError('subsample2d: x %s must be 4-D' % (tuple(x_shape),))
+    if not isinstance(stride, int) or stride < 1:
+        raise NotImplementedError('subsample2d: stride %r is not supported (an int >= 1)' % (stride,))
+    if not isinstance(off, int) or off < 0 or off >= max(stride, 2):
+        raise NotImplementedError('subsample2d: off %r is not supported (0 .. stride - 1)' % (off,))
+
+
+class _Subsample2d(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, stride, off):
+        _subsample_check(x.shape, stride, off)
+        require_cuda(x)
+        xn = to_nhwc(x.float())
+        N, H, W, C = xn.shape
+        P, Q = (H - 1) // stride + 1, (W - 1) // stride + 1
+        y = torch.empty((N, P, Q, C), dtype=torch.float32, device=x.device)
+        ctx.cfg = (N, H, W, C, P, Q, stride, off)
+        check(lib.nnl_subsample2d_fwd(ptr(xn), ptr(y), *ctx.cfg, stream()))
+        return from_nhwc(y)
+
+    @staticmethod
+    def backward(ctx, dy):
+        N, H, W, C = ctx.cfg[:4]
+        dyn = to_nhwc(dy.float())
+        dx = torch.empty((N, H, W, C), dtype=torch.float32, device=dy.device)
+        check(lib.nnl_subsample2d_bwd(ptr(dyn), ptr(dx), *ctx.cfg, stream()))
+        return from_nhwc(dx), None, None
+
+
+def subsample2d(x, stride, off):
+    """y[p, q] = x[p stride + off, q stride + off] (0 outside the image), (H - 1) // stride + 1 outputs per axis: AvgPool2d(1, stride)
+    for off = 0, and the ZeroPad2d((0, 1, 0, 1)) -> [1:, 1:] -> AvgPool2d(1, 2) chain of nasnet.py:232-238, 263-266 for off = 1."""
+    return _Subsample2d.apply(x, stride, off)
 
 
 # ---------------------------------------------------------------------------------------------------------
