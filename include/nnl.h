@@ -379,6 +379,26 @@ size_t nnl_dwconv2d_wgrad_workspace_bytes(int64_t N, int64_t H, int64_t W, int64
 int nnl_dwconv2d_wgrad(const float* x, const float* dy, float* dw, void* ws, size_t ws_bytes, int64_t N, int64_t H, int64_t W, int64_t C,
                        int64_t P, int64_t Q, int R, int stride, int pad_lo, int relu_in, void* stream);
 
+/* ---- K19: line convolution, nn.Conv2d(C, K, (1, T) | (T, 1), stride 1, padding (0, T/2) | (T/2, 0)) ---------------------------------------
+ * The factorised convolutions of InceptionV4 (Applications/VisionModels/inceptionv4.py:114-115 Mixed_4a, :201-210 Inception_B, :239-240
+ * Reduction_B, :262-269 Inception_C).  Activations NHWC fp32; w is the channels_last parameter as it is stored, [K, T, C]; dw comes back in
+ * that layout.  axis = 1: the filter runs along W (kernel_size (1, T)); axis = 0: along H (kernel_size (T, 1)).  With p = T / 2
+ *   y[n,h,w,k] = bias[k] + sum_{t,c} x[n, h + (t - p) [axis == 0], w + (t - p) [axis == 1], c] * w[k,t,c],
+ * positions outside the line read zero, the other axis is not padded, y is [N,H,W,K].
+ * Domain: T in {3, 5, 7}, axis in {0, 1}, C % 4 == 0, K % 4 == 0, all sizes >= 1, every tensor below 2^31 elements, no null pointer except
+ * bias and a zero-byte ws.  Anything else is NNL_ERR_INVALID_ARG before any launch, and nothing is written.
+ * Every sum runs in a fixed order and there are no atomics: two calls on the same inputs give the same bits.
+ * nnl_lineconv2d_fwd: flip != 0 reads tap T - 1 - t where flip == 0 reads tap t.  The input gradient is this entry on dy with C and K
+ * exchanged, w = W^T [C, T, K] (nnl_conv2d_weight_transpose(w, wt, K, T, 1, C)) and flip = 1.  relu != 0 applies max(., 0) to the output. */
+int nnl_lineconv2d_fwd(const float* x, const float* w, const float* bias, float* y, int64_t N, int64_t H, int64_t W, int64_t C, int64_t K,
+                       int T, int axis, int flip, int relu, void* stream);
+/* nnl_lineconv2d_wgrad: dw[k,t,c] = sum over the N*H*W pixels of dy[., k] * x[. shifted by t - p along the axis, c].  The pixels are cut into
+ * slabs whose partial sums go to the workspace (nnl_lineconv2d_wgrad_workspace_bytes; 0 = one slab, ws may be NULL) and are added in slab
+ * order by a second launch; a workspace that is too small is NNL_ERR_WORKSPACE. */
+size_t nnl_lineconv2d_wgrad_workspace_bytes(int64_t N, int64_t H, int64_t W, int64_t C, int64_t K, int T, int axis);
+int nnl_lineconv2d_wgrad(const float* x, const float* dy, float* dw, void* ws, size_t ws_bytes, int64_t N, int64_t H, int64_t W, int64_t C,
+                         int64_t K, int T, int axis, void* stream);
+
 /* ---- K18: average pooling and strided subsampling of the NASNet cells (nasnet.py AvgPoolPad, the cells' AvgPool2d, path_1 / path_2) ----
  * nnl_avgpool2d_*: nn.AvgPool2d(ksize, stride, pad, count_include_pad), NHWC, any C, with the same stated-P/Q, pad_lo convention and
  * checks as the depthwise convolution (1 <= ksize <= 15, 0 <= pad_lo <= ksize - 1).  The divisor of a window is the number of its taps

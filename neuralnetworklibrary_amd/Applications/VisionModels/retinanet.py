@@ -18,7 +18,7 @@ import torch.nn as nn
 from ... import ops
 from ...General.Core import default_device
 
-__all__ = ['HipConv2d', 'HipGroupedConv2d', 'HipDepthwiseConv2d', 'HipAvgPool2d', 'conv3x3', 'BasicBlock', 'Bottleneck', 'PyramidFeatures', 'RegressionModel',
+__all__ = ['HipConv2d', 'HipGroupedConv2d', 'HipDepthwiseConv2d', 'HipLineConv2d', 'HipAvgPool2d', 'conv3x3', 'BasicBlock', 'Bottleneck', 'PyramidFeatures', 'RegressionModel',
            'ClassificationModel', 'RetinaNet', 'retinanet18', 'retinanet34', 'retinanet50', 'retinanet101',
            'retinanet152', 'get_anchor_set', 'get_anchor_shifts', 'AnchorGenerator', 'intersections', 'jaccard', 'nms',
            'BBoxPredictor']
@@ -101,6 +101,34 @@ class HipDepthwiseConv2d(nn.Conv2d):
             (lo, P), (_, Q) = ops.fold_zero_pad(x.shape[2], R, s, p, zero_pad), ops.fold_zero_pad(x.shape[3], R, s, p, zero_pad)
             size = (P, Q)
         return ops.depthwise_conv2d(x, self.weight, self.bias, s, p, pad_lo=lo, out_size=size, relu_in=relu_in)
+
+
+class HipLineConv2d(nn.Conv2d):
+    """nn.Conv2d(C, K, (1, T) | (T, 1), padding=(0, T // 2) | (T // 2, 0)) (same parameters / state_dict) on the line-convolution kernels of
+    csrc/lineconv.hip (ops.line_conv2d): the factorised convolutions of InceptionV4 (inceptionv4.py:114-115, 201-210, 239-240, 262-269).
+    The weight keeps its logical shape and is STORED channels_last (= [K, T, C], the kernels' filter layout).  Deliberately not marked
+    `nnl_hip_conv`: the prepared-filter window serves ops.conv2d only."""
+    fuse_relu = False
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.weight.data = self.weight.data.contiguous(memory_format=torch.channels_last)
+
+    def forward(self, x):
+        R, S = self.kernel_size
+        if min(R, S) != 1 or max(R, S) not in (3, 5, 7):
+            raise NotImplementedError('HipLineConv2d: kernel_size %r is not supported ((1, T) or (T, 1) with T in 3, 5, 7)' % (self.kernel_size,))
+        if self.padding_mode != 'zeros' or isinstance(self.padding, str):
+            raise NotImplementedError('HipLineConv2d: padding_mode %r / padding %r is not supported' % (self.padding_mode, self.padding))
+        if tuple(self.padding) != (R // 2, S // 2):
+            raise NotImplementedError('HipLineConv2d: padding %r must be %r for kernel_size %r' % (self.padding, (R // 2, S // 2), self.kernel_size))
+        if self.stride != (1, 1):
+            raise NotImplementedError('HipLineConv2d: stride %r is not supported (1)' % (self.stride,))
+        if self.dilation != (1, 1):
+            raise NotImplementedError('HipLineConv2d: dilation %r is not supported' % (self.dilation,))
+        if self.groups != 1:
+            raise NotImplementedError('HipLineConv2d: groups %r is not supported (1)' % (self.groups,))
+        return ops.line_conv2d(x, self.weight, self.bias, relu=self.fuse_relu)
 
 
 class HipAvgPool2d(nn.AvgPool2d):

@@ -91,6 +91,9 @@ SIGNATURES = {
     'nnl_dwconv2d_dgrad': (C.c_int, [c_p, c_p, c_p, c_p, i64, i64, i64, i64, i64, i64, C.c_int, C.c_int, C.c_int, C.c_int, c_p]),
     'nnl_dwconv2d_wgrad_workspace_bytes': (sz, [i64, i64, i64, i64, i64, i64, C.c_int, C.c_int, C.c_int]),
     'nnl_dwconv2d_wgrad': (C.c_int, [c_p, c_p, c_p, c_p, sz, i64, i64, i64, i64, i64, i64, C.c_int, C.c_int, C.c_int, C.c_int, c_p]),
+    'nnl_lineconv2d_fwd': (C.c_int, [c_p, c_p, c_p, c_p, i64, i64, i64, i64, i64, C.c_int, C.c_int, C.c_int, C.c_int, c_p]),
+    'nnl_lineconv2d_wgrad_workspace_bytes': (sz, [i64, i64, i64, i64, i64, C.c_int, C.c_int]),
+    'nnl_lineconv2d_wgrad': (C.c_int, [c_p, c_p, c_p, c_p, sz, i64, i64, i64, i64, i64, C.c_int, C.c_int, c_p]),
     'nnl_avgpool2d_fwd': (C.c_int, [c_p, c_p, i64, i64, i64, i64, i64, i64, C.c_int, C.c_int, C.c_int, C.c_int, c_p]),
     'nnl_avgpool2d_bwd': (C.c_int, [c_p, c_p, i64, i64, i64, i64, i64, i64, C.c_int, C.c_int, C.c_int, C.c_int, c_p]),
     'nnl_subsample2d_fwd': (C.c_int, [c_p, c_p, i64, i64, i64, i64, i64, i64, C.c_int, C.c_int, c_p]),

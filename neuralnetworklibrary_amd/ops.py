@@ -1529,6 +1529,76 @@ def subsample2d(x, stride, off):
 
 
 # ---------------------------------------------------------------------------------------------------------
+# K19 line convolution: the (1, T) / (T, 1) factorised convolutions of InceptionV4 (Applications/VisionModels/inceptionv4.py)
+# ---------------------------------------------------------------------------------------------------------
+def _lineconv_check(x_shape, w_shape):
+    "the domain of csrc/lineconv.hip, checked before any device is needed: names the offending argument; -> (T, axis)"
+    if len(x_shape) != 4 or len(w_shape) != 4:
+        raise NotImplementedError('line_conv2d: x %s and weight %s must be 4-D' % (tuple(x_shape), tuple(w_shape)))
+    K, C, R, S = w_shape
+    T = max(R, S)
+    if min(R, S) != 1 or T % 2 == 0 or not 3 <= T <= 7:
+        raise NotImplementedError('line_conv2d: kernel_size %dx%d is not supported ((1, T) or (T, 1) with T in 3, 5, 7)' % (R, S))
+    if C != x_shape[1] or C % 4:
+        raise NotImplementedError('line_conv2d: in_channels %d (x has %d) must be a multiple of 4' % (C, x_shape[1]))
+    if K % 4:
+        raise NotImplementedError('line_conv2d: out_channels %d must be a multiple of 4' % K)
+    return T, (0 if R > 1 else 1)
+
+
+class _LineConv2d(torch.autograd.Function):
+    """nn.Conv2d(C, K, (1, T) | (T, 1), padding (0, T // 2) | (T // 2, 0)) forward / backward (reference inceptionv4.py:114-115, 201-210,
+    239-240, 262-269) on csrc/lineconv.hip; optional fused bias + ReLU epilogue.  Plain autograd: no GradSlot, no prepared filters."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, relu):
+        T, axis = _lineconv_check(x.shape, weight.shape)
+        require_cuda(x, weight, bias)
+        xn, wn = to_nhwc(x.float()), to_nhwc(weight.float())                 # [K, T, C] in memory (no copy when stored channels_last)
+        b = None if bias is None else _f32c(bias)
+        N, H, W, C = xn.shape
+        K = wn.shape[0]
+        y = torch.empty((N, H, W, K), dtype=torch.float32, device=x.device)
+        check(lib.nnl_lineconv2d_fwd(ptr(xn), ptr(wn), ptr(b), ptr(y), N, H, W, C, K, T, axis, 0, int(relu), stream()))
+        ctx.cfg = (N, H, W, C, K, T, axis, bool(relu), bias is not None)
+        ctx.save_for_backward(xn, wn, y if relu else None)
+        return from_nhwc(y)
+
+    @staticmethod
+    def backward(ctx, dy):
+        xn, wn, y = ctx.saved_tensors
+        N, H, W, C, K, T, axis, relu, has_bias = ctx.cfg
+        g = _geom(N, H, W, C, K, 1, 1, 1, 0)                                 # rows and K of the gate and the bias sum
+        want_db = has_bias and ctx.needs_input_grad[2]
+        dyn, db = to_nhwc(dy.float()), None
+        if relu:
+            dyn, db = _conv_act_gate(y, dyn, g, 1, want_db)
+        dx = dw = None
+        if ctx.needs_input_grad[0]:                                          # the flipped forward on dy and W^T [C, T, K]
+            wt = torch.empty((C, T, K), dtype=torch.float32, device=dyn.device)
+            check(lib.nnl_conv2d_weight_transpose(ptr(wn), ptr(wt), K, T, 1, C, stream()))
+            dx = torch.empty_like(xn)
+            check(lib.nnl_lineconv2d_fwd(ptr(dyn), ptr(wt), None, ptr(dx), N, H, W, K, C, T, axis, 1, 0, stream()))
+            dx = from_nhwc(dx)
+        if ctx.needs_input_grad[1]:
+            dw = torch.empty_like(wn)                                        # [K, R, S, C]: the parameter's own layout
+            wsb = int(lib.nnl_lineconv2d_wgrad_workspace_bytes(N, H, W, C, K, T, axis))
+            ws = _workspace(wsb, dyn.device)
+            check(lib.nnl_lineconv2d_wgrad(ptr(xn), ptr(dyn), ptr(dw), ptr(ws), wsb, N, H, W, C, K, T, axis, stream()))
+            dw = from_nhwc(dw)
+        if db is None and want_db:
+            db = _conv_bias_grad(dyn, g, K)
+        return dx, dw, db, None
+
+
+def line_conv2d(x, weight, bias=None, relu=False):
+    """y = [relu](conv2d(x, weight, bias, stride 1, padding "same" along the filter)); x logical [N,C,H,W], weight [K,C,1,T] (along W) or
+    [K,C,T,1] (along H), the axis read off its shape.  Domain: T in {3, 5, 7}, C and K multiples of 4; anything else raises
+    NotImplementedError naming the argument."""
+    return _LineConv2d.apply(x, weight, bias, bool(relu))
+
+
+# ---------------------------------------------------------------------------------------------------------
 # K3 tabular front end
 # ---------------------------------------------------------------------------------------------------------
 class TabularPlan:
