@@ -343,6 +343,9 @@ int nnl_concat_pool_bwd(const float* dout, const int32_t* argmax, float* dx, int
  * Domain: G divides C and K (any Cg = C/G >= 1, Kg = K/G >= 1), R in {1, 3}, stride in {1, 2}, 0 <= pad <= R / 2, N < 65536, every
  * tensor below 2^31 elements; anything else is NNL_ERR_INVALID_ARG and nothing is launched.  P = (H + 2 pad - R) / stride + 1, Q likewise.
  * Direct kernels (csrc/gconv.hip), every sum in a fixed order and no atomics: two calls on the same inputs give the same bits.
+ * Cg and Kg both in {16, 32} (R, stride and pad as above) take the MFMA kernels of csrc/gconv_mfma.h in all three directions, with the
+ * same guarantees and differently ordered fp32 sums; NNL_GCONV_MFMA=0 keeps those shapes on the direct kernels.  Route notes:
+ * gconv_fwd<lds|cache>, gconv_dgrad<lds|cache>, gconv_wgrad@sS; gconv_mfma_fwd<cgC,kgK>, gconv_mfma_dgrad<cgC,kgK>, gconv_mfma_wgrad<cgC,kgK>@sS.
  * nnl_gconv2d_fwd (Applications/VisionModels/senet.py:178-180, 205-206, 229-230): y = conv(x, w) + bias (bias may be NULL), ReLU when relu != 0. */
 int nnl_gconv2d_fwd(const float* x, const float* w, const float* bias, float* y, int64_t N, int64_t H, int64_t W, int64_t C, int64_t K,
                     int64_t G, int R, int stride, int pad, int relu, void* stream);

@@ -45,7 +45,7 @@ class HipConv2d(nn.Conv2d):
 
 
 class HipGroupedConv2d(nn.Conv2d):
-    """nn.Conv2d(groups=G) (same parameters / state_dict) computed by the direct grouped kernels of csrc/gconv.hip (ops.grouped_conv2d):
+    """nn.Conv2d(groups=G) (same parameters / state_dict) computed by the grouped kernels of csrc/gconv.hip (ops.grouped_conv2d; direct, or MFMA at 16 / 32 channels per group both ways):
     the 3x3 of the SENet / SE-ResNeXt bottlenecks (senet.py:178-180, 229-230).  The weight keeps its logical [K, C/G, R, R] shape and is
     STORED channels_last (= [K, R, R, C/G], the kernels' filter layout).  Deliberately not marked `nnl_hip_conv`: the prepared-filter
     window (ops._Filters) transposes the weights of the marked modules as dense [K, C, R, S] filters."""
@@ -136,7 +136,8 @@ class HipAvgPool2d(nn.AvgPool2d):
     strided subsample.  zero_pad=z folds `ZeroPad2d((z, 0, z, 0))` -> pool -> `[1:, 1:]` (NASNet's AvgPoolPad) into one launch."""
 
     def forward(self, x, zero_pad=None):
-        k, s, p = self.kernel_size, self.stride, self.padding
+        # ((7, 7), (1, 1)), as the converted ResNeXt spells its square window, is 7, 1
+        k, s, p = (v[0] if isinstance(v, tuple) and len(set(v)) == 1 else v for v in (self.kernel_size, self.stride, self.padding))
         if self.ceil_mode or self.divisor_override is not None or not all(isinstance(v, int) for v in (k, s, p)):
             raise NotImplementedError('HipAvgPool2d: only the square floor-mode pooling the reference uses')
         if k == 1 and p == 0 and zero_pad is None:

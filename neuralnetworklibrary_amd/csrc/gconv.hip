@@ -13,6 +13,9 @@
 //                    its partial filter gradient to its own slab of the workspace and a second launch adds the slabs in slice order.
 //                    S == 1 writes dw directly.
 // No atomics anywhere: two calls on the same inputs give the same bits.
+//
+// Cg and Kg both in {16, 32} (the 14 x 14 and 7 x 7 stages of ResNeXt-101 and of the SENet family) leave that regime: the layer is bound by
+// its arithmetic and by filter traffic, and runs on the MFMA kernels of gconv_mfma.h instead (NNL_GCONV_MFMA = 0: the direct kernels).
 #include "nnl_common.h"
 
 namespace {
@@ -246,6 +249,8 @@ long wgrad_rows(const GGeom& g) {
 
 }  // namespace
 
+#include "gconv_mfma.h"
+
 extern "C" int nnl_gconv2d_fwd(const float* x, const float* w, const float* bias, float* y, int64_t N, int64_t H, int64_t W, int64_t C,
                                int64_t K, int64_t G, int R, int stride, int pad, int relu, void* stream) {
   GGeom g;
@@ -253,6 +258,12 @@ extern "C" int nnl_gconv2d_fwd(const float* x, const float* w, const float* bias
   NNL_CHECK_ARG(x && w && y, "gconv2d_fwd: null pointer");
   hipStream_t s = (hipStream_t)stream;
   NnlProfScope prof(NNL_PROF_CONV_FWD, s, 2.0 * N * g.P * g.Q * K * R * R * g.Cg);
+  if (mfma_route(g, MF_FWD)) {
+    NNL_ROUTE("gconv_mfma_fwd<cg%d,kg%d>", g.Cg, g.Kg);
+    launch_mfma<false>(x, w, bias, y, g, relu, s);
+    NNL_CHECK_LAUNCH();
+    return NNL_OK;
+  }
   const bool lds = g.Cg <= LDS_RED;
   const int GB = groups_per_block(g.Cg);
   const int HT = (TILE - 1) * stride + R;
@@ -274,6 +285,12 @@ extern "C" int nnl_gconv2d_dgrad(const float* dy, const float* w, float* dx, int
   NNL_CHECK_ARG(dy && w && dx, "gconv2d_dgrad: null pointer");
   hipStream_t s = (hipStream_t)stream;
   NnlProfScope prof(NNL_PROF_CONV_DGRAD, s, 2.0 * N * g.P * g.Q * K * R * R * g.Cg);
+  if (mfma_route(g, MF_DGRAD)) {
+    NNL_ROUTE("gconv_mfma_dgrad<cg%d,kg%d>", g.Cg, g.Kg);
+    launch_mfma<true>(dy, w, nullptr, dx, g, 0, s);
+    NNL_CHECK_LAUNCH();
+    return NNL_OK;
+  }
   const bool lds = g.Kg <= LDS_RED;
   const int GB = groups_per_block(g.Kg);
   const int DT = (TILE - 1 + R - 1) / stride + 2;
@@ -292,7 +309,7 @@ extern "C" size_t nnl_gconv2d_workspace_bytes(int64_t N, int64_t H, int64_t W, i
                                               int pad) {
   GGeom g;
   if (make_geom("gconv2d_workspace_bytes", N, H, W, C, K, G, R, stride, pad, &g)) return 0;
-  const long slices = nnl_cdiv((long)g.N * g.P * g.Q, wgrad_rows(g));
+  const long slices = nnl_cdiv((long)g.N * g.P * g.Q, mfma_route(g, MF_WGRAD) ? mfma_wgrad_rows(g) : wgrad_rows(g));
   return slices > 1 ? (size_t)slices * K * R * R * g.Cg * sizeof(float) : 0;
 }
 
@@ -301,16 +318,22 @@ extern "C" int nnl_gconv2d_wgrad(const float* x, const float* dy, float* dw, voi
   GGeom g;
   if (int e = make_geom("gconv2d_wgrad", N, H, W, C, K, G, R, stride, pad, &g)) return e;
   NNL_CHECK_ARG(x && dy && dw, "gconv2d_wgrad: null pointer");
-  const long npq = (long)g.N * g.P * g.Q, rows = wgrad_rows(g), slices = nnl_cdiv(npq, rows);
+  const bool mfma = mfma_route(g, MF_WGRAD);
+  const long npq = (long)g.N * g.P * g.Q, rows = mfma ? mfma_wgrad_rows(g) : wgrad_rows(g), slices = nnl_cdiv(npq, rows);
   const long numel = (long)K * R * R * g.Cg;
   if (slices > 1 && (ws == nullptr || ws_bytes < (size_t)slices * numel * sizeof(float)))
     return nnl_set_error(NNL_ERR_WORKSPACE, "gconv2d_wgrad: workspace too small");
   hipStream_t s = (hipStream_t)stream;
   NnlProfScope prof(NNL_PROF_CONV_WGRAD, s, 2.0 * npq * K * R * R * g.Cg);
   const long units = (long)G * ((g.Kg + 3) / 4) * R * R * g.Cg;
-  NNL_ROUTE("gconv_wgrad@s%ld", slices);
-  hipLaunchKernelGGL(gconv_wgrad_kernel, dim3((unsigned)nnl_cdiv(units, 256), (unsigned)slices), dim3(256), 0, s, x, dy,
-                     slices > 1 ? (float*)ws : dw, g, units, npq, rows, numel);
+  if (mfma) {
+    NNL_ROUTE("gconv_mfma_wgrad<cg%d,kg%d>@s%ld", g.Cg, g.Kg, slices);
+    launch_mfma_wgrad(x, dy, slices > 1 ? (float*)ws : dw, g, npq, rows, slices, numel, s);
+  } else {
+    NNL_ROUTE("gconv_wgrad@s%ld", slices);
+    hipLaunchKernelGGL(gconv_wgrad_kernel, dim3((unsigned)nnl_cdiv(units, 256), (unsigned)slices), dim3(256), 0, s, x, dy,
+                       slices > 1 ? (float*)ws : dw, g, units, npq, rows, numel);
+  }
   NNL_CHECK_LAUNCH();
   if (slices > 1) {
     hipLaunchKernelGGL(gconv_wgrad_reduce_kernel, dim3((unsigned)nnl_cdiv(numel, 256)), dim3(256), 0, s, (const float*)ws, dw, numel,

@@ -1256,7 +1256,7 @@ def _gconv_check(x_shape, w_shape, stride, pad, groups):
 
 class _GroupedConv2d(torch.autograd.Function):
     """nn.Conv2d(groups=G) forward / backward (reference Applications/VisionModels/senet.py:178-180, 205-206, 229-230) on the direct
-    kernels of csrc/gconv.hip; optional fused bias + ReLU epilogue.  Plain autograd: no GradSlot, no prepared filters."""
+    kernels of csrc/gconv.hip (Cg and Kg both 16 or 32: the MFMA kernels of csrc/gconv_mfma.h); optional fused bias + ReLU epilogue.  Plain autograd: no GradSlot, no prepared filters."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, stride, pad, groups, relu):

@@ -1,13 +1,16 @@
-"""Grouped 3x3 convolution (csrc/gconv.hip) at the four stage shapes of se_resnext50_32x4d and of senet154, bs 64 at 224 x 224:
-forward, dgrad and wgrad through the C ABI (no autograd / Python overhead between the launches).
+"""Grouped 3x3 convolution (csrc/gconv.hip) at the four stage shapes of se_resnext50_32x4d and of senet154, and at the stride-1 and
+stride-2 shapes of resnext101_32x4d / _64x4d, bs 64 at 224 x 224: forward, dgrad and wgrad through the C ABI (no autograd / Python
+overhead between the launches).  Rows with Cg and Kg in {16, 32} get two more columns: the direct kernels (NNL_GCONV_MFMA=0) against the
+MFMA kernels of csrc/gconv_mfma.h, alternated in this process in the same way, after their outputs were compared at the timed size.
 
 Per kernel: time per launch by HIP events — after a warm-up, three alternations of (ours, the baseline), each a block of `--iters`
 launches; the median of the three blocks and their spread (max - min) — that time against the larger of the traffic bound (activations
 in + out once, filter once, at 6.29 TB/s) and the flop bound (157.3 TFLOP/s fp32), and against torch.nn.functional.conv2d(groups=G) on
 the same device: ATen's library path, used in this tool only and never in the package.  Its input is torch's own NCHW layout; the
 backward baseline is one autograd.grad call giving dx AND dw, so it is set against dgrad + wgrad.
-Then one Learner.train1minibatch of ImageClassificationNet(senet154) at 224 x 224, frozen and unfrozen (--model-bs, 0 to skip).
-Usage: python tools/bench_gconv.py [--bs 64] [--iters 20] [--model-bs 16] [--skip-shapes]"""
+Then one Learner.train1minibatch of ImageClassificationNet(--model, default senet154) at 224 x 224, frozen and unfrozen (--model-bs, 0 to
+skip); run it once per setting of NNL_GCONV_MFMA for the model-level A/B.
+Usage: python tools/bench_gconv.py [--bs 64] [--iters 20] [--model-bs 16] [--model resnext101_32x4d] [--skip-shapes]"""
 import argparse
 import os
 import statistics
@@ -21,9 +24,13 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from neuralnetworklibrary_amd._lib import check, lib, ptr, stream  # noqa: E402
 
 HBM_TBS, FP32_TFLOPS = 6.29, 157.3
-# (name, C, K, G, H): the steady-state 3x3 / stride 1 grouped convolution of each stage
-SHAPES = [('se_resnext50 layer%d' % (i + 1), 128 << i, 128 << i, 32, 56 >> i) for i in range(4)] + \
-         [('senet154 layer%d' % (i + 1), 128 << i, 256 << i, 64, 56 >> i) for i in range(4)]
+# (name, C, K, G, H, stride): the steady-state 3x3 / stride 1 grouped convolution of each stage, then ResNeXt-101's (both flavours) with
+# the stride-2 convolution that opens stages 2 - 4 (it reads the previous stage's map)
+SHAPES = [('se_resnext50 layer%d' % (i + 1), 128 << i, 128 << i, 32, 56 >> i, 1) for i in range(4)] + \
+         [('senet154 layer%d' % (i + 1), 128 << i, 256 << i, 64, 56 >> i, 1) for i in range(4)] + \
+         [('resnext101_%dx4d s%d' % (G, i + 1), (4 * G) << i, (4 * G) << i, G, 56 >> i, 1) for G in (32, 64) for i in range(4)] + \
+         [('resnext101_%dx4d s%d/2' % (G, i + 1), (4 * G) << i, (4 * G) << i, G, 112 >> i, 2) for G in (32, 64) for i in range(1, 4)] + \
+         [('senet154 layer4/2', 1024, 2048, 64, 14, 2)]
 
 
 def block_us(fn, iters):
@@ -49,42 +56,80 @@ def alternate(ours, base, iters):
     return (statistics.median(a), max(a) - min(a)), (statistics.median(b), max(b) - min(b))
 
 
+def set_mfma(on):
+    os.environ['NNL_GCONV_MFMA'] = '1' if on else '0'
+    lib.nnl_reload_env()
+
+
 def bench_shapes(bs, iters):
     dev = 'cuda'
-    print('%-22s %-6s | %9s %7s | %9s %7s | %11s %7s' % ('shape (bs %d)' % bs, 'kernel', 'us', 'spread', 'bound us', 'x bound', 'ATen us', 'spread'))
-    for name, C, K, G, H in SHAPES:
-        Cg = C // G
+    print('%-32s %-6s | %9s %7s | %9s %7s | %11s %7s | %9s %7s %9s %7s' % ('shape (bs %d)' % bs, 'kernel', 'us', 'spread', 'bound us', 'x bound',
+                                                                        'ATen us', 'spread', 'direct us', 'spread', 'MFMA us', 'spread'))
+    for name, C, K, G, H, stride in SHAPES:
+        Cg, P = C // G, (H - 1) // stride + 1
         x = torch.randn(bs, H, H, C, device=dev)
         w = torch.randn(K, 3, 3, Cg, device=dev) / (9 * Cg) ** 0.5
-        y, dy = torch.empty(bs, H, H, K, device=dev), torch.randn(bs, H, H, K, device=dev)
+        y, dy = torch.empty(bs, P, P, K, device=dev), torch.randn(bs, P, P, K, device=dev)
         dx, dw = torch.empty_like(x), torch.empty_like(w)
-        dims = (bs, H, H, C, K, G, 3, 1, 1)
+        dims = (bs, H, H, C, K, G, 3, stride, 1)
+        ab = Cg in (16, 32) and K // G in (16, 32)
+        set_mfma(False)
         wsb = int(lib.nnl_gconv2d_workspace_bytes(*dims))
+        set_mfma(True)
+        wsb = max(wsb, int(lib.nnl_gconv2d_workspace_bytes(*dims)))            # enough for either route
         ws = torch.empty(max(wsb // 4, 1), device=dev)
         xt = x.permute(0, 3, 1, 2).contiguous().requires_grad_(True)           # ATen's own layout
         wt = w.permute(0, 3, 1, 2).contiguous().requires_grad_(True)
         dyt = dy.permute(0, 3, 1, 2).contiguous()
-        yt = F.conv2d(xt, wt, None, 1, 1, 1, G)
-        flop = 2.0 * bs * H * H * K * 9 * Cg
-        act = 4.0 * bs * H * H * (C + K)
+        yt = F.conv2d(xt, wt, None, stride, 1, 1, G)
+        flop = 2.0 * bs * P * P * K * 9 * Cg
+        act = 4.0 * bs * (H * H * C + P * P * K)
         bound = max((act + 4.0 * w.numel()) / (HBM_TBS * 1e6), flop / (FP32_TFLOPS * 1e6))
         ours = {
-            'fwd': lambda: check(lib.nnl_gconv2d_fwd(ptr(x), ptr(w), None, ptr(y), *dims, 0, stream())),
-            'dgrad': lambda: check(lib.nnl_gconv2d_dgrad(ptr(dy), ptr(w), ptr(dx), *dims, stream())),
-            'wgrad': lambda: check(lib.nnl_gconv2d_wgrad(ptr(x), ptr(dy), ptr(dw), ptr(ws), wsb, *dims, stream())),
+            'fwd': (lambda: check(lib.nnl_gconv2d_fwd(ptr(x), ptr(w), None, ptr(y), *dims, 0, stream())), y),
+            'dgrad': (lambda: check(lib.nnl_gconv2d_dgrad(ptr(dy), ptr(w), ptr(dx), *dims, stream())), dx),
+            'wgrad': (lambda: check(lib.nnl_gconv2d_wgrad(ptr(x), ptr(dy), ptr(dw), ptr(ws), wsb, *dims, stream())), dw),
         }
-        base_fwd = lambda: F.conv2d(xt, wt, None, 1, 1, 1, G)                  # noqa: E731
+        base_fwd = lambda: F.conv2d(xt, wt, None, stride, 1, 1, G)             # noqa: E731
         base_bwd = lambda: torch.autograd.grad(yt, (xt, wt), dyt, retain_graph=True)      # noqa: E731
         bwd_sum = 0.0
         for kern in ('fwd', 'dgrad', 'wgrad'):
-            (t, sp), (tb, spb) = alternate(ours[kern], base_fwd if kern == 'fwd' else base_bwd, iters)
+            fn, out = ours[kern]
+            (t, sp), (tb, spb) = alternate(fn, base_fwd if kern == 'fwd' else base_bwd, iters)
             bwd_sum += t if kern != 'fwd' else 0.0
             base = '%11.1f %7.1f' % (tb, spb) if kern != 'dgrad' else '%11s %7s' % ('(see wgrad)', '')
-            print('%-22s %-6s | %9.1f %7.1f | %9.1f %7.2f | %s' % ('%s %dx%d g%d %d' % (name, Cg, K // G, G, H), kern, t, sp, bound, t / bound, base))
-        print('%-22s %-6s | %9.1f' % ('', 'dg+wg', bwd_sum))
+            two = ''
+            if ab:
+                def direct(fn=fn):
+                    set_mfma(False)
+                    fn()
+                    set_mfma(True)
+                direct()
+                ref = out.clone()
+                fn()
+                err = ((out - ref).abs().max() / ref.abs().max()).item()
+                assert err < 1e-5, '%s %s: the two routes differ by %.2e of the largest value' % (name, kern, err)
+
+                def block_direct(fn=fn):                                       # the switch is read once per block, not per launch
+                    set_mfma(False)
+                    for _ in range(3):
+                        fn()
+                    t_ = block_us(fn, iters)
+                    set_mfma(True)
+                    return t_
+                for _ in range(3):
+                    fn()
+                a, b = [], []
+                for _ in range(3):
+                    a.append(block_direct())
+                    b.append(block_us(fn, iters))
+                two = ' | %9.1f %7.1f %9.1f %7.1f' % (statistics.median(a), max(a) - min(a), statistics.median(b), max(b) - min(b))
+            print('%-32s %-6s | %9.1f %7.1f | %9.1f %7.2f | %s%s' % ('%s %dx%d g%d %d' % (name, Cg, K // G, G, H), kern, t, sp, bound, t / bound, base, two),
+                  flush=True)
+        print('%-32s %-6s | %9.1f' % ('', 'dg+wg', bwd_sum))
 
 
-def bench_model(bs):
+def bench_model(bs, name):
     import types
 
     from neuralnetworklibrary_amd.Applications import Vision as V
@@ -95,7 +140,7 @@ def bench_model(bs):
     data.train_dl = [(None, torch.zeros(bs))]
     data.val_dl = data.train_dl
     torch.manual_seed(0)
-    model = V.ImageClassificationNet(data, vmods.senet154()).cuda()
+    model = V.ImageClassificationNet(data, getattr(vmods, name)()).cuda()
     learner = Learner('/tmp/nnl_bench_gconv', data, model, optimizer='SGD_Mom')
     learner.init_optimizer(wd=1e-4)
     x, y = torch.randn(bs, 3, 224, 224, device='cuda'), torch.randint(0, 120, (bs,), device='cuda')
@@ -115,8 +160,8 @@ def bench_model(bs):
             torch.cuda.synchronize()
             ts.append((time.perf_counter() - t0) * 1e3)
         steady = ts[2:]
-        print('senet154 train1minibatch bs %d at 224, %-8s: median %.1f ms, spread %.1f ms over %d steps after 2 warm-up steps (loss %.4f)'
-              % (bs, what, statistics.median(steady), max(steady) - min(steady), len(steady), loss), flush=True)
+        print('%s train1minibatch bs %d at 224 (NNL_GCONV_MFMA=%s), %-8s: median %.1f ms, spread %.1f ms over %d steps after 2 warm-up steps (loss %.4f)'
+              % (name, bs, os.environ.get('NNL_GCONV_MFMA', '1'), what, statistics.median(steady), max(steady) - min(steady), len(steady), loss), flush=True)
 
 
 if __name__ == '__main__':
@@ -124,9 +169,10 @@ if __name__ == '__main__':
     ap.add_argument('--bs', type=int, default=64)
     ap.add_argument('--iters', type=int, default=20)
     ap.add_argument('--model-bs', type=int, default=16)
+    ap.add_argument('--model', default='senet154', help='a vmods factory, e.g. resnext101_32x4d')
     ap.add_argument('--skip-shapes', action='store_true')
     a = ap.parse_args()
     if not a.skip_shapes:
         bench_shapes(a.bs, a.iters)
     if a.model_bs:
-        bench_model(a.model_bs)
+        bench_model(a.model_bs, a.model)
