@@ -402,6 +402,29 @@ size_t nnl_lineconv2d_wgrad_workspace_bytes(int64_t N, int64_t H, int64_t W, int
 int nnl_lineconv2d_wgrad(const float* x, const float* dy, float* dw, void* ws, size_t ws_bytes, int64_t N, int64_t H, int64_t W, int64_t C,
                          int64_t K, int T, int axis, void* stream);
 
+/* ---- K20: concat-fused residual 1x1 projection, the tail of the residual blocks of InceptionResNetV2 -----------------------------------------
+ * (Applications/VisionModels/inceptionresnetv2.py:142-150 Block35, :194-201 Block17, :256-264 Block8)
+ *   y[m,k] = act( residual[m,k] + scale (bias[k] + sum_s sum_c x_s[m,c] w[k, off_s + c]) ),   act = max(., 0) when relu != 0.
+ * NHWC fp32, M = N H W rows.  The sources are n_src separate tensors [M, C_s], given as a HOST array of device pointers `srcs` and a host
+ * array of channel counts `chans`; w is the 1x1 parameter as it is stored, [K, Ctot] with Ctot = sum C_s, and source s owns the columns
+ * off_s .. off_s + C_s (off_s = C_0 + .. + C_{s-1}).  The concatenation is never written to memory.
+ * Domain: 1 <= n_src <= 4, every C_s % 4 == 0, Ctot <= 512, K % 4 == 0, all sizes >= 1, every tensor below 2^31 elements, no null pointer
+ * except bias, residual, a zero-byte ws and, without relu, y and dres of the backward entries.  Anything else is NNL_ERR_INVALID_ARG before
+ * any launch, and nothing is written.  Every sum runs in a fixed order and there are no atomics: two calls on the same inputs give the
+ * same bits, whatever grid the forward's planner picks (it splits output tiles, never a sum). */
+int nnl_catproj_fwd(const float* const* srcs, const int64_t* chans, int n_src, const float* w, const float* bias, const float* residual,
+                    float* y, int64_t M, int64_t K, float scale, int relu, void* stream);
+/* nnl_catproj_dgrad: dsrcs[s][m,c] = scale sum_k g[m,k] w[k, off_s + c] with g = dy [y > 0] when relu != 0, else g = dy.  With relu, g is also
+ * stored to dres [M, K] (the gradient of `residual`); without, dres is dy itself and nothing is written to it. */
+int nnl_catproj_dgrad(const float* dy, const float* y, const float* w, float* const* dsrcs, const int64_t* chans, int n_src, float* dres,
+                      int64_t M, int64_t K, float scale, int relu, void* stream);
+/* nnl_catproj_wgrad: dw[k, off_s + c] = scale sum_m g[m,k] x_s[m,c], g as above.  The rows are cut into slabs whose partial sums go to the
+ * workspace (nnl_catproj_wgrad_workspace_bytes; 0 = one slab, ws may be NULL) and are added in slab order by a second launch; a workspace
+ * that is too small is NNL_ERR_WORKSPACE.  The bias gradient is scale x nnl_colsum of g. */
+size_t nnl_catproj_wgrad_workspace_bytes(const int64_t* chans, int n_src, int64_t M, int64_t K);
+int nnl_catproj_wgrad(const float* const* srcs, const int64_t* chans, int n_src, const float* dy, const float* y, float* dw, void* ws,
+                      size_t ws_bytes, int64_t M, int64_t K, float scale, int relu, void* stream);
+
 /* ---- K18: average pooling and strided subsampling of the NASNet cells (nasnet.py AvgPoolPad, the cells' AvgPool2d, path_1 / path_2) ----
  * nnl_avgpool2d_*: nn.AvgPool2d(ksize, stride, pad, count_include_pad), NHWC, any C, with the same stated-P/Q, pad_lo convention and
  * checks as the depthwise convolution (1 <= ksize <= 15, 0 <= pad_lo <= ksize - 1).  The divisor of a window is the number of its taps

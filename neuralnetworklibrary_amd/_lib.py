@@ -94,6 +94,10 @@ SIGNATURES = {
     'nnl_lineconv2d_fwd': (C.c_int, [c_p, c_p, c_p, c_p, i64, i64, i64, i64, i64, C.c_int, C.c_int, C.c_int, C.c_int, c_p]),
     'nnl_lineconv2d_wgrad_workspace_bytes': (sz, [i64, i64, i64, i64, i64, C.c_int, C.c_int]),
     'nnl_lineconv2d_wgrad': (C.c_int, [c_p, c_p, c_p, c_p, sz, i64, i64, i64, i64, i64, C.c_int, C.c_int, c_p]),
+    'nnl_catproj_fwd': (C.c_int, [c_p, c_p, C.c_int, c_p, c_p, c_p, c_p, i64, i64, f32, C.c_int, c_p]),
+    'nnl_catproj_dgrad': (C.c_int, [c_p, c_p, c_p, c_p, c_p, C.c_int, c_p, i64, i64, f32, C.c_int, c_p]),
+    'nnl_catproj_wgrad_workspace_bytes': (sz, [c_p, C.c_int, i64, i64]),
+    'nnl_catproj_wgrad': (C.c_int, [c_p, c_p, C.c_int, c_p, c_p, c_p, c_p, sz, i64, i64, f32, C.c_int, c_p]),
     'nnl_avgpool2d_fwd': (C.c_int, [c_p, c_p, i64, i64, i64, i64, i64, i64, C.c_int, C.c_int, C.c_int, C.c_int, c_p]),
     'nnl_avgpool2d_bwd': (C.c_int, [c_p, c_p, i64, i64, i64, i64, i64, i64, C.c_int, C.c_int, C.c_int, C.c_int, c_p]),
     'nnl_subsample2d_fwd': (C.c_int, [c_p, c_p, i64, i64, i64, i64, i64, i64, C.c_int, C.c_int, c_p]),

@@ -1599,6 +1599,96 @@ def line_conv2d(x, weight, bias=None, relu=False):
 
 
 # ---------------------------------------------------------------------------------------------------------
+# K20 concat-fused residual 1x1 projection: the tail of InceptionResNetV2's residual blocks (Applications/VisionModels/inceptionresnetv2.py)
+# ---------------------------------------------------------------------------------------------------------
+def _catproj_check(src_shapes, w_shape, b_shape, r_shape):
+    "the domain of csrc/catproj.hip, checked before any device is needed: names the offending argument; -> (N, H, W, chans, K)"
+    if not 1 <= len(src_shapes) <= 4:
+        raise NotImplementedError('cat_conv1x1_residual: sources has %d tensors (1 .. 4)' % len(src_shapes))
+    if any(len(s) != 4 for s in src_shapes) or any(tuple(s[:1] + s[2:]) != tuple(src_shapes[0][:1] + src_shapes[0][2:]) for s in src_shapes):
+        raise NotImplementedError('cat_conv1x1_residual: sources %s must be 4-D and agree in all but the channels' % ([tuple(s) for s in src_shapes],))
+    chans = [int(s[1]) for s in src_shapes]
+    if any(c < 4 or c % 4 for c in chans) or sum(chans) > 512:
+        raise NotImplementedError('cat_conv1x1_residual: sources have %s channels (each a multiple of 4, at most 512 together)' % (chans,))
+    if len(w_shape) != 4 or tuple(w_shape[1:]) != (sum(chans), 1, 1):
+        raise NotImplementedError('cat_conv1x1_residual: weight %s is not [K, %d, 1, 1]' % (tuple(w_shape), sum(chans)))
+    K = int(w_shape[0])
+    if K < 4 or K % 4:
+        raise NotImplementedError('cat_conv1x1_residual: weight has %d out_channels (a multiple of 4)' % K)
+    if b_shape is not None and tuple(b_shape) != (K,):
+        raise NotImplementedError('cat_conv1x1_residual: bias %s is not [%d]' % (tuple(b_shape), K))
+    N, _, H, W = src_shapes[0]
+    if r_shape is not None and tuple(r_shape) != (N, K, H, W):
+        raise NotImplementedError('cat_conv1x1_residual: residual %s is not %s' % (tuple(r_shape), (N, K, H, W)))
+    return int(N), int(H), int(W), chans, K
+
+
+def _ptr_array(tensors):
+    return (_lib.c_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+class _CatConv1x1Residual(torch.autograd.Function):
+    """relu(residual + scale * conv1x1(cat(sources), weight, bias)) forward / backward (reference inceptionresnetv2.py:142-150, 194-201,
+    256-264) on csrc/catproj.hip: the concatenation is never written.  Plain autograd: no GradSlot, no prepared filters."""
+
+    @staticmethod
+    def forward(ctx, weight, bias, residual, scale, relu, *sources):
+        N, H, W, chans, K = _catproj_check([s.shape for s in sources], weight.shape, None if bias is None else bias.shape,
+                                           None if residual is None else residual.shape)
+        require_cuda(weight, bias, residual, *sources)
+        xs = [to_nhwc(s.float()) for s in sources]
+        wn = _f32c(weight).reshape(K, sum(chans))                            # [K, Ctot] in memory, dense or channels_last alike
+        b = None if bias is None else _f32c(bias)
+        r = None if residual is None else to_nhwc(residual.float())
+        M, ch = N * H * W, (_lib.i64 * len(chans))(*chans)
+        y = torch.empty((N, H, W, K), dtype=torch.float32, device=weight.device)
+        check(lib.nnl_catproj_fwd(_ptr_array(xs), ch, len(xs), ptr(wn), ptr(b), ptr(r), ptr(y), M, K, float(scale), int(relu), stream()))
+        if any(ctx.needs_input_grad):                                        # nothing is kept for a forward without autograd
+            ctx.cfg = (N, H, W, chans, K, float(scale), bool(relu), bias is not None)
+            ctx.save_for_backward(wn, y if relu else None, *xs)
+        return from_nhwc(y)
+
+    @staticmethod
+    def backward(ctx, dy):
+        wn, y, *xs = ctx.saved_tensors
+        N, H, W, chans, K, scale, relu, has_bias = ctx.cfg
+        M, ch, dev = N * H * W, (_lib.i64 * len(chans))(*chans), dy.device
+        need_w, need_b, need_r = ctx.needs_input_grad[0], has_bias and ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        dyn = to_nhwc(dy.float())
+        g, db, dxs = (None if relu else dyn), None, [None] * len(xs)         # g: the gated dy, once some kernel has produced it
+        if any(ctx.needs_input_grad[5:]):
+            dxs = [torch.empty_like(x) for x in xs]
+            if relu:
+                g = torch.empty_like(dyn)                                    # the dgrad stores the gate it applies: the residual's gradient
+            check(lib.nnl_catproj_dgrad(ptr(dyn), ptr(y), ptr(wn), _ptr_array(dxs), ch, len(xs), ptr(g) if relu else None, M, K, scale,
+                                        int(relu), stream()))
+            dxs = [from_nhwc(d) if need else None for d, need in zip(dxs, ctx.needs_input_grad[5:])]
+        elif relu and (need_r or need_b):
+            g, db = _conv_act_gate(y, dyn, _geom(N, H, W, K, K, 1, 1, 1, 0), 1, need_b)
+        dw = None
+        if need_w:
+            dw = torch.empty_like(wn)
+            wsb = int(lib.nnl_catproj_wgrad_workspace_bytes(ch, len(xs), M, K))
+            ws = _workspace(wsb, dev)
+            gated = g is not None                                            # otherwise the wgrad gates dy by y itself
+            check(lib.nnl_catproj_wgrad(_ptr_array(xs), ch, len(xs), ptr(g if gated else dyn), None if gated else ptr(y), ptr(dw), ptr(ws), wsb,
+                                        M, K, scale, int(not gated), stream()))
+            dw = dw.reshape(K, sum(chans), 1, 1)
+        if need_b:
+            if db is None:
+                db = _conv_bias_grad(g, _geom(N, H, W, K, K, 1, 1, 1, 0), K)
+            db = db * scale
+        return (dw, db, from_nhwc(g) if need_r else None, None, None) + tuple(dxs)
+
+
+def cat_conv1x1_residual(sources, weight, bias, residual, scale=1.0, relu=True):
+    """y = [relu](residual + scale * conv2d(cat(sources, 1), weight, bias)) without the concatenation ever being written: sources are 1 .. 4
+    logical [N,C_s,H,W] tensors, weight [K, sum C_s, 1, 1], bias [K] or None, residual [N,K,H,W] or None.  Domain: every C_s and K a
+    multiple of 4, sum C_s <= 512; anything else raises NotImplementedError naming the argument."""
+    return _CatConv1x1Residual.apply(weight, bias, residual, float(scale), bool(relu), *sources)
+
+
+# ---------------------------------------------------------------------------------------------------------
 # K3 tabular front end
 # ---------------------------------------------------------------------------------------------------------
 class TabularPlan:
