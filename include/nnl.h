@@ -425,6 +425,30 @@ size_t nnl_catproj_wgrad_workspace_bytes(const int64_t* chans, int n_src, int64_
 int nnl_catproj_wgrad(const float* const* srcs, const int64_t* chans, int n_src, const float* dy, const float* y, float* dw, void* ws,
                       size_t ws_bytes, int64_t M, int64_t K, float scale, int relu, void* stream);
 
+/* ---- K21: opt-in bf16 matrix-core convolutions (csrc/conv_bf16.hip) -----------------------------------------------------------------------
+ * The dense body convolutions that nnl_conv2d_fwd / nnl_conv2d_dgrad / nnl_conv2d_wgrad serve (nn.Conv2d inside BasicBlock.forward /
+ * Bottleneck.forward, retinanet.py:43-59, 77-97, the 1x1 downsample :344-348, and their autograd backward) with bf16 OPERANDS: every tensor
+ * is fp32 in memory, the operands are rounded to bf16 (nearest even) on their way into LDS, products on v_mfma_f32_32x32x16_bf16, fp32
+ * accumulation and epilogue.  Layouts as K1: x [N,H,W,C], w [K,R,S,C], y [N,P,Q,K].
+ * Domain (nnl_conv2d_bf16_supported: 1 inside, 0 outside): R == S, R S <= 49, stride 1 or 2, pad >= 0, C % 8 == 0, K % 8 == 0, P and Q the
+ * output size of the geometry, every tensor below 2^31 elements.  The compute entries refuse anything else (and a null pointer other than
+ * bias, addend and a zero-byte workspace) with NNL_ERR_INVALID_ARG before any launch: nothing is written.  No atomics: two calls on the
+ * same inputs give the same bits.
+ *   nnl_conv2d_bf16_pack_filter: wp = bf16 copy of w, K R S C x 2 bytes; transpose == 0: [K][R S][C], the forward's filter;
+ *     transpose != 0: [C][R S][K], the dgrad's (replaces nnl_conv2d_weight_transpose at half the bytes).
+ *   nnl_conv2d_bf16_fwd: y = act(conv(x, w) (+ bias)), relu 0 none / 1 ReLU / 2 sigmoid as nnl_conv2d_fwd; wp from pack_filter(transpose 0).
+ *   nnl_conv2d_bf16_dgrad: dx = dgrad(dy, w) (+ addend [N,H,W,C], at either stride); wpt from pack_filter(transpose 1).
+ *   nnl_conv2d_bf16_wgrad: dw [K,R,S,C]; the output pixels are cut into slabs whose partial sums go to the workspace
+ *     (nnl_conv2d_bf16_wgrad_workspace_bytes = slabs x K R S C x 4, or 0 for one slab: ws may be NULL then) and are added in slab order by
+ *     a second launch; a workspace that is too small is NNL_ERR_WORKSPACE. */
+int nnl_conv2d_bf16_supported(const nnl_conv_geom_t* g);
+int nnl_conv2d_bf16_pack_filter(const float* w, void* wp, const nnl_conv_geom_t* g, int transpose, void* stream);
+int nnl_conv2d_bf16_fwd(const float* x, const void* wp, const float* bias, float* y, const nnl_conv_geom_t* g, int relu, void* stream);
+int nnl_conv2d_bf16_dgrad(const float* dy, const void* wpt, float* dx, const nnl_conv_geom_t* g, const float* addend, void* stream);
+size_t nnl_conv2d_bf16_wgrad_workspace_bytes(const nnl_conv_geom_t* g);
+int nnl_conv2d_bf16_wgrad(const float* x, const float* dy, float* dw, const nnl_conv_geom_t* g, void* workspace, size_t workspace_bytes,
+                          void* stream);
+
 /* ---- K18: average pooling and strided subsampling of the NASNet cells (nasnet.py AvgPoolPad, the cells' AvgPool2d, path_1 / path_2) ----
  * nnl_avgpool2d_*: nn.AvgPool2d(ksize, stride, pad, count_include_pad), NHWC, any C, with the same stated-P/Q, pad_lo convention and
  * checks as the depthwise convolution (1 <= ksize <= 15, 0 <= pad_lo <= ksize - 1).  The divisor of a window is the number of its taps

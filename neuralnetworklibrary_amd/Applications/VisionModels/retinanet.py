@@ -30,6 +30,7 @@ class HipConv2d(nn.Conv2d):
     and the weight gradient comes back in the parameter's own layout; state_dict load / save are unaffected."""
     fuse_relu = False
     nnl_hip_conv = True               # ops.prepare_backward batches the filter transposes of these modules
+    compute = 'fp32'                  # 'bf16' on an instance (Learner.use_bf16_conv): ops.conv2d_bf16, operands rounded to bf16, fp32 sums
 
     def __init__(self, *args, **kwargs):
         super().__init__(*args, **kwargs)
@@ -40,8 +41,9 @@ class HipConv2d(nn.Conv2d):
                 or self.padding[0] != self.padding[1] or self.padding_mode != 'zeros':
             raise NotImplementedError('HipConv2d: only the symmetric, dense convolutions the reference uses')
         # (inside ops.shared_params — the detection heads on the five pyramid levels — weight / bias are this call's aliases)
-        return ops.conv2d(x, ops.fan_param(self.weight), ops.fan_param(self.bias), self.stride[0], self.padding[0], relu=self.fuse_relu,
-                          grad_slot=grad_slot, give_slot=give_slot)
+        conv = ops.conv2d_bf16 if self.compute == 'bf16' else ops.conv2d
+        return conv(x, ops.fan_param(self.weight), ops.fan_param(self.bias), self.stride[0], self.padding[0], relu=self.fuse_relu,
+                    grad_slot=grad_slot, give_slot=give_slot)
 
 
 class HipGroupedConv2d(nn.Conv2d):

@@ -360,6 +360,22 @@ class Learner(object):
         self._graph_warmup, self._graphs, self._dp_graph_ok, self._graph_stateless = (int(warmup) if flag else None), {}, None, None
         return self
 
+    def use_bf16_conv(self, flag=True):
+        """MI355X addition: run the dense convolutions of the model on the bf16 matrix cores (csrc/conv_bf16.hip) — every HipConv2d
+        whose layer shape `nnl_conv2d_bf16_supported` accepts (groups 1, dilation 1, square filter up to 7x7, stride 1 or 2, channel
+        counts multiples of 8: the body convolutions of the ResNet / RetinaNet / SENet / ResNeXt / Inception models; the 3-channel
+        stem, RetinaNet's 36- / 180-channel output convolutions and the grouped / depthwise / line families keep their kernels).
+        The operands are rounded to bf16 inside the kernels, sums are fp32, and every tensor — activations, weights, gradients,
+        BatchNorm, the optimizer state, the state_dict — stays fp32.  Off by default: the fp32 MFMA path is the one that matches the
+        reference to fp32 rounding.  flag=False restores it.  Captured graphs are dropped (the next steps warm up and capture
+        again); works with distribute() and use_graphs()."""
+        from .. import ops
+        for m in self.model.modules():
+            if getattr(m, 'nnl_hip_conv', False):
+                m.compute = 'bf16' if flag and ops.conv2d_bf16_supported(m) else 'fp32'
+        self._graphs = {}
+        return self
+
     def _reattach(self):
         self._graphs = {}
         if self.grad_sync is not None:

@@ -98,6 +98,12 @@ SIGNATURES = {
     'nnl_catproj_dgrad': (C.c_int, [c_p, c_p, c_p, c_p, c_p, C.c_int, c_p, i64, i64, f32, C.c_int, c_p]),
     'nnl_catproj_wgrad_workspace_bytes': (sz, [c_p, C.c_int, i64, i64]),
     'nnl_catproj_wgrad': (C.c_int, [c_p, c_p, C.c_int, c_p, c_p, c_p, c_p, sz, i64, i64, f32, C.c_int, c_p]),
+    'nnl_conv2d_bf16_supported': (C.c_int, [C.POINTER(ConvGeom)]),
+    'nnl_conv2d_bf16_pack_filter': (C.c_int, [c_p, c_p, C.POINTER(ConvGeom), C.c_int, c_p]),
+    'nnl_conv2d_bf16_fwd': (C.c_int, [c_p, c_p, c_p, c_p, C.POINTER(ConvGeom), C.c_int, c_p]),
+    'nnl_conv2d_bf16_dgrad': (C.c_int, [c_p, c_p, c_p, C.POINTER(ConvGeom), c_p, c_p]),
+    'nnl_conv2d_bf16_wgrad_workspace_bytes': (sz, [C.POINTER(ConvGeom)]),
+    'nnl_conv2d_bf16_wgrad': (C.c_int, [c_p, c_p, c_p, C.POINTER(ConvGeom), c_p, sz, c_p]),
     'nnl_avgpool2d_fwd': (C.c_int, [c_p, c_p, i64, i64, i64, i64, i64, i64, C.c_int, C.c_int, C.c_int, C.c_int, c_p]),
     'nnl_avgpool2d_bwd': (C.c_int, [c_p, c_p, i64, i64, i64, i64, i64, i64, C.c_int, C.c_int, C.c_int, C.c_int, c_p]),
     'nnl_subsample2d_fwd': (C.c_int, [c_p, c_p, i64, i64, i64, i64, i64, i64, C.c_int, C.c_int, c_p]),

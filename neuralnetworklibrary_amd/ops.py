@@ -318,7 +318,7 @@ class _Filters:
     def __init__(self, model):
         # the module walk costs ~0.1 ms per step on a host-bound model: done once.  A conv added later transforms its own filter (slower, correct)
         self.mods = [m for m in model.modules() if getattr(m, 'nnl_hip_conv', False)]
-        self.step = 0         # training-step counter (open): the recorded modes of a weight are those of its LAST step
+        self.step = 0        # training-step counter (open): the recorded modes of a weight are those of its LAST step
         self.modes = {}       # weight data_ptr -> [[step stamp, modes the forward calls took], [stamp, modes the dgrad calls took]] (sets; 1 = 1-D,
                               # 2 = 2-D kernel): a weight shared between geometries (RetinaNet's heads: five pyramid levels) may need BOTH layouts
         self.batches = {}     # 'fwd' / 'bwd' / 'wt' -> the persistent forward U / dgrad U' / W^T batch (_FilterBatch)
@@ -326,6 +326,10 @@ class _Filters:
         self.u = ({}, {})     # [0] forward, [1] dgrad: (weight data_ptr, kernel mode) -> U [K,4|16,3|1,C] / U' [C,...,K] in that kernel's layout
         self.wt = {}          # weight data_ptr -> W^T tensor [C,R,S,K]
         self.wt_padded = {}   # (weight data_ptr, shape, pad) -> transposed, channel-padded filter of a K % 16 != 0 dgrad
+
+    def fp32_mods(self):
+        "the modules whose calls can take a prepared filter: all but those switched to the bf16 kernels (Learner.use_bf16_conv), which read none"
+        return [m for m in self.mods if getattr(m, 'compute', 'fp32') == 'fp32']
 
     def open(self):
         global _OPEN
@@ -356,7 +360,7 @@ class _Filters:
     def prepare_forward(self):
         self.open()
         srcs = []
-        for m in self.mods:
+        for m in self.fp32_mods():
             w = m.weight
             modes = self.recorded(w.data_ptr(), 0)
             if (modes and w.is_cuda and w.dim() == 4 and w.shape[2] == 3 and w.shape[3] == 3 and w.dtype == torch.float32
@@ -367,7 +371,7 @@ class _Filters:
     def prepare_backward(self):
         if _OPEN is not self:
             self.open()
-        ws = [m.weight for m in self.mods
+        ws = [m.weight for m in self.fp32_mods()
               if m.weight.is_cuda and m.weight.dim() == 4 and m.weight.shape[1] % 4 == 0
               and m.weight.shape[0] % 4 == 0 and m.weight.dtype == torch.float32
               and m.weight.is_contiguous(memory_format=torch.channels_last)]
@@ -730,12 +734,16 @@ def _conv_wgrad(st, xn, dy4, g4, K):
     wsb = int(lib.nnl_conv2d_wgrad_workspace_bytes(g4))
     ws = _workspace(wsb, dy4.device, floor=True)            # never a null
     check(lib.nnl_conv2d_wgrad(ptr(xn), ptr(dy4), ptr(dwn), g4, ptr(ws), wsb, stream()))
-    dw = from_nhwc(dwn[:K, :, :, :st.c_in])
+    return _in_param_strides(st, from_nhwc(dwn[:K, :, :, :st.c_in]), g4)
+
+
+def _in_param_strides(st, dw, g):
+    "the logical weight gradient dw (a view of the kernel's KRSC output) in the parameter's own strides"
     # a 1x1 filter's [K, C, 1, 1] gradient: give it EXACTLY the parameter's strides (the size-1 dimensions make them ambiguous);
     # otherwise AccumulateGrad sees a layout mismatch and clones it into the parameter's layout — one device copy per 1x1
     # convolution and step (53 of RetinaNet's 68 rocclr_copyBuffer launches, profiles/r5_retinanet_kernel_stats.csv)
     wshape, wstride = st.w_layout
-    if (g4.R == 1 and g4.S == 1 and wshape == tuple(dw.shape) and wstride != tuple(dw.stride()) and dw.is_contiguous(memory_format=torch.channels_last)
+    if (g.R == 1 and g.S == 1 and wshape == tuple(dw.shape) and wstride != tuple(dw.stride()) and dw.is_contiguous(memory_format=torch.channels_last)
             and wstride[1] == 1 and wstride[0] == dw.shape[1]):
         dw = dw.as_strided(wshape, wstride)
     return dw
@@ -836,6 +844,110 @@ def conv2d_with_bn_stats(x, weight, bias, stride, pad, bn_pivot, grad_slot=None,
     """conv2d whose epilogue also reduces the BatchNorm batch statistics of its output against `bn_pivot` [K].  Returns (y, partials);
     partials is empty when this launch could not produce them (the BatchNorm then runs its own statistics pass)."""
     return _conv(x, weight, bias, stride=stride, pad=pad, slot=grad_slot, bn_pivot=bn_pivot, give_slot=give_slot)
+
+
+# ---- K21: the same convolution with bf16 operands on the bf16 matrix cores (csrc/conv_bf16.hip); opt-in, tensors stay fp32 ------------
+def _conv_bf16_check(x_shape, w_shape, stride, pad):
+    "the domain of csrc/conv_bf16.hip, checked before any launch (and before any device is needed): names the offending argument"
+    if len(x_shape) != 4 or len(w_shape) != 4:
+        raise NotImplementedError('conv2d_bf16: x %s and weight %s must be 4-D' % (tuple(x_shape), tuple(w_shape)))
+    (_, C, H, W), (K, Cw, R, S) = x_shape, w_shape
+    if R != S or R * S > 49:
+        raise NotImplementedError('conv2d_bf16: kernel_size %dx%d is not supported (square, at most 7x7)' % (R, S))
+    if stride not in (1, 2):
+        raise NotImplementedError('conv2d_bf16: stride %r is not supported (1 or 2)' % (stride,))
+    if pad < 0 or H + 2 * pad < R or W + 2 * pad < S:
+        raise NotImplementedError('conv2d_bf16: padding %r is not supported for a %dx%d input and a %dx%d filter' % (pad, H, W, R, S))
+    if C != Cw or C % 8:
+        raise NotImplementedError('conv2d_bf16: in_channels %d (weight: %d) must be a multiple of 8 (groups = 1)' % (C, Cw))
+    if K % 8:
+        raise NotImplementedError('conv2d_bf16: out_channels %d must be a multiple of 8' % K)
+
+
+def conv2d_bf16_supported(conv):
+    "whether the layer shape of an nn.Conv2d lies in conv2d_bf16's domain: nnl_conv2d_bf16_supported on a nominal input raster"
+    k, s, p = conv.kernel_size, conv.stride, conv.padding
+    if conv.groups != 1 or conv.dilation != (1, 1) or conv.padding_mode != 'zeros' or isinstance(p, str) or s[0] != s[1] or p[0] != p[1]:
+        return False
+    side = max(k) + 2
+    return bool(lib.nnl_conv2d_bf16_supported(_geom(1, side, side, conv.in_channels, conv.out_channels, k[0], k[1], s[0], p[0])))
+
+
+def _bf16_filter(wn, g, transpose):
+    "the bf16 copy of the KRSC filter the kernels read: [K][R S][C], or the dgrad's transpose [C][R S][K]"
+    wp = torch.empty(wn.numel(), dtype=torch.bfloat16, device=wn.device)
+    check(lib.nnl_conv2d_bf16_pack_filter(ptr(wn), ptr(wp), g, int(transpose), stream()))
+    return wp
+
+
+def _conv_bf16_dgrad(st, dyn, wn):
+    "_conv_dgrad on the bf16 kernel: the logical input gradient (GradSlot shortcut added), or None when it was parked in st.give_slot"
+    g = st.g
+    dxn = torch.empty((g.N, g.H, g.W, g.C), dtype=torch.float32, device=dyn.device)
+    shortcut = None
+    if st.slot is not None:
+        shortcut, st.slot.tensor, st.slot.closed = st.slot.tensor, None, True
+    # every dx pixel passes through this kernel's epilogue, at either stride: the addend is fused whenever it is a dense image of dx
+    fuse = shortcut is not None and shortcut.numel() == dxn.numel() and shortcut.dtype == torch.float32 and shortcut.is_contiguous()
+    check(lib.nnl_conv2d_bf16_dgrad(ptr(dyn), ptr(_bf16_filter(wn, g, 1)), ptr(dxn), g, ptr(shortcut) if fuse else None, stream()))
+    if shortcut is not None and not fuse:
+        dxn += shortcut.view_as(dxn)
+    give = st.give_slot
+    if give is not None and not give.closed:
+        give.tensor = dxn                           # the block's first conv adds it inside its dgrad kernel
+        return None
+    return from_nhwc(dxn)
+
+
+def _conv_bf16_wgrad(st, xn, dyn):
+    "the weight gradient in the parameter's own strides (a fresh tensor: never written into the data-parallel bucket in place)"
+    g = st.g
+    dwn = torch.empty((g.K, g.R, g.S, g.C), dtype=torch.float32, device=dyn.device)
+    wsb = int(lib.nnl_conv2d_bf16_wgrad_workspace_bytes(g))
+    check(lib.nnl_conv2d_bf16_wgrad(ptr(xn), ptr(dyn), ptr(dwn), g, ptr(_workspace(wsb, dyn.device)), wsb, stream()))
+    return _in_param_strides(st, from_nhwc(dwn), g)
+
+
+class _Conv2dBf16(torch.autograd.Function):
+    """nn.Conv2d forward / backward (the call sites of _Conv2d) with operands rounded to bf16 and fp32 accumulation.  x, weight, the
+    output and every gradient are fp32 tensors; the ReLU / sigmoid gate and the bias gradient are _Conv2d's own fp32 passes."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, stride, pad, relu, slot=None, give_slot=None):
+        _conv_bf16_check(x.shape, weight.shape, stride, pad)
+        require_cuda(x, weight, bias)
+        xn, wn, b, g, y = _conv_operands(x, weight, bias, stride, pad)
+        ctx.st = _conv_state(x, weight, bias, g, relu, slot, give_slot)
+        check(lib.nnl_conv2d_bf16_fwd(ptr(xn), ptr(_bf16_filter(wn, g, 0)), ptr(b), ptr(y), g, int(relu), stream()))
+        ctx.save_for_backward(xn, wn, y if relu else None)
+        return from_nhwc(y)
+
+    @staticmethod
+    def backward(ctx, dy):
+        xn, wn, y = ctx.saved_tensors
+        st, needs = ctx.st, ctx.needs_input_grad
+        want_db = st.has_bias and needs[2]
+        dyn, db = to_nhwc(dy.float()), None
+        if st.relu:
+            dyn, db = _conv_act_gate(y, dyn, st.g, st.relu, want_db)
+        dx = dw = None
+        if needs[0]:
+            dx = _conv_bf16_dgrad(st, dyn, wn)
+        elif st.slot is not None:               # closed even when nobody wants dx (as _conv_backward)
+            st.slot.tensor, st.slot.closed = None, True
+        if needs[1]:
+            dw = _conv_bf16_wgrad(st, xn, dyn)
+        if db is None and want_db:
+            db = _conv_bias_grad(dyn, st.g, st.g.K)
+        return dx, dw, db, None, None, None, None, None
+
+
+def conv2d_bf16(x, weight, bias=None, stride=1, pad=0, relu=False, grad_slot=None, give_slot=None):
+    """ops.conv2d with its products on the bf16 matrix cores: x and weight are rounded to bf16 (nearest even) inside the kernels, sums
+    and epilogue are fp32, and so is every tensor in memory; relu / grad_slot / give_slot as ops.conv2d.  Domain: groups 1, dilation 1,
+    square filter up to 7x7, stride 1 or 2, in_channels and out_channels multiples of 8; anything else raises NotImplementedError
+    naming the argument.  Bitwise reproducible run to run."""
+    return _Conv2dBf16.apply(x, weight, bias, int(stride), int(pad), int(relu), grad_slot, give_slot)
 
 
 def _rows_in_place(x):
@@ -1092,6 +1204,7 @@ def conv_bn_act(conv, bn, x, residual=None, relu=True, conv_slot=None, bn_slot=N
     step (no pivot yet) runs the stand-alone statistics pass."""
     fuse = (bn.training and bn.track_running_stats and bn.running_mean is not None and bn.momentum is not None
             and getattr(bn, 'nnl_sync', None) is None and x.is_cuda and conv.bias is None and not conv.fuse_relu
+            and getattr(conv, 'compute', 'fp32') == 'fp32'          # the bf16 kernels produce no epilogue statistics
             and torch.is_grad_enabled() and os.environ.get('NNL_BN_EPI_STATS', '1') != '0')
 
     def unfused(**kw):
