@@ -449,6 +449,31 @@ size_t nnl_conv2d_bf16_wgrad_workspace_bytes(const nnl_conv_geom_t* g);
 int nnl_conv2d_bf16_wgrad(const float* x, const float* dy, float* dw, const nnl_conv_geom_t* g, void* workspace, size_t workspace_bytes,
                           void* stream);
 
+/* ---- K22: opt-in bf16 matrix-core Linear (csrc/linear_bf16.hip) ----------------------------------------------------------------------------
+ * The Linear GEMMs of the language model: the tied decoder (reference Applications/Text.py:572, self.lin over [seq bs, emb] with V = 47 343
+ * output features) and the input projection gx = x w_ih^T + b of nn.LSTM (Text.py:495-513), and their autograd backward, with bf16
+ * OPERANDS: every tensor is fp32 in memory, the operands are rounded to bf16 (nearest even) on their way into LDS, products on
+ * v_mfma_f32_32x32x16_bf16, fp32 accumulation and epilogue.  Row-major matrices with explicit row strides in elements: x [M][ldx >= K],
+ * w [N][ldw >= K], y [M][ldy >= N], dy [M][lddy >= N] (a zero-padded row length is read in place); dx [M][K], dw [N][K] and db [N] are dense.
+ * Domain: any 0 < M, N, K < 2^31 - 256; no alignment is required (16-byte aligned operands with strides that are multiples of 4 take the
+ * float4 loads, others dword loads).  A null pointer (other than bias, db and a zero-byte ws), a stride shorter than its row or a
+ * non-positive size is NNL_ERR_INVALID_ARG, a workspace that is NULL or too small NNL_ERR_WORKSPACE, both before any launch: nothing is
+ * written.  No atomics: two calls on the same inputs give the same bits.
+ *   nnl_linear_bf16_fwd: y = rb(x) rb(w)^T (+ bias) (+ ReLU when relu != 0); the sum over K is never split.
+ *   nnl_linear_bf16_dgrad: dx = rb(dy) rb(w).  The reduction over N is cut into slabs whose partial [M][K] results go to the workspace
+ *     (nnl_linear_bf16_dgrad_workspace_bytes = slabs x M K x 4, or 0 for one slab: ws may be NULL then) and are added in slab order by a
+ *     second launch.
+ *   nnl_linear_bf16_wgrad: dw = rb(dy)^T rb(x), and, when db is not NULL, db = the fp32 column sums of the UNROUNDED dy in a fixed order.
+ *     The reduction over M is cut into slabs the same way: nnl_linear_bf16_wgrad_workspace_bytes = slabs x (N K + N) x 4, or 0. */
+int nnl_linear_bf16_fwd(const float* x, const float* w, const float* bias, float* y, int64_t M, int64_t N, int64_t K, int64_t ldx, int64_t ldw,
+                        int64_t ldy, int relu, void* stream);
+size_t nnl_linear_bf16_dgrad_workspace_bytes(int64_t M, int64_t N, int64_t K);
+int nnl_linear_bf16_dgrad(const float* dy, const float* w, float* dx, int64_t M, int64_t N, int64_t K, int64_t lddy, int64_t ldw,
+                          void* workspace, size_t workspace_bytes, void* stream);
+size_t nnl_linear_bf16_wgrad_workspace_bytes(int64_t M, int64_t N, int64_t K);
+int nnl_linear_bf16_wgrad(const float* x, const float* dy, float* dw, float* db, int64_t M, int64_t N, int64_t K, int64_t ldx, int64_t lddy,
+                          void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- K18: average pooling and strided subsampling of the NASNet cells (nasnet.py AvgPoolPad, the cells' AvgPool2d, path_1 / path_2) ----
  * nnl_avgpool2d_*: nn.AvgPool2d(ksize, stride, pad, count_include_pad), NHWC, any C, with the same stated-P/Q, pad_lo convention and
  * checks as the depthwise convolution (1 <= ksize <= 15, 0 <= pad_lo <= ksize - 1).  The divisor of a window is the number of its taps

@@ -510,6 +510,8 @@ class WeightDropLSTM1(nn.Module):
     all timesteps) — Text.py:477-513."""
 
     nnl_stateful_forward = True        # the weight-drop seed of a call is drawn on the host (ops_text.lstm_layer): not replayable
+    nnl_hip_linear = True              # Learner.use_bf16_linear() sets `compute`
+    compute = 'fp32'                   # 'bf16': the input projection gx on the bf16 matrix cores (ops.linear_bf16)
 
     def __init__(self, input_size, hidden_size, drop):
         super().__init__()
@@ -529,7 +531,7 @@ class WeightDropLSTM1(nn.Module):
         # W = Dropout_p(W_raw) (Text.py:511) is applied INSIDE the layer: one pass that also pads W for the recurrence kernels
         drop_p = self.weight_drop.p if (self.training and weight_mask is None) else 0.0
         return ops.lstm_layer(x, h0c0[0], h0c0[1], p.weight_ih_l0, p.weight_hh_l0_raw, p.bias_ih_l0, p.bias_hh_l0,
-                              weight_mask=weight_mask, weight_p=drop_p)
+                              weight_mask=weight_mask, weight_p=drop_p, compute=self.compute)
 
 
 class LSTM_Encoder(nn.Module):
@@ -575,6 +577,9 @@ class LSTM_Encoder(nn.Module):
 class LanguageModelDecoder(nn.Module):
     "Locked dropout -> tied linear -> [bs, vocab, seqlen] (Text.py:553-573)"
 
+    nnl_hip_linear = True              # Learner.use_bf16_linear() sets `compute`
+    compute = 'fp32'                   # 'bf16': the decoder GEMM on the bf16 matrix cores (ops.linear_bf16)
+
     def __init__(self, vocab_size, emb_dim, drop, tied_weight):
         super().__init__()
         self.lin = nn.Linear(emb_dim, vocab_size, bias=False)
@@ -583,7 +588,8 @@ class LanguageModelDecoder(nn.Module):
         self.fixed_mask = None
 
     def forward(self, enc_out):
-        pred = ops.linear(self.drop(enc_out, self.fixed_mask), self.lin.weight, None)      # [seq, bs, V]
+        lin = ops.linear_bf16 if self.compute == 'bf16' else ops.linear
+        pred = lin(self.drop(enc_out, self.fixed_mask), self.lin.weight, None)             # [seq, bs, V]
         return pred.permute(1, 2, 0), enc_out
 
 

@@ -376,6 +376,21 @@ class Learner(object):
         self._graphs = {}
         return self
 
+    def use_bf16_linear(self, flag=True):
+        """MI355X addition: run the large Linear GEMMs of the language model on the bf16 matrix cores (csrc/linear_bf16.hip) — every
+        module marked `nnl_hip_linear`: the tied decoder (LanguageModelDecoder, [seq bs, emb] x [V, emb]^T) and the input projection
+        gx of every WeightDropLSTM1; forward, input gradient and weight gradient.  The recurrent w_hh products, the attention and
+        fully-connected layers of the classifier and the 1 - 4 column heads keep their fp32 kernels.  The operands are rounded to
+        bf16 inside the kernels, sums are fp32, and every tensor — activations, logits, weights, gradients, the optimizer state, the
+        state_dict — stays fp32.  Off by default: the fp32 MFMA path is the one that matches the reference to fp32 rounding.
+        flag=False restores it bit for bit.  Captured graphs are dropped (the next steps warm up and capture again); works with
+        distribute() and use_graphs()."""
+        for m in self.model.modules():
+            if getattr(m, 'nnl_hip_linear', False):
+                m.compute = 'bf16' if flag else 'fp32'
+        self._graphs = {}
+        return self
+
     def _reattach(self):
         self._graphs = {}
         if self.grad_sync is not None:

@@ -16,7 +16,7 @@ import torch
 from . import _lib
 from ._lib import check, lib, ptr, require_cuda, stream
 
-__all__ = ['mse_loss', 'bce_with_logits', 'fbeta', 'scaled_sigmoid', 'embdotbias', 'index_error_flag', 'raise_if_index_error', 'conv2d', 'to_nhwc', 'from_nhwc', 'linear', 'bn_act', 'concat_pool2d', 'TabularPlan', 'tab_embed_concat', 'embedding_renorm_drop', 'retina_loss', 'image_aug', 'grouped_conv2d', 'se_excite']
+__all__ = ['mse_loss', 'bce_with_logits', 'fbeta', 'scaled_sigmoid', 'embdotbias', 'index_error_flag', 'raise_if_index_error', 'conv2d', 'to_nhwc', 'from_nhwc', 'linear', 'linear_bf16', 'bn_act', 'concat_pool2d', 'TabularPlan', 'tab_embed_concat', 'embedding_renorm_drop', 'retina_loss', 'image_aug', 'grouped_conv2d', 'se_excite']
 
 _ERR_FLAGS = {}
 
@@ -999,6 +999,86 @@ def linear(x, weight, bias=None, relu=False):
     if not relu and weight.shape[0] <= 4 and x2.is_cuda and x2.shape[0] > 0:
         return _LinearSmall.apply(x2, weight, bias).reshape(*lead, weight.shape[0])
     y = _conv(x2[:, :, None, None], weight[:, :, None, None], bias, relu=relu)[0]
+    return y.reshape(*lead, weight.shape[0])
+
+
+def _ld(m):
+    "row stride of a matrix whose rows are dense (one row: its length, the stride of a size-1 dimension means nothing)"
+    return m.stride(0) if m.shape[0] > 1 else m.shape[1]
+
+
+def _linear_bf16_dy(dy, N):
+    """(the matrix nnl_linear_bf16_dgrad / _wgrad read, its row stride) for an output gradient of logical shape [M, N]: the base that
+    register_padded_grad holds with its padded row length when dy is a view over one (_SoftmaxCE's Vp-wide dlogits, the LSTM's Gp-wide
+    dgates), any other matrix with dense rows in place, anything else as a contiguous copy"""
+    base = dy._base if dy._is_view() else None
+    ent = _PADDED_GRADS.get(id(base)) if base is not None else None
+    if ent is not None and ent[0]() is base and dy.dtype == torch.float32 and dy.dim() == 2 and dy.stride() == (ent[1], 1) and ent[1] >= N \
+            and dy.storage_offset() % ent[1] == 0 and dy.storage_offset() + dy.shape[0] * ent[1] <= base.numel():
+        return torch.as_strided(base, (dy.shape[0], ent[1]), (ent[1], 1), dy.storage_offset()), ent[1]
+    dy = dy if _rows_in_place(dy) else _f32c(dy)
+    return dy, _ld(dy)
+
+
+class _LinearBf16(torch.autograd.Function):
+    """nn.Linear forward / backward (the call sites of ops.linear) on csrc/linear_bf16.hip: operands rounded to bf16 inside the kernels,
+    fp32 accumulation; x, weight, the output and every gradient are fp32 tensors.  The ReLU gate is _Conv2d's fp32 pass; the bias
+    gradient comes from the weight-gradient kernel's staging pass (unrounded dy)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, relu):
+        require_cuda(x, weight, bias)
+        if weight.dim() != 2 or x.shape[1] != weight.shape[1]:
+            raise ValueError('linear_bf16: weight %r does not match %d input features' % (tuple(weight.shape), x.shape[1]))
+        x = x if _rows_in_place(x) else _f32c(x)
+        w = weight if _rows_in_place(weight) else _f32c(weight)
+        b = None if bias is None else _f32c(bias)
+        (M, K), N = x.shape, w.shape[0]
+        y = torch.empty(M, N, dtype=torch.float32, device=x.device)
+        check(lib.nnl_linear_bf16_fwd(ptr(x), ptr(w), ptr(b), ptr(y), M, N, K, _ld(x), _ld(w), N, int(relu), stream()))
+        ctx.save_for_backward(x, w, y if relu else None)
+        ctx.cfg = (relu, bias is not None, (tuple(weight.shape), tuple(weight.stride())))
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w, y = ctx.saved_tensors
+        relu, has_bias, (wshape, wstride) = ctx.cfg
+        (M, K), N, dev = x.shape, w.shape[0], x.device
+        needs = ctx.needs_input_grad
+        want_db = has_bias and needs[2]
+        dx = dw = db = None
+        if relu:
+            dym, db = _conv_act_gate(y, _f32c(dy), _geom(M, 1, 1, K, N, 1, 1, 1, 0), 1, want_db)
+            ld = N
+        else:
+            dym, ld = _linear_bf16_dy(dy, N)
+        if needs[0]:
+            dx = torch.empty(M, K, dtype=torch.float32, device=dev)
+            wsb = int(lib.nnl_linear_bf16_dgrad_workspace_bytes(M, N, K))
+            check(lib.nnl_linear_bf16_dgrad(ptr(dym), ptr(w), ptr(dx), M, N, K, ld, _ld(w), ptr(_workspace(wsb, dev)), wsb, stream()))
+        if needs[1] or (want_db and db is None):
+            dw = torch.empty(N, K, dtype=torch.float32, device=dev)
+            if want_db and db is None:
+                db = torch.empty(N, dtype=torch.float32, device=dev)
+                dbk = db
+            else:
+                dbk = None
+            wsb = int(lib.nnl_linear_bf16_wgrad_workspace_bytes(M, N, K))
+            check(lib.nnl_linear_bf16_wgrad(ptr(x), ptr(dym), ptr(dw), ptr(dbk), M, N, K, _ld(x), ld, ptr(_workspace(wsb, dev)), wsb, stream()))
+            if not needs[1]:
+                dw = None
+            elif wstride != tuple(dw.stride()):                 # the parameter's own strides: AccumulateGrad keeps the tensor as is
+                dw = torch.empty_strided(wshape, wstride, dtype=torch.float32, device=dev).copy_(dw)
+        return dx, dw, db, None
+
+
+def linear_bf16(x, weight, bias=None, relu=False):
+    """ops.linear with its products on the bf16 matrix cores (nn.Linear; reference Text.py:572 and the nn.LSTM input projection): x and
+    weight — and dy in the backward — are rounded to bf16 (nearest even) inside the kernels, sums and epilogue are fp32, and so is every
+    tensor in memory.  Any shape; leading dims of x are flattened into rows.  Bitwise reproducible run to run."""
+    lead = x.shape[:-1]
+    y = _LinearBf16.apply(x.reshape(-1, x.shape[-1]), weight, bias, bool(relu))
     return y.reshape(*lead, weight.shape[0])
 
 

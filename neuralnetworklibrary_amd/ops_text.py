@@ -104,15 +104,19 @@ class _LSTMRecurrence(torch.autograd.Function):
         return dgates[:, :, :G], dw, dh0.view_as(h0), dc0.view_as(c0), None, None, None
 
 
-def lstm_layer(x, h0, c0, w_ih, w_hh, b_ih, b_hh, weight_mask=None, weight_p=0.0):
+def lstm_layer(x, h0, c0, w_ih, w_hh, b_ih, b_hh, weight_mask=None, weight_p=0.0, compute='fp32'):
     """One-layer LSTM over x [T,B,I] with initial state (h0, c0) [1,B,H] (or [B,H]).  w_hh is the RAW recurrent matrix: the
     weight drop of WeightDropLSTM1 (Text.py:495-513) happens inside (`weight_mask`: an explicit scaled mask; else a fresh
     Bernoulli(1 - weight_p) mask per call, its seed drawn from torch's CPU generator so `torch.manual_seed` governs it).
+    compute selects the op of the input projection gx only: 'fp32' ops.linear, 'bf16' ops.linear_bf16; the recurrence is fp32 either way.
     Returns y [T,B,H], (hT [1,B,H], cT [1,B,H]) like nn.LSTM."""
     from . import ops
+    if compute not in ('fp32', 'bf16'):
+        raise ValueError("lstm_layer: compute must be 'fp32' or 'bf16', not %r" % (compute,))
     T, B, _ = x.shape
     H = w_hh.shape[1]
-    gx = ops.linear(x.reshape(T * B, -1), w_ih, b_ih + b_hh).view(T, B, 4 * H)
+    lin = ops.linear_bf16 if compute == 'bf16' else ops.linear
+    gx = lin(x.reshape(T * B, -1), w_ih, b_ih + b_hh).view(T, B, 4 * H)
     seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if (weight_mask is None and weight_p > 0) else 0
     y, hT, cT = _LSTMRecurrence.apply(gx, w_hh, h0.reshape(B, H), c0.reshape(B, H), weight_mask, float(weight_p), seed)
     return y, (hT.view(1, B, H), cT.view(1, B, H))
