@@ -474,6 +474,29 @@ size_t nnl_linear_bf16_wgrad_workspace_bytes(int64_t M, int64_t N, int64_t K);
 int nnl_linear_bf16_wgrad(const float* x, const float* dy, float* dw, float* db, int64_t M, int64_t N, int64_t K, int64_t ldx, int64_t lddy,
                           void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- K23: fused bf16 decoder + softmax cross-entropy (csrc/linear_ce_bf16.hip) --------------------------------------------------------------
+ * loss = mean_r( logsumexp_j z[r, j] - z[r, target[r]] ) with z = rb(x) rb(w)^T summed in fp32 (rb: round to bf16, nearest even, as K22), for
+ * x [M][ldx >= K], w [N][ldw >= K] fp32 and target [M] int64, without an [M, N] buffer in either direction: the forward GEMM's epilogue keeps a
+ * running {max, sum} per row, the backward recomputes the logits tile by tile.  Domain (nnl_linear_ce_bf16_supported): 0 < M, N < 2^31 - 256,
+ * 0 < K <= 512; no alignment is required.  A row whose target lies outside [0, N) has loss 0 and no one-hot term and sets *err_flag (which may
+ * be NULL) to 1, as in nnl_softmax_ce_fwd; the mean is over all M rows.  A null pointer (other than err_flag, one of dx / dw, and a zero-byte
+ * ws), a stride shorter than its row or a size outside the domain is NNL_ERR_INVALID_ARG, a workspace that is NULL or too small
+ * NNL_ERR_WORKSPACE, both before any launch: nothing is written.  No atomics: two calls on the same inputs give the same bits.
+ *   nnl_linear_ce_bf16_fwd: lse [M] (for the backward), loss_rows [M], loss_mean [1]; the workspace (nnl_linear_ce_bf16_fwd_workspace_bytes =
+ *     ranges x 3 M x 4, never 0 inside the domain) holds {max, sum, z_target} per row and vocabulary range, merged in range order.
+ *   nnl_linear_ce_bf16_bwd: with D = (exp(z - lse) - onehot) g[0] / M in fp32, carried as two bf16 operands hi = rb(D), lo = rb(D - hi)
+ *     (2^-16 of D): dx [M][K] = (hi + lo) rb(w) when dx is not NULL, dw [N][K] = (hi + lo)^T rb(x) when dw is not NULL (dense).  Each reduction is cut into slabs whose partials go to the workspace
+ *     and are added in slab order: nnl_linear_ce_bf16_bwd_workspace_bytes(M, N, K, want_dx, want_dw) = the sum over the wanted gradients of
+ *     slabs x rows K x 4, 0 for one slab. */
+int nnl_linear_ce_bf16_supported(int64_t M, int64_t N, int64_t K);
+size_t nnl_linear_ce_bf16_fwd_workspace_bytes(int64_t M, int64_t N, int64_t K);
+int nnl_linear_ce_bf16_fwd(const float* x, const float* w, const int64_t* target, float* lse, float* loss_rows, float* loss_mean, int64_t M,
+                           int64_t N, int64_t K, int64_t ldx, int64_t ldw, void* workspace, size_t workspace_bytes, int32_t* err_flag,
+                           void* stream);
+size_t nnl_linear_ce_bf16_bwd_workspace_bytes(int64_t M, int64_t N, int64_t K, int want_dx, int want_dw);
+int nnl_linear_ce_bf16_bwd(const float* x, const float* w, const int64_t* target, const float* lse, const float* g, float* dx, float* dw,
+                           int64_t M, int64_t N, int64_t K, int64_t ldx, int64_t ldw, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- K18: average pooling and strided subsampling of the NASNet cells (nasnet.py AvgPoolPad, the cells' AvgPool2d, path_1 / path_2) ----
  * nnl_avgpool2d_*: nn.AvgPool2d(ksize, stride, pad, count_include_pad), NHWC, any C, with the same stated-P/Q, pad_lo convention and
  * checks as the depthwise convolution (1 <= ksize <= 15, 0 <= pad_lo <= ksize - 1).  The divisor of a window is the number of its taps

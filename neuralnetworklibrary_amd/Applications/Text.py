@@ -579,6 +579,8 @@ class LanguageModelDecoder(nn.Module):
 
     nnl_hip_linear = True              # Learner.use_bf16_linear() sets `compute`
     compute = 'fp32'                   # 'bf16': the decoder GEMM on the bf16 matrix cores (ops.linear_bf16)
+    fuse_loss = False                  # Learner.use_fused_decoder_loss(): while training, hand the loss ops_text.DeferredLogits instead of
+                                       # logits (ops.linear_cross_entropy_bf16: bf16 operands whatever `compute` says); eval is unchanged
 
     def __init__(self, vocab_size, emb_dim, drop, tied_weight):
         super().__init__()
@@ -589,6 +591,8 @@ class LanguageModelDecoder(nn.Module):
 
     def forward(self, enc_out):
         lin = ops.linear_bf16 if self.compute == 'bf16' else ops.linear
+        if self.fuse_loss and self.training:
+            return ops_text.DeferredLogits(self.drop(enc_out, self.fixed_mask), self.lin.weight), enc_out
         pred = lin(self.drop(enc_out, self.fixed_mask), self.lin.weight, None)             # [seq, bs, V]
         return pred.permute(1, 2, 0), enc_out
 

@@ -391,6 +391,26 @@ class Learner(object):
         self._graphs = {}
         return self
 
+    def use_fused_decoder_loss(self, flag=True):
+        """MI355X addition: take the language model's cross-entropy straight from the tied decoder's operands
+        (csrc/linear_ce_bf16.hip, ops.linear_cross_entropy_bf16): while training, every LanguageModelDecoder whose shape the kernels
+        support (emb_dim <= 512) returns ops_text.DeferredLogits instead of its [bs, V, seq] logits, and ops.cross_entropy_nd — inside
+        RegSeqCrossEntropyLoss or on its own — computes the loss and the gradients of the activations and of the tied weight without
+        the logits or their gradient ever existing in memory (V = 47 343: two 848 MB buffers per step).  The decoder's operands are
+        rounded to bf16 as under use_bf16_linear(); every tensor stays fp32.  Evaluation and prediction materialise logits as before.
+        Off by default; flag=False restores the step bit for bit.  Raises ValueError for a model without such a decoder.  Captured
+        graphs are dropped."""
+        from .. import ops
+        from ..Applications.Text import LanguageModelDecoder
+        decs = [m for m in self.model.modules() if isinstance(m, LanguageModelDecoder)]
+        if not decs:
+            raise ValueError('use_fused_decoder_loss: the model has no LanguageModelDecoder')
+        for m in decs:
+            V, emb = m.lin.weight.shape
+            m.fuse_loss = bool(flag) and ops.linear_ce_bf16_supported(1, V, emb)
+        self._graphs = {}
+        return self
+
     def _reattach(self):
         self._graphs = {}
         if self.grad_sync is not None:

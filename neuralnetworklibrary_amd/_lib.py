@@ -109,6 +109,11 @@ SIGNATURES = {
     'nnl_linear_bf16_dgrad': (C.c_int, [c_p, c_p, c_p, i64, i64, i64, i64, i64, c_p, sz, c_p]),
     'nnl_linear_bf16_wgrad_workspace_bytes': (sz, [i64, i64, i64]),
     'nnl_linear_bf16_wgrad': (C.c_int, [c_p, c_p, c_p, c_p, i64, i64, i64, i64, i64, c_p, sz, c_p]),
+    'nnl_linear_ce_bf16_supported': (C.c_int, [i64, i64, i64]),
+    'nnl_linear_ce_bf16_fwd_workspace_bytes': (sz, [i64, i64, i64]),
+    'nnl_linear_ce_bf16_fwd': (C.c_int, [c_p, c_p, c_p, c_p, c_p, c_p, i64, i64, i64, i64, i64, c_p, sz, c_p, c_p]),
+    'nnl_linear_ce_bf16_bwd_workspace_bytes': (sz, [i64, i64, i64, C.c_int, C.c_int]),
+    'nnl_linear_ce_bf16_bwd': (C.c_int, [c_p, c_p, c_p, c_p, c_p, c_p, c_p, i64, i64, i64, i64, i64, c_p, sz, c_p]),
     'nnl_avgpool2d_fwd': (C.c_int, [c_p, c_p, i64, i64, i64, i64, i64, i64, C.c_int, C.c_int, C.c_int, C.c_int, c_p]),
     'nnl_avgpool2d_bwd': (C.c_int, [c_p, c_p, i64, i64, i64, i64, i64, i64, C.c_int, C.c_int, C.c_int, C.c_int, c_p]),
     'nnl_subsample2d_fwd': (C.c_int, [c_p, c_p, i64, i64, i64, i64, i64, i64, C.c_int, C.c_int, c_p]),

@@ -26,96 +26,14 @@
 //     no fold.  The wgrad workgroups of the first k-tile column also sum the UNROUNDED dy they stage, per column in a fixed order (thread,
 //     then the 8 reduction quads through LDS, then the slabs): the bias gradient.
 // No atomics anywhere: two calls on the same inputs give the same bits.
-#include "nnl_common.h"
+#include "linear_bf16_tiles.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int BN = 128;                        // operand rows of a streamed tile (= columns of a forward tile, both sides of a backward tile)
-constexpr int KS = 32;                         // reduction indices per step
-constexpr int TP = 80;                         // bytes of a streamed tile row: 4 chunks + 1 pad
-constexpr int TILEB = BN * TP;                 // bytes of one streamed tile
 constexpr int SLAB_MIN = 512;                  // fewest reduction indices per backward slab (a multiple of KS)
 constexpr int SLAB_MAX = 16;                   // most slabs
 constexpr int SPLIT_GRID = 1024;                 // slabs are added until the backward grid has about this many workgroups
 static_assert(SLAB_MIN % KS == 0, "a slab is a whole number of steps");
-
-__device__ __forceinline__ unsigned pk_bf16(float a, float b) {
-  bf16x2 t = {(__bf16)a, (__bf16)b};           // v_cvt_pk_bf16_f32: round to nearest even; a is the low half
-  return __builtin_bit_cast(unsigned, t);
-}
-
-// p[0 .. 3] where they exist (`valid` elements from p on), zeros elsewhere; one float4 load when the operand allows it
-__device__ __forceinline__ f32x4 load4(const float* __restrict__ p, long valid, bool vec) {
-  f32x4 v = {0.f, 0.f, 0.f, 0.f};
-  if (valid <= 0) return v;
-  if (vec && valid >= 4) return *reinterpret_cast<const f32x4*>(p);
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-    if (j < valid) v[j] = p[j];
-  return v;
-}
-
-__device__ __forceinline__ u32x4 pack8(f32x4 a, f32x4 b) {
-  return u32x4{pk_bf16(a[0], a[1]), pk_bf16(a[2], a[3]), pk_bf16(b[0], b[1]), pk_bf16(b[2], b[3])};
-}
-
-__device__ __forceinline__ int tile_off(int row, int chunk) { return row * TP + ((chunk ^ ((row >> 4) & 3)) * 16); }
-
-__device__ __forceinline__ bf16x8 frag(const unsigned char* tile, int row, int chunk) {
-  return *reinterpret_cast<const bf16x8*>(tile + tile_off(row, chunk));
-}
-
-// DIRECT operand: matrix rows row0 .. row0 + 127 (those below nrows), reduction indices red0 .. red0 + 31 (those below red_end) contiguous
-// in memory.  Thread t holds chunk t & 3 of rows t >> 2 and 64 + (t >> 2).
-__device__ __forceinline__ void load_direct(const float* __restrict__ base, long ld, long row0, long nrows, long red0, long red_end, bool vec,
-                                            f32x4 (&r)[4]) {
-  const int tid = threadIdx.x;
-  const long red = red0 + (tid & 3) * 8;
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const long row = row0 + (tid >> 2) + 64 * h;
-    r[2 * h] = r[2 * h + 1] = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (row < nrows) {
-      const float* p = base + row * ld + red;
-      r[2 * h] = load4(p, red_end - red, vec);
-      r[2 * h + 1] = load4(p + 4, red_end - red - 4, vec);
-    }
-  }
-}
-
-__device__ __forceinline__ void commit_direct(unsigned char* tile, const f32x4 (&r)[4]) {
-  const int tid = threadIdx.x;
-#pragma unroll
-  for (int h = 0; h < 2; ++h) *reinterpret_cast<u32x4*>(tile + tile_off((tid >> 2) + 64 * h, tid & 3)) = pack8(r[2 * h], r[2 * h + 1]);
-}
-
-// TRANSPOSED operand: the reduction index is the matrix ROW (red0 .. red0 + 31, those below red_end), the operand rows are its columns
-// col0 .. col0 + 127 (those below ncols).  Thread t holds reduction rows 4 (t >> 5) .. + 3 of columns 4 (t & 31) .. + 3.
-__device__ __forceinline__ void load_trans(const float* __restrict__ base, long ld, long col0, long ncols, long red0, long red_end, bool vec,
-                                           f32x4 (&r)[4]) {
-  const int tid = threadIdx.x;
-  const long col = col0 + (tid & 31) * 4;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const long red = red0 + (tid >> 5) * 4 + i;
-    r[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (red < red_end) r[i] = load4(base + red * ld + col, ncols - col, vec);
-  }
-}
-
-__device__ __forceinline__ void commit_trans(unsigned char* tile, const f32x4 (&r)[4]) {
-  const int tid = threadIdx.x, cq = tid & 31, pq = tid >> 5;
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-    *reinterpret_cast<u32x2*>(tile + tile_off(cq * 4 + j, pq >> 1) + (pq & 1) * 8) = u32x2{pk_bf16(r[0][j], r[1][j]), pk_bf16(r[2][j], r[3][j])};
-}
 
 struct StreamPlan {
   long R, C;                                   // the output matrix [R][C]: dgrad M x K, wgrad N x K
@@ -229,10 +147,6 @@ __global__ __launch_bounds__(256) void linear_bf16_fold_kernel(const float* __re
   for (int sl = 1; sl < slabs; ++sl) s += part[(long)sl * numel + i];            // slab order: fixed
   out[i] = s;
 }
-
-bool vec_ok(const void* p, long ld) { return ((uintptr_t)p & 15) == 0 && ld % 4 == 0; }
-
-const long DIM_MAX = (1L << 31) - 256;         // tile arithmetic on an axis stays inside an int
 
 int check_dims(const char* who, int64_t M, int64_t N, int64_t K) {
   NNL_CHECK_ARG(M > 0 && N > 0 && K > 0, "%s: M = %ld, N = %ld, K = %ld must be positive", who, (long)M, (long)N, (long)K);

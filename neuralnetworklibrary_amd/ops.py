@@ -16,7 +16,7 @@ import torch
 from . import _lib
 from ._lib import check, lib, ptr, require_cuda, stream
 
-__all__ = ['mse_loss', 'bce_with_logits', 'fbeta', 'scaled_sigmoid', 'embdotbias', 'index_error_flag', 'raise_if_index_error', 'conv2d', 'to_nhwc', 'from_nhwc', 'linear', 'linear_bf16', 'bn_act', 'concat_pool2d', 'TabularPlan', 'tab_embed_concat', 'embedding_renorm_drop', 'retina_loss', 'image_aug', 'grouped_conv2d', 'se_excite']
+__all__ = ['mse_loss', 'bce_with_logits', 'fbeta', 'scaled_sigmoid', 'embdotbias', 'index_error_flag', 'raise_if_index_error', 'conv2d', 'to_nhwc', 'from_nhwc', 'linear', 'linear_bf16', 'linear_cross_entropy_bf16', 'bn_act', 'concat_pool2d', 'TabularPlan', 'tab_embed_concat', 'embedding_renorm_drop', 'retina_loss', 'image_aug', 'grouped_conv2d', 'se_excite']
 
 _ERR_FLAGS = {}
 
@@ -1080,6 +1080,69 @@ def linear_bf16(x, weight, bias=None, relu=False):
     lead = x.shape[:-1]
     y = _LinearBf16.apply(x.reshape(-1, x.shape[-1]), weight, bias, bool(relu))
     return y.reshape(*lead, weight.shape[0])
+
+
+def linear_ce_bf16_supported(M, N, K):
+    "whether an [M, K] x [N, K]^T decoder lies in linear_cross_entropy_bf16's domain (K <= 512)"
+    return bool(lib.nnl_linear_ce_bf16_supported(int(M), int(N), int(K)))
+
+
+class _LinearCeBf16(torch.autograd.Function):
+    """softmax_cross_entropy(linear_bf16(x, weight), target) on csrc/linear_ce_bf16.hip: neither the logits nor their gradient exist in
+    memory.  The forward saves lse [M]; the backward recomputes the logits tile by tile for dx and again for dw."""
+
+    @staticmethod
+    def forward(ctx, x, weight, target):
+        require_cuda(x, weight, target)
+        x = x if _rows_in_place(x) else _f32c(x)
+        w = weight if _rows_in_place(weight) else _f32c(weight)
+        target = target.contiguous().long()
+        (M, K), N, dev = x.shape, w.shape[0], x.device
+        lse = torch.empty(M, dtype=torch.float32, device=dev)
+        loss_rows = torch.empty(M, dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        wsb = int(lib.nnl_linear_ce_bf16_fwd_workspace_bytes(M, N, K))
+        check(lib.nnl_linear_ce_bf16_fwd(ptr(x), ptr(w), ptr(target), ptr(lse), ptr(loss_rows), ptr(loss), M, N, K, _ld(x), _ld(w),
+                                         ptr(_workspace(wsb, dev)), wsb, ptr(index_error_flag(dev)), stream()))
+        ctx.save_for_backward(x, w, target, lse)
+        ctx.wgeom = (tuple(weight.shape), tuple(weight.stride()))
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        x, w, target, lse = ctx.saved_tensors
+        (M, K), N, dev = x.shape, w.shape[0], x.device
+        want_dx, want_dw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (want_dx or want_dw):
+            return None, None, None
+        g = _f32c(dloss).view(1)
+        dx = torch.empty(M, K, dtype=torch.float32, device=dev) if want_dx else None
+        dw = torch.empty(N, K, dtype=torch.float32, device=dev) if want_dw else None
+        wsb = int(lib.nnl_linear_ce_bf16_bwd_workspace_bytes(M, N, K, int(want_dx), int(want_dw)))
+        check(lib.nnl_linear_ce_bf16_bwd(ptr(x), ptr(w), ptr(target), ptr(lse), ptr(g), ptr(dx), ptr(dw), M, N, K, _ld(x), _ld(w),
+                                         ptr(_workspace(wsb, dev)), wsb, stream()))
+        wshape, wstride = ctx.wgeom
+        if dw is not None and wstride != tuple(dw.stride()):        # the parameter's own strides: AccumulateGrad keeps the tensor as is
+            dw = torch.empty_strided(wshape, wstride, dtype=torch.float32, device=dev).copy_(dw)
+        return dx, dw, None
+
+
+def linear_cross_entropy_bf16(x, w, target):
+    """softmax_cross_entropy(linear_bf16(x, w), target) without the logits: the 0-dim fp32 mean over the M rows of
+    logsumexp_j z[r, j] - z[r, target[r]], z = rb(x) rb(w)^T summed in fp32, for x [M, K], w [N, K] fp32 and target [M] int64; K <= 512.
+    A target outside [0, N) gives its row the loss 0 and raises the index-error flag (raise_if_index_error).  dx and dw are fp32, from
+    the gradient of the logits carried as two bf16 matrix-core operands (hi + lo, 2^-16 relative).  Bitwise reproducible run to run."""
+    if x.dim() != 2:
+        raise NotImplementedError('linear_cross_entropy_bf16: x must be [M, K], not %r' % (tuple(x.shape),))
+    if w.dim() != 2 or w.shape[1] != x.shape[1]:
+        raise NotImplementedError('linear_cross_entropy_bf16: w %r does not match the %d features of x' % (tuple(w.shape), x.shape[1]))
+    if target.dim() != 1 or target.shape[0] != x.shape[0] or target.dtype != torch.int64:
+        raise NotImplementedError('linear_cross_entropy_bf16: target must be int64 [%d], not %s %r' % (x.shape[0], target.dtype, tuple(target.shape)))
+    if x.dtype != torch.float32 or w.dtype != torch.float32:
+        raise NotImplementedError('linear_cross_entropy_bf16: x and w must be fp32, not %s and %s' % (x.dtype, w.dtype))
+    if not linear_ce_bf16_supported(x.shape[0], w.shape[0], x.shape[1]):
+        raise NotImplementedError('linear_cross_entropy_bf16: x %r, w %r outside the domain M, N >= 1, 1 <= K <= 512' % (tuple(x.shape), tuple(w.shape)))
+    return _LinearCeBf16.apply(x, w, target)
 
 
 def _rows_view(x):

@@ -196,8 +196,25 @@ def softmax_cross_entropy(logits, target):
     return _SoftmaxCE.apply(logits, target)
 
 
+class DeferredLogits:
+    """What LanguageModelDecoder returns in place of its [bs, V, seq] logits while `fuse_loss` is set and it is training: the dropped-out
+    activations x [seq, bs, emb] and the tied weight [V, emb].  cross_entropy_nd takes the loss straight from them
+    (ops.linear_cross_entropy_bf16: the logits never exist); materialize() gives the logits after all."""
+
+    def __init__(self, x, weight):
+        self.x, self.weight = x, weight
+
+    def materialize(self):
+        from . import ops
+        return ops.linear_bf16(self.x, self.weight, None).permute(1, 2, 0)
+
+
 def cross_entropy_nd(preds, target):
     """F.cross_entropy(preds, target) for class-dim-1 inputs: [N,C] with target [N], or [N,C,d1..] with [N,d1..]."""
+    if isinstance(preds, DeferredLogits):
+        from . import ops
+        # rows in [seq, bs] order, as the materialised route below takes them
+        return ops.linear_cross_entropy_bf16(preds.x.reshape(-1, preds.x.shape[-1]), preds.weight, target.transpose(0, 1).reshape(-1))
     if preds.dim() == 2:
         return softmax_cross_entropy(preds, target)
     C = preds.shape[1]
