@@ -449,7 +449,32 @@ size_t nnl_conv2d_bf16_wgrad_workspace_bytes(const nnl_conv_geom_t* g);
 int nnl_conv2d_bf16_wgrad(const float* x, const float* dy, float* dw, const nnl_conv_geom_t* g, void* workspace, size_t workspace_bytes,
                           void* stream);
 
-/* ---- K22: opt-in bf16 matrix-core Linear (csrc/linear_bf16.hip) ----------------------------------------------------------------------------
+/* ---- K24: opt-in bf16 matrix-core grouped convolutions (csrc/gconv_bf16.hip) ---------------------------------------------------------------
+ * The grouped 3x3 of the SENet / SE-ResNeXt / ResNeXt bottlenecks (K15's call sites: Applications/VisionModels/senet.py:178-180, 205-206,
+ * 229-230, and the 3x3 of resnext.py's _block through the same module) with bf16 OPERANDS: tensors, layouts and dims as the nnl_gconv2d_* entries
+ * (NHWC fp32 activations, the filter [K, R, R, Cg] fp32 in the parameter's own memory, dw in that layout); the operands are rounded to bf16
+ * (nearest even) on their way into LDS, products on v_mfma_f32_16x16x32_bf16 against block-diagonal filter tiles, fp32 sums and epilogue.
+ * No atomics: two calls on the same inputs give the same bits.
+ * Domain (nnl_gconv2d_bf16_supported: 1 inside, 0 outside): G divides C and K, Cg = C/G and Kg = K/G each in {4, 8, 16, 32}, R in {1, 3},
+ * stride in {1, 2}, 0 <= pad <= R / 2, N < 65536, C and K < 2^18, every tensor below 2^31 elements.  Anything else (senet154's layer1 with
+ * Cg = 2 among it), or a null pointer, is NNL_ERR_INVALID_ARG and nothing is launched.
+ * Route notes: gconv_bf16_fwd<cgC,kgK>, gconv_bf16_dgrad<cgC,kgK>, gconv_bf16_wgrad<cgC,kgK>@sS.
+ *   nnl_gconv2d_bf16_fwd (senet.py:178-180, 205-206, 229-230; resnext.py _block's grouped 3x3): y = conv(rb(x), rb(w)) + bias (bias may be
+ *     NULL), ReLU when relu != 0.
+ *   nnl_gconv2d_bf16_dgrad (their backward): dx [N,H,W,C] = dgrad(rb(dy), rb(w)); every element of dx is written.
+ *   nnl_gconv2d_bf16_wgrad (their backward): dw [K, R, R, Cg] = rb(dy)^T rb(x) per tap.  The N*P*Q pixels are cut into slabs whose partial
+ *     sums go to the workspace (nnl_gconv2d_bf16_workspace_bytes = slabs x K R R Cg x 4, or 0 for one slab: ws may be NULL then) and are
+ *     added in slab order by a second launch; a workspace that is too small is NNL_ERR_WORKSPACE. */
+int nnl_gconv2d_bf16_supported(int64_t N, int64_t H, int64_t W, int64_t C, int64_t K, int64_t G, int R, int stride, int pad);
+int nnl_gconv2d_bf16_fwd(const float* x, const float* w, const float* bias, float* y, int64_t N, int64_t H, int64_t W, int64_t C, int64_t K,
+                         int64_t G, int R, int stride, int pad, int relu, void* stream);
+int nnl_gconv2d_bf16_dgrad(const float* dy, const float* w, float* dx, int64_t N, int64_t H, int64_t W, int64_t C, int64_t K, int64_t G,
+                           int R, int stride, int pad, void* stream);
+size_t nnl_gconv2d_bf16_workspace_bytes(int64_t N, int64_t H, int64_t W, int64_t C, int64_t K, int64_t G, int R, int stride, int pad);
+int nnl_gconv2d_bf16_wgrad(const float* x, const float* dy, float* dw, void* ws, size_t ws_bytes, int64_t N, int64_t H, int64_t W, int64_t C,
+                           int64_t K, int64_t G, int R, int stride, int pad, void* stream);
+
+/* ---- K22: opt-in bf16 matrix-core Linear (csrc/linear_bf16.hip)----------------------------------------------------------------------------
  * The Linear GEMMs of the language model: the tied decoder (reference Applications/Text.py:572, self.lin over [seq bs, emb] with V = 47 343
  * output features) and the input projection gx = x w_ih^T + b of nn.LSTM (Text.py:495-513), and their autograd backward, with bf16
  * OPERANDS: every tensor is fp32 in memory, the operands are rounded to bf16 (nearest even) on their way into LDS, products on

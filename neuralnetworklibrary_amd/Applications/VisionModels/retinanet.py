@@ -49,9 +49,12 @@ class HipConv2d(nn.Conv2d):
 class HipGroupedConv2d(nn.Conv2d):
     """nn.Conv2d(groups=G) (same parameters / state_dict) computed by the grouped kernels of csrc/gconv.hip (ops.grouped_conv2d; direct, or MFMA at 16 / 32 channels per group both ways):
     the 3x3 of the SENet / SE-ResNeXt bottlenecks (senet.py:178-180, 229-230).  The weight keeps its logical [K, C/G, R, R] shape and is
-    STORED channels_last (= [K, R, R, C/G], the kernels' filter layout).  Deliberately not marked `nnl_hip_conv`: the prepared-filter
+    STORED channels_last (= [K, R, R, C/G], the kernels' filter layout).  With `compute = 'bf16'` on an instance (Learner.use_bf16_conv, for
+    4 / 8 / 16 / 32 channels per group) the bf16 matrix-core kernels of csrc/gconv_bf16.hip run instead.  Deliberately not marked `nnl_hip_conv`: the prepared-filter
     window (ops._Filters) transposes the weights of the marked modules as dense [K, C, R, S] filters."""
     fuse_relu = False
+    nnl_hip_gconv = True              # what Learner.use_bf16_conv looks for (not nnl_hip_conv: see above)
+    compute = 'fp32'                  # 'bf16' on an instance (Learner.use_bf16_conv): ops.grouped_conv2d_bf16 (csrc/gconv_bf16.hip)
 
     def __init__(self, *args, **kwargs):
         super().__init__(*args, **kwargs)
@@ -66,7 +69,8 @@ class HipGroupedConv2d(nn.Conv2d):
             raise NotImplementedError('HipGroupedConv2d: stride %r must be the same in both directions' % (self.stride,))
         if self.padding[0] != self.padding[1]:
             raise NotImplementedError('HipGroupedConv2d: padding %r must be the same in both directions' % (self.padding,))
-        return ops.grouped_conv2d(x, self.weight, self.bias, self.stride[0], self.padding[0], self.groups, relu=self.fuse_relu)
+        conv = ops.grouped_conv2d_bf16 if self.compute == 'bf16' else ops.grouped_conv2d
+        return conv(x, self.weight, self.bias, self.stride[0], self.padding[0], self.groups, relu=self.fuse_relu)
 
 
 class HipMaxPool2d(nn.MaxPool2d):

@@ -361,18 +361,23 @@ class Learner(object):
         return self
 
     def use_bf16_conv(self, flag=True):
-        """MI355X addition: run the dense convolutions of the model on the bf16 matrix cores (csrc/conv_bf16.hip) — every HipConv2d
-        whose layer shape `nnl_conv2d_bf16_supported` accepts (groups 1, dilation 1, square filter up to 7x7, stride 1 or 2, channel
-        counts multiples of 8: the body convolutions of the ResNet / RetinaNet / SENet / ResNeXt / Inception models; the 3-channel
-        stem, RetinaNet's 36- / 180-channel output convolutions and the grouped / depthwise / line families keep their kernels).
+        """MI355X addition: run the convolutions of the model on the bf16 matrix cores — every HipConv2d whose layer shape
+        `nnl_conv2d_bf16_supported` accepts (csrc/conv_bf16.hip: groups 1, dilation 1, square filter up to 7x7, stride 1 or 2, channel
+        counts multiples of 8: the body convolutions of the ResNet / RetinaNet / SENet / ResNeXt / Inception models) and every
+        HipGroupedConv2d whose layer shape `nnl_gconv2d_bf16_supported` accepts (csrc/gconv_bf16.hip: 1x1 or 3x3, stride 1 or 2, 4, 8,
+        16 or 32 channels per group in and out: the grouped 3x3 of ResNeXt-101, SE-ResNeXt and SENet-154 but for the latter's layer1
+        with 2 channels per group).  The 3-channel stem, RetinaNet's 36- / 180-channel output convolutions and the depthwise / line
+        families keep their kernels.
         The operands are rounded to bf16 inside the kernels, sums are fp32, and every tensor — activations, weights, gradients,
         BatchNorm, the optimizer state, the state_dict — stays fp32.  Off by default: the fp32 MFMA path is the one that matches the
-        reference to fp32 rounding.  flag=False restores it.  Captured graphs are dropped (the next steps warm up and capture
-        again); works with distribute() and use_graphs()."""
+        reference to fp32 rounding.  flag=False restores it bit for bit.  Captured graphs are dropped (the next steps warm up and
+        capture again); works with distribute() and use_graphs()."""
         from .. import ops
         for m in self.model.modules():
             if getattr(m, 'nnl_hip_conv', False):
                 m.compute = 'bf16' if flag and ops.conv2d_bf16_supported(m) else 'fp32'
+            elif getattr(m, 'nnl_hip_gconv', False):
+                m.compute = 'bf16' if flag and ops.grouped_conv2d_bf16_supported(m) else 'fp32'
         self._graphs = {}
         return self
 

@@ -104,6 +104,11 @@ SIGNATURES = {
     'nnl_conv2d_bf16_dgrad': (C.c_int, [c_p, c_p, c_p, C.POINTER(ConvGeom), c_p, c_p]),
     'nnl_conv2d_bf16_wgrad_workspace_bytes': (sz, [C.POINTER(ConvGeom)]),
     'nnl_conv2d_bf16_wgrad': (C.c_int, [c_p, c_p, c_p, C.POINTER(ConvGeom), c_p, sz, c_p]),
+    'nnl_gconv2d_bf16_supported': (C.c_int, [i64, i64, i64, i64, i64, i64, C.c_int, C.c_int, C.c_int]),
+    'nnl_gconv2d_bf16_fwd': (C.c_int, [c_p, c_p, c_p, c_p, i64, i64, i64, i64, i64, i64, C.c_int, C.c_int, C.c_int, C.c_int, c_p]),
+    'nnl_gconv2d_bf16_dgrad': (C.c_int, [c_p, c_p, c_p, i64, i64, i64, i64, i64, i64, C.c_int, C.c_int, C.c_int, c_p]),
+    'nnl_gconv2d_bf16_workspace_bytes': (sz, [i64, i64, i64, i64, i64, i64, C.c_int, C.c_int, C.c_int]),
+    'nnl_gconv2d_bf16_wgrad': (C.c_int, [c_p, c_p, c_p, c_p, sz, i64, i64, i64, i64, i64, i64, C.c_int, C.c_int, C.c_int, c_p]),
     'nnl_linear_bf16_fwd': (C.c_int, [c_p, c_p, c_p, c_p, i64, i64, i64, i64, i64, i64, C.c_int, c_p]),
     'nnl_linear_bf16_dgrad_workspace_bytes': (sz, [i64, i64, i64]),
     'nnl_linear_bf16_dgrad': (C.c_int, [c_p, c_p, c_p, i64, i64, i64, i64, i64, c_p, sz, c_p]),

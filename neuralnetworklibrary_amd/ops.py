@@ -1517,41 +1517,51 @@ class _GroupedConv2d(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, weight, bias, stride, pad, groups, relu):
         _gconv_check(x.shape, weight.shape, stride, pad, groups)
-        require_cuda(x, weight, bias)
-        xn, wn = to_nhwc(x.float()), to_nhwc(weight.float())                 # (no copy: both are stored channels_last)
-        b = None if bias is None else _f32c(bias)
-        N, H, W, C = xn.shape
-        K, R = wn.shape[0], wn.shape[1]
-        g = _geom(N, H, W, C, K, R, R, stride, pad)
-        y = torch.empty((N, g.P, g.Q, K), dtype=torch.float32, device=x.device)
-        check(lib.nnl_gconv2d_fwd(ptr(xn), ptr(wn), ptr(b), ptr(y), N, H, W, C, K, groups, R, stride, pad, int(relu), stream()))
-        ctx.cfg = (g, groups, bool(relu), bias is not None)
-        ctx.save_for_backward(xn, wn, y if relu else None)
-        return from_nhwc(y)
+        return _gconv_forward(ctx, 'nnl_gconv2d', x, weight, bias, stride, pad, groups, relu)
 
     @staticmethod
     def backward(ctx, dy):
-        xn, wn, y = ctx.saved_tensors
-        g, groups, relu, has_bias = ctx.cfg
-        dims = (g.N, g.H, g.W, g.C, g.K, groups, g.R, g.stride, g.pad)
-        want_db = has_bias and ctx.needs_input_grad[2]
-        dyn, db = to_nhwc(dy.float()), None
-        if relu:
-            dyn, db = _conv_act_gate(y, dyn, g, 1, want_db)
-        dx = dw = None
-        if ctx.needs_input_grad[0]:
-            dx = torch.empty_like(xn)
-            check(lib.nnl_gconv2d_dgrad(ptr(dyn), ptr(wn), ptr(dx), *dims, stream()))
-            dx = from_nhwc(dx)
-        if ctx.needs_input_grad[1]:
-            dw = torch.empty_like(wn)                                        # [K, R, R, Cg]: the parameter's own layout
-            wsb = int(lib.nnl_gconv2d_workspace_bytes(*dims))
-            ws = _workspace(wsb, dyn.device)
-            check(lib.nnl_gconv2d_wgrad(ptr(xn), ptr(dyn), ptr(dw), ptr(ws), wsb, *dims, stream()))
-            dw = from_nhwc(dw)
-        if db is None and want_db:
-            db = _conv_bias_grad(dyn, g, g.K)
-        return dx, dw, db, None, None, None, None
+        return _gconv_backward(ctx, 'nnl_gconv2d', dy)
+
+
+def _gconv_forward(ctx, entry, x, weight, bias, stride, pad, groups, relu):
+    "the forward of both grouped families: `entry` is the prefix of the C entries, nnl_gconv2d (fp32) or nnl_gconv2d_bf16"
+    require_cuda(x, weight, bias)
+    xn, wn = to_nhwc(x.float()), to_nhwc(weight.float())                     # (no copy: both are stored channels_last)
+    b = None if bias is None else _f32c(bias)
+    N, H, W, C = xn.shape
+    K, R = wn.shape[0], wn.shape[1]
+    g = _geom(N, H, W, C, K, R, R, stride, pad)
+    y = torch.empty((N, g.P, g.Q, K), dtype=torch.float32, device=x.device)
+    check(getattr(lib, entry + '_fwd')(ptr(xn), ptr(wn), ptr(b), ptr(y), N, H, W, C, K, groups, R, stride, pad, int(relu), stream()))
+    ctx.cfg = (g, groups, bool(relu), bias is not None)
+    ctx.save_for_backward(xn, wn, y if relu else None)
+    return from_nhwc(y)
+
+
+def _gconv_backward(ctx, entry, dy):
+    "the backward of both grouped families; the ReLU gate and the bias gradient are fp32 passes over the unrounded dy in either"
+    xn, wn, y = ctx.saved_tensors
+    g, groups, relu, has_bias = ctx.cfg
+    dims = (g.N, g.H, g.W, g.C, g.K, groups, g.R, g.stride, g.pad)
+    want_db = has_bias and ctx.needs_input_grad[2]
+    dyn, db = to_nhwc(dy.float()), None
+    if relu:
+        dyn, db = _conv_act_gate(y, dyn, g, 1, want_db)
+    dx = dw = None
+    if ctx.needs_input_grad[0]:
+        dx = torch.empty_like(xn)
+        check(getattr(lib, entry + '_dgrad')(ptr(dyn), ptr(wn), ptr(dx), *dims, stream()))
+        dx = from_nhwc(dx)
+    if ctx.needs_input_grad[1]:
+        dw = torch.empty_like(wn)                                            # [K, R, R, Cg]: the parameter's own layout
+        wsb = int(getattr(lib, entry + '_workspace_bytes')(*dims))
+        ws = _workspace(wsb, dyn.device)
+        check(getattr(lib, entry + '_wgrad')(ptr(xn), ptr(dyn), ptr(dw), ptr(ws), wsb, *dims, stream()))
+        dw = from_nhwc(dw)
+    if db is None and want_db:
+        db = _conv_bias_grad(dyn, g, g.K)
+    return dx, dw, db, None, None, None, None
 
 
 def grouped_conv2d(x, weight, bias, stride, pad, groups, relu=False):
@@ -1559,6 +1569,59 @@ def grouped_conv2d(x, weight, bias, stride, pad, groups, relu=False):
     channels_last.  Domain: R in {1, 3}, stride in {1, 2}, pad in {0, 1} and <= R // 2, groups divides C and K; anything else raises
     NotImplementedError naming the argument."""
     return _GroupedConv2d.apply(x, weight, bias, int(stride), int(pad), int(groups), bool(relu))
+
+
+# K24: the same convolution on the bf16 matrix cores (csrc/gconv_bf16.hip)
+_GCONV_BF16_WIDTHS = (4, 8, 16, 32)
+
+
+def _gconv_bf16_check(x_shape, w_shape, stride, pad, groups):
+    "the domain of csrc/gconv_bf16.hip, checked before any launch (and before any device is needed): names the offending argument"
+    if len(x_shape) != 4 or len(w_shape) != 4:
+        raise NotImplementedError('grouped_conv2d_bf16: x %s and weight %s must be 4-D' % (tuple(x_shape), tuple(w_shape)))
+    C, (K, Cg, R, S) = x_shape[1], w_shape
+    if R != S or R not in (1, 3):
+        raise NotImplementedError('grouped_conv2d_bf16: kernel_size %dx%d is not supported (1x1 or 3x3)' % (R, S))
+    if stride not in (1, 2):
+        raise NotImplementedError('grouped_conv2d_bf16: stride %r is not supported (1 or 2)' % (stride,))
+    if pad not in (0, 1) or pad > R // 2:
+        raise NotImplementedError('grouped_conv2d_bf16: padding %r is not supported (0 .. kernel_size // 2)' % (pad,))
+    if groups < 1 or C % groups or K % groups or C // groups != Cg:
+        raise NotImplementedError('grouped_conv2d_bf16: groups %r must divide the %d input and %d output channels (weight holds %d inputs per group)'
+                                  % (groups, C, K, Cg))
+    if Cg not in _GCONV_BF16_WIDTHS or K // groups not in _GCONV_BF16_WIDTHS:
+        raise NotImplementedError('grouped_conv2d_bf16: channels per group %d in, %d out (each must be 4, 8, 16 or 32)' % (Cg, K // groups))
+
+
+def grouped_conv2d_bf16_supported(conv):
+    "whether the layer shape of an nn.Conv2d(groups=G) lies in grouped_conv2d_bf16's domain: nnl_gconv2d_bf16_supported on a nominal raster"
+    k, s, p = conv.kernel_size, conv.stride, conv.padding
+    if conv.dilation != (1, 1) or conv.padding_mode != 'zeros' or isinstance(p, str) or k[0] != k[1] or s[0] != s[1] or p[0] != p[1]:
+        return False
+    side = k[0] + 2
+    return bool(lib.nnl_gconv2d_bf16_supported(1, side, side, conv.in_channels, conv.out_channels, conv.groups, k[0], s[0], p[0]))
+
+
+class _GroupedConv2dBf16(torch.autograd.Function):
+    """_GroupedConv2d with its products on the bf16 matrix cores (csrc/gconv_bf16.hip): x, weight and dy are rounded to bf16 inside the
+    kernels, sums and epilogue are fp32, every tensor is fp32 in memory."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, stride, pad, groups, relu):
+        _gconv_bf16_check(x.shape, weight.shape, stride, pad, groups)
+        return _gconv_forward(ctx, 'nnl_gconv2d_bf16', x, weight, bias, stride, pad, groups, relu)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return _gconv_backward(ctx, 'nnl_gconv2d_bf16', dy)
+
+
+def grouped_conv2d_bf16(x, weight, bias, stride, pad, groups, relu=False):
+    """ops.grouped_conv2d with its products on the bf16 matrix cores: x, weight and the output gradient are rounded to bf16 (nearest
+    even) inside the kernels, sums and epilogue are fp32, and so is every tensor in memory.  Domain: R in {1, 3}, stride in {1, 2},
+    pad <= R // 2, groups divides C and K, and the channels per group (in and out) are each 4, 8, 16 or 32; anything else raises
+    NotImplementedError naming the argument.  Bitwise reproducible run to run."""
+    return _GroupedConv2dBf16.apply(x, weight, bias, int(stride), int(pad), int(groups), bool(relu))
 
 
 class _SEExcite(torch.autograd.Function):
